@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- aligned audio-seconds per wall-second of the AlignModel hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 Workload = BASELINE.json configs[1]: Whisper-medium encoder + BiGRU/FC head + CTC forced alignment,
@@ -12,6 +12,9 @@ mel [32,80,3000] -> conv stem -> 24 blocks -> ln_post -> 2 x BiGRU -> Mish -> fu
 Multi-GPU: clips are independent, so every rank aligns its own batch with NO data-path collective
 ("weak" scaling); torch.distributed (RCCL) is only used for the barrier and the MAX over ranks of the time.
 Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the steps and prints the headline; --full adds everything else the bench measures
+(the roofline pass and per-launch timer, socket power, the CPU baseline and self-check against the oracle, the other compute
+modes and BASELINE configs).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (rank 0).
 """
 from __future__ import annotations
 
@@ -323,6 +326,25 @@ def log(msg: str):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 if it was 32 bits or narrower floating point, else float64
+    (integer frames and status codes are exact in it), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+        host[name] = a.float().numpy() if a.is_floating_point() and a.element_size() <= 4 else a.double().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte limit")
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in host.items()))
+
+
 def _cpu_stage_times(p, n_head: int, audio: np.ndarray, label: np.ndarray) -> dict:
     """One clip through the CPU oracle stage by stage (SURVEY 8(d) / BASELINE.md section 3 item 1): waveform -> log-mel + pad_or_trim
     (module/align_model.py:84-90) -> encoder (:91) -> BiGRU / Mish / Linear head (:107) -> emission prep (utils/alignment.py:123-134)
@@ -482,6 +504,7 @@ def run_finetune(args, rank, world, local_rank, device, dist):
     dec_in = torch.from_numpy(rs.randint(0, 50000, size=(B, n_tok)))
     dec_out = torch.from_numpy(rs.randint(0, 50000, size=(B, n_tok)))
     ar_events = []
+    last = {}
 
     micro = dict(audios=audios, ctc_labels=labels, frame_labels=fl, decoder_input=dec_in, decoder_output=dec_out)
 
@@ -490,7 +513,7 @@ def run_finetune(args, rank, world, local_rank, device, dist):
         # (FineTuner.accumulate; --accum-mode loop = accum separate micro-steps, the round-1/2 form)
         # the exchange step of the data-parallel path rides on the last backward (finetune.OverlappedAllReduce: chunks of the flat
         # buckets are all-reduced as autograd completes them); step() waits for it -- what is left exposed is bracketed there
-        tuner.accumulate([micro] * args.accum, accum_grad_steps=args.accum, fused=args.accum_mode == "fused")
+        last["losses"] = tuner.accumulate([micro] * args.accum, accum_grad_steps=args.accum, fused=args.accum_mode == "fused")
         if tuner.overlap is None:               # --allreduce-chunks 0: one blocking all-reduce per bucket, bracketed here
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -498,9 +521,9 @@ def run_finetune(args, rank, world, local_rank, device, dist):
             e1.record()
             if timed:
                 ar_events.append((e0, e1))
-            tuner.step(allreduced=True)
+            last["grad_sqnorm"] = tuner.step(allreduced=True)
             return
-        tuner.step()
+        last["grad_sqnorm"] = tuner.step()
         if timed and getattr(tuner.overlap, "_events", None) is not None:
             ar_events.append(tuner.overlap._events)
 
@@ -524,6 +547,15 @@ def run_finetune(args, rank, world, local_rank, device, dist):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     L.la_timer_disable()
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        # what a training step hands its caller: the summed loss vector and the gradient's squared norm, plus a seeded sample of
+        # the updated parameters (the flat buffers hold ~0.8 G values)
+        arrays = {"losses": last["losses"], "grad_sqnorm": last["grad_sqnorm"].reshape(-1)}
+        g = torch.Generator(device="cpu").manual_seed(0)
+        for i, f in enumerate(tuner.flat):
+            idx = torch.randint(0, f.numel(), (min(f.numel(), 1 << 16),), generator=g).to(f.device)
+            arrays[f"params_sample_{i}"] = f.view(-1)[idx]
+        dump_outputs(args.dump_outputs, arrays)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -659,6 +691,8 @@ def run_other_config(args, rank, world, local_rank, device, dist, model=None):
     eng.check_gru()
     if int((last["out"][3] != 0).sum()) != 0:
         raise SystemExit("alignment reported non-OK status on the synthetic batch")
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("onset", "offset", "score", "status"), last["out"])))
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -846,7 +880,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=DEFAULT_STEPS)
     ap.add_argument("--warmup", type=int, default=DEFAULT_WARMUP)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="align mode: after the headline also measure the rest -- the roofline pass and per-launch GEMM timer, socket power, "
+                         "the CPU baseline with the self-check against the oracle, and the extra legs (\"modes\", \"other_configs\")")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (align: onset / offset frames, score, status) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the self-check")
     ap.add_argument("--no-overlap", action="store_true", help="single stream: no encoder/head overlap across batches")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16",
                     help="16-bit operand type of the throughput kernels (BASELINE configs[1] is quoted on bf16)")
@@ -854,7 +893,7 @@ def main():
                     help="HIP streams the encoders of consecutive batches alternate between (2: one batch's kernel tails and launch gaps "
                          "are filled by the other's kernels, ~2 %% per step; the roofline leg is then measured on a separate one-stream pass)")
     ap.add_argument("--roofline-steps", type=int, default=ROOFLINE_PASS_STEPS,
-                    help="align mode: steps of the untimed single-encoder-stream pass after the timed region on which the per-launch timer runs")
+                    help="align mode with --full: steps of the untimed single-encoder-stream pass after the timed region on which the per-launch timer runs")
     ap.add_argument("--head-group", type=int, default=DEFAULT_HEAD_GROUP,
                     help="batches whose head (GRU / FC / DP) runs as one launch set in the two-stream pipeline "
                          "(same-box sweep, profiles/r4_sweep_pipeline_shape.txt: 2 -> 42.47, 4 -> 42.27, 5 -> 42.23, 10 -> 42.69 ms per step)")
@@ -876,10 +915,10 @@ def main():
                     help="align mode: the step starts one stage earlier, at the resident 16 kHz waveform [32, 480000] f32 -- the device "
                          "log-mel (la_logmel_f32_prepared) runs inside the timed step and feeds the encoder; adds logmel_ms_per_step")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="align mode, N = 1: skip the short passes after the timed region that fill \"modes\" (float32-parity and float16 on the "
+                    help="align mode with --full, N = 1: skip the short passes after the timed region that fill \"modes\" (float32-parity and float16 on the "
                          "headline workload) and \"other_configs\" (BASELINE configs[2..4]) in the JSON line")
     ap.add_argument("--timer-period", type=int, default=7,
-                    help="align mode: the roofline leg brackets every n-th launch of the GEMM family with HIP events (1 = every launch; odd and not a divisor of the 199 launches per pair of batches, so every shape is sampled alike)")
+                    help="align mode with --full: the roofline leg brackets every n-th launch of the GEMM family with HIP events (1 = every launch; odd and not a divisor of the 199 launches per pair of batches, so every shape is sampled alike)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -948,13 +987,16 @@ def main():
     from lyricalignment_amd.engine import PipelinedAligner
     pipe = None if args.no_overlap else PipelinedAligner(eng, head_group=args.head_group, encoder_streams=args.encoder_streams)
 
+    last = {}      # (onset, offset, score, status) device tensors of the latest step: what --dump-outputs writes
+
     def step():
         with torch.no_grad():
             mel_in = mel if wave is None else log_mel_spectrogram(wave, device=device)     # 2 launches on the encoder's stream
             if pipe is not None:   # encoder of this batch overlaps the head (GRU/FC/DP) of the previous one
-                pipe.submit(mel_in, labels, n_labels, n_frames=T_FRAMES, use_ctc=True, host_out=(pinned[0], pinned[1], pinned_status))
+                last["out"] = pipe.submit(mel_in, labels, n_labels, n_frames=T_FRAMES, use_ctc=True,
+                                          host_out=(pinned[0], pinned[1], pinned_status))
                 return
-            onset, offset, score, status = eng.align_mel(mel_in, labels, n_labels, n_frames=T_FRAMES, use_ctc=True)
+            last["out"] = onset, offset, score, status = eng.align_mel(mel_in, labels, n_labels, n_frames=T_FRAMES, use_ctc=True)
         pinned[0].copy_(onset, non_blocking=True)
         pinned[1].copy_(offset, non_blocking=True)
         pinned_status.copy_(status, non_blocking=True)
@@ -975,13 +1017,15 @@ def main():
     # The per-launch timer of the roofline leg reads kernel durations only while ONE encoder stream feeds the chip (two co-running
     # GEMMs share the CUs and each reads twice its own time).  With the default two encoder streams the timed region therefore runs
     # untimed per launch, and the leg is measured on a short pass of the same steps through a one-encoder-stream pipeline afterwards
-    # (same engine, inputs, head group; the head stream still co-runs, as it does in the timed region).
-    separate_pass = pipe is not None and args.encoder_streams > 1 and args.roofline_steps > 0
-    L.la_timer_reset()
-    L.la_timer_sample(args.timer_period)
-    if not separate_pass:
-        L.la_timer_enable(os.environ.get("LA_BENCH_TIMER", "gemm_bf16").encode())
-    power = PowerSampler(local_rank) if rank == 0 else None
+    # (same engine, inputs, head group; the head stream still co-runs, as it does in the timed region).  A plain run times the
+    # steps only: no per-launch timer and no power sampling.
+    separate_pass = args.full and pipe is not None and args.encoder_streams > 1 and args.roofline_steps > 0
+    if args.full:
+        L.la_timer_reset()
+        L.la_timer_sample(args.timer_period)
+        if not separate_pass:
+            L.la_timer_enable(os.environ.get("LA_BENCH_TIMER", "gemm_bf16").encode())
+    power = PowerSampler(local_rank) if rank == 0 and args.full else None
     barrier()
     torch.cuda.synchronize()
     if power is not None:
@@ -995,11 +1039,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     power_reading = power.stop() if power is not None else None
-    L.la_timer_disable()
+    if args.full:
+        L.la_timer_disable()
     log(f"timed region: {args.steps} steps in {elapsed:.3f} s")
     eng.check_gru()
     if int((pinned_status != 0).sum()) != 0:
         raise SystemExit("alignment reported non-OK status on the synthetic batch")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("onset", "offset", "score", "status"), last["out"])))
     last_onset, last_offset = pinned[0].numpy().copy(), pinned[1].numpy().copy()     # the timed region's last batch (self-check)
 
     if dist is not None:
@@ -1031,18 +1078,34 @@ def main():
         pipe = timed_pipe
     roofline_steps = args.roofline_steps if roofline_pass_ms is not None else args.steps
 
-    import ctypes
-    total_ms, launches, work, seen = ctypes.c_double(0.0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_int64(0)
-    _lib.check(L.la_timer_read_work(ctypes.byref(total_ms), ctypes.byref(launches), ctypes.byref(work), ctypes.byref(seen)), "timer_read_work")
-    # achieved = algorithmic flops of the bracketed launches / their summed HIP-event durations.  The library sums 2 M N K of what it
-    # launched; the only launch that computes padding is conv1 (80 mel channels padded to 128): scaled out analytically.
-    d_ = dims.n_audio_state
-    alg = algorithmic_gemm_flops_per_clip(d_, dims.n_audio_layer)
-    launched = alg + 2.0 * 3000 * (128 - 80) * 3 * d_
-    achieved_tf = work.value * (alg / launched) / (total_ms.value * 1e-3) / 1e12 if total_ms.value > 0 else 0.0
+    roofline = None
+    if args.full:
+        import ctypes
+        total_ms, launches, work, seen = ctypes.c_double(0.0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_int64(0)
+        _lib.check(L.la_timer_read_work(ctypes.byref(total_ms), ctypes.byref(launches), ctypes.byref(work), ctypes.byref(seen)), "timer_read_work")
+        # achieved = algorithmic flops of the bracketed launches / their summed HIP-event durations.  The library sums 2 M N K of what it
+        # launched; the only launch that computes padding is conv1 (80 mel channels padded to 128): scaled out analytically.
+        d_ = dims.n_audio_state
+        alg = algorithmic_gemm_flops_per_clip(d_, dims.n_audio_layer)
+        launched = alg + 2.0 * 3000 * (128 - 80) * 3 * d_
+        achieved_tf = work.value * (alg / launched) / (total_ms.value * 1e-3) / 1e12 if total_ms.value > 0 else 0.0
+        roofline = {"bound": "mfma", "kernel": "gemm_pp_kernel / gemm_kernel <bf16> (every Linear, conv-as-GEMM and GRU input projection launch)",
+                     "achieved": achieved_tf, "peak": 2500.0, "unit": "TFLOP/s", "frac": achieved_tf / 2500.0,
+                     "traffic": measured_gemm_traffic_per_launch(), "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/" + PMC_SUMMARY + ")",
+                     "launches_per_step": seen.value / max(roofline_steps, 1),
+                     "avg_launch_ms": total_ms.value / max(launches.value, 1),
+                     "timed_launches": launches.value,
+                     "power": power_reading,
+                     "timing": (f"HIP events around every {args.timer_period}. launch of the family on its own stream, " +
+                                (f"taken on a separate pass of {args.roofline_steps} steps AFTER the timed region through a pipeline with ONE "
+                                 f"encoder stream ({roofline_pass_ms:.2f} ms per step there; same engine, inputs and head group, frames checked "
+                                 "equal): the timed region runs two encoder streams, whose co-running launches would each read twice their "
+                                 "own time.  value / ms_per_step / whole_path_tflops / power are the timed region's"
+                                 if roofline_pass_ms is not None else
+                                 "inside the timed region (an event record is a barrier packet: ~6.6 us of stream idle time each)"))}
 
     logmel_ms = None
-    if wave is not None:                      # the log-mel alone on the chip (it overlaps the previous batch's encoder inside the step)
+    if wave is not None and args.full:        # the log-mel alone on the chip (it overlaps the previous batch's encoder inside the step)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
         for a_, b_ in evs:
             a_.record(); log_mel_spectrogram(wave, device=device); b_.record()
@@ -1075,28 +1138,17 @@ def main():
                                     f"{args.encoder_streams} encoder stream(s) + 1 head stream, head over {args.head_group} batches"),
                        "sharding": "clips over ranks, no collective"},
             "whole_path_tflops": total_flops_per_clip(dims.n_audio_state, dims.n_audio_layer) * BATCH * world * args.steps / elapsed / 1e12,
-            "roofline": {"bound": "mfma", "kernel": "gemm_pp_kernel / gemm_kernel <bf16> (every Linear, conv-as-GEMM and GRU input projection launch)",
-                         "achieved": achieved_tf, "peak": 2500.0, "unit": "TFLOP/s", "frac": achieved_tf / 2500.0,
-                         "traffic": measured_gemm_traffic_per_launch(), "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/" + PMC_SUMMARY + ")",
-                         "launches_per_step": seen.value / max(roofline_steps, 1),
-                         "avg_launch_ms": total_ms.value / max(launches.value, 1),
-                         "timed_launches": launches.value,
-                         "power": power_reading,
-                         "timing": (f"HIP events around every {args.timer_period}. launch of the family on its own stream, " +
-                                    (f"taken on a separate pass of {args.roofline_steps} steps AFTER the timed region through a pipeline with ONE "
-                                     f"encoder stream ({roofline_pass_ms:.2f} ms per step there; same engine, inputs and head group, frames checked "
-                                     "equal): the timed region runs two encoder streams, whose co-running launches would each read twice their "
-                                     "own time.  value / ms_per_step / whole_path_tflops / power are the timed region's"
-                                     if roofline_pass_ms is not None else
-                                     "inside the timed region (an event record is a barrier packet: ~6.6 us of stream idle time each)"))},
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if wave is not None:
             out["config"]["input"] = "16 kHz waveform [32, 480000] f32 resident in HBM; device log-mel inside the timed step"
+        if logmel_ms is not None:
             out["logmel_ms_per_step"] = logmel_ms
             out["logmel_launches_per_step"] = 2
             out["logmel_algorithmic_bytes"] = BATCH * (480000 * 4 + 80 * 3000 * 4)
-        if world > 1:
-            out["cpu_baseline"] = None          # the host baseline is timed on rank 0 of the N = 1 run only
+        if world > 1 or not args.full:
+            out["cpu_baseline"] = None          # the host baseline is timed on rank 0 of an N = 1 --full run only
         elif not args.no_cpu_baseline:
             lab_cpu = labels.cpu().numpy()
             base, cpu_res = cpu_baseline(model, mel[:3].cpu().numpy(), [lab_cpu[i, : int(Ls[i])] for i in range(3)], dims.n_audio_head)
@@ -1105,7 +1157,7 @@ def main():
             out["selfcheck"] = chk
             out["cpu_vs_gpu_onset_mae_s"] = chk["onset_mae_s"]
             selfcheck_failed = max(chk["onset_mae_s"], chk["offset_mae_s"]) > SELFCHECK_TOL_S
-        if world == 1 and not args.no_extra_legs and not args.no_overlap and wave is None:
+        if args.full and world == 1 and not args.no_extra_legs and not args.no_overlap and wave is None:
             # the headline dict above is complete; what follows only ADDS keys.  The headline's pipeline buffers go first (the fine-tune
             # leg keeps ~60 GB of activations).
             t_legs = time.perf_counter()

@@ -231,3 +231,30 @@ def test_float32_parity_mode_at_the_headline_size_equals_the_oracle(headline):
           f"{same} of {2 * int(mask.sum())} boundaries equal")
     assert same >= 0.9 * 2 * int(mask.sum())
     eng.check_gru()
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_last_step(headline, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (how every change is timed): set-up, warm-up, K timed steps and the headline keys,
+    with no roofline pass, power sampling, CPU baseline or extra legs (those are --full's).  --dump-outputs writes what the last timed step
+    returned, as float64; its frames are this workload's single-stream result."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    d = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1500:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "bf16" and out["higher_is_better"] is True
+    assert out["unit"] == "audio-sec/sec" and abs(out["value"] - 32 * 30.0 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert out["cpu_baseline"] is None and not {"roofline", "selfcheck", "modes", "other_configs"} & set(out)
+    on, off, score, status = (np.load(d / f"{n}.npy") for n in ("onset", "offset", "score", "status"))
+    assert on.dtype == off.dtype == score.dtype == status.dtype == np.float64
+    assert on.shape == off.shape == headline["ref"][0].shape and score.shape == status.shape == (headline["bench"].BATCH,)
+    assert (status == 0).all() and np.isfinite(score).all()
+    mask = np.arange(headline["labels"].shape[1])[None, :] < headline["Ls"][:, None]
+    assert (on[mask] == headline["ref"][0][mask]).all() and (off[mask] == headline["ref"][1][mask]).all()

@@ -269,7 +269,7 @@ def test_bench_two_ranks_on_one_device_runs_the_multi_rank_control_flow():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -361,7 +361,7 @@ def test_bench_process_group_over_rccl_at_world_size_one(extra):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", *extra]
+           "--no-cpu-baseline", "--full", *extra]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -369,7 +369,7 @@ def test_bench_process_group_over_rccl_at_world_size_one(extra):
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["value"] > 0
     if not extra:
-        # the default run's extra legs (round 6): the other compute modes of the headline workload and BASELINE configs[2..4], measured in the same
+        # the --full run's extra legs (round 6): the other compute modes of the headline workload and BASELINE configs[2..4], measured in the same
         # process after the headline is complete -- present, error-free, and the float32-parity mode ran on the f16x2 GEMM family
         modes, others = out["modes"], out["other_configs"]
         assert modes["f32_parity"]["status_ok"] and modes["f32_parity"]["gemm_family"] == "gemm_f16x2" and modes["f32_parity"]["ms_per_step"] > 0

@@ -825,6 +825,22 @@ def test_bench_gpus_n_without_launcher_becomes_a_launcher_and_touches_no_gpu(mon
     assert "WORLD_SIZE=2" in str(e.value.code)
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: integer frames / status codes are written as exact float64, 16- and 32-bit floats as float32,
+    float64 stays float64; more than 64 MB in all is refused before anything is written."""
+    import bench
+    frames = torch.tensor([[3, 70000], [5, -1]], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "d"), {"onset": frames, "score": torch.tensor([1.5, -2.25], dtype=torch.float64),
+                                             "emb": torch.tensor([0.5, 1.0], dtype=torch.bfloat16), "loss": np.float32([0.25])})
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("onset", "score", "emb", "loss")}
+    assert got["onset"].dtype == np.float64 and got["onset"].tolist() == frames.tolist()
+    assert got["score"].dtype == np.float64 and got["score"].tolist() == [1.5, -2.25]
+    assert got["emb"].dtype == np.float32 and got["emb"].tolist() == [0.5, 1.0] and got["loss"].dtype == np.float32
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros((bench.DUMP_MAX_BYTES // 8 + 1,), dtype=torch.float64)})
+    assert not os.path.exists(tmp_path / "big" / "x.npy")
+
+
 def _hf_whisper(dims, meta: bool):
     from transformers import WhisperConfig, WhisperForConditionalGeneration
     cfg = WhisperConfig(vocab_size=dims.n_vocab, num_mel_bins=dims.n_mels, d_model=dims.n_audio_state, encoder_layers=dims.n_audio_layer,
