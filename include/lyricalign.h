@@ -131,6 +131,9 @@ int la_timer_read_work(double *total_ms, int64_t *timed_launches, double *timed_
  *                                         time out.  0 = off (default)
  *   "x2_inference"    LA_X2_INFERENCE     1 = float32 inference (la_encoder_forward / la_align_head_forward with LA_F32 weights that carry f16x2
  *                                         planes) on the f16 matrix pipe at float32 accuracy (default) | 0 = the float32-MFMA kernels (A/B partner)
+ *   "x2_small"        LA_X2_SMALL         0 = the x2_inference route only where every product fills the 256 x 256 kernel (9 clips on at d = 1024;
+ *                                         default) | 1 = at every batch size: the products outside that kernel's domain run on the 128 x 128
+ *                                         f16x2 kernel (la_gemm_f16x2_small) instead of the float32-MFMA kernel (needs x2_inference = 1)
  * A library built with -DLA_EXPERIMENTS (tools/build_variant.sh; la_has_experiments() == 1) additionally carries the measured-slower
  * kernel structures of rounds 2-4 and their per-launch developer switches; the shipped library has neither. */
 int la_set_option(const char *name, int64_t value);
@@ -503,6 +506,14 @@ int la_split_f16x2_t_tmax(const float *x, int64_t ldx, int32_t rows, int32_t col
                           float *colsum, const uint32_t *tmax, void *stream);
 int la_gemm_f16x2(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
                   float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream);
+/* la_gemm_f16x2 on the 128 x 128 tile, for the products outside the 256 x 256 kernel's domain (few rows: float32 inference at 1-8 clips,
+ * option x2_small).  Same operands, epilogue and `slots` meaning; where both kernels accept a shape with slots = 1 the results are
+ * bit-identical (same f16 MFMA sequence per output element, same epilogue arithmetic).  Domain: M, N >= 1, K / slots a multiple of 32, at
+ * most 64 slots -- else LA_EUNSUPPORTED.  slots = 0: la_gemm_f16x2_small_slots(M, N, K), which fills about 512 workgroups (two per CU)
+ * and keeps at least 256 of K per slot. */
+int la_gemm_f16x2_small(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
+                        float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream);
+int la_gemm_f16x2_small_slots(int32_t M, int32_t N, int32_t K);
 /* la_layernorm (eps 1e-5, statistics in float32 over the row) whose result leaves as the f16x2 planes of the next Linear's operand instead of
  * as float32 rows: planes [rows][2][kp] + inv_scale [rows] as la_split_f16x2 would make them from LN(x) gamma + beta (float32 inference on the
  * f16x2 products: module/align_model.py:72-123 is float32 throughout).  d % 4 == 0, d <= 4096. */

@@ -15,9 +15,13 @@
 //   la_split_f16x2_t   the same of x^T: planes [cols][2][mp] + inverse scales [cols]  (weight-gradient operands: contraction over rows)
 //   la_gemm_f16x2      C = epi((A W^T) o sa sw^T): the 256 x 256 f16 kernel over segmented K (la_gemm_pp.h mainloop_duo_seg_asm),
 //                      scales applied in the epilogue; `slots` > 1 cuts K over batch slots (few tiles, long K), summed in a fixed order
+//   la_gemm_f16x2_small the same contract on the 128 x 128 tile (la_gemm_core.h Cfg<2,2>: 4 waves, two workgroups per CU) for the products
+//                      outside the 256 x 256 kernel's domain (float32 inference at 1-8 clips: option x2_small); same MFMA sequence per
+//                      output element and the same epilogue arithmetic, so bit-identical to la_gemm_f16x2 wherever both run
 #include <algorithm>
 
 #include "la_gemm_core.h"
+#include "la_gemm_epilogue.h"
 #include "la_gemm_params.h"
 
 using namespace la::gemm;
@@ -486,6 +490,232 @@ extern "C" int la_gemm_f16x2(int32_t M, int32_t N, int32_t K, int32_t slots, con
     p.ln_stats = sa; p.ln_csum = sw;
     const int rc = launch_x2_f16(p, slots, stream);
     if (rc != LA_OK || slots == 1) return rc;
+    const int64_t total = (int64_t)M * N;
+    hipLaunchKernelGGL(x2_reduce_kernel, dim3((unsigned)la::cdiv(total, (int64_t)256)), dim3(256), 0, stream, out, slots, M, N, C, ldc, bias,
+                       residual, ldr, epilogue);
+    LA_LAUNCH_CHECK();
+    return LA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// la_gemm_f16x2_small: the segmented-K product on the 128 x 128 tile.  K is walked in the order of the 256 x 256 kernel (duo_stage_src):
+// sub-stage s (32 elements of K, 64 B per row) = chunk s / 3, product s % 3 = (a_lo, w_hi), (a_hi, w_lo), (a_hi, w_hi).  One LDS stage of
+// la_gemm_core.h (128 rows x 128 B per operand) holds two consecutive sub-stages: its 16-byte slots 0-3 come from sub-stage 2 kt, slots
+// 4-7 from 2 kt + 1 (the source-side swizzle of stage_tile picks, per lane, which of the two it fetches).  Fragment reads and MFMAs are
+// those of the 16-bit 128 x 128 kernel (ks = 0, 1 = the two sub-stages), so every output element sees v_mfma_f32_16x16x32_f16 over the
+// same k groups, lanes and operand order as in the 256 x 256 kernel, from a zero accumulator, in the same sequence: identical bits.
+// K / slots a multiple of 32: an odd number of sub-stages leaves the last stage's second half unloaded and uncomputed.
+namespace {
+
+typedef Cfg<2, 2> SmallX2;
+
+// byte offset inside an operand row of sub-stage s: plane (lo: + plane bytes) and chunk column
+__device__ __forceinline__ unsigned x2s_off(int s, bool is_w, unsigned plane_bytes) {
+    const int col = s / 3, seg = s - 3 * col;
+    const bool lo = is_w ? seg == 1 : seg == 0;                   // A: lo, hi, hi;  W: hi, lo, hi
+    return (lo ? plane_bytes : 0u) + (unsigned)col * 64u;
+}
+
+// 128 rows of one operand, sub-stages s0 (slots 0-3) and s1 (slots 4-7): 4 wave instructions of 8 rows x 128 B per wave
+__device__ __forceinline__ void x2s_stage(const unsigned char *src, int64_t ld_bytes, int row0, int last_row, unsigned off0, unsigned off1,
+                                          unsigned char *lds_tile, int wave, int lane) {
+    const int r8 = lane >> 3, slot = lane & 7;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int piece = wave * 4 + i;
+        const int rt = piece * 8 + r8;
+        int row = row0 + rt;
+        row = row > last_row ? last_row : row;
+        const int ls = slot ^ swz(rt);                            // the logical 16-byte slot this lane's LDS position holds
+        const unsigned off = (ls < 4 ? off0 : off1) + (unsigned)(ls & 3) * 16u;
+        la::glds16(src + (int64_t)row * ld_bytes + off, lds_tile + piece * 1024);
+    }
+}
+
+__global__ __launch_bounds__(SmallX2::THREADS, 2) void gemm_f16x2_small_kernel(GemmParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int nwg = p.tiles_m * p.tiles_n;
+    const int tile = xcd_remap(blockIdx.x, nwg);
+    const TileCoord tc = tile_coord(tile, p.tiles_m, p.tiles_n, p.group);
+    const int m0 = tc.tm * SmallX2::TM, n0 = tc.tn * BN;
+    const int z = blockIdx.y;
+    const unsigned char *A = reinterpret_cast<const unsigned char *>(p.A) + (int64_t)z * p.strideA * 2;
+    const unsigned char *W = reinterpret_cast<const unsigned char *>(p.W) + (int64_t)z * p.strideW * 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 15, q = lane >> 4;
+    const int64_t lda_b = p.lda * 2, ldw_b = p.ldw * 2;
+    const unsigned pa = (unsigned)(p.plane_a * 2), pw = (unsigned)(p.plane_w * 2);
+    const int nsub = 3 * (p.K / 32), nk = (nsub + 1) / 2;
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto stage = [&](int kt, int buf) {
+        unsigned char *st = lds + buf * SmallX2::STAGE;
+        const int s0 = 2 * kt, s1 = 2 * kt + 1 < nsub ? 2 * kt + 1 : s0;     // (an odd tail re-reads s0: never computed)
+        x2s_stage(A, lda_b, m0, p.M - 1, x2s_off(s0, false, pa), x2s_off(s1, false, pa), st, wave, lane);
+        x2s_stage(W, ldw_b, n0, p.N - 1, x2s_off(s0, true, pw), x2s_off(s1, true, pw), st + SmallX2::TM * BKB, wave, lane);
+    };
+    auto compute = [&](int buf, bool second) {
+        const unsigned char *st = lds + buf * SmallX2::STAGE;
+        const unsigned char *at = st + (wm * 64) * BKB;
+        const unsigned char *wt = st + SmallX2::TM * BKB + (wn * 64) * BKB;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            if (ks == 1 && !second) break;
+            uint4 af[4], wf[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                af[i] = read_frag(at, i * 16 + r, ks * 4 + q);
+                wf[i] = read_frag(wt, i * 16 + r, ks * 4 + q);
+            }
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) Mma<_Float16>::run(wf[ni], af[mi], acc[mi][ni]);
+        }
+    };
+    // the two-stage form of la_gemm_core.h mainloop (two workgroups per CU cover each other's barriers)
+    stage(0, 0);
+    wait_vmcnt<0>();
+    __syncthreads();
+    int cur = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) stage(kt + 1, cur ^ 1);
+        compute(cur, 2 * kt + 1 < nsub);
+        wait_vmcnt<0>();
+        __syncthreads();
+        cur ^= 1;
+    }
+
+    // epilogue in the accumulator layout (a lane holds 4 consecutive columns of one row: epi_quad's quad): scales, bias, GELU as the 256 x 256
+    // kernel's epi_quad<true, 6>; then the residual on the row-major store path of the 128 x 128 kernel
+    float *C = reinterpret_cast<float *>(p.C) + (int64_t)z * p.strideC;
+    const float *R = p.residual;
+    const bool has_bias = (p.epilogue & LA_EPI_BIAS) && p.bias;
+    const bool do_gelu = p.epilogue & LA_EPI_GELU;
+    const bool do_res = (p.epilogue & LA_EPI_RESIDUAL) && R;
+    const bool gelu_grad = p.epilogue & LA_EPI_RES_GELU_GRAD;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+        const int n = n0 + wn * 64 + ni * 16 + q * 4;
+        float b4[4], cs4[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            b4[j] = has_bias ? p.bias[min(n + j, p.N - 1)] : 0.f;
+            cs4[j] = p.ln_csum[min(n + j, p.N - 1)];
+        }
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const float2 st = make_float2(0.f, p.ln_stats[min(m0 + wm * 64 + mi * 16 + r, p.M - 1)]);
+            epi_quad<true, 6>(acc[mi][ni], b4, cs4, st, has_bias, do_gelu, p.epilogue);
+        }
+    }
+    constexpr int PITCH = 272;
+    unsigned char *reg = lds + wave * (32 * PITCH);              // (the loop ended behind a barrier: the stages are dead)
+    const int wrow0 = m0 + wm * 64, wcol0 = n0 + wn * 64;
+    const bool fast_c = (p.ldc % 4 == 0) && ((uintptr_t)C % 16 == 0);
+    const bool fast_r = do_res && (p.ldr % 4 == 0) && ((uintptr_t)R % 16 == 0);
+    const bool interior = wrow0 + 64 <= p.M && wcol0 + 64 <= p.N && fast_c && (!do_res || fast_r);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                *reinterpret_cast<f32x4 *>(reg + (mm * 16 + r) * PITCH + (ni * 16 + q * 4) * 4) = acc[2 * h + mm][ni];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int rl = it * 4 + q;
+            const int m = wrow0 + h * 32 + rl, n = wcol0 + r * 4;
+            f32x4 v = *reinterpret_cast<const f32x4 *>(reg + rl * PITCH + r * 16);
+            if (interior) {
+                if (do_res) {
+                    const float4 t = *reinterpret_cast<const float4 *>(R + (int64_t)m * p.ldr + n);
+                    if (gelu_grad) {
+                        v[0] *= la::gelu_erf_grad(t.x); v[1] *= la::gelu_erf_grad(t.y); v[2] *= la::gelu_erf_grad(t.z); v[3] *= la::gelu_erf_grad(t.w);
+                    } else { v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+                }
+                *reinterpret_cast<float4 *>(C + (int64_t)m * p.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
+                continue;
+            }
+            if (m >= p.M || n >= p.N) continue;
+            const int nv = min(4, p.N - n);
+            if (do_res) {
+                const float *rr = R + (int64_t)m * p.ldr + n;
+                for (int j = 0; j < nv; ++j) v[j] = gelu_grad ? v[j] * la::gelu_erf_grad(rr[j]) : v[j] + rr[j];
+            }
+            float *c = C + (int64_t)m * p.ldc + n;
+            for (int j = 0; j < nv; ++j) c[j] = v[j];
+        }
+    }
+}
+
+}  // namespace
+
+// Split-K slots of the 128 x 128 f16x2 product (slots = 0): the float32 la_gemm split-K rule's counterpart (la_gemm.hip), sized for TWO
+// workgroups per CU -- double the slots while the grid stays within ~512 workgroups (256 CUs x 2; up to 640 keeps M = 1500 rows x
+// N = 3072 at 2 and N = 1024 at 4) and every slot keeps at least 256 of K (a multiple of 32).  At M = 1500: QKV 2, out-proj 4, MLP-up 1,
+// MLP-down 4, GRU input projection (N = 2304) 2.
+extern "C" int la_gemm_f16x2_small_slots(int32_t M, int32_t N, int32_t K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 1;
+    const int64_t tiles = (int64_t)la::cdiv(M, 128) * la::cdiv(N, 128);
+    int S = 1;
+    while (S < 16 && tiles * S * 2 <= 640 && K % (S * 2 * 32) == 0 && K / (S * 2) >= 256) S *= 2;
+    return S;
+}
+
+extern "C" int la_gemm_f16x2_small(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
+                                   float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream_) {
+    if (M == 0 || N == 0) return LA_OK;
+    LA_CHECK_ARG(A && sa && W && sw && C, "gemm_f16x2_small: null pointer");
+    LA_CHECK_ARG(M > 0 && N > 0 && K > 0 && slots >= 0, "gemm_f16x2_small: bad sizes");
+    LA_CHECK_ARG((epilogue & ~(LA_EPI_BIAS | LA_EPI_GELU | LA_EPI_RESIDUAL | LA_EPI_RES_GELU_GRAD)) == 0,
+                 "gemm_f16x2_small: epilogue takes BIAS, GELU, RESIDUAL, RES_GELU_GRAD only");
+    LA_CHECK_ARG(!(epilogue & LA_EPI_RES_GELU_GRAD) || (epilogue & LA_EPI_RESIDUAL), "gemm_f16x2_small: RES_GELU_GRAD reads the residual operand (set RESIDUAL too)");
+    LA_CHECK_ARG(!(epilogue & LA_EPI_BIAS) || bias, "gemm_f16x2_small: bias epilogue without pointer");
+    LA_CHECK_ARG(!(epilogue & LA_EPI_RESIDUAL) || residual, "gemm_f16x2_small: residual epilogue without pointer");
+    LA_CHECK_ARG((uintptr_t)A % 16 == 0 && (uintptr_t)W % 16 == 0, "gemm_f16x2_small: planes must be 16-byte aligned");
+    LA_CHECK_ARG(ldc >= N && (!(epilogue & LA_EPI_RESIDUAL) || ldr >= N), "gemm_f16x2_small: row pitches must cover N");
+    if (slots == 0) slots = la_gemm_f16x2_small_slots(M, N, K);
+    if (K % slots != 0 || (K / slots) % 32 != 0 || slots > 64) {
+        la::set_error("gemm_f16x2_small: M=%d N=%d K=%d slots=%d outside the 128x128 kernel's domain (K / slots a multiple of 32, at most 64 slots)",
+                      M, N, K, slots);
+        return LA_EUNSUPPORTED;
+    }
+    const int Kc = K / slots;
+    hipStream_t stream = (hipStream_t)stream_;
+    float *out = C;
+    int64_t out_ld = ldc, out_stride = 0;
+    int epi = epilogue;
+    if (slots > 1) {
+        out = static_cast<float *>(la::stream_scratch(stream, la::SCRATCH_SPLITK, (size_t)slots * M * N * sizeof(float)));
+        if (!out) { la::set_error("gemm_f16x2_small: split-K scratch allocation failed"); return LA_EHIP; }
+        out_ld = N; out_stride = (int64_t)M * N;
+        epi = 0;                                       // bias / activation / residual after the slots are summed
+    }
+    const int tiles_n = la::cdiv(N, BN);
+    GemmParams p{M, N, Kc, A, (int64_t)2 * K, (int64_t)Kc, W, (int64_t)2 * K, (int64_t)Kc, out, out_ld, out_stride,
+                 slots > 1 ? nullptr : bias, 0, slots > 1 ? nullptr : residual, ldr, 0, epi, la::cdiv(M, SmallX2::TM), tiles_n,
+                 pick_group(2 * Kc, 2, tiles_n)};
+    p.plane_a = K; p.plane_w = K;
+    p.ln_stats = sa; p.ln_csum = sw;
+    {
+        static la::DeviceOnce attr_once;
+        if (attr_once.pending()) {
+            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16x2_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SmallX2::LDS));
+            attr_once.mark();
+        }
+        // its own timer family (exact-name matching: "gemm_f16x2" counts the 256 x 256 kernel only), at the algorithmic flops as there
+        la::TimerScope ts("gemm_f16x2_small", stream, 2.0 * M * N * (double)K);
+        hipLaunchKernelGGL(gemm_f16x2_small_kernel, dim3(p.tiles_m * p.tiles_n, slots), dim3(SmallX2::THREADS), SmallX2::LDS, stream, p);
+        LA_LAUNCH_CHECK();
+    }
+    if (slots == 1) return LA_OK;
     const int64_t total = (int64_t)M * N;
     hipLaunchKernelGGL(x2_reduce_kernel, dim3((unsigned)la::cdiv(total, (int64_t)256)), dim3(256), 0, stream, out, slots, M, N, C, ldc, bias,
                        residual, ldr, epilogue);

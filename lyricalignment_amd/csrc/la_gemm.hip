@@ -309,6 +309,8 @@ static int gemm_run_ldw(int dtype, int M, int N, int K, int batch, const void *A
     // float32 (training / parity mode) with few tiles and a long K -- the text decoder's 80-row GEMMs are 8 tiles on 256 CUs,
     // each a serial K = 1024..4096 walk: K is cut into S equal chunks that run as S batch slots of the same kernel into a
     // partial-sum buffer, and a second kernel adds them in a fixed order and applies the epilogue.
+    // (The 128 x 128 f16x2 product's rule, la_gemm_f16x2_small_slots in la_f32x2.hip, is the same doubling sized for TWO workgroups per CU:
+    //  up to ~512 workgroups, >= 256 of K per slot.)
     if (batch == 1) {
         const int tiles = la::cdiv(M, Small::TM) * la::cdiv(N, BN);
         // S: chunks of whole 32-element k-steps, the last one may be shorter.  Few tiles -> fill the chip (<= 256 workgroups);

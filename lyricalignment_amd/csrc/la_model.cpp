@@ -35,18 +35,32 @@ struct EncBufs {
     size_t total;
 };
 
+// la_gemm_f16x2's domain at slots = 1 (the 256 x 256 kernel): K a multiple of 128 and >= 256, N > 128, >= 192 tiles
+bool x2_big_ok(int64_t M, int N, int K) { return K % 128 == 0 && K >= 256 && N > 128 && la::cdiv(M, 256) * la::cdiv(N, 256) >= 192; }
+
 // Does the float32 encoder run its blocks on the f16 matrix pipe (la_gemm_f16x2 + la_layernorm_f16x2 + la_attention_lse_f16x2)?  The blocks
 // carry the weight planes, the option is on, and every Linear of a block lies in the 256 x 256 kernel's domain: >= 192 tiles for the narrowest
-// (N = d), K = d a multiple of 128 and >= 256.
+// (N = d), K = d a multiple of 128 and >= 256.  With option x2_small at every batch size: the products outside that domain run on the
+// 128 x 128 f16x2 kernel (x2_gemm), which takes any d that is a multiple of 32.
 bool encoder_x2(const la_encoder_weights *w, int batch) {
     if ((w->dtype & 0xff) != LA_F32 || w->n_layer < 1 || !la::opts().x2_inference) return false;
     const int d = w->d;
-    if (d % 128 != 0 || d < 256 || d > 1024 * 4) return false;
+    const bool small = la::opts().x2_small != 0;
+    if (small ? (d % 32 != 0 || d > 1024 * 4) : (d % 128 != 0 || d < 256 || d > 1024 * 4)) return false;
     for (int l = 0; l < w->n_layer; ++l) {
         const la_encoder_block &k = w->blocks[l];
         if (!(k.wqkv_x2 && k.wqkv_x2s && k.wo_x2 && k.wo_x2s && k.w1_x2 && k.w1_x2s && k.w2_x2 && k.w2_x2s)) return false;
     }
-    return la::cdiv((int64_t)batch * N_CTX, 256) * la::cdiv(d, 256) >= 192;
+    return small || la::cdiv((int64_t)batch * N_CTX, 256) * la::cdiv(d, 256) >= 192;
+}
+
+// One f16x2 product of the float32 routes: the 256 x 256 kernel wherever the shape lies in its domain, else (option x2_small) the 128 x 128
+// kernel with its own split-K rule (slots = 0; split-K partial sums in the library's stream scratch, as float32 la_gemm's).  engine.py
+// _x2_gemm makes the same choice.
+int x2_gemm(int M, int N, int K, const void *A, const float *sa, const void *W, const float *sw, float *C, int64_t ldc, const float *bias,
+            const float *residual, int64_t ldr, int epilogue, hipStream_t stream) {
+    if (x2_big_ok(M, N, K)) return la_gemm_f16x2(M, N, K, 1, A, sa, W, sw, C, ldc, bias, residual, ldr, epilogue, stream);
+    return la_gemm_f16x2_small(M, N, K, 0, A, sa, W, sw, C, ldc, bias, residual, ldr, epilogue, stream);
 }
 
 EncBufs carve_encoder(void *ws, int dtype, int batch, int d, bool x2 = false, int n_head = 0) {
@@ -173,15 +187,15 @@ extern "C" int la_encoder_forward(const la_encoder_weights *w, const float *mel,
             // (no float32 copy), the MLP's gelu(u) is applied inside its operand split, the residual adds stay in the float32 stream b.x.
             float *qkv = static_cast<float *>(b.qkv), *att = static_cast<float *>(b.att), *u = static_cast<float *>(b.u);
             LA_TRY(la_layernorm_f16x2(b.x, d, M, d, k.ln1_g, k.ln1_b, b.pl_d, d, b.inv, stream));
-            LA_TRY(la_gemm_f16x2(M, 3 * d, d, 1, b.pl_d, b.inv, k.wqkv_x2, k.wqkv_x2s, qkv, 3 * d, k.bqkv, nullptr, 0, LA_EPI_BIAS, stream));
+            LA_TRY(x2_gemm(M, 3 * d, d, b.pl_d, b.inv, k.wqkv_x2, k.wqkv_x2s, qkv, 3 * d, k.bqkv, nullptr, 0, LA_EPI_BIAS, stream));
             LA_TRY(la_attention_lse_f16x2(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, batch, N_CTX, N_CTX, w->n_head, 0, nullptr, b.attn_ws,
                                           b.attn_ws_bytes, stream));
             LA_TRY(la_split_f16x2(att, d, M, d, b.pl_d, d, b.inv, stream));
-            LA_TRY(la_gemm_f16x2(M, d, d, 1, b.pl_d, b.inv, k.wo_x2, k.wo_x2s, b.x, d, k.bo, b.x, d, LA_EPI_BIAS | LA_EPI_RESIDUAL, stream));
+            LA_TRY(x2_gemm(M, d, d, b.pl_d, b.inv, k.wo_x2, k.wo_x2s, b.x, d, k.bo, b.x, d, LA_EPI_BIAS | LA_EPI_RESIDUAL, stream));
             LA_TRY(la_layernorm_f16x2(b.x, d, M, d, k.ln2_g, k.ln2_b, b.pl_d, d, b.inv, stream));
-            LA_TRY(la_gemm_f16x2(M, 4 * d, d, 1, b.pl_d, b.inv, k.w1_x2, k.w1_x2s, u, 4 * d, k.b1, nullptr, 0, LA_EPI_BIAS, stream));
+            LA_TRY(x2_gemm(M, 4 * d, d, b.pl_d, b.inv, k.w1_x2, k.w1_x2s, u, 4 * d, k.b1, nullptr, 0, LA_EPI_BIAS, stream));
             LA_TRY(la_split_f16x2_act(u, 4 * d, M, 4 * d, b.pl_u, 4 * d, b.inv, 1 /* exact-erf GELU */, stream));
-            LA_TRY(la_gemm_f16x2(M, d, 4 * d, 1, b.pl_u, b.inv, k.w2_x2, k.w2_x2s, b.x, d, k.b2, b.x, d, LA_EPI_BIAS | LA_EPI_RESIDUAL, stream));
+            LA_TRY(x2_gemm(M, d, 4 * d, b.pl_u, b.inv, k.w2_x2, k.w2_x2s, b.x, d, k.b2, b.x, d, LA_EPI_BIAS | LA_EPI_RESIDUAL, stream));
         } else {
             LA_TRY(la_layernorm(b.x, d, M, d, k.ln1_g, k.ln1_b, b.h, d, dt, stream));
             LA_TRY(la_gemm(dt, M, 3 * d, d, 1, b.h, d, 0, k.wqkv, b.qkv, 3 * d, 0, k.bqkv, nullptr, 0, 0, LA_EPI_BIAS, stream));
@@ -224,8 +238,8 @@ struct HeadBufs {
 bool head_x2(const la_head_weights *w) {
     return w->dtype == LA_F32 && la::opts().x2_inference && w->w_ih_x2[0] && w->w_ih_x2s[0] && w->w_ih_x2[1] && w->w_ih_x2s[1] && w->w_fc_x2 && w->w_fc_x2s;
 }
-// one input projection [rows][K] x [6H][K]^T in la_gemm_f16x2's domain?
-bool proj_x2_ok(int64_t rows, int K, int H) { return K % 128 == 0 && K >= 256 && la::cdiv(rows, 256) * la::cdiv(6 * H, 256) >= 192; }
+// one input projection [rows][K] x [6H][K]^T in la_gemm_f16x2's domain -- or, with option x2_small, in la_gemm_f16x2_small's (x2_gemm picks)?
+bool proj_x2_ok(int64_t rows, int K, int H) { return x2_big_ok(rows, 6 * H, K) || (la::opts().x2_small && K % 32 == 0); }
 
 int carve_head(void *ws, const la_head_weights *w, int batch, int frames, int max_labels, HeadBufs *b) {
     Carve c(ws);
@@ -303,8 +317,8 @@ extern "C" int la_align_head_forward(const la_head_weights *w, const void *feats
                         LA_TRY(la_split_f16x2(xf + (int64_t)c * stride_a, lda, frames, in_dim, static_cast<unsigned char *>(b.planes) + (size_t)c * frames * 2 * in_dim * 2,
                                               in_dim, b.inv + (size_t)c * frames, stream));
                 }
-                LA_TRY(la_gemm_f16x2(nb * frames, 6 * H, in_dim, 1, b.planes, b.inv, w->w_ih_x2[layer], w->w_ih_x2s[layer], b.gi, 6 * H, w->b_ih[layer],
-                                     nullptr, 0, LA_EPI_BIAS, stream));
+                LA_TRY(x2_gemm(nb * frames, 6 * H, in_dim, b.planes, b.inv, w->w_ih_x2[layer], w->w_ih_x2s[layer], b.gi, 6 * H, w->b_ih[layer],
+                               nullptr, 0, LA_EPI_BIAS, stream));
             } else
             LA_TRY(la_gemm(dt, frames, 6 * H, in_dim, nb, x, lda, stride_a, w->w_ih[layer], b.gi, 6 * H, (int64_t)frames * 6 * H, w->b_ih[layer],
                            nullptr, 0, 0, LA_EPI_BIAS | out_f32, stream));

@@ -60,7 +60,7 @@ const OptionDesc kOptions[] = {
     {"gru_handoff", "LA_GRU_HANDOFF", &Options::gru_handoff, false}, {"gru_poll_delay", "LA_GRU_POLL_DELAY", &Options::gru_poll_delay, false},
     {"viterbi_dpp", "LA_VITERBI_NO_DPP", &Options::viterbi_dpp, true}, {"head_clip_cap", "LA_HEAD_CLIP_CAP", &Options::head_clip_cap, false},
     {"ln_fusion", "LA_LN_FUSION", &Options::ln_fusion, false},       {"resid_split", "LA_RESID_SPLIT", &Options::resid_split, false},
-    {"x2_inference", "LA_X2_INFERENCE", &Options::x2_inference, false},
+    {"x2_inference", "LA_X2_INFERENCE", &Options::x2_inference, false}, {"x2_small", "LA_X2_SMALL", &Options::x2_small, false},
     {"gru_timeout_us", "LA_GRU_TIMEOUT_US", &Options::gru_timeout_us, false}, {"gru_fault_step", "LA_GRU_FAULT_STEP", &Options::gru_fault_step, false},
 };
 }  // namespace

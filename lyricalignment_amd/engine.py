@@ -89,6 +89,21 @@ def _x2_domain(M: int, N: int, K: int) -> bool:
     return K % 128 == 0 and K >= 256 and N > 128 and -(-M // 256) * -(-N // 256) >= 192
 
 
+def x2_small_on() -> bool:
+    """Library option "x2_small" (include/lyricalign.h): the x2_inference route at every batch size, the products outside the 256 x 256 kernel's
+    domain on the 128 x 128 f16x2 kernel."""
+    return _lib.get_option("x2_small") != 0
+
+
+def _x2_gemm(a, w, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One f16x2 product of the float32 routes, on the kernel la_model.cpp x2_gemm picks: the 256 x 256 one in its domain, else the 128 x 128 one
+    with its own split-K rule (option x2_small)."""
+    from . import f32x2
+    if _x2_domain(a.rows, w.rows, a.kp):
+        return f32x2.gemm(a, w, out=out, bias=bias, residual=residual)
+    return f32x2.gemm_small(a, w, out=out, bias=bias, residual=residual)
+
+
 def _x2_linear(x: torch.Tensor, w_x2: Tuple[torch.Tensor, torch.Tensor], bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
                residual: Optional[torch.Tensor] = None, x_planes=None) -> torch.Tensor:
     """out [M, N] f32 = x [M, K] f32 (or its ready planes) . w^T + bias (+ residual) with w as packed f16x2 planes: three f16 products at float32 accuracy."""
@@ -96,7 +111,7 @@ def _x2_linear(x: torch.Tensor, w_x2: Tuple[torch.Tensor, torch.Tensor], bias: O
     planes, inv = w_x2
     N, _, K = planes.shape
     a = x_planes if x_planes is not None else f32x2.split(x, K)
-    return f32x2.gemm(a, f32x2.Planes(planes, inv, N, K, K), out=out, bias=bias, residual=residual)
+    return _x2_gemm(a, f32x2.Planes(planes, inv, N, K, K), out=out, bias=bias, residual=residual)
 
 
 # LA_X2_PACK=0: float32 engines are packed without the f16x2 planes of their weights (every float32 product stays on the float32-MFMA
@@ -408,17 +423,17 @@ class AlignEngine:
                     ops.gemm(u, blk.w2, x, bias=blk.b2, residual=x, out_f32=True, out16=h, ln_part=part)     # x += mlp; h = bf16(x)
                 row_stats()
         elif (dt == torch.float32 and e.blocks and all(b_.x2 is not None for b_ in e.blocks) and x2_inference_on() and d <= 4096
-              and -(-M // 256) * -(-d // 256) >= 192):
+              and (-(-M // 256) * -(-d // 256) >= 192 or (x2_small_on() and d % 32 == 0))):
             # float32 on the f16 matrix pipe at float32 accuracy: la_encoder_forward's x2 route, spelled out over the op-level calls
             from . import f32x2
             pl = lambda t: f32x2.Planes(t[0], t[1], t[0].shape[0], t[0].shape[2], t[0].shape[2])
             for blk in e.blocks:
                 wq, wo_, w1_, w2_ = (pl(t) for t in blk.x2)
-                f32x2.gemm(f32x2.layernorm_split(x, blk.ln1_g, blk.ln1_b), wq, out=qkv, bias=blk.bqkv)
+                _x2_gemm(f32x2.layernorm_split(x, blk.ln1_g, blk.ln1_b), wq, out=qkv, bias=blk.bqkv)
                 ops.attention_ex(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], B, N_CTX, N_CTX, e.n_head, out=att, x2=True)
-                f32x2.gemm(f32x2.split(att, d), wo_, out=x, bias=blk.bo, residual=x)
-                f32x2.gemm(f32x2.layernorm_split(x, blk.ln2_g, blk.ln2_b), w1_, out=u, bias=blk.b1)
-                f32x2.gemm(f32x2.split(u, 4 * d, act="gelu"), w2_, out=x, bias=blk.b2, residual=x)
+                _x2_gemm(f32x2.split(att, d), wo_, out=x, bias=blk.bo, residual=x)
+                _x2_gemm(f32x2.layernorm_split(x, blk.ln2_g, blk.ln2_b), w1_, out=u, bias=blk.b1)
+                _x2_gemm(f32x2.split(u, 4 * d, act="gelu"), w2_, out=x, bias=blk.b2, residual=x)
         else:
             for blk in e.blocks:
                 ops.layernorm(x, blk.ln1_g, blk.ln1_b, dt, out=h)
@@ -653,8 +668,18 @@ class AlignEngine:
         for layer in range(n_layers):
             gi = self._get("gi", (Bbuf, T, 2, 3 * H), torch.float32)[:B]
             K = hw.w_ih[layer].shape[1]
+            small = hw.w_ih_x2 is not None and K % 32 == 0 and x2_inference_on() and x2_small_on()
             if (hw.w_ih_x2 is not None and stride_a == T * lda and lda == K and _x2_domain(B * T, 6 * H, K) and x2_inference_on()):
                 _x2_linear(x[: B * T] if x.dim() == 2 else x.view(-1, K)[: B * T], hw.w_ih_x2[layer], hw.b_ih[layer], out=gi.view(B * T, 6 * H))
+            elif small and x.dim() == 2 and x.stride(1) == 1:
+                # (option x2_small: la_align_head_forward's proj_x2_ok -- the clips' rows split clip by clip where they are not adjacent)
+                from . import f32x2
+                if stride_a == T * lda:
+                    a = f32x2.split(x[: B * T, :K], K)
+                else:
+                    parts = [f32x2.split(x[c * feat_clip_stride: c * feat_clip_stride + T, :K], K) for c in range(B)]
+                    a = f32x2.Planes(torch.cat([p_.planes for p_ in parts]), torch.cat([p_.inv_scale for p_ in parts]), B * T, K, K)
+                _x2_linear(None, hw.w_ih_x2[layer], hw.b_ih[layer], out=gi.view(B * T, 6 * H), x_planes=a)
             else:
                 ops.gemm(x, hw.w_ih[layer], gi.view(B * T, 6 * H), bias=hw.b_ih[layer], out_f32=True, M=T, lda=lda, batch=B,
                          stride_a=stride_a, stride_c=T * 6 * H, ldc=6 * H)

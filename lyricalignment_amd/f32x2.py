@@ -187,6 +187,43 @@ def gemm(a: Planes, w: Planes, out: Optional[torch.Tensor] = None, bias: Optiona
     return out
 
 
+def slots_small(M: int, N: int, K: int) -> int:
+    """Split-K slots gemm_small takes by default (la_gemm_f16x2_small_slots): about 512 workgroups of 128 x 128 (two per CU), at least 256 of
+    K per slot."""
+    return int(lib().la_gemm_f16x2_small_slots(M, N, K))
+
+
+def gemm_small(a: Planes, w: Planes, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None, gelu: bool = False, gelu_grad_of: Optional[torch.Tensor] = None,
+               slots: Optional[int] = None) -> torch.Tensor:
+    """gemm on the 128 x 128 f16x2 kernel (la_gemm_f16x2_small): the same arguments and result, for the products outside the 256 x 256
+    kernel's domain (any M, N; plane length / slots a multiple of 32).  slots None = slots_small(M, N, K); where both kernels take a
+    shape with slots = 1 the bits equal gemm's."""
+    if a.kp != w.kp:
+        raise ValueError(f"f32x2.gemm_small: operands were split to different plane lengths ({a.kp}, {w.kp})")
+    M, N = a.rows, w.rows
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.planes.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (M, N):
+        raise ValueError(f"f32x2.gemm_small: out must be a float32 [{M}, {N}] row view")
+    epi = 0
+    if bias is not None:
+        epi |= _lib.EPI_BIAS
+    if gelu_grad_of is not None:
+        if residual is not None:
+            raise ValueError("f32x2.gemm_small: gelu_grad_of takes the residual operand's place")
+        residual = gelu_grad_of
+        epi |= _lib.EPI_RES_GELU_GRAD
+    if residual is not None:
+        epi |= _lib.EPI_RESIDUAL
+    if gelu:
+        epi |= _lib.EPI_GELU
+    check(lib().la_gemm_f16x2_small(M, N, a.kp, 0 if slots is None else int(slots), ptr(a.planes), ptr(a.inv_scale), ptr(w.planes),
+                                    ptr(w.inv_scale), ptr(out), out.stride(0), ptr(bias), ptr(residual),
+                                    residual.stride(0) if residual is not None else 0, epi, stream_ptr()), "gemm_f16x2_small")
+    return out
+
+
 def _plain2d(t: torch.Tensor) -> bool:
     return t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
 
