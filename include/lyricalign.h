@@ -184,6 +184,48 @@ int la_viterbi_core(const float *em, int64_t em_row_stride, const int32_t *label
                     double *dp, long long *bt, int32_t *scratch_i32, double *scratch_f64,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
+ * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
+ * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable
+ * cells weigh zero.  With alpha / beta the forward / backward log-sums (both including e_t(k)) and
+ * log_z = logsumexp(alpha_{T-1}(S-1), alpha_{T-1}(S-2)):
+ *   gamma_t(k) = exp(alpha_t(k) + beta_t(k) - e_t(k) - log_z)          P(the path is in state k at frame t)
+ *   entry_t(n) = P(frame t is the FIRST frame of label n),  exit_t(n) = P(frame t is its LAST frame)
+ * em, labels, n_labels, n_frames as la_viterbi_batch; onset / offset are la_viterbi_batch's outputs for the same
+ * emissions (device, row pitch out_stride); boundary_window = w >= 0 frames.  Outputs ([batch][out_stride] float32):
+ *   occupancy[b][n]   = mean over t in [onset, offset) of gamma_t(2n+1): the share of the model's belief that the
+ *                       reported segment is this character
+ *   onset_prob[b][n]  = sum of entry_t(n) over |t - onset| <= w;  offset_prob[b][n] = sum of exit_t(n) over
+ *                       |t - (offset - 1)| <= w: probability that the boundary lies within w frames of the reported one
+ *   log_z[b] (float64): final_score[b] - log_z[b] <= 0 is the log-posterior of the reported path
+ *   gamma_out (optional, NULL = none) [batch][max_frames][>= 2 max_labels + 1] float32, strides in elements:
+ *                       gamma_t(k), zero outside T_b / S_b
+ *   status[b] = LA_OK; LA_EEMPTY (no labels); LA_EINFEASIBLE (log_z = -inf: no path, T_b too short for the labels);
+ *               LA_EINVAL (T_b / L_b outside max_frames / max_labels).  Rows of failed utterances, rows n >= L_b and
+ *               labels with onset < 0 are written as 0; log_z of a failed utterance is 0 (-inf when infeasible).
+ * These are posteriors UNDER THE MODEL, comparable between utterances; they are not measured accuracies.
+ * Scores are float64; a step's log-sum-exp takes its maximum in float64 and its correction (in [0, ln 3]) in float32:
+ * every probability and log_z within 8 T 2^-23 absolute of a float64 evaluation (measured: DESIGN.md).
+ * `workspace` (8-byte aligned, always needed) holds the alpha rows: batch * max_frames * S_pad * 8 bytes, S_pad = 64 *
+ * the smallest power of two of waves that holds 2 max_labels + 1 states (25 MB for 32 clips of 1500 frames and up to
+ * 31 labels).  Limit: max_labels <= 511 (one lane per lattice state, 1024 states per workgroup; the CTC loss's limit),
+ * LA_EUNSUPPORTED above.  Argument errors are answered on the host before anything is enqueued.  Option viterbi_dpp = 0
+ * also pins this kernel's LDS-exchange form for lattices of at most 64 states.
+ */
+int la_alignment_posteriors_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                            const int32_t *labels, int32_t labels_stride,
+                            const int32_t *n_labels, const int32_t *n_frames,
+                            int32_t batch, int32_t max_frames, int32_t max_labels,
+                            const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                            int32_t boundary_window,
+                            float *occupancy, float *onset_prob, float *offset_prob,
+                            double *log_z, int32_t *status,
+                            float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* emission prep from materialised logits                                     */
 /*   (replaces utils/alignment.py:123-134 [CTC] and :14-20 [plain])           */

@@ -710,10 +710,11 @@ class AlignEngine:
                                 w_x2=self.head.w_fc_x2 if (self.head.w_fc_x2 is not None and x2_inference_on()) else None)
 
     def align_feats(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, labels: torch.Tensor, n_labels: torch.Tensor,
-                    variant: int, flag: Optional[torch.Tensor] = None):
+                    variant: int, flag: Optional[torch.Tensor] = None, want_emissions: bool = False):
         """Encoder rows -> (onset, offset, final_score, status): head + emission prep + DP (one C call unless LA_ENGINE_PY=1).
         The op-by-op Python sequence below is also taken when HEAD_CLIPS_MAX was lowered (a test knob of that sequence; the C
-        call slices by its own cap, LA_HEAD_CLIP_CAP) and for heads the C struct does not describe (not 2 GRU layers)."""
+        call slices by its own cap, LA_HEAD_CLIP_CAP) and for heads the C struct does not describe (not 2 GRU layers).
+        want_emissions: also return the compact emissions [B, T, Lmax+1] f32 the DP consumed (ops.alignment_posteriors' input)."""
         if self._gru_flag is None:
             self._gru_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
         if ENGINE_PY or self._head_c is None or HEAD_CLIPS_MAX != 256:
@@ -723,24 +724,29 @@ class AlignEngine:
             finally:
                 self._gru_flag = own
             nf = torch.full((B,), T, dtype=torch.int32, device=self.device)
-            return ops.viterbi_batch(em, labels, n_labels, nf)
+            res = ops.viterbi_batch(em, labels, n_labels, nf)
+            return res + (em,) if want_emissions else res
+        if want_emissions:
+            return ops.align_head_forward(self._head_c, feats, feat_clip_stride, B, T, labels, n_labels, variant,
+                                          flag if flag is not None else self._gru_flag, want_emissions=True, ws_cache=self._ws)
         return ops.align_head_forward(self._head_c, feats, feat_clip_stride, B, T, labels, n_labels, variant,
                                       flag if flag is not None else self._gru_flag, ws_cache=self._ws)
 
     def align_feats_checked(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, labels: torch.Tensor, n_labels: torch.Tensor,
-                            variant: int):
+                            variant: int, want_emissions: bool = False):
         """align_feats with the persistent GRU's time-out handled (synchronises): the recurrence needs every workgroup of its launch set
         co-resident, which HIP does not promise while other streams own the CUs; a launch that waited out its bound (option
         gru_timeout_us, 3 s) leaves garbage.  The device is then idle -- the head is re-enqueued ONCE, alone, as a fresh launch -- and only a
         second time-out raises TimeoutError.  self.gru_recoveries counts the re-launches."""
         if self._gru_flag is None:
             self._gru_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        res = self.align_feats(feats, B, T, feat_clip_stride, labels, n_labels, variant)
+        kw = {"want_emissions": True} if want_emissions else {}
+        res = self.align_feats(feats, B, T, feat_clip_stride, labels, n_labels, variant, **kw)
         if int(self._gru_flag.item()) != 0:
             self._gru_flag.zero_()
             torch.cuda.synchronize(self.device)
             self.gru_recoveries = getattr(self, "gru_recoveries", 0) + 1
-            res = self.align_feats(feats, B, T, feat_clip_stride, labels, n_labels, variant)
+            res = self.align_feats(feats, B, T, feat_clip_stride, labels, n_labels, variant, **kw)
             self.check_gru()
         return res
 

@@ -59,13 +59,20 @@ def evaluate_batches(model, batches: Sequence[Any], lut: Optional[PinyinClassLUT
     return avg, maes
 
 
-def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, use_ctc_loss: bool = True) -> List[list]:
+def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, use_ctc_loss: bool = True,
+                  with_confidence: bool = False) -> List[list]:
     """inference_alignment_nogt.py:130-178: one record at a time, returns [[onset, offset, char], ...] per record.
-    `tokenize(text) -> list[int]` are the BERT ids without [CLS]/[SEP] (the reference slices [1:-1], :158-163)."""
+    `tokenize(text) -> list[int]` are the BERT ids without [CLS]/[SEP] (the reference slices [1:-1], :158-163).
+    with_confidence (addition): each entry is [onset, offset, char, occupancy] (AlignModel.align(return_confidence=True))."""
     out = []
     with torch.no_grad():
         for rec in records:
             ids = torch.tensor([tokenize(rec.text)], dtype=torch.long)
+            if with_confidence:
+                res, scores = model.align([rec.audio], lut(ids), use_ctc=use_ctc_loss, return_confidence=True)
+                res, occ = res[0], scores[0]["occupancy"]
+                out.append([[res[j][0], res[j][1], rec.text[j], occ[j]] for j in range(len(res))])
+                continue
             res = model.align([rec.audio], lut(ids), use_ctc=use_ctc_loss)[0]
             out.append([[res[j][0], res[j][1], rec.text[j]] for j in range(len(res))])
     return out

@@ -301,17 +301,32 @@ class AlignModel(torch.nn.Module):
     # ------------------------------------------------------------------ fused fast path (addition)
     @torch.no_grad()
     def align(self, audios: Optional[Sequence[np.ndarray]] = None, labels=None, *, mel: Optional[torch.Tensor] = None,
-              use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False):
+              use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
+              return_confidence: bool = False, boundary_window: int = 2):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
-        except the [L,2] integer frames."""
-        from ..utils.alignment import _labels_to_device, _seconds_from_frames
+        except the [L,2] integer frames.
+        return_confidence (addition; the reference has no counterpart): -> (seconds, scores), scores[b] = {"occupancy": [L],
+        "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} -- posteriors under the model from the
+        forward-backward sweep of the same lattice (ops.alignment_posteriors; boundary_window in frames), not accuracies.
+        With return_frames the device tensors: (onset, offset, score, status, occupancy, onset_prob, offset_prob, log_z)."""
+        from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames
         eng = self.engine()
         if mel is None:
             mel = self._mel_of(audios)
         feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
+        if return_confidence:
+            onset, offset, score, status, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
+                                                                       _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
+                                                                       want_emissions=True)
+            nf = torch.full((B,), T, dtype=torch.int32, device=eng.device)
+            occ, onp, offp, log_z, _ = ops.alignment_posteriors(em, lab_dev, n_lab, nf, onset, offset, boundary_window)
+            if return_frames:
+                return onset, offset, score, status, occ, onp, offp, log_z
+            seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second)
+            return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists)
         onset, offset, score, status = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
                                                                _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN)
         if return_frames:

@@ -61,6 +61,45 @@ def viterbi_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor
     return onset, offset, score, status
 
 
+def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                         onset: torch.Tensor, offset: torch.Tensor, boundary_window: int = 2, want_gamma: bool = False):
+    """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,
+    onset / offset [B,Lmax] i32 = viterbi_batch's (or align_head_forward's) outputs for the same emissions.
+    -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32 [, gamma [B,T,2*Lmax+1] f32] (device)."""
+    _dev(em, "em", torch.float32); _dev(labels, "labels", torch.int32)
+    _dev(n_labels, "n_labels", torch.int32); _dev(n_frames, "n_frames", torch.int32)
+    _dev(onset, "onset", torch.int32); _dev(offset, "offset", torch.int32)
+    if em.dim() != 3 or labels.dim() != 2 or em.stride(2) != 1 or labels.stride(1) != 1:
+        raise ValueError("alignment_posteriors: em [B,T,E] / labels [B,Lmax] with unit inner stride expected")
+    B, T, E = em.shape
+    Lmax = labels.shape[1]
+    if labels.shape[0] != B or n_labels.shape != (B,) or n_frames.shape != (B,) or E < Lmax + 1:
+        raise ValueError("alignment_posteriors: inconsistent shapes")
+    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
+        raise ValueError("alignment_posteriors: onset / offset must be [B,Lmax]")
+    if int(boundary_window) < 0:
+        raise ValueError("alignment_posteriors: boundary_window must be >= 0")
+    n_labels = n_labels.contiguous(); n_frames = n_frames.contiguous()
+    onset = onset.contiguous(); offset = offset.contiguous()
+    dev = em.device
+    occupancy = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    onset_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    offset_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
+    need = ctypes.c_size_t(0)
+    check(lib().la_alignment_posteriors_workspace_bytes(B, T, Lmax, ctypes.byref(need)), "alignment_posteriors_workspace_bytes")
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
+    check(lib().la_alignment_posteriors(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
+                                        ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
+                                        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(log_z), ptr(status), ptr(gamma),
+                                        gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
+                                        ptr(ws), need.value, stream_ptr()), "alignment_posteriors")
+    res = (occupancy, onset_prob, offset_prob, log_z, status)
+    return res + (gamma,) if want_gamma else res
+
+
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:
     """logits [B,T,V] f32 device -> compact emissions [B,T,Lmax+1] f32."""
     _dev(logits, "logits", torch.float32); _dev(labels, "labels", torch.int32); _dev(n_labels, "n_labels", torch.int32)

@@ -56,6 +56,17 @@ def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second):
     return result
 
 
+def _scores_from_posteriors(occupancy, onset_prob, offset_prob, log_z, final_score, label_lists):
+    """Device outputs of ops.alignment_posteriors -> per-utterance dicts of Python floats (after _seconds_from_frames
+    has raised for failed utterances).  path_log_posterior = final_score - log_z <= 0: log-probability of the reported path."""
+    occ, onp, offp = occupancy.cpu().numpy(), onset_prob.cpu().numpy(), offset_prob.cpu().numpy()
+    lz, fs = log_z.cpu().numpy(), final_score.cpu().numpy()
+    return [{"occupancy": [float(v) for v in occ[b, : len(labs)]],
+             "onset_prob": [float(v) for v in onp[b, : len(labs)]],
+             "offset_prob": [float(v) for v in offp[b, : len(labs)]],
+             "path_log_posterior": float(fs[b] - lz[b])} for b, labs in enumerate(label_lists)]
+
+
 def _device_of(prediction) -> torch.device:
     _lib.require_gpu()
     if torch.is_tensor(prediction) and prediction.is_cuda:
@@ -63,7 +74,7 @@ def _device_of(prediction) -> torch.device:
     return torch.device(f"cuda:{torch.cuda.current_device()}")
 
 
-def _perform(prediction, labels, hop_size_second, variant):
+def _perform(prediction, labels, hop_size_second, variant, boundary_window=None):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -74,8 +85,12 @@ def _perform(prediction, labels, hop_size_second, variant):
     lab, n_lab, lists = _labels_to_device(labels, B, dev)
     em = ops.emissions_from_logits(pred, lab, n_lab, variant)
     nf = torch.full((B,), T, dtype=torch.int32, device=dev)
-    onset, offset, _, status = ops.viterbi_batch(em, lab, n_lab, nf)
-    return _seconds_from_frames(onset, offset, status, lists, hop_size_second)
+    onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
+    seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second)
+    if boundary_window is None:
+        return seconds
+    occ, onp, offp, log_z, _ = ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)
+    return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02):
@@ -84,6 +99,18 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02):
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC)
+
+
+def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2):
+    """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
+    scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
+    sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window))
+
+
+def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2):
+    """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window))
 
 
 def run_viterbi_core(dp_matrix, backtrace_dp_matrix, cur_log_prediction, cur_log_silence_prediction, cur_label):
