@@ -270,9 +270,24 @@ int la_logmel_f32_prepared(const float *audio, int32_t batch, int32_t n_samples,
                            const void *consts,
                            float *mel, int64_t mel_batch_stride, int64_t mel_row_stride,
                            void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * Ragged form (an addition: upstream pads a batch to its longest clip BEFORE the log-mel and floors at the batch maximum, which
+ * la_logmel_* reproduce).  Clip b = the first n_samples[b] (device int32 [batch]) samples of row b of audio [batch][max_samples].
+ * mel [batch][80][out_frames] receives, per clip, what la_logmel_f32_prepared gives for that clip ALONE -- reflect padding at the
+ * clip's own end, n_samples[b] / 160 frames, floor at the clip's own maximum - 8 -- followed by literal zeros up to out_frames
+ * (= pad_or_trim; out_frames >= max_samples / 160, 3000 for the encoder).  Tiles wholly past a clip's end do no DFT.  2 launches.
+ * Every n_samples[b] must be > 200 (reflect padding; the caller checks it: the array lives on the device) and <= max_samples
+ * (larger values are clamped).  max_samples <= 200 is refused.  Workspace: la_logmel_ragged_workspace_bytes(batch, max_samples),
+ * 256-byte aligned.
+ */
+int la_logmel_ragged_workspace_bytes(int32_t batch, int32_t max_samples, size_t *bytes);
+int la_logmel_ragged_f32_prepared(const float *audio, const int32_t *n_samples, int32_t batch, int32_t max_samples,
+                                  const void *consts,
+                                  float *mel, int64_t mel_batch_stride, int64_t mel_row_stride, int32_t out_frames,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------- */
-/* building blocks of embed_audio / align_rnn                                 */
+/* building blocks of embed_audio / align_rnn                                */
 /* ------------------------------------------------------------------------- */
 /* epilogue flags for la_gemm */
 enum {
@@ -389,6 +404,18 @@ int la_gru_workspace_bytes(int32_t batch, int32_t frames, int32_t hidden, size_t
 int la_gru_layer(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh,
                  void *out, void *out_mish, int32_t batch, int32_t frames, int32_t hidden,
                  void *workspace, size_t workspace_bytes, int32_t *timeout_flag, void *stream);
+/*
+ * The same recurrence over clips of different lengths: n_frames [batch] (device int32), 0 <= n_frames[b] <= frames = the launch's
+ * maximum.  Rows t < n_frames[b] of out / out_mish are what la_gru_layer gives for clip b alone over n_frames[b] frames (the reverse
+ * direction enters frame n_frames[b] - 1 with h = 0); rows t >= n_frames[b] are unspecified.  Every inference form takes it (float32
+ * v_fma / MFMA and f16x2 forms, 16-bit counter and granule forms) as a compile-time variant of its kernel: after the gate arithmetic
+ * a lane SELECTS h = 0 at steps past its clip's end (gi there may hold anything, NaN included); the hand-off protocol, the time-out
+ * flag and the workspace are la_gru_layer's, and every clip of the launch still takes `frames` steps.  la_gru_layer itself launches
+ * the kernels it launched before.
+ */
+int la_gru_layer_ragged(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh,
+                        void *out, void *out_mish, int32_t batch, int32_t frames, const int32_t *n_frames, int32_t hidden,
+                        void *workspace, size_t workspace_bytes, int32_t *timeout_flag, void *stream);
 
 /*
  * Fused head tail: Linear(2H -> V) + emission prep, WITHOUT materialising the
@@ -725,6 +752,19 @@ int la_align_head_forward(const la_head_weights *w, const void *feats, int64_t l
                           const int32_t *n_labels, int32_t max_labels, int32_t *onset, int32_t *offset, int32_t out_stride,
                           double *final_score, int32_t *status, float *emissions_out, void *workspace, size_t workspace_bytes,
                           int32_t *timeout_flag, void *stream);
+/*
+ * Clips of different lengths in one call (an addition; the reference runs one frame count over a whole batch, which
+ * la_align_head_forward reproduces): n_frames [batch] (device int32), n_frames[b] <= frames = the maximum.  The input projections
+ * and the fused Linear + emission prep run over `frames` rows per clip, the two recurrences (la_gru_layer_ragged) and the DP take
+ * the lengths: clip b's onset / offset / final_score / status are those of la_align_head_forward for that clip alone with
+ * frames = n_frames[b] (n_frames[b] = 0: status LA_EINVAL for that clip only).  emissions_out rows t >= n_frames[b] are
+ * unspecified.  Slices of clips (see above) get their own part of n_frames.  Workspace: la_align_head_workspace_bytes.
+ */
+int la_align_head_forward_ragged(const la_head_weights *w, const void *feats, int64_t ld_feats, int64_t clip_stride_rows,
+                                 int32_t batch, int32_t frames, const int32_t *n_frames, int32_t variant, const int32_t *labels,
+                                 int32_t labels_stride, const int32_t *n_labels, int32_t max_labels, int32_t *onset, int32_t *offset,
+                                 int32_t out_stride, double *final_score, int32_t *status, float *emissions_out, void *workspace,
+                                 size_t workspace_bytes, int32_t *timeout_flag, void *stream);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,11 @@ SYMBOLS = {
     "la_align_head_workspace_bytes": (c_int32, [_P, _I32, _I32, _I32, POINTER(_SZ)]),
     "la_align_head_forward": (c_int32, [_P, _P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
     "la_cast_bf16_to_f32": (c_int32, [_P, _P, _I64, _P]),
+    # clips of different lengths in one launch set (per-clip sample / frame counts on the device)
+    "la_logmel_ragged_workspace_bytes": (c_int32, [_I32, _I32, POINTER(_SZ)]),
+    "la_logmel_ragged_f32_prepared": (c_int32, [_P, _P, _I32, _I32, _P, _P, _I64, _I64, _I32, _P, _SZ, _P]),
+    "la_gru_layer_ragged": (c_int32, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P, _SZ, _P, _P]),
+    "la_align_head_forward_ragged": (c_int32, [_P, _P, _I64, _I64, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
 }
 
 # symbols of the EXPERIMENT build only (csrc/lab/; bound when the loaded library has them: tools/build_variant.sh lab -DLA_EXPERIMENTS)

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
-from typing import Sequence, Union
+from typing import List, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -87,3 +87,28 @@ def log_mel_spectrogram(audio: Union[np.ndarray, torch.Tensor], device="cuda") -
     check(lib().la_logmel_f32_prepared(ptr(a), B, N, ptr(consts), ptr(mel), mel.stride(0), mel.stride(1), ptr(ws), need.value,
                                        stream_ptr()), "logmel_f32_prepared")
     return mel[0] if squeeze else mel.reshape(*audio.shape[:-1], N_MELS, frames)
+
+
+def log_mel_spectrogram_per_clip(audios: Sequence[np.ndarray], device="cuda", out_frames: int = 3000) -> Tuple[torch.Tensor, List[int]]:
+    """Clips of different lengths in ONE launch set, each treated as if it were alone (an addition: whisper's log-mel of a padded
+    batch pads first and floors at the batch maximum, which log_mel_spectrogram reproduces).  -> (mel [B, 80, out_frames] float32 on
+    `device`, n_mel list[int]): clip b's own log-mel -- reflect padding at its own end, len(audios[b]) // 160 frames, floor at its own
+    maximum - 8 -- followed by zeros (pad_or_trim to the encoder's 3000 frames).  Clips of more than out_frames * 160 samples or fewer
+    than 201 raise ValueError."""
+    _lib.require_gpu()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.LyricAlignHipError("log_mel_spectrogram_per_clip runs on the MI355X only (no CPU fallback)")
+    ns = [int(len(a)) for a in audios]
+    if not ns:
+        raise ValueError("log_mel_spectrogram_per_clip: no clips")
+    n_mel = [n // HOP_LENGTH for n in ns]
+    if max(n_mel) > int(out_frames):
+        raise ValueError(f"log_mel_spectrogram_per_clip: a clip has {max(n_mel)} mel frames, more than out_frames = {int(out_frames)}")
+    batch = np.zeros((len(ns), max(ns)), dtype=np.float32)
+    for i, a in enumerate(audios):
+        batch[i, : ns[i]] = np.asarray(a, dtype=np.float32)
+    from . import ops
+    consts = _device_constants(dev.index if dev.index is not None else torch.cuda.current_device())
+    mel = ops.logmel_ragged(torch.from_numpy(batch).to(dev), ns, consts, int(out_frames))
+    return mel, n_mel

@@ -50,6 +50,7 @@ struct GruParams {
     float *gates;        // optional [B][T][2][4H] f32: r, z, n, (W_hn h + b_hn) of every step, for the backward sweep
     unsigned long long poll_budget = 300000000ull;   // bound of one inter-workgroup wait in 100 MHz ticks (option gru_timeout_us; default 3 s)
     int fault_step = 0;  // test hook (option gru_fault_step, one launch): workgroup (0, 0, 0) leaves at this step without publishing, as if it had never become resident
+    const int *n_frames = nullptr;   // RAGGED instantiations: [B] frames of each clip (<= T); at steps with t >= n_frames[b] clip b's h is exactly 0
 };
 
 // Gate non-linearities on the hardware exponential / reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each).  The libm forms
@@ -135,7 +136,12 @@ __device__ __forceinline__ void mma_step(const uint4 &a, const uint4 &w, f32x4 &
 //     workgroups = CUs instead of hidden / 64: the resident recurrence takes 24 instead of 48 CUs from the encoder's GEMMs at 64
 //     clips, and a step's hand-off has 3 instead of 6 participants.  (768-thread workgroups -- 16 CUs -- do not fit: three waves
 //     per SIMD leave 168 registers per wave, 144 of which the W slice takes; acc + gates + prefetched inputs need ~50 more.)
-template <typename T, int MAXKS, bool WT, int MT, int NW = GruTraits<T>::NW>
+// RAGGED: per-clip lengths (la_gru_layer_ragged).  All clips of the launch still take T steps -- the hand-off protocol is the dense one --
+//     but a lane replaces its clip's h by exactly 0 at steps with t >= n_frames[clip], AFTER the gate arithmetic and by a select, so
+//     whatever the inputs of those frames hold (NaN included) never reaches a frame t < n_frames[clip]: the reverse direction enters
+//     frame n_frames - 1 with h = 0 as if the clip had been launched alone; the forward direction's rows t < n_frames never read later
+//     ones.  The lengths are read once per lane before the loop.  The dense instantiations (RAGGED = false) compile to what they were.
+template <typename T, int MAXKS, bool WT, int MT, int NW = GruTraits<T>::NW, bool RAGGED = false>
 __global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruParams p) {
     typedef GruTraits<T> TR;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -195,6 +201,14 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruParams p) {
     int arow[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) arow[mt] = b0 + min(mt * 16 + r16, nb - 1);
+
+    [[maybe_unused]] int nfr[MT][4];   // RAGGED: frames of this lane's clips (C rows b0 + mt*16 + 4q + i)
+    if constexpr (RAGGED) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) nfr[mt][i] = p.n_frames[b0 + min(mt * 16 + 4 * q + i, nb - 1)];
+    }
 
     float gin[MT][4][3];  // prefetched input projections of the current step
     auto load_gi = [&](int t) {
@@ -384,6 +398,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruParams p) {
                 const float hn = acc[2][mt][i] + bhn;
                 const float n = tanh_fast(gin[mt][i][2] + r * hn);
                 hnew[mt][i] = (1.0f - z) * n + z * hprev[mt][i];
+                if constexpr (RAGGED) hnew[mt][i] = t < nfr[mt][i] ? hnew[mt][i] : 0.f;     // a select: NaN past the clip's end stays there
                 hprev[mt][i] = hnew[mt][i];
                 if (p.gates) {
                     const int bl = mt * 16 + 4 * q + i;
@@ -468,12 +483,13 @@ struct GruGranuleParams {
     int poll_delay;            // 64-clock sleeps between a step's publish and its first poll (option gru_poll_delay)
     unsigned long long poll_budget = 300000000ull;
     int fault_step = 0;
+    const int *n_frames = nullptr;   // RAGGED: see GruParams
 };
 
 #ifndef LA_GRU_PROBE
 #define LA_GRU_PROBE 0      // experiment build: timing-only knock-outs (1 = no gi loads after step 0, 2 = no out / out_mish stores)
 #endif
-template <typename T, int MAXKS>
+template <typename T, int MAXKS, bool RAGGED = false>    // RAGGED: per-clip lengths, as in gru_kernel
 __global__ __launch_bounds__(512, 1) void gru_granule_kernel(GruGranuleParams p) {
     constexpr int NW = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -512,6 +528,11 @@ __global__ __launch_bounds__(512, 1) void gru_granule_kernel(GruGranuleParams p)
 
     const float bhr = bh[jcol], bhz = bh[H + jcol], bhn = bh[2 * H + jcol];
     float hprev[4] = {0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] int nfr[4];
+    if constexpr (RAGGED) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) nfr[i] = p.n_frames[b0 + min(4 * q + i, nb - 1)];
+    }
     float gin[4][3];  // prefetched input projections of the coming step
     auto load_gi = [&](int t) {
 #pragma unroll
@@ -605,6 +626,7 @@ __global__ __launch_bounds__(512, 1) void gru_granule_kernel(GruGranuleParams p)
             const float hn = acc[2][i] + bhn;
             const float n = tanh_fast(gin[i][2] + r * hn);
             hnew[i] = (1.0f - z) * n + z * hprev[i];
+            if constexpr (RAGGED) hnew[i] = t < nfr[i] ? hnew[i] : 0.f;
             hprev[i] = hnew[i];
         }
         // ---- publish: one 8-byte granule per (clip, unit pair), written by the even lane of the pair; clips beyond nb publish too
@@ -652,6 +674,7 @@ struct GruTrainX2Params {
     int *abort_flag, *timeout_flag;
     unsigned long long poll_budget = 300000000ull;
     int fault_step = 0;
+    const int *n_frames = nullptr;   // RAGGED: see GruParams
 };
 
 __device__ __forceinline__ unsigned x2_pack_hi_lo(float x) {          // x (already scaled) -> f16 hi | f16 lo << 16
@@ -660,7 +683,7 @@ __device__ __forceinline__ unsigned x2_pack_hi_lo(float x) {          // x (alre
     return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
 }
 
-template <int MAXKS>
+template <int MAXKS, bool RAGGED = false>                // RAGGED (inference only, gates == NULL): per-clip lengths, as in gru_kernel
 __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p) {
     constexpr int NW = 4;
     typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
@@ -724,6 +747,11 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p
 
     const float bhr = bh[jcol], bhz = bh[H + jcol], bhn = bh[2 * H + jcol];
     float hprev[4] = {0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] int nfr[4];
+    if constexpr (RAGGED) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) nfr[i] = p.n_frames[b0 + min(4 * q + i, nb - 1)];
+    }
     float gin[4][3];
     auto load_gi = [&](int t) {
 #pragma unroll
@@ -805,6 +833,7 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p
             const float hn = acc[2][i] * wscale[2] + bhn;
             const float n = tanh_fast(gin[i][2] + r * hn);
             hnew[i] = (1.0f - z) * n + z * hprev[i];
+            if constexpr (RAGGED) hnew[i] = t < nfr[i] ? hnew[i] : 0.f;
             hprev[i] = hnew[i];
             gr[i] = r; gz[i] = z; gn[i] = n; ghn[i] = hn;
         }
@@ -857,7 +886,7 @@ extern "C" int la_gru_workspace_bytes(int32_t batch, int32_t frames, int32_t hid
 // gates != nullptr: the training forward (float32) also stores r, z, n and W_hn h + b_hn of every step
 static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
                        int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
-                       int32_t *timeout_flag, float *gates, void *stream_) {
+                       int32_t *timeout_flag, float *gates, void *stream_, const int32_t *n_frames = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (batch == 0 || frames == 0) return LA_OK;
     LA_CHECK_ARG(gi && w_hh && b_hh && out && workspace, "gru_layer: null pointer");
@@ -895,10 +924,11 @@ static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const f
         LA_HIP(hipMemsetAsync(wsb, 0, 16, stream));
         LA_HIP(hipMemsetAsync(wsb + ctrb, 0, gru_xch_fwd_bytes(batch, hidden), stream));
         GruTrainX2Params tp{gi, reinterpret_cast<const float *>(w_hh), b_hh, reinterpret_cast<float *>(out), gates, reinterpret_cast<float *>(out_mish), batch, frames, hidden,
-                            reinterpret_cast<unsigned long long *>(wsb + ctrb), reinterpret_cast<int *>(workspace), timeout_flag, budget, fault};
+                            reinterpret_cast<unsigned long long *>(wsb + ctrb), reinterpret_cast<int *>(workspace), timeout_flag, budget, fault, n_frames};
         const size_t lds_t = 16 + (size_t)2 * 2 * 16 * (hidden * 2 + 16);
         la::TimerScope ts("gru_f32", stream);
-        hipLaunchKernelGGL((gru_train_x2_kernel<12>), dim3(hidden / 64, 2, groups), dim3(256), lds_t, stream, tp);
+        if (n_frames) hipLaunchKernelGGL((gru_train_x2_kernel<12, true>), dim3(hidden / 64, 2, groups), dim3(256), lds_t, stream, tp);
+        else hipLaunchKernelGGL((gru_train_x2_kernel<12>), dim3(hidden / 64, 2, groups), dim3(256), lds_t, stream, tp);
         LA_LAUNCH_CHECK();
         return LA_OK;
     }
@@ -914,9 +944,13 @@ static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const f
         LA_HIP(hipMemsetAsync(wsb, 0, 16, stream));
         LA_HIP(hipMemsetAsync(wsb + ctrb, 0, gru_xch_fwd_bytes(batch, hidden), stream));
         GruGranuleParams gp{gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, reinterpret_cast<unsigned long long *>(wsb + ctrb),
-                            reinterpret_cast<int *>(workspace), timeout_flag, nsplit, la::opts().gru_poll_delay, budget, fault};
+                            reinterpret_cast<int *>(workspace), timeout_flag, nsplit, la::opts().gru_poll_delay, budget, fault, n_frames};
         const size_t lds_g = 16 + (size_t)2 * 16 * (hidden * 2 + 16);          // flag + two h stages
         la::TimerScope ts("gru_bf16", stream);
+        if (n_frames) {
+            if (dtype == LA_F16) hipLaunchKernelGGL((gru_granule_kernel<la::f16_t, 12, true>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
+            else hipLaunchKernelGGL((gru_granule_kernel<bf16_t, 12, true>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
+        } else
         if (dtype == LA_F16) hipLaunchKernelGGL((gru_granule_kernel<la::f16_t, 12>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
         else hipLaunchKernelGGL((gru_granule_kernel<bf16_t, 12>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
         LA_LAUNCH_CHECK();
@@ -925,7 +959,7 @@ static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const f
     LA_HIP(hipMemsetAsync(workspace, 0, gru_ctr_bytes(batch, frames), stream));
     GruParams p{gi, w_hh, b_hh, out, out_mish, batch, frames, hidden,
                 reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(workspace) + 16),
-                reinterpret_cast<int *>(workspace), timeout_flag, nsplit, gates, budget, fault};
+                reinterpret_cast<int *>(workspace), timeout_flag, nsplit, gates, budget, fault, n_frames};
     const dim3 grid(nsplit, 2, groups);
     // Hand-off forms (tools/kbench.py gru, 32 clips, T=1500, H=384; tools/handoff_bench.hip for the bare protocol costs):
     // write-through (sc1 stores, drained; relaxed counter; sc1 loads) 5.4 ms per layer, release / acquire fences 9.0 ms.
@@ -939,7 +973,10 @@ static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const f
         // MAXKS = the W slice's compile-time k-steps: 12 with 8 waves (hidden <= 384, 144 registers), 16 with 4 (hidden <= 512, 192)
 #define LA_GRU_LAUNCH16_(T_, KS_, NW_)                                                                                     \
     do {                                                                                                                   \
-        if (mt == 1) {                                                                                                     \
+        if (n_frames) {      /* per-clip lengths: one batch tile per workgroup (GROUP = 16), both hand-off forms */            \
+            if (use_fence) hipLaunchKernelGGL((gru_kernel<T_, KS_, false, 1, NW_, true>), grid, dim3(NW_ * 64), lds_b, stream, p); \
+            else hipLaunchKernelGGL((gru_kernel<T_, KS_, true, 1, NW_, true>), grid, dim3(NW_ * 64), lds_b, stream, p);    \
+        } else if (mt == 1) {                                                                                              \
             if (use_fence) hipLaunchKernelGGL((gru_kernel<T_, KS_, false, 1, NW_>), grid, dim3(NW_ * 64), lds_b, stream, p); \
             else hipLaunchKernelGGL((gru_kernel<T_, KS_, true, 1, NW_>), grid, dim3(NW_ * 64), lds_b, stream, p);          \
         } else {                                                                                                           \
@@ -964,10 +1001,15 @@ static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const f
             LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
             LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
             LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, false, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, true, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
             attr_once.mark();
         }
         la::TimerScope ts("gru_f32", stream);
-        if (batch <= 16 || GROUP == 16) {
+        if (n_frames) {
+            if (use_fence) hipLaunchKernelGGL((gru_kernel<float, 24, false, 1, 2, true>), grid, dim3(128), lds_bytes, stream, p);
+            else hipLaunchKernelGGL((gru_kernel<float, 24, true, 1, 2, true>), grid, dim3(128), lds_bytes, stream, p);
+        } else if (batch <= 16 || GROUP == 16) {
             if (use_fence) hipLaunchKernelGGL((gru_kernel<float, 24, false, 1>), grid, dim3(128), lds_bytes, stream, p);
             else hipLaunchKernelGGL((gru_kernel<float, 24, true, 1>), grid, dim3(128), lds_bytes, stream, p);
         } else {
@@ -983,6 +1025,16 @@ extern "C" int la_gru_layer(int32_t dtype, const float *gi, const void *w_hh, co
                             int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
                             int32_t *timeout_flag, void *stream) {
     return gru_forward(dtype, gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, nullptr, stream);
+}
+
+// Per-clip lengths: n_frames [batch] (device), 1 <= n_frames[b] <= frames.  Rows t < n_frames[b] of clip b are what la_gru_layer gives for
+// that clip alone over n_frames[b] frames; rows past them are unspecified.  Every clip of the launch takes `frames` steps.
+extern "C" int la_gru_layer_ragged(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
+                                   int32_t batch, int32_t frames, const int32_t *n_frames, int32_t hidden, void *workspace,
+                                   size_t workspace_bytes, int32_t *timeout_flag, void *stream) {
+    LA_CHECK_ARG(n_frames || batch == 0 || frames == 0, "gru_layer_ragged: n_frames missing");
+    static_assert(GROUP == 16, "the ragged instantiations are the one-batch-tile forms");
+    return gru_forward(dtype, gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, nullptr, stream, n_frames);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -67,9 +67,14 @@ __global__ void logmel_constants_kernel(const float *window, const float *filter
 
 // One 64-frame tile of one clip: waveform span -> log10 mel [80][64] (unfloored) into mel[b][m][j0 ..], the maximum of the
 // tile's valid values into blockmax[b * gridDim.x + tile].
-__global__ __launch_bounds__(256, 2) void logmel_tile_kernel(const float *__restrict__ audio, int N, int frames,
+// RAGGED (la_logmel_ragged_f32_prepared): the rows of `audio` are `row_len` samples apart and clip b owns the first n_samples[b] of its
+// row: the reflect padding turns at the clip's own end, its frame count is n_samples[b] / 160, and a tile wholly past that does no DFT
+// (its blockmax slot gets -inf; logmel_finish_ragged_kernel writes the zeros there).
+template <bool RAGGED>
+__global__ __launch_bounds__(256, 2) void logmel_tile_kernel(const float *__restrict__ audio, int row_len, int frames,
                                                              const float *__restrict__ consts, float *__restrict__ mel,
-                                                             int64_t mbs, int64_t mrs, float *__restrict__ blockmax) {
+                                                             int64_t mbs, int64_t mrs, float *__restrict__ blockmax,
+                                                             const int *__restrict__ n_samples) {
     extern __shared__ float lds[];
     float *span = lds;                 // [SPAN] waveform, later pw[64][PWP]
     float *outt = lds + LDS_MAIN;      // [80][OUTP]
@@ -77,7 +82,16 @@ __global__ __launch_bounds__(256, 2) void logmel_tile_kernel(const float *__rest
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 15, lq = lane >> 4;
     const int b = blockIdx.y, j0 = blockIdx.x * FT;
-    const float *a = audio + (int64_t)b * N;
+    const float *a = audio + (int64_t)b * row_len;
+    int N = row_len;
+    if constexpr (RAGGED) {
+        N = min(max(n_samples[b], 0), row_len);          // never past the row, whatever the caller's array holds
+        frames = N / HOP;
+        if (j0 >= frames) {                              // (uniform over the workgroup: before the first barrier)
+            if (tid == 0) blockmax[(int64_t)b * gridDim.x + blockIdx.x] = -INFINITY;
+            return;
+        }
+    }
 
     // ---- the tile's span of the reflect-padded waveform: padded[p] = audio[reflect(p - 200)], zero past N + 400 ----
     const int64_t p0 = (int64_t)j0 * HOP;
@@ -178,6 +192,26 @@ __global__ __launch_bounds__(256) void logmel_finish_kernel(float *mel, int64_t 
     }
 }
 
+// The ragged form's finish: clip b's floor from the maximum over ITS tiles, frames j < n_samples[b] / 160 floored and scaled in place,
+// literal zeros from there to out_frames (whisper's pad_or_trim of the clip's own log-mel).  One workgroup per (4 mel rows, clip).
+__global__ __launch_bounds__(256) void logmel_finish_ragged_kernel(float *mel, int64_t mbs, int64_t mrs, int out_frames, const int *n_samples,
+                                                                   int row_len, const float *blockmax, int tiles) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < tiles; i += 256) m = fmaxf(m, blockmax[(int64_t)b * tiles + i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    const float floor_v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) - 8.0f;
+    const int frames = min(min(max(n_samples[b], 0), row_len) / HOP, out_frames);
+    for (int r = 0; r < 4; ++r) {
+        float *row = mel + (int64_t)b * mbs + (int64_t)(blockIdx.x * 4 + r) * mrs;
+        for (int j = threadIdx.x; j < out_frames; j += 256) row[j] = j < frames ? (fmaxf(row[j], floor_v) + 4.0f) / 4.0f : 0.f;
+    }
+}
+
 struct MelPlan {
     int frames, tiles;
     size_t off_consts, off_bmax, total;
@@ -199,12 +233,12 @@ int run_logmel(const float *audio, int batch, int n_samples, const float *consts
                float *bmax, const MelPlan &p, hipStream_t stream) {
     static la::DeviceOnce attr_once;
     if (attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(logmel_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(logmel_tile_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    LDS_FLOATS * 4));
         attr_once.mark();
     }
-    hipLaunchKernelGGL(logmel_tile_kernel, dim3(p.tiles, batch), dim3(256), LDS_FLOATS * 4, stream, audio, n_samples, p.frames,
-                       consts, mel, mbs, mrs, bmax);
+    hipLaunchKernelGGL(logmel_tile_kernel<false>, dim3(p.tiles, batch), dim3(256), LDS_FLOATS * 4, stream, audio, n_samples, p.frames,
+                       consts, mel, mbs, mrs, bmax, (const int *)nullptr);
     hipLaunchKernelGGL(logmel_finish_kernel, dim3(NMEL / 4, batch), dim3(256), 0, stream, mel, mbs, mrs, p.frames, bmax,
                        batch * p.tiles);
     LA_LAUNCH_CHECK();
@@ -276,4 +310,39 @@ extern "C" int la_logmel_f32_prepared(const float *audio, int32_t batch, int32_t
     la::TimerScope ts("logmel", stream);
     return run_logmel(audio, batch, n_samples, reinterpret_cast<const float *>(consts), mel, mel_batch_stride, mel_row_stride,
                       reinterpret_cast<float *>(ws + p.off_bmax), p, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ragged form: clip b = the first n_samples[b] (device) samples of row b of audio [batch][max_samples]; mel [batch][80][out_frames] receives
+// the clip's OWN log-mel (reflect padding at its own end, floor at its own maximum - 8) in frames 0 .. n_samples[b] / 160 - 1 and zeros from
+// there to out_frames.  Two launches, the workspace of la_logmel_workspace_bytes(batch, max_samples).
+extern "C" int la_logmel_ragged_workspace_bytes(int32_t batch, int32_t max_samples, size_t *bytes) {
+    LA_CHECK_ARG(bytes && batch > 0 && max_samples >= HOP, "logmel_ragged_workspace_bytes: bad arguments");
+    *bytes = plan_mel(batch, max_samples).total;
+    return LA_OK;
+}
+
+extern "C" int la_logmel_ragged_f32_prepared(const float *audio, const int32_t *n_samples, int32_t batch, int32_t max_samples, const void *consts,
+                                             float *mel, int64_t mel_batch_stride, int64_t mel_row_stride, int32_t out_frames, void *workspace,
+                                             size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LA_CHECK_ARG(consts && (uintptr_t)consts % 16 == 0, "logmel_ragged: constants missing or misaligned");
+    LA_CHECK_ARG(n_samples, "logmel_ragged: n_samples missing");
+    const MelPlan p = plan_mel(batch > 0 ? batch : 1, max_samples >= HOP ? max_samples : HOP);
+    int rc = logmel_checks(audio, batch, max_samples, mel, mel_row_stride, workspace, workspace_bytes, p);
+    if (rc != LA_OK) return rc;
+    LA_CHECK_ARG(out_frames >= p.frames && mel_row_stride >= out_frames, "logmel_ragged: out_frames < max_samples / 160 or mel_row_stride < out_frames");
+    static la::DeviceOnce attr_once;
+    if (attr_once.pending()) {
+        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(logmel_tile_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FLOATS * 4));
+        attr_once.mark();
+    }
+    float *bmax = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) + p.off_bmax);
+    la::TimerScope ts("logmel", stream);
+    hipLaunchKernelGGL(logmel_tile_kernel<true>, dim3(p.tiles, batch), dim3(256), LDS_FLOATS * 4, stream, audio, max_samples, p.frames,
+                       reinterpret_cast<const float *>(consts), mel, mel_batch_stride, mel_row_stride, bmax, n_samples);
+    hipLaunchKernelGGL(logmel_finish_ragged_kernel, dim3(NMEL / 4, batch), dim3(256), 0, stream, mel, mel_batch_stride, mel_row_stride, out_frames,
+                       n_samples, max_samples, bmax, p.tiles);
+    LA_LAUNCH_CHECK();
+    return LA_OK;
 }

@@ -280,11 +280,12 @@ extern "C" int la_align_head_workspace_bytes(const la_head_weights *w, int32_t b
     return LA_OK;
 }
 
-extern "C" int la_align_head_forward(const la_head_weights *w, const void *feats, int64_t ld_feats, int64_t clip_stride_rows,
-                                     int32_t batch, int32_t frames, int32_t variant, const int32_t *labels, int32_t labels_stride,
-                                     const int32_t *n_labels, int32_t max_labels, int32_t *onset, int32_t *offset, int32_t out_stride,
-                                     double *final_score, int32_t *status, float *emissions_out, void *workspace,
-                                     size_t workspace_bytes, int32_t *timeout_flag, void *stream_) {
+// n_frames == NULL: every clip has `frames` frames (la_align_head_forward); else the per-clip lengths (la_align_head_forward_ragged)
+static int head_forward(const la_head_weights *w, const void *feats, int64_t ld_feats, int64_t clip_stride_rows,
+                        int32_t batch, int32_t frames, const int32_t *n_frames, int32_t variant, const int32_t *labels, int32_t labels_stride,
+                        const int32_t *n_labels, int32_t max_labels, int32_t *onset, int32_t *offset, int32_t out_stride,
+                        double *final_score, int32_t *status, float *emissions_out, void *workspace,
+                        size_t workspace_bytes, int32_t *timeout_flag, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (batch == 0) return LA_OK;
     LA_CHECK_ARG(w && feats && labels && n_labels && onset && offset && final_score && status && workspace, "align_head_forward: null pointer");
@@ -298,7 +299,7 @@ extern "C" int la_align_head_forward(const la_head_weights *w, const void *feats
     const int out_f32 = dt == LA_F32 ? 0 : LA_EPI_OUT_F32;
     const int cap = head_clip_cap(w, frames);
     const bool x2 = head_x2(w);
-    LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.n_frames), frames, batch < cap ? batch : cap, stream));
+    if (!n_frames) LA_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.n_frames), frames, batch < cap ? batch : cap, stream));
     const int64_t em_clip = (int64_t)frames * (max_labels + 1);
     for (int b0 = 0; b0 < batch; b0 += cap) {        // the persistent recurrence takes one launch set of clips at a time
         const int nb = batch - b0 < cap ? batch - b0 : cap;
@@ -322,6 +323,10 @@ extern "C" int la_align_head_forward(const la_head_weights *w, const void *feats
             } else
             LA_TRY(la_gemm(dt, frames, 6 * H, in_dim, nb, x, lda, stride_a, w->w_ih[layer], b.gi, 6 * H, (int64_t)frames * 6 * H, w->b_ih[layer],
                            nullptr, 0, 0, LA_EPI_BIAS | out_f32, stream));
+            if (n_frames)
+                LA_TRY(la_gru_layer_ragged(dt, b.gi, w->w_hh[layer], w->b_hh[layer], b.gru[layer], layer == 1 ? b.act : nullptr, nb, frames, n_frames + b0, H,
+                                           b.gru_ws, b.gru_ws_bytes, timeout_flag, stream));
+            else
             LA_TRY(la_gru_layer(dt, b.gi, w->w_hh[layer], w->b_hh[layer], b.gru[layer], layer == 1 ? b.act : nullptr, nb, frames, H, b.gru_ws,
                                 b.gru_ws_bytes, timeout_flag, stream));
             x = static_cast<const unsigned char *>(b.gru[layer]);
@@ -337,9 +342,31 @@ extern "C" int la_align_head_forward(const la_head_weights *w, const void *feats
         else
         LA_TRY(la_fc_emissions(dt, b.act, 2 * H, w->w_fc, w->b_fc, nb, frames, 2 * H, w->vocab, variant, lab, labels_stride, n_labels + b0, max_labels,
                                em, em_clip, max_labels + 1, b.fc_ws, b.fc_ws_bytes, stream));
-        LA_TRY(la_viterbi_batch(em, em_clip, max_labels + 1, lab, labels_stride, n_labels + b0, b.n_frames, nb, frames, max_labels,
+        LA_TRY(la_viterbi_batch(em, em_clip, max_labels + 1, lab, labels_stride, n_labels + b0, n_frames ? n_frames + b0 : b.n_frames, nb, frames, max_labels,
                                 onset + (int64_t)b0 * out_stride, offset + (int64_t)b0 * out_stride, out_stride, final_score + b0, status + b0,
                                 b.vit_ws, b.vit_ws_bytes, stream));
     }
     return LA_OK;
+}
+
+extern "C" int la_align_head_forward(const la_head_weights *w, const void *feats, int64_t ld_feats, int64_t clip_stride_rows,
+                                     int32_t batch, int32_t frames, int32_t variant, const int32_t *labels, int32_t labels_stride,
+                                     const int32_t *n_labels, int32_t max_labels, int32_t *onset, int32_t *offset, int32_t out_stride,
+                                     double *final_score, int32_t *status, float *emissions_out, void *workspace,
+                                     size_t workspace_bytes, int32_t *timeout_flag, void *stream) {
+    return head_forward(w, feats, ld_feats, clip_stride_rows, batch, frames, nullptr, variant, labels, labels_stride, n_labels, max_labels, onset, offset,
+                        out_stride, final_score, status, emissions_out, workspace, workspace_bytes, timeout_flag, stream);
+}
+
+// Clips of different lengths in one launch set: clip b has n_frames[b] (device, <= frames) frames.  The input projections and the fused
+// Linear + emission prep run over `frames` rows per clip as in the dense call; the two recurrences and the DP take the lengths, so clip b's
+// result is the dense call's for that clip alone with frames = n_frames[b].  Workspace: la_align_head_workspace_bytes(w, batch, frames, ...).
+extern "C" int la_align_head_forward_ragged(const la_head_weights *w, const void *feats, int64_t ld_feats, int64_t clip_stride_rows,
+                                            int32_t batch, int32_t frames, const int32_t *n_frames, int32_t variant, const int32_t *labels,
+                                            int32_t labels_stride, const int32_t *n_labels, int32_t max_labels, int32_t *onset, int32_t *offset,
+                                            int32_t out_stride, double *final_score, int32_t *status, float *emissions_out, void *workspace,
+                                            size_t workspace_bytes, int32_t *timeout_flag, void *stream) {
+    LA_CHECK_ARG(n_frames || batch == 0, "align_head_forward_ragged: n_frames missing");
+    return head_forward(w, feats, ld_feats, clip_stride_rows, batch, frames, n_frames, variant, labels, labels_stride, n_labels, max_labels, onset, offset,
+                        out_stride, final_score, status, emissions_out, workspace, workspace_bytes, timeout_flag, stream);
 }

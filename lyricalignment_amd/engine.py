@@ -647,19 +647,23 @@ class AlignEngine:
         by_desc = (2 ** 31 - 1) // (max(1, T) * 2 * hw.hidden * es)
         return max(1, min(HEAD_CLIPS_MAX, by_cus, by_desc))
 
-    def head_hidden(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int) -> torch.Tensor:
+    def head_hidden(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, n_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
         """feats: rows [.., d] in compute dtype, clip b at rows b*feat_clip_stride .. +T.  -> Mish(GRU) [B*T, 2H].
-        More clips than one launch set of the recurrence takes (head_clip_cap) run as consecutive slices of clips."""
+        More clips than one launch set of the recurrence takes (head_clip_cap) run as consecutive slices of clips.
+        n_frames (device int32 [B], values <= T): per-clip lengths -- clip b's rows t < n_frames[b] are its own recurrences over n_frames[b]
+        frames, later rows unspecified (every slice gets its part of the lengths)."""
         hw = self.head
         H, dt = hw.hidden, hw.dtype
         cap = self.head_clip_cap(T)
         act = self._get("head_act", (B * T, 2 * H), dt)
         for b0 in range(0, B, cap):
             b1 = min(B, b0 + cap)
-            self._head_slice(feats[b0 * feat_clip_stride:], b1 - b0, T, feat_clip_stride, min(B, cap), act[b0 * T: b1 * T])
+            self._head_slice(feats[b0 * feat_clip_stride:], b1 - b0, T, feat_clip_stride, min(B, cap), act[b0 * T: b1 * T],
+                             None if n_frames is None else n_frames[b0:b1])
         return act
 
-    def _head_slice(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, Bbuf: int, act_out: torch.Tensor) -> None:
+    def _head_slice(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, Bbuf: int, act_out: torch.Tensor,
+                    n_frames: Optional[torch.Tensor] = None) -> None:
         hw = self.head
         H, dt = hw.hidden, hw.dtype
         x = feats
@@ -688,13 +692,14 @@ class AlignEngine:
             if self._gru_flag is None:
                 self._gru_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
             ops.gru_layer(gi, hw.w_hh[layer], hw.b_hh[layer], out=out, out_mish=act_out.view(B, T, 2 * H) if last else None,
-                          flag=self._gru_flag)
+                          flag=self._gru_flag, n_frames=n_frames)
             x = out.view(B * T, 2 * H)
             lda, stride_a = 2 * H, T * 2 * H
 
-    def logits(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int) -> torch.Tensor:
-        """Materialised align logits [B, T, V] f32 (the reference's frame_manual_forward output)."""
-        act = self.head_hidden(feats, B, T, feat_clip_stride)
+    def logits(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, n_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Materialised align logits [B, T, V] f32 (the reference's frame_manual_forward output); with n_frames rows t >= n_frames[b] are
+        unspecified."""
+        act = self.head_hidden(feats, B, T, feat_clip_stride, n_frames)
         out = torch.empty((B * T, self.head.vocab), dtype=torch.float32, device=self.device)
         hw = self.head
         if hw.w_fc_x2 is not None and _x2_domain(B * T, hw.vocab, hw.w_fc.shape[1]) and x2_inference_on():
@@ -704,36 +709,39 @@ class AlignEngine:
         return out.view(B, T, hw.vocab)
 
     def emissions(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, labels: torch.Tensor,
-                  n_labels: torch.Tensor, variant: int) -> torch.Tensor:
-        act = self.head_hidden(feats, B, T, feat_clip_stride)
+                  n_labels: torch.Tensor, variant: int, n_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        act = self.head_hidden(feats, B, T, feat_clip_stride, n_frames)
         return ops.fc_emissions(act, self.head.w_fc, self.head.b_fc, B, T, labels, n_labels, variant,
                                 w_x2=self.head.w_fc_x2 if (self.head.w_fc_x2 is not None and x2_inference_on()) else None)
 
     def align_feats(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, labels: torch.Tensor, n_labels: torch.Tensor,
-                    variant: int, flag: Optional[torch.Tensor] = None, want_emissions: bool = False):
+                    variant: int, flag: Optional[torch.Tensor] = None, want_emissions: bool = False,
+                    n_frames: Optional[torch.Tensor] = None):
         """Encoder rows -> (onset, offset, final_score, status): head + emission prep + DP (one C call unless LA_ENGINE_PY=1).
         The op-by-op Python sequence below is also taken when HEAD_CLIPS_MAX was lowered (a test knob of that sequence; the C
         call slices by its own cap, LA_HEAD_CLIP_CAP) and for heads the C struct does not describe (not 2 GRU layers).
-        want_emissions: also return the compact emissions [B, T, Lmax+1] f32 the DP consumed (ops.alignment_posteriors' input)."""
+        want_emissions: also return the compact emissions [B, T, Lmax+1] f32 the DP consumed (ops.alignment_posteriors' input).
+        n_frames (device int32 [B], values <= T): clips of different lengths -- recurrences and DP over n_frames[b] frames of clip b
+        (la_align_head_forward_ragged; the op-by-op sequence carries the same lengths and gives the same bits)."""
         if self._gru_flag is None:
             self._gru_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
         if ENGINE_PY or self._head_c is None or HEAD_CLIPS_MAX != 256:
             own, self._gru_flag = self._gru_flag, (flag if flag is not None else self._gru_flag)
             try:
-                em = self.emissions(feats, B, T, feat_clip_stride, labels, n_labels, variant)
+                em = self.emissions(feats, B, T, feat_clip_stride, labels, n_labels, variant, n_frames)
             finally:
                 self._gru_flag = own
-            nf = torch.full((B,), T, dtype=torch.int32, device=self.device)
+            nf = torch.full((B,), T, dtype=torch.int32, device=self.device) if n_frames is None else n_frames
             res = ops.viterbi_batch(em, labels, n_labels, nf)
             return res + (em,) if want_emissions else res
         if want_emissions:
             return ops.align_head_forward(self._head_c, feats, feat_clip_stride, B, T, labels, n_labels, variant,
-                                          flag if flag is not None else self._gru_flag, want_emissions=True, ws_cache=self._ws)
+                                          flag if flag is not None else self._gru_flag, want_emissions=True, ws_cache=self._ws, n_frames=n_frames)
         return ops.align_head_forward(self._head_c, feats, feat_clip_stride, B, T, labels, n_labels, variant,
-                                      flag if flag is not None else self._gru_flag, ws_cache=self._ws)
+                                      flag if flag is not None else self._gru_flag, ws_cache=self._ws, n_frames=n_frames)
 
     def align_feats_checked(self, feats: torch.Tensor, B: int, T: int, feat_clip_stride: int, labels: torch.Tensor, n_labels: torch.Tensor,
-                            variant: int, want_emissions: bool = False):
+                            variant: int, want_emissions: bool = False, n_frames: Optional[torch.Tensor] = None):
         """align_feats with the persistent GRU's time-out handled (synchronises): the recurrence needs every workgroup of its launch set
         co-resident, which HIP does not promise while other streams own the CUs; a launch that waited out its bound (option
         gru_timeout_us, 3 s) leaves garbage.  The device is then idle -- the head is re-enqueued ONCE, alone, as a fresh launch -- and only a
@@ -741,6 +749,8 @@ class AlignEngine:
         if self._gru_flag is None:
             self._gru_flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
         kw = {"want_emissions": True} if want_emissions else {}
+        if n_frames is not None:
+            kw["n_frames"] = n_frames                       # (the re-launch below runs over the same lengths)
         res = self.align_feats(feats, B, T, feat_clip_stride, labels, n_labels, variant, **kw)
         if int(self._gru_flag.item()) != 0:
             self._gru_flag.zero_()

@@ -32,10 +32,64 @@ class PinyinClassLUT:
         return t
 
 
+PER_CLIP_MAX_SAMPLES = 3000 * 160 + 159        # the longest clip AlignModel.align(per_clip=True) takes: 3000 mel frames = 30 s
+
+
+def _evaluate_grouped(model, batches: Sequence[Any], lut, use_ctc_loss: bool, group: int):
+    """evaluate_batches' per-batch MAEs with `group` consecutive evaluated one-clip batches per device call (per_clip=True: every clip
+    as if it ran alone).  Clips longer than 30 s go alone through the dense call, as with group = 1."""
+    maes: List[Optional[float]] = [None] * len(batches)
+    todo = []
+    for i, (audios, tokens, _, onset_offset, _, _) in enumerate(batches):
+        if len(audios) != 1:
+            raise ValueError(f"evaluate_batches(group={group}): batch {i} holds {len(audios)} clips; grouping is defined for one-clip batches "
+                             "(the reference couples the clips of a larger batch)")
+        labels = lut(tokens) if lut is not None else torch.as_tensor(tokens)
+        if onset_offset == (None,):
+            continue
+        todo.append((i, audios[0], labels, onset_offset))
+
+    def flush(items):
+        if not items:
+            return
+        rows = [[int(v) for v in torch.as_tensor(lab)[0].tolist() if int(v) != -100] for _, _, lab, _ in items]
+        res = model.align([a for _, a, _, _ in items], rows, use_ctc=use_ctc_loss, per_clip=True)
+        for (i, _, _, gt), r in zip(items, res):
+            maes[i] = get_mae(gt, [r])
+
+    pending = []
+    for item in todo:
+        if len(item[1]) > PER_CLIP_MAX_SAMPLES:
+            maes[item[0]] = get_mae(item[3], model.align([item[1]], item[2], use_ctc=use_ctc_loss))
+            continue
+        pending.append(item)
+        if len(pending) == group:
+            flush(pending)
+            pending = []
+    flush(pending)
+    return maes
+
+
 def evaluate_batches(model, batches: Sequence[Any], lut: Optional[PinyinClassLUT] = None, use_ctc_loss: bool = False,
-                     two_step: bool = False, rank: int = 0, world: int = 1):
+                     two_step: bool = False, rank: int = 0, world: int = 1, group: int = 1):
     """batches: sequence of (audios, tokens, _, lyric_word_onset_offset, _, _) as the reference's DataLoader yields.
-    Returns (avg_mae, per_batch_maes) with skipped batches as None; identical on every rank."""
+    Returns (avg_mae, per_batch_maes) with skipped batches as None; identical on every rank.
+    group (addition; default 1 = one device call per batch): `group` consecutive ONE-clip batches (the reference's default
+    --batch-size 1) share one device call through AlignModel.align(per_clip=True); per-batch MAEs, skipped batches and the mean of
+    per-batch means are those of group = 1.  A batch of more than one clip with group > 1 is a ValueError; so are two_step and
+    world > 1 (the grouped path is the fused, single-rank one)."""
+    if int(group) < 1:
+        raise ValueError("evaluate_batches: group must be >= 1")
+    if int(group) > 1:
+        if two_step or world != 1:
+            raise ValueError("evaluate_batches: group > 1 goes with two_step=False and world=1")
+        with torch.no_grad():
+            maes = _evaluate_grouped(model, batches, lut, use_ctc_loss, int(group))
+        done = [m for m in maes if m is not None]
+        total = 0
+        for m in done:
+            total += m
+        return (total / len(done) if done else float("nan")), maes
 
     def run(i: int):
         audios, tokens, _, onset_offset, _, _ = batches[i]
@@ -59,11 +113,44 @@ def evaluate_batches(model, batches: Sequence[Any], lut: Optional[PinyinClassLUT
     return avg, maes
 
 
+def _align_records_batched(model, records: List[Any], lut, tokenize, use_ctc_loss: bool, with_confidence: bool, batch_size: int) -> List[list]:
+    """align_records with records of at most 30 s sorted by length and aligned `batch_size` at a time (per_clip=True: each as if alone);
+    results in the caller's order.  Longer records go one at a time through the dense long-form call."""
+    out: List[Optional[list]] = [None] * len(records)
+    short = sorted((i for i, r in enumerate(records) if len(r.audio) <= PER_CLIP_MAX_SAMPLES), key=lambda i: len(records[i].audio))
+    for i, rec in enumerate(records):
+        if len(rec.audio) > PER_CLIP_MAX_SAMPLES:
+            out[i] = align_records(model, [rec], lut, tokenize, use_ctc_loss, with_confidence)[0]
+    for k in range(0, len(short), batch_size):
+        idx = short[k: k + batch_size]
+        labels = [[int(v) for v in lut(torch.tensor([tokenize(records[i].text)], dtype=torch.long))[0].tolist()] for i in idx]
+        audios = [records[i].audio for i in idx]
+        if with_confidence:
+            res, scores = model.align(audios, labels, use_ctc=use_ctc_loss, return_confidence=True, per_clip=True)
+        else:
+            res, scores = model.align(audios, labels, use_ctc=use_ctc_loss, per_clip=True), None
+        for j, i in enumerate(idx):
+            text = records[i].text
+            if with_confidence:
+                out[i] = [[res[j][n][0], res[j][n][1], text[n], scores[j]["occupancy"][n]] for n in range(len(res[j]))]
+            else:
+                out[i] = [[res[j][n][0], res[j][n][1], text[n]] for n in range(len(res[j]))]
+    return out
+
+
 def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, use_ctc_loss: bool = True,
-                  with_confidence: bool = False) -> List[list]:
+                  with_confidence: bool = False, batch_size: int = 1) -> List[list]:
     """inference_alignment_nogt.py:130-178: one record at a time, returns [[onset, offset, char], ...] per record.
     `tokenize(text) -> list[int]` are the BERT ids without [CLS]/[SEP] (the reference slices [1:-1], :158-163).
-    with_confidence (addition): each entry is [onset, offset, char, occupancy] (AlignModel.align(return_confidence=True))."""
+    with_confidence (addition): each entry is [onset, offset, char, occupancy] (AlignModel.align(return_confidence=True)).
+    batch_size (addition; default 1 = one record per device call, as the reference): records of at most 30 s are sorted by length and
+    aligned batch_size at a time with AlignModel.align(per_clip=True) -- every record's result is the one it gets alone -- and returned
+    in the caller's order; longer records go one at a time."""
+    if int(batch_size) < 1:
+        raise ValueError("align_records: batch_size must be >= 1")
+    if int(batch_size) > 1:
+        with torch.no_grad():
+            return _align_records_batched(model, list(records), lut, tokenize, use_ctc_loss, with_confidence, int(batch_size))
     out = []
     with torch.no_grad():
         for rec in records:

@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from .. import _lib, ops
-from ..audio_frontend import log_mel_spectrogram
+from ..audio_frontend import log_mel_spectrogram, log_mel_spectrogram_per_clip
 from ..engine import N_CTX, N_FRAMES, AlignEngine, pack_decoder, pack_encoder, pack_head
 from ..whisper_compat import pad_or_trim
 
@@ -298,11 +298,38 @@ class AlignModel(torch.nn.Module):
             transcribe_logit = eng.decode(y_in, feats, N_CTX)
         return align_logit, transcribe_logit
 
+    # ------------------------------------------------------------------ clips of different lengths, each as if alone (addition)
+    def _features_per_clip(self, audios: Sequence[np.ndarray]):
+        """-> (feats rows [B*1500, d], B, Tmax, n_frames device int32 [B], T list[int]): ONE log-mel launch set and ONE encoder batch over
+        clips of at most 30 s; clip b's log-mel is its own (log_mel_spectrogram_per_clip) and T_b = round(n_mel_b / 2) as frame_plan has it."""
+        if audios is None or len(audios) == 0:
+            raise ValueError("per_clip: a non-empty sequence of waveforms is expected")
+        n_mel = [len(a) // 160 for a in audios]
+        if max(n_mel) > N_FRAMES:
+            raise ValueError(f"per_clip: clips of more than 30 s ({max(n_mel)} > {N_FRAMES} mel frames) are not batched per clip; "
+                             "align them one at a time (the long-form path)")
+        eng = self.engine()
+        mel, n_mel = log_mel_spectrogram_per_clip(audios, device=eng.device, out_frames=N_FRAMES)
+        T = [frame_plan(n, True)[0][2] for n in n_mel]
+        feats = eng.encode(mel)
+        return feats, len(T), max(1, max(T)), torch.tensor(T, dtype=torch.int32).to(eng.device), T
+
+    @torch.no_grad()
+    def frame_logits_per_clip(self, audios: Sequence[np.ndarray]) -> List[torch.Tensor]:
+        """Materialised logits of a ragged batch: list of [T_b, V] float32 device tensors, clip b's being frame_manual_forward([audios[b]])'s
+        -- one log-mel launch set, one encoder batch, one head launch set for all clips (the two-step route: perform_viterbi(_ctc) on
+        torch.nn.utils.rnn.pad_sequence of them with n_frames=)."""
+        feats, B, Tmax, nf, T = self._features_per_clip(audios)
+        eng = self.engine()
+        out = eng.logits(feats, B, Tmax, N_CTX, n_frames=nf)
+        eng.check_gru()
+        return [out[b, : T[b]] for b in range(B)]
+
     # ------------------------------------------------------------------ fused fast path (addition)
     @torch.no_grad()
     def align(self, audios: Optional[Sequence[np.ndarray]] = None, labels=None, *, mel: Optional[torch.Tensor] = None,
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
-              return_confidence: bool = False, boundary_window: int = 2):
+              return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -310,25 +337,38 @@ class AlignModel(torch.nn.Module):
         return_confidence (addition; the reference has no counterpart): -> (seconds, scores), scores[b] = {"occupancy": [L],
         "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} -- posteriors under the model from the
         forward-backward sweep of the same lattice (ops.alignment_posteriors; boundary_window in frames), not accuracies.
-        With return_frames the device tensors: (onset, offset, score, status, occupancy, onset_prob, offset_prob, log_z)."""
+        With return_frames the device tensors: (onset, offset, score, status, occupancy, onset_prob, offset_prob, log_z).
+        per_clip (addition; default False = the reference's batch semantics: every waveform zero-padded to the batch maximum before the
+        log-mel, one -8 floor and ONE frame count for the whole batch, so a shorter clip's result depends on its batch mates): with True
+        clip b's result is what this call returns for [audios[b]] alone -- its own log-mel, T_b = round(n_mel_b / 2) frames, both GRU layers,
+        the DP and the posteriors over exactly T_b frames -- while the batch still shares one log-mel launch set, one encoder batch, one
+        head launch set and one DP launch.  Needs `audios` (not `mel`), get_orig_len=True and clips of at most 30 s (ValueError)."""
         from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames
         eng = self.engine()
-        if mel is None:
-            mel = self._mel_of(audios)
-        feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
+        kw = {}
+        if per_clip:
+            if mel is not None or not get_orig_len:
+                raise ValueError("align(per_clip=True) takes waveforms (audios=) and get_orig_len=True")
+            feats, B, T, nf_clip, _ = self._features_per_clip(audios)
+            stride = N_CTX
+            kw["n_frames"] = nf_clip
+        else:
+            if mel is None:
+                mel = self._mel_of(audios)
+            feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
         if return_confidence:
             onset, offset, score, status, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
                                                                        _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
-                                                                       want_emissions=True)
-            nf = torch.full((B,), T, dtype=torch.int32, device=eng.device)
+                                                                       want_emissions=True, **kw)
+            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
             occ, onp, offp, log_z, _ = ops.alignment_posteriors(em, lab_dev, n_lab, nf, onset, offset, boundary_window)
             if return_frames:
                 return onset, offset, score, status, occ, onp, offp, log_z
             seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second)
             return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists)
         onset, offset, score, status = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
-                                                               _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN)
+                                                               _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN, **kw)
         if return_frames:
             return onset, offset, score, status
         return _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second)

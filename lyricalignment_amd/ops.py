@@ -360,11 +360,50 @@ def attention(qkv: torch.Tensor, batch: int, frames: int, n_head: int, out: Opti
     return out
 
 
+def _frame_counts(n_frames: torch.Tensor, batch: int, what: str) -> torch.Tensor:
+    """Per-clip frame counts of the ragged entry points: a device int32 [batch] tensor (values are the caller's to keep <= frames: they
+    live on the device and are not read back here)."""
+    _dev(n_frames, "n_frames", torch.int32)
+    if n_frames.shape != (batch,):
+        raise ValueError(f"{what}: n_frames must be int32 [{batch}]")
+    return n_frames.contiguous()
+
+
+def logmel_ragged(audio: torch.Tensor, n_samples, consts: torch.Tensor, out_frames: int = 3000) -> torch.Tensor:
+    """la_logmel_ragged_f32_prepared: audio [B, Nmax] f32 (device; clip b = the first n_samples[b] samples of row b), n_samples = host
+    sequence of ints -> mel [B, 80, out_frames] f32: each clip's own log-mel (its own reflect padding and -8 floor) in frames
+    0 .. n_samples[b] // 160 - 1, zeros after.  Clips of fewer than 201 samples are refused here (the reflect padding needs them)."""
+    _dev(audio, "audio", torch.float32); _dev(consts, "consts", torch.uint8)
+    if audio.dim() != 2 or not audio.is_contiguous():
+        raise ValueError("logmel_ragged: audio must be contiguous [B, Nmax]")
+    B, N = audio.shape
+    ns = [int(v) for v in n_samples]
+    if len(ns) != B:
+        raise ValueError("logmel_ragged: one sample count per clip expected")
+    if any(v < 201 for v in ns):
+        raise ValueError("logmel_ragged: every clip needs more than 200 samples (reflect padding)")
+    if any(v > N for v in ns):
+        raise ValueError("logmel_ragged: a sample count exceeds the row length")
+    if N // 160 > int(out_frames):
+        raise ValueError("logmel_ragged: out_frames < Nmax // 160")
+    nsd = torch.tensor(ns, dtype=torch.int32).to(audio.device)
+    mel = torch.empty((B, 80, int(out_frames)), dtype=torch.float32, device=audio.device)
+    need = ctypes.c_size_t(0)
+    check(lib().la_logmel_ragged_workspace_bytes(B, N, ctypes.byref(need)), "logmel_ragged_workspace_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=audio.device)
+    check(lib().la_logmel_ragged_f32_prepared(ptr(audio), ptr(nsd), B, N, ptr(consts), ptr(mel), mel.stride(0), mel.stride(1), int(out_frames),
+                                              ptr(ws), need.value, stream_ptr()), "logmel_ragged_f32_prepared")
+    return mel
+
+
 def gru_layer(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor, out: Optional[torch.Tensor] = None,
-              want_mish: bool = False, out_mish: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None):
+              want_mish: bool = False, out_mish: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None,
+              n_frames: Optional[torch.Tensor] = None):
     """gi [B,T,2,3H] f32; w_hh [2,3H,H] (f32 | bf16); b_hh [2,3H] f32 -> out [B,T,2H] (w_hh dtype) [, Mish(out)].
     `out_mish`: caller-owned [B,T,2H] buffer for Mish(out) (implies want_mish); `flag`: caller-owned int32 [1] word the
-    kernel sets when one of its bounded waits times out (default: a fresh zeroed one per call)."""
+    kernel sets when one of its bounded waits times out (default: a fresh zeroed one per call).
+    `n_frames` (device int32 [B], values <= T): per-clip lengths (la_gru_layer_ragged) -- rows t < n_frames[b] are the clip's own
+    recurrence over n_frames[b] frames, rows past them unspecified."""
     _dev(gi, "gi", torch.float32); _dev(w_hh, "w_hh"); _dev(b_hh, "b_hh", torch.float32)
     dt = dtype_code(w_hh.dtype)
     if gi.dim() != 4 or gi.shape[2] != 2 or not gi.is_contiguous() or not w_hh.is_contiguous() or not b_hh.is_contiguous():
@@ -389,8 +428,13 @@ def gru_layer(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor, out: Opt
     if flag is None:
         flag = torch.zeros((1,), dtype=torch.int32, device=gi.device)
     _dev(flag, "flag", torch.int32)
-    check(lib().la_gru_layer(dt, ptr(gi), ptr(w_hh), ptr(b_hh), ptr(out), ptr(out_mish), B, T, H, ptr(ws), need.value,
-                             ptr(flag), stream_ptr()), "gru_layer")
+    if n_frames is not None:
+        nf = _frame_counts(n_frames, B, "gru_layer")
+        check(lib().la_gru_layer_ragged(dt, ptr(gi), ptr(w_hh), ptr(b_hh), ptr(out), ptr(out_mish), B, T, ptr(nf), H, ptr(ws), need.value,
+                                        ptr(flag), stream_ptr()), "gru_layer_ragged")
+    else:
+        check(lib().la_gru_layer(dt, ptr(gi), ptr(w_hh), ptr(b_hh), ptr(out), ptr(out_mish), B, T, H, ptr(ws), need.value,
+                                 ptr(flag), stream_ptr()), "gru_layer")
     return (out, out_mish, flag) if want_mish else (out, flag)
 
 
@@ -570,9 +614,10 @@ def encoder_forward(weights_c, mel: torch.Tensor, out: torch.Tensor, ws_cache: O
 
 def align_head_forward(weights_c, feats: torch.Tensor, clip_stride_rows: int, batch: int, frames: int, labels: torch.Tensor,
                        n_labels: torch.Tensor, variant: int, flag: torch.Tensor, want_emissions: bool = False,
-                       ws_cache: Optional[dict] = None):
+                       ws_cache: Optional[dict] = None, n_frames: Optional[torch.Tensor] = None):
     """la_align_head_forward: encoder rows -> BiGRU x 2 -> Mish -> fused FC + emission prep -> DP, ONE C call.
-    -> (onset, offset, score, status[, emissions])."""
+    -> (onset, offset, score, status[, emissions]).  n_frames (device int32 [batch], values <= frames): per-clip lengths
+    (la_align_head_forward_ragged)."""
     _dev(feats, "feats"); _dev(labels, "labels", torch.int32); _dev(n_labels, "n_labels", torch.int32); _dev(flag, "flag", torch.int32)
     if feats.dim() != 2 or feats.stride(1) != 1 or feats.shape[1] != weights_c.in_dim:
         raise ValueError("align_head_forward: feats must be [rows, in_dim] with unit inner stride")
@@ -588,7 +633,14 @@ def align_head_forward(weights_c, feats: torch.Tensor, clip_stride_rows: int, ba
     need = ctypes.c_size_t(0)
     check(lib().la_align_head_workspace_bytes(ctypes.byref(weights_c), batch, frames, Lmax, ctypes.byref(need)), "align_head_workspace_bytes")
     ws = _workspace(need.value, dev, ws_cache, "head")
-    check(lib().la_align_head_forward(ctypes.byref(weights_c), ptr(feats), feats.stride(0), clip_stride_rows, batch, frames, variant,
-                                      ptr(labels), labels.stride(0), ptr(n_labels.contiguous()), Lmax, ptr(onset), ptr(offset), Lmax,
-                                      ptr(score), ptr(status), ptr(em), ptr(ws), ws.numel(), ptr(flag), stream_ptr()), "align_head_forward")
+    if n_frames is not None:
+        nf = _frame_counts(n_frames, batch, "align_head_forward")
+        check(lib().la_align_head_forward_ragged(ctypes.byref(weights_c), ptr(feats), feats.stride(0), clip_stride_rows, batch, frames, ptr(nf), variant,
+                                                 ptr(labels), labels.stride(0), ptr(n_labels.contiguous()), Lmax, ptr(onset), ptr(offset), Lmax,
+                                                 ptr(score), ptr(status), ptr(em), ptr(ws), ws.numel(), ptr(flag), stream_ptr()),
+              "align_head_forward_ragged")
+    else:
+        check(lib().la_align_head_forward(ctypes.byref(weights_c), ptr(feats), feats.stride(0), clip_stride_rows, batch, frames, variant,
+                                          ptr(labels), labels.stride(0), ptr(n_labels.contiguous()), Lmax, ptr(onset), ptr(offset), Lmax,
+                                          ptr(score), ptr(status), ptr(em), ptr(ws), ws.numel(), ptr(flag), stream_ptr()), "align_head_forward")
     return (onset, offset, score, status, em) if want_emissions else (onset, offset, score, status)

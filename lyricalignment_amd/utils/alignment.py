@@ -74,7 +74,7 @@ def _device_of(prediction) -> torch.device:
     return torch.device(f"cuda:{torch.cuda.current_device()}")
 
 
-def _perform(prediction, labels, hop_size_second, variant, boundary_window=None):
+def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -84,7 +84,13 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None)
     B, T, V = pred.shape
     lab, n_lab, lists = _labels_to_device(labels, B, dev)
     em = ops.emissions_from_logits(pred, lab, n_lab, variant)
-    nf = torch.full((B,), T, dtype=torch.int32, device=dev)
+    if n_frames is None:
+        nf = torch.full((B,), T, dtype=torch.int32, device=dev)
+    else:                                    # (addition) utterance b owns the first n_frames[b] rows of a zero-padded [B, Tmax, V] prediction
+        counts = [int(v) for v in (n_frames.tolist() if torch.is_tensor(n_frames) else n_frames)]
+        if len(counts) != B or any(v < 0 or v > T for v in counts):
+            raise ValueError(f"n_frames: {B} frame counts in 0..{T} expected")
+        nf = torch.tensor(counts, dtype=torch.int32).to(dev)
     onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
     seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second)
     if boundary_window is None:
@@ -93,24 +99,26 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None)
     return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists)
 
 
-def perform_viterbi(prediction, labels, hop_size_second=0.02):
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN)
+def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None):
+    """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
+    aligned over its first n_frames[b] rows, as if it had been handed over alone."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames)
 
 
-def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02):
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC)
+def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None):
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames)
 
 
-def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2):
+def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None):
     """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
     scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
     sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi."""
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window))
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames)
 
 
-def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2):
+def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None):
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window))
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames)
 
 
 def run_viterbi_core(dp_matrix, backtrace_dp_matrix, cur_log_prediction, cur_log_silence_prediction, cur_label):
