@@ -185,6 +185,40 @@ int la_viterbi_core(const float *em, int64_t em_row_stride, const int32_t *label
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same DP on a lattice with OPTIONAL label spans (no counterpart in the reference, where every label must occupy at
+ * least one frame): lyric sheets whose lines are not all sung.  Every argument of la_viterbi_batch in the same order, then
+ * skip_from [batch][skip_stride] int32 (device, skip_stride >= max_labels + 1; entries 0 .. L_b of row b are read) and
+ * skip_penalty >= 0 (float64).  skip_from[b][n] = a with 0 <= a < n declares labels a .. n-1 an optional span: a path may
+ * pass from before label a to position n without visiting them.  Any other value (-1 by convention) means "no span ends
+ * at n" and is never used as an index; one span per end position; n = L_b is a span at the end of the lyrics.  The two
+ * states at position n -- 2n (the silence before label n, the final silence when n = L_b) and 2n+1 (label n, n < L_b) --
+ * get two more predecessors: J = 2a, the silence before the span (always), and J-1 = 2a-1, the label before it (a >= 1;
+ * into 2n+1 only if labels[n] != labels[a-1], the equal-neighbour rule).  Per state and frame: the existing rule picks
+ * (best, source) among k, k-1, k-2; then dp[J] - skip_penalty replaces it if STRICTLY greater, then dp[J-1] - skip_penalty
+ * likewise; the emission is added last.  Start states and termination are la_viterbi_batch's, so a skipped span at either
+ * end of the lyrics costs one frame of the silence state there, and two adjacent spans skipped together one frame of the
+ * silence between them.  All float64 adds and subtracts in this order: bit-reproducible; with every entry -1 the outputs
+ * are la_viterbi_batch's bit for bit.
+ * Outputs as la_viterbi_batch; labels inside a span whose jump the best path took get onset = offset = -1 with status
+ * LA_OK; LA_EINFEASIBLE only if a label is unvisited and not inside a taken jump.
+ * Limit: max_labels <= 511 (one lane per lattice state), LA_EUNSUPPORTED above.  Backpointers are three 64-bit masks per
+ * wave per frame: `workspace` (8-byte aligned) is needed when la_viterbi_spans_workspace_bytes() > 0 (batch * max_frames *
+ * waves * 24 bytes, once the masks no longer fit in LDS).  Argument errors (a negative or NaN skip_penalty included) are
+ * answered on the host before anything is enqueued; never synchronises, allocates or frees.  Option viterbi_dpp = 0 pins
+ * the LDS-exchange form for lattices of at most 64 states, as for la_viterbi_batch.
+ */
+int la_viterbi_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                           const int32_t *labels, int32_t labels_stride,
+                           const int32_t *n_labels, const int32_t *n_frames,
+                           int32_t batch, int32_t max_frames, int32_t max_labels,
+                           int32_t *onset, int32_t *offset, int32_t out_stride,
+                           double *final_score, int32_t *status,
+                           const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
  * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
  * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable

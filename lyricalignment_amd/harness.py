@@ -163,3 +163,30 @@ def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, 
             res = model.align([rec.audio], lut(ids), use_ctc=use_ctc_loss)[0]
             out.append([[res[j][0], res[j][1], rec.text[j]] for j in range(len(res))])
     return out
+
+
+def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
+                       use_ctc_loss: bool = True, skip_penalty: float = 0.0) -> List[Optional[list]]:
+    """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
+    optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
+    align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
+    [[onset, offset, char], ...] (AlignModel.align(optional_spans=...), skip_penalty >= 0 per skipped line)."""
+    from .utils.alignment import spans_from_lines
+    lines = list(lines)
+    ids = [list(tokenize(line)) for line in lines]
+    for line, tok in zip(lines, ids):
+        if len(tok) != len(line):
+            raise ValueError(f"align_record_lines: {len(tok)} tokens for the {len(line)} characters of {line!r}")
+    skip_from = spans_from_lines([len(t) for t in ids], optional)
+    spans = [(a, n) for n, a in enumerate(skip_from) if a >= 0]
+    labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
+    with torch.no_grad():
+        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)[0]
+    out: List[Optional[list]] = []
+    pos = 0
+    for line in lines:
+        part = res[pos: pos + len(line)]
+        pos += len(line)
+        # a span is taken or left as a whole: its characters are None together
+        out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
+    return out

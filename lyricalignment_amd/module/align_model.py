@@ -329,7 +329,8 @@ class AlignModel(torch.nn.Module):
     @torch.no_grad()
     def align(self, audios: Optional[Sequence[np.ndarray]] = None, labels=None, *, mel: Optional[torch.Tensor] = None,
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
-              return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False):
+              return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
+              skip_penalty: float = 0.0):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -342,8 +343,12 @@ class AlignModel(torch.nn.Module):
         log-mel, one -8 floor and ONE frame count for the whole batch, so a shorter clip's result depends on its batch mates): with True
         clip b's result is what this call returns for [audios[b]] alone -- its own log-mel, T_b = round(n_mel_b / 2) frames, both GRU layers,
         the DP and the posteriors over exactly T_b frames -- while the batch still shares one log-mel launch set, one encoder batch, one
-        head launch set and one DP launch.  Needs `audios` (not `mel`), get_orig_len=True and clips of at most 30 s (ValueError)."""
-        from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames
+        head launch set and one DP launch.  Needs `audios` (not `mel`), get_orig_len=True and clips of at most 30 s (ValueError).
+        optional_spans (addition): optional_spans[b] = list of (a, n) pairs -- labels a .. n-1 of clip b (a lyric line that may not be sung)
+        may be left out by the path; the head's emissions go through the DP on the lattice with optional spans (ops.viterbi_spans_batch,
+        skip_penalty >= 0 per taken jump) and skipped characters come back as None (onset = offset = -1 with return_frames).  None or
+        all-empty: the call as it was.  Not with return_confidence (ValueError: no posteriors over that lattice); at most 511 labels."""
+        from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames, _skip_from_of_spans
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -357,6 +362,17 @@ class AlignModel(torch.nn.Module):
                 mel = self._mel_of(audios)
             feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
+        skip_from = _skip_from_of_spans(optional_spans, lab_lists)
+        if skip_from is not None:
+            if return_confidence:
+                raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice)")
+            *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
+                                             want_emissions=True, **kw)
+            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
+            onset, offset, score, status = ops.viterbi_spans_batch(em, lab_dev, n_lab, nf, skip_from.to(eng.device), skip_penalty)
+            if return_frames:
+                return onset, offset, score, status
+            return _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=True)
         if return_confidence:
             onset, offset, score, status, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
                                                                        _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,

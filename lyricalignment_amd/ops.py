@@ -61,6 +61,40 @@ def viterbi_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor
     return onset, offset, score, status
 
 
+def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                        skip_from: torch.Tensor, skip_penalty: float = 0.0
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """la_viterbi_spans_batch: viterbi_batch on the lattice with optional label spans.  skip_from [B, >= Lmax+1] i32 (device):
+    skip_from[b, n] = a (0 <= a < n) makes labels a..n-1 of clip b optional, anything else = no span ends at n.
+    -> the tuple of viterbi_batch; labels inside a taken jump have onset = offset = -1 under status LA_OK."""
+    _dev(em, "em", torch.float32); _dev(labels, "labels", torch.int32)
+    _dev(n_labels, "n_labels", torch.int32); _dev(n_frames, "n_frames", torch.int32); _dev(skip_from, "skip_from", torch.int32)
+    if em.dim() != 3 or labels.dim() != 2 or em.stride(2) != 1 or labels.stride(1) != 1:
+        raise ValueError("viterbi_spans_batch: em [B,T,E] / labels [B,Lmax] with unit inner stride expected")
+    B, T, E = em.shape
+    Lmax = labels.shape[1]
+    if labels.shape[0] != B or n_labels.shape != (B,) or n_frames.shape != (B,) or E < Lmax + 1:
+        raise ValueError("viterbi_spans_batch: inconsistent shapes")
+    if skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1:
+        raise ValueError("viterbi_spans_batch: skip_from [B, >= Lmax+1] with unit inner stride expected")
+    skip_penalty = float(skip_penalty)
+    if not skip_penalty >= 0.0:
+        raise ValueError("viterbi_spans_batch: skip_penalty must be >= 0")
+    n_labels = n_labels.contiguous(); n_frames = n_frames.contiguous()
+    onset = torch.empty((B, Lmax), dtype=torch.int32, device=em.device)
+    offset = torch.empty((B, Lmax), dtype=torch.int32, device=em.device)
+    score = torch.empty((B,), dtype=torch.float64, device=em.device)
+    status = torch.empty((B,), dtype=torch.int32, device=em.device)
+    need = ctypes.c_size_t(0)
+    check(lib().la_viterbi_spans_workspace_bytes(B, T, Lmax, ctypes.byref(need)), "viterbi_spans_workspace_bytes")
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=em.device)
+    check(lib().la_viterbi_spans_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
+                                       ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
+                                       ptr(skip_from), skip_from.stride(0), skip_penalty, ptr(ws), need.value, stream_ptr()),
+          "viterbi_spans_batch")
+    return onset, offset, score, status
+
+
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
                          onset: torch.Tensor, offset: torch.Tensor, boundary_window: int = 2, want_gamma: bool = False):
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,

@@ -40,7 +40,48 @@ def _labels_to_device(labels, batch: int, device) -> Tuple[torch.Tensor, torch.T
     return lab.to(device), n.to(device), lists
 
 
-def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second):
+def spans_from_lines(line_lengths: Sequence[int], optional: Sequence[bool]) -> List[int]:
+    """One clip's skip_from array (include/lyricalign.h la_viterbi_spans_batch) for lyrics given as consecutive lines of
+    line_lengths[i] characters: L + 1 entries, skip_from[end of line i] = start of line i for every line with optional[i], -1 elsewhere."""
+    lengths = [int(v) for v in line_lengths]
+    if len(lengths) != len(optional):
+        raise ValueError("spans_from_lines: one optional flag per line expected")
+    if any(v <= 0 for v in lengths):
+        raise ValueError("spans_from_lines: every line must hold at least one character")
+    skip_from = [-1] * (sum(lengths) + 1)
+    a = 0
+    for n_chars, opt in zip(lengths, optional):
+        if opt:
+            skip_from[a + n_chars] = a
+        a += n_chars
+    return skip_from
+
+
+def _skip_from_of_spans(optional_spans, label_lists: List[List[int]]):
+    """optional_spans[b] = list of (a, n) pairs: labels a .. n-1 of utterance b may be skipped -> host int32 tensor [B, Lmax + 1] of
+    skip_from rows (-1 = none), or None when no utterance has a span.  ValueError for a < 0, a >= n, n > L_b or two spans with one end."""
+    if optional_spans is None:
+        return None
+    if len(optional_spans) != len(label_lists):
+        raise ValueError(f"optional_spans: {len(label_lists)} span lists expected, one per utterance")
+    Lmax = max(1, max((len(l) for l in label_lists), default=1))
+    rows = torch.full((len(label_lists), Lmax + 1), -1, dtype=torch.int32)
+    any_span = False
+    for b, spans in enumerate(optional_spans):
+        L = len(label_lists[b])
+        for a, n in (spans or ()):
+            a, n = int(a), int(n)
+            if a < 0 or a >= n or n > L:
+                raise ValueError(f"optional_spans[{b}]: span ({a}, {n}) needs 0 <= a < n <= {L}")
+            if int(rows[b, n]) >= 0:
+                raise ValueError(f"optional_spans[{b}]: two spans end at {n} (one span per end position)")
+            rows[b, n] = a
+            any_span = True
+    return rows if any_span else None
+
+
+def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second, skipped_as_none: bool = False):
+    """skipped_as_none (the span lattice): a label with onset -1 under LA_OK was inside a taken jump -> None in place of [onset, offset]."""
     on, off, st = onset.cpu().numpy(), offset.cpu().numpy(), status.cpu().numpy()
     result = []
     for b, labs in enumerate(label_lists):
@@ -51,7 +92,8 @@ def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second):
             raise ValueError(f"{k} is not in list")                                         # (:183)
         if st[b] != LA_OK:
             raise _lib.LyricAlignHipError(f"viterbi status {int(st[b])} for utterance {b}")
-        result.append([[float(int(on[b, n])) * hop_size_second, float(int(off[b, n])) * hop_size_second]
+        result.append([None if (skipped_as_none and on[b, n] < 0) else
+                       [float(int(on[b, n])) * hop_size_second, float(int(off[b, n])) * hop_size_second]
                        for n in range(len(labs))])                                         # (:185) float(frame) * hop
     return result
 
@@ -74,7 +116,7 @@ def _device_of(prediction) -> torch.device:
     return torch.device(f"cuda:{torch.cuda.current_device()}")
 
 
-def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None):
+def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -91,6 +133,12 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         if len(counts) != B or any(v < 0 or v > T for v in counts):
             raise ValueError(f"n_frames: {B} frame counts in 0..{T} expected")
         nf = torch.tensor(counts, dtype=torch.int32).to(dev)
+    skip_from = _skip_from_of_spans(optional_spans, lists)
+    if skip_from is not None:                # (addition) the lattice with optional spans; None / all-empty takes the path below unchanged
+        if boundary_window is not None:
+            raise ValueError("posteriors over the lattice with optional spans are not defined: optional_spans goes without confidence")
+        onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_from.to(dev), skip_penalty)
+        return _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=True)
     onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
     seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second)
     if boundary_window is None:
@@ -99,14 +147,19 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists)
 
 
-def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None):
+def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
-    aligned over its first n_frames[b] rows, as if it had been handed over alone."""
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames)
+    aligned over its first n_frames[b] rows, as if it had been handed over alone.
+    optional_spans (addition): optional_spans[b] = list of (a, n) pairs, labels a .. n-1 of utterance b may be left out by the path
+    (la_viterbi_spans_batch; skip_penalty >= 0 per taken jump); skipped characters come back as None in place of [onset, offset].
+    None or all-empty: today's DP.  ValueError for a < 0, a >= n, n > L or two spans with one end."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
+                    skip_penalty=skip_penalty)
 
 
-def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None):
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames)
+def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0):
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
+                    skip_penalty=skip_penalty)
 
 
 def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None):
