@@ -15,9 +15,11 @@
 //                    as the Viterbi kernel with max replaced by log-sum-exp)
 //   dense_grad       one workgroup per row: dlogits = scale * ( w_ctc_b * softmax_[0,V) + valid/n_valid * softmax_[1,V)
 //                    - one-hot terms ), column V gets the BCE gradient
-#include "la_common.h"
+#include "la_lattice.h"
 
 namespace {
+
+using namespace la::lattice;
 
 __device__ __forceinline__ float wave_max_f(float v) {
 #pragma unroll
@@ -29,14 +31,6 @@ __device__ __forceinline__ float wave_sum_f(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-// log(exp(a) + exp(b)), -inf safe.  float64: path scores reach -T*log(V) ~ -1e4, where float32 has ~1e-3 absolute
-// resolution and the occupancies exp(alpha+beta+nll-lp) lose 2-3 digits over a 1500-step recursion (measured 0.4 %).
-__device__ __forceinline__ double log_add(double a, double b) {
-    const double m = fmax(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log1p(exp(fmin(a, b) - m));
-}
-
 struct LossAcc {  // device accumulators (double): [0] sum CE, [1] #valid frames, [2] sum BCE, [3] sum_b nll_b / L_b, [4] #inf
     double v[8];
 };
@@ -191,22 +185,7 @@ __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, in
 // log-sum-exp with its maximum in float64 and the correction log(sum exp(x - max)) in float32 -- the correction lies in [0, ln 3], so its
 // float32 rounding is <= 1e-7 ABSOLUTE per step (the path scores themselves, ~ -1e4, stay float64: the reason the lattice is float64 at
 // all) -- and the emissions / stored alpha rows prefetched a block of 8 steps ahead of the chain.
-__device__ __forceinline__ double wave_shr1(double x, double fill) {      // lane i <- lane i-1, lane 0 <- fill
-    const int lo = __double2loint(x), hi = __double2hiint(x), flo = __double2loint(fill), fhi = __double2hiint(fill);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(fhi, hi, 0x138, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(flo, lo, 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double wave_shl1(double x, double fill) {      // lane i <- lane i+1, lane 63 <- fill
-    const int lo = __double2loint(x), hi = __double2hiint(x), flo = __double2loint(fill), fhi = __double2hiint(fill);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(fhi, hi, 0x130, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(flo, lo, 0x130, 0xf, 0xf, false));
-}
-// log(exp(a) + exp(b) + exp(c)), -inf safe
-__device__ __forceinline__ double log_add3(double a, double b, double c) {
-    const double m = fmax(a, fmax(b, c));
-    if (m == -INFINITY) return -INFINITY;
-    const float sum = __expf((float)(a - m)) + __expf((float)(b - m)) + __expf((float)(c - m));
-    return m + (double)__logf(sum);
-}
-
+// (la_lattice.h: wave_shr1 / wave_shl1 and log_add3.)
 __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logits, int64_t ld_b, int64_t ldl, int T, int V, const float *lse_all,
                                                               const int32_t *labels, int labels_stride, const int32_t *n_labels, double *alpha_ws,
                                                               int S_pad, float *dlogits, int64_t ldd_b, int64_t ldd, float scale, int batch,

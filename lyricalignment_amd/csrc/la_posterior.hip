@@ -16,12 +16,14 @@
 // frame.  Emissions and stored alpha rows are prefetched a block of steps (8; 4 in the multi-wave form) ahead of the dependency chain.
 //
 // Arithmetic: path scores are float64 (they reach -T * 35).  The log-sum-exp of a step takes its maximum in float64 and the
-// correction log(sum exp(x - max)), which lies in [0, ln 3], in float32 (la_loss.hip's form): <= ~1e-7 absolute per step,
+// correction log(sum exp(x - max)), which lies in [0, ln 3], in float32 (la_lattice.h log_add3, shared with la_loss.hip): <= ~1e-7 absolute per step,
 // and a third of the float64 exp / log latency on a kernel that is nothing but a 2T-step latency chain.  Unreachable cells
 // are -inf (weight zero); the DP's finite -1e7 is a max-product device and does not appear here.
-#include "la_common.h"
+#include "la_lattice.h"
 
 namespace {
+
+using namespace la::lattice;
 
 struct PostParams {
     const float *em;
@@ -41,35 +43,6 @@ struct PostParams {
     int64_t gamma_bs, gamma_rs;
     double *alpha_ws;  // [batch][max_frames][NT]
 };
-
-__device__ __forceinline__ double wave_shr1(double x, double fill) {  // lane i <- lane i-1, lane 0 <- fill
-    const int lo = __double2loint(x), hi = __double2hiint(x), flo = __double2loint(fill), fhi = __double2hiint(fill);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(fhi, hi, 0x138, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(flo, lo, 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double wave_shl1(double x, double fill) {  // lane i <- lane i+1, lane 63 <- fill
-    const int lo = __double2loint(x), hi = __double2hiint(x), flo = __double2loint(fill), fhi = __double2hiint(fill);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(fhi, hi, 0x130, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(flo, lo, 0x130, 0xf, 0xf, false));
-}
-// log(exp(a) + exp(b) [+ exp(c)]), -inf safe: float64 maximum, float32 correction
-__device__ __forceinline__ double log_add3(double a, double b, double c) {
-    const double m = fmax(a, fmax(b, c));
-    if (m == -INFINITY) return -INFINITY;
-    const float sum = __expf((float)(a - m)) + __expf((float)(b - m)) + __expf((float)(c - m));
-    return m + (double)__logf(sum);
-}
-__device__ __forceinline__ double log_add2(double a, double b) {
-    const double m = fmax(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    const float sum = __expf((float)(a - m)) + __expf((float)(b - m));
-    return m + (double)__logf(sum);
-}
-__device__ __forceinline__ double log_add_f64(double a, double b) {  // once per utterance: log_z
-    const double m = fmax(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log1p(exp(fmin(a, b) - m));
-}
 
 template <int NW, bool DPP>
 __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
@@ -165,7 +138,7 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     if (k == S - 2) fin[1] = a;
     __threadfence_block();   // the backward sweep of the multi-wave form reads alpha columns written by other lanes
     __syncthreads();
-    const double log_z = log_add_f64(fin[0], fin[1]);
+    const double log_z = log_add(fin[0], fin[1]);
     if (log_z == -INFINITY) { fail(LA_EINFEASIBLE, log_z); return; }  // no path at all: T too short for the labels
 
     // ---- backward: beta in a register, gamma / entry / exit per step, lane-local sums ----
@@ -267,14 +240,10 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     if (k == 0) { p.status[b] = LA_OK; p.log_z[b] = log_z; }
 }
 
-// one lane per state: the smallest power-of-two wave count that holds 2 * max_labels + 1 states; false above 16 waves
+// one lane per state; false above 16 waves
 bool plan_posterior(int max_labels, int *nw_out) {
-    const int S = 2 * max_labels + 1;
-    int nw = 1;
-    while (nw * 64 < S) nw *= 2;
-    if (nw > 16) return false;
-    *nw_out = nw;
-    return true;
+    *nw_out = waves_for_labels(max_labels);
+    return *nw_out <= 16;
 }
 
 template <int NW, bool DPP>

@@ -1,4 +1,4 @@
-// la_viterbi.hip -- batched forced-alignment DP for gfx950.
+// la_viterbi.hip -- batched forced-alignment DP for gfx950, on the reference's lattice and on the lattice with OPTIONAL label spans.
 //
 // Replaces utils/alignment.py:73-119 (run_viterbi_core) and :141-185 (init,
 // termination, backtrace, first/last frame per label) of the reference.
@@ -14,12 +14,30 @@
 // per wave per frame and kept in LDS when they fit (T * 16 B per wave), otherwise
 // in the caller's workspace.  The kernel is latency-bound (T dependent steps),
 // not bandwidth-bound: emissions are prefetched PF frames ahead into registers.
-#include "la_common.h"
+//
+// Optional spans (the SPANS instantiations, la_viterbi_spans_batch; no counterpart in the reference, whose lattice makes every
+// label occupy at least one frame).  States: 0 = leading silence, 2n+1 = label n, 2n+2 = the silence after it.  skip_from[n] = a
+// with 0 <= a < n declares labels a .. n-1 optional: the two states at position n (2n, and 2n+1 when n < L) get two more
+// predecessors, J = 2a (the silence before the span) and J-1 = 2a-1 (the label before it; a >= 1, and for the odd target
+// only when labels[n] != labels[a-1] -- the equal-neighbour rule).  Both are charged `penalty` and must beat the existing
+// rule's winner strictly, J before J-1.  Float64 adds / subtracts in that order: results are reproducible to the bit.
+// The single-wave form fetches the jump sources with ds_bpermute of p0 and of the already-shifted p1 (lane J of p1 holds
+// dp[J-1]); the multi-wave forms read dp[J] / dp[J-1] from the LDS row they exchange anyway.  "This clip has a span" is a
+// workgroup-uniform test taken ONCE, outside the frame loop: a span-free clip runs the loop of the plain DP, without any of the
+// jump code.  Backpointers are then five outcomes {stay, advance, skip, jump from J, jump from J-1}: three ballot masks per wave
+// per frame (T * 24 B per wave; the third is written and read only where spans exist), and J(s) stays in an LDS int array for
+// the backtrace thread.
+#include <type_traits>
+
+#include "la_lattice.h"
 
 namespace {
 
+using namespace la::lattice;
+
 constexpr double kNeg = -10000000.0;  // utils/alignment.py:144
 constexpr int PF = 8;                 // emission prefetch depth (frames)
+constexpr int kSkipped = -2;          // off_s marker of a label inside a taken jump (written out as -1)
 
 struct VitParams {
     const float *em;
@@ -33,32 +51,31 @@ struct VitParams {
     int32_t out_stride;
     double *final_score;
     int32_t *status;
-    unsigned long long *bt_global;  // [batch][max_frames][NW][2] when !bt_in_lds
+    // optional spans (SPANS instantiations only)
+    const int32_t *skip_from;
+    int32_t skip_stride;
+    double penalty;
+    unsigned long long *bt_global;  // [batch][max_frames][NW][2, with spans 3] when !bt_in_lds
     int32_t bt_in_lds;
     // run_viterbi_core face (DUMP instantiation only, batch 1): row 0 of dp is READ, rows >= 1 of dp / bt are written
     double *dp_dump;    // [T][S]
     long long *bt_dump; // [T][S]
 };
 
-__device__ __forceinline__ double wave_shr1(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    // DPP wave_shr:1 -- lane i receives lane i-1 across the whole wave64 (gfx9 family)
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x138, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-template <int NW, bool DPP, bool DUMP = false>
+template <int NW, bool DPP, bool SPANS, bool DUMP = false>
 __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     static_assert(!DPP || NW == 1, "DPP neighbour exchange is single-wave only");
+    static_assert(!DUMP || (!DPP && !SPANS), "the dp / bt dump is a face of the plain LDS-exchange form");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = NW * 64;
-    // carve: row exchange [2][NT+2] f64 | on/off [2][max_labels] i32 | bt masks
+    constexpr int MW = SPANS ? 3 : 2;  // backpointer mask words per wave per frame
+    // carve: row exchange [2][NT+2] f64 | on/off [2][max_labels] i32 | with spans: J [NT] i32 | bt masks
     double *rowbuf = reinterpret_cast<double *>(smem);
     int32_t *on_s = reinterpret_cast<int32_t *>(smem + 2 * (NT + 2) * sizeof(double));
     const int Lpad = (p.max_labels + 3) & ~3;
     int32_t *off_s = on_s + Lpad;
-    unsigned long long *bt_lds = reinterpret_cast<unsigned long long *>(off_s + Lpad);
+    int32_t *j_s = off_s + Lpad;
+    unsigned long long *bt_lds = reinterpret_cast<unsigned long long *>(j_s + (SPANS ? NT : 0));
 
     const int b = blockIdx.x;
     const int k = threadIdx.x;
@@ -83,17 +100,29 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         return;
     }
 
-    unsigned long long *bt = p.bt_in_lds ? bt_lds : p.bt_global + (int64_t)b * p.max_frames * NW * 2;
+    unsigned long long *bt = p.bt_in_lds ? bt_lds : p.bt_global + (int64_t)b * p.max_frames * NW * MW;
 
     const bool valid = k < S;
     const bool odd = (k & 1) != 0;
     const int n = k >> 1;
     const int col = (odd && valid) ? 1 + n : 0;
+    const int32_t *lab = p.labels + (int64_t)b * p.labels_stride;
     bool can_skip = false;  // label[k//2] != label[k//2-1], odd k >= 3 (:104)
-    if (odd && valid && k >= 3) {
-        const int32_t *lab = p.labels + (int64_t)b * p.labels_stride;
-        can_skip = lab[n] != lab[n - 1];
+    if (odd && valid && k >= 3) can_skip = lab[n] != lab[n - 1];
+    // the span that ends at this state's position n (n <= L for every valid state); anything outside 0 <= a < n is "none"
+    int J = -1;
+    bool jm1_ok = false;
+    if constexpr (SPANS) {
+        if (valid && n >= 1) {
+            const int a = p.skip_from[(int64_t)b * p.skip_stride + n];
+            if (a >= 0 && a < n) {
+                J = 2 * a;
+                jm1_ok = a >= 1 && (!odd || lab[n] != lab[a - 1]);
+            }
+        }
+        j_s[k] = J;
     }
+    const double pen = p.penalty;
     const float *emb = p.em + (int64_t)b * p.em_bs + col;
 
     // row 0 (:144-152); the run_viterbi_core face takes row 0 from the caller like the reference does (:73-76)
@@ -103,6 +132,9 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     if (!DPP) {
         if (k < 2) { rowbuf[k] = kNeg; rowbuf[NT + 2 + k] = kNeg; }  // slots for k-1, k-2 of states 0,1
     }
+    // workgroup-uniform (one wave: a ballot): a clip without a span runs a frame loop without any of the jump code
+    const bool has_span = SPANS && (NW == 1 ? __ballot(J >= 0) != 0ull : __syncthreads_or(J >= 0) != 0);
+    const int gather_addr = (J >= 0 ? J : lane) << 2;   // (single wave: J < S <= 64)
 
     float e_buf[PF];
 #pragma unroll
@@ -111,50 +143,74 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         e_buf[i] = jj < T ? emb[(int64_t)jj * p.em_rs] : 0.0f;
     }
     int parity = 0;
-    for (int j0 = 1; j0 < T; j0 += PF) {
-        float e_cur[PF];
+    auto sweep = [&](auto has_c) {
+        constexpr bool HAS = decltype(has_c)::value;  // this clip has a span
+        for (int j0 = 1; j0 < T; j0 += PF) {
+            float e_cur[PF];
 #pragma unroll
-        for (int i = 0; i < PF; ++i) e_cur[i] = e_buf[i];
+            for (int i = 0; i < PF; ++i) e_cur[i] = e_buf[i];
 #pragma unroll
-        for (int i = 0; i < PF; ++i) {
-            const int jj = j0 + PF + i;
-            e_buf[i] = jj < T ? emb[(int64_t)jj * p.em_rs] : 0.0f;
+            for (int i = 0; i < PF; ++i) {
+                const int jj = j0 + PF + i;
+                e_buf[i] = jj < T ? emb[(int64_t)jj * p.em_rs] : 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < PF; ++i) {
+                const int j = j0 + i;
+                if (j >= T) break;
+                double p0 = cur, p1, p2, pj = kNeg, pjm1 = kNeg;
+                if (DPP) {
+                    p1 = wave_shr1(p0, 0.0);
+                    p2 = wave_shr1(p1, 0.0);
+                    if (HAS) {
+                        pj = wave_gather(p0, gather_addr);
+                        pjm1 = wave_gather(p1, gather_addr);   // lane J of the shifted row holds dp[J-1]
+                    }
+                } else {
+                    double *rb = rowbuf + parity * (NT + 2);
+                    rb[k + 2] = p0;
+                    __syncthreads();
+                    p1 = rb[k + 1];
+                    p2 = rb[k];
+                    if (HAS && J >= 0) {
+                        pj = rb[J + 2];
+                        pjm1 = rb[J + 1];
+                    }
+                    parity ^= 1;
+                }
+                const bool stay = p0 > p1;                                   // strict (:85,:94,:110)
+                const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);      // (:104-105)
+                int code = skip ? 2 : (stay ? 0 : 1);
+                double best = skip ? p2 : (stay ? p0 : p1);
+                if (k == 0) { code = 0; best = p0; }                         // (:78-82)
+                if (HAS && J >= 0) {
+                    const double vj = pj - pen;
+                    if (vj > best) { best = vj; code = 3; }                  // strict, J before J-1
+                    if (jm1_ok) {
+                        const double vm = pjm1 - pen;
+                        if (vm > best) { best = vm; code = 4; }
+                    }
+                }
+                cur = best + (double)e_cur[i];
+                if (DUMP && valid) {
+                    p.dp_dump[(int64_t)j * S + k] = cur;
+                    p.bt_dump[(int64_t)j * S + k] = k - code;
+                }
+                const unsigned long long m0 = __ballot(code & 1);
+                const unsigned long long m1 = __ballot((code >> 1) & 1);
+                unsigned long long m2 = 0ull;
+                if (HAS) m2 = __ballot(code >> 2);
+                if (lane == 0) {
+                    unsigned long long *row = bt + ((int64_t)j * NW + wave) * MW;
+                    row[0] = m0;
+                    row[1] = m1;
+                    if (HAS) row[2] = m2;                                    // (read back only for states with a span)
+                }
+            }
         }
-#pragma unroll
-        for (int i = 0; i < PF; ++i) {
-            const int j = j0 + i;
-            if (j >= T) break;
-            double p0 = cur, p1, p2;
-            if (DPP) {
-                p1 = wave_shr1(p0);
-                p2 = wave_shr1(p1);
-            } else {
-                double *rb = rowbuf + parity * (NT + 2);
-                rb[k + 2] = p0;
-                __syncthreads();
-                p1 = rb[k + 1];
-                p2 = rb[k];
-                parity ^= 1;
-            }
-            const bool stay = p0 > p1;                                   // strict (:85,:94,:110)
-            const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);      // (:104-105)
-            int code = skip ? 2 : (stay ? 0 : 1);
-            double best = skip ? p2 : (stay ? p0 : p1);
-            if (k == 0) { code = 0; best = p0; }                         // (:78-82)
-            cur = best + (double)e_cur[i];
-            if (DUMP && valid) {
-                p.dp_dump[(int64_t)j * S + k] = cur;
-                p.bt_dump[(int64_t)j * S + k] = k - code;
-            }
-            const unsigned long long lo = __ballot(code & 1);
-            const unsigned long long hi = __ballot(code >> 1);
-            if (lane == 0) {
-                unsigned long long *row = bt + ((int64_t)j * NW + wave) * 2;
-                row[0] = lo;
-                row[1] = hi;
-            }
-        }
-    }
+    };
+    if (has_span) sweep(std::bool_constant<SPANS>{});
+    else sweep(std::false_type{});
 
     // termination + backtrace (:157-185) by one thread
     __syncthreads();
@@ -174,15 +230,27 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
             }
             knext = kk;
             if (j > 0) {
-                const unsigned long long *row = bt + ((int64_t)j * NW + (kk >> 6)) * 2;
+                const unsigned long long *row = bt + ((int64_t)j * NW + (kk >> 6)) * MW;
                 const int sh = kk & 63;
-                const int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
+                int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
+                if constexpr (SPANS) {
+                    if (has_span) {                      // (uniform: a span-free clip's backtrace is the plain DP's)
+                        const int Jk = j_s[kk];          // the third mask exists only where spans do
+                        if (Jk >= 0) code |= (int)((row[2] >> sh) & 1ull) << 2;
+                        if (code >= 3) {
+                            for (int m = Jk >> 1; m < (kk >> 1); ++m) off_s[m] = kSkipped;
+                            code = kk - (Jk - (code - 3));
+                        }
+                    }
+                }
                 kk -= code;
             }
         }
         int st = LA_OK;
-        for (int nn = 0; nn < L; ++nn)
-            if (on_s[nn] < 0) st = LA_EINFEASIBLE;  // reference: ValueError from list.index (:183)
+        for (int nn = 0; nn < L; ++nn) {
+            if (SPANS && off_s[nn] == kSkipped) off_s[nn] = -1;
+            else if (on_s[nn] < 0) st = LA_EINFEASIBLE;  // reference: ValueError from list.index (:183)
+        }
         p.status[b] = st;
     }
     __syncthreads();
@@ -191,7 +259,6 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         p.offset[(int64_t)b * p.out_stride + nn] = off_s[nn];
     }
 }
-
 
 // Lattices beyond 1024 states (whole songs with more than 511 characters; the reference's run_viterbi_core has no limit):
 // 1024 threads, each owning R CONSECUTIVE states k = tid*R + r, so 1024*R states per workgroup (R = 2, 4, 8 -> up to 4095
@@ -333,17 +400,15 @@ struct VitPlan {
     size_t ws_bytes;
 };
 
-constexpr size_t kLdsBudget = 160 * 1024 - 1024;
-
-bool plan_viterbi(int batch, int max_frames, int max_labels, VitPlan *pl) {
-    const int S = 2 * max_labels + 1;
-    int nw = 1;
-    while (nw * 64 < S) nw *= 2;
+// false: more labels than a workgroup holds -- 4095 for the plain DP (strip kernel, R = 8), 511 with spans (one lane per state)
+bool plan_viterbi(int batch, int max_frames, int max_labels, bool spans, VitPlan *pl) {
+    const int nw = waves_for_labels(max_labels);
     pl->strip = 0;
     if (nw > 16) {
+        const int S = 2 * max_labels + 1;
         int R = 2;
         while (1024 * R < S) R *= 2;
-        if (R > 8) return false;
+        if (spans || R > 8) return false;
         pl->strip = R;
         pl->nw = 16;
         pl->bt_in_lds = false;
@@ -351,9 +416,10 @@ bool plan_viterbi(int batch, int max_frames, int max_labels, VitPlan *pl) {
         pl->ws_bytes = (size_t)batch * max_frames * R * 32 * sizeof(unsigned long long);
         return true;
     }
-    const size_t fixed = 2 * (size_t)(nw * 64 + 2) * sizeof(double) + 2 * (size_t)((max_labels + 3) & ~3) * sizeof(int32_t);
+    const size_t fixed = 2 * (size_t)(nw * 64 + 2) * sizeof(double) + 2 * (size_t)((max_labels + 3) & ~3) * sizeof(int32_t) +
+                         (spans ? (size_t)nw * 64 * sizeof(int32_t) : 0);
     const size_t fixed_al = (fixed + 15) & ~(size_t)15;
-    const size_t bt_bytes = (size_t)max_frames * nw * 16;
+    const size_t bt_bytes = (size_t)max_frames * nw * (spans ? 3 : 2) * sizeof(unsigned long long);
     pl->nw = nw;
     pl->bt_in_lds = fixed_al + bt_bytes <= kLdsBudget;
     pl->lds_bytes = pl->bt_in_lds ? fixed_al + bt_bytes : fixed_al;
@@ -361,31 +427,88 @@ bool plan_viterbi(int batch, int max_frames, int max_labels, VitPlan *pl) {
     return true;
 }
 
-template <int NW, bool DPP>
-int launch_viterbi(const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
-    auto kern = viterbi_kernel<NW, DPP>;
+template <void (*Kern)(VitParams)>
+int launch(const char *timer, int threads, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
     static la::DeviceOnce attr_once;            // once per instantiation, to the planner's budget (pl.lds_bytes never exceeds it)
     if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
         attr_once.mark();
     }
-    la::TimerScope ts("viterbi", stream);
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(NW * 64), pl.lds_bytes, stream, p);
+    la::TimerScope ts(timer, stream);
+    hipLaunchKernelGGL(Kern, dim3(batch), dim3(threads), pl.lds_bytes, stream, p);
     LA_LAUNCH_CHECK();
     return LA_OK;
+}
+
+// the lane-per-state forms; the single wave takes its neighbours by DPP unless the option is off or dp / bt are dumped
+template <bool SPANS, bool DUMP>
+int launch_lanes(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
+    switch (pl.nw) {
+        case 1:
+            if (!DUMP && la::opts().viterbi_dpp) return launch<viterbi_kernel<1, true, SPANS>>(timer, 64, p, pl, batch, stream);
+            return launch<viterbi_kernel<1, false, SPANS, DUMP>>(timer, 64, p, pl, batch, stream);
+        case 2: return launch<viterbi_kernel<2, false, SPANS, DUMP>>(timer, 128, p, pl, batch, stream);
+        case 4: return launch<viterbi_kernel<4, false, SPANS, DUMP>>(timer, 256, p, pl, batch, stream);
+        case 8: return launch<viterbi_kernel<8, false, SPANS, DUMP>>(timer, 512, p, pl, batch, stream);
+        case 16: return launch<viterbi_kernel<16, false, SPANS, DUMP>>(timer, 1024, p, pl, batch, stream);
+    }
+    return LA_EUNSUPPORTED;
+}
+
+int query_workspace(bool spans, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", spans ? "viterbi_spans" : "viterbi");
+    VitPlan pl;
+    if (!plan_viterbi(batch, max_frames, max_labels, spans, &pl)) {
+        if (spans) la::set_error("viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)", max_labels);
+        else la::set_error("viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
+        return LA_EUNSUPPORTED;
+    }
+    *bytes = pl.ws_bytes;
+    return LA_OK;
+}
+
+// la_viterbi_batch (p.skip_from unused) and la_viterbi_spans_batch: p holds the caller's arguments, the workspace fields are set here
+int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    const char *who = spans ? "viterbi_spans_batch" : "viterbi_batch";
+    if (batch == 0) return LA_OK;
+    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && p.final_score && p.status && (!spans || p.skip_from),
+                 "%s: null pointer", who);
+    LA_CHECK_ARG(batch > 0 && p.max_frames > 0 && p.max_labels > 0, "%s: bad sizes", who);
+    LA_CHECK_ARG(!spans || p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
+    const bool strides_ok = p.em_rs >= p.max_labels + 1 && p.out_stride >= p.max_labels && p.labels_stride >= p.max_labels &&
+                            (!spans || p.skip_stride >= p.max_labels + 1);
+    VitPlan pl;
+    const bool planned = plan_viterbi(batch, p.max_frames, p.max_labels, spans, &pl);
+    // the label limit is reported after the strides by la_viterbi_batch and before them by la_viterbi_spans_batch
+    LA_CHECK_ARG(strides_ok || (spans && !planned), "%s: strides smaller than max_labels", who);
+    if (!planned) {
+        if (spans) la::set_error("viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)", p.max_labels);
+        else la::set_error("viterbi: max_labels %d exceeds 4095", p.max_labels);
+        return LA_EUNSUPPORTED;
+    }
+    LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes), "%s: workspace too small (%zu < %zu)", who,
+                 workspace_bytes, pl.ws_bytes);
+    LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+    p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
+    p.bt_in_lds = pl.bt_in_lds ? 1 : 0;
+    if (spans) return launch_lanes<true, false>("viterbi_spans", p, pl, batch, stream);
+    switch (pl.strip) {
+        case 0: return launch_lanes<false, false>("viterbi", p, pl, batch, stream);
+        case 2: return launch<viterbi_strip_kernel<2>>("viterbi", 1024, p, pl, batch, stream);
+        case 4: return launch<viterbi_strip_kernel<4>>("viterbi", 1024, p, pl, batch, stream);
+        case 8: return launch<viterbi_strip_kernel<8>>("viterbi", 1024, p, pl, batch, stream);
+    }
+    return LA_EUNSUPPORTED;
 }
 
 }  // namespace
 
 extern "C" int la_viterbi_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "viterbi_workspace_bytes: bad arguments");
-    VitPlan pl;
-    if (!plan_viterbi(batch, max_frames, max_labels, &pl)) {
-        la::set_error("viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
-        return LA_EUNSUPPORTED;
-    }
-    *bytes = pl.ws_bytes;
-    return LA_OK;
+    return query_workspace(false, batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_viterbi_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace(true, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -393,54 +516,20 @@ extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_
                                 const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
                                 int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (batch == 0) return LA_OK;
-    LA_CHECK_ARG(em && labels && n_labels && n_frames && onset && offset && final_score && status,
-                 "viterbi_batch: null pointer");
-    LA_CHECK_ARG(batch > 0 && max_frames > 0 && max_labels > 0, "viterbi_batch: bad sizes");
-    LA_CHECK_ARG(em_row_stride >= max_labels + 1 && out_stride >= max_labels && labels_stride >= max_labels,
-                 "viterbi_batch: strides smaller than max_labels");
-    VitPlan pl;
-    if (!plan_viterbi(batch, max_frames, max_labels, &pl)) {
-        la::set_error("viterbi: max_labels %d exceeds 4095", max_labels);
-        return LA_EUNSUPPORTED;
-    }
-    LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes),
-                 "viterbi_batch: workspace too small (%zu < %zu)", workspace_bytes, pl.ws_bytes);
-    LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "viterbi_batch: workspace must be 8-byte aligned");
     VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
-                max_labels, onset, offset, out_stride, final_score, status,
-                reinterpret_cast<unsigned long long *>(workspace), pl.bt_in_lds ? 1 : 0, nullptr, nullptr};
-    const bool no_dpp = !la::opts().viterbi_dpp;
-    if (pl.strip) {
-        la::TimerScope ts("viterbi", stream);
-#define LA_STRIP_CASE(RV)                                                                                                  \
-    case RV: {                                                                                                             \
-        static la::DeviceOnce attr_once;                                                                                     \
-        if (attr_once.pending()) {                                                                                                  \
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(viterbi_strip_kernel<RV>),                           \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));                      \
-            attr_once.mark();                                                                                              \
-        }                                                                                                                  \
-        hipLaunchKernelGGL(viterbi_strip_kernel<RV>, dim3(batch), dim3(1024), pl.lds_bytes, stream, p);                    \
-        break;                                                                                                             \
-    }
-        switch (pl.strip) {
-            LA_STRIP_CASE(2) LA_STRIP_CASE(4) LA_STRIP_CASE(8)
-            default: return LA_EUNSUPPORTED;
-        }
-#undef LA_STRIP_CASE
-        LA_LAUNCH_CHECK();
-        return LA_OK;
-    }
-    switch (pl.nw) {
-        case 1: return no_dpp ? launch_viterbi<1, false>(p, pl, batch, stream) : launch_viterbi<1, true>(p, pl, batch, stream);
-        case 2: return launch_viterbi<2, false>(p, pl, batch, stream);
-        case 4: return launch_viterbi<4, false>(p, pl, batch, stream);
-        case 8: return launch_viterbi<8, false>(p, pl, batch, stream);
-        case 16: return launch_viterbi<16, false>(p, pl, batch, stream);
-    }
-    return LA_EUNSUPPORTED;
+                max_labels, onset, offset, out_stride, final_score, status};
+    return run_batch(false, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                      const int32_t *labels, int32_t labels_stride, const int32_t *n_labels,
+                                      const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
+                                      int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
+                                      int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                      void *workspace, size_t workspace_bytes, void *stream_) {
+    VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
+                max_labels, onset, offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty};
+    return run_batch(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // run_viterbi_core(dp, bt, lp, ls, label) of the reference (utils/alignment.py:73-119) for ONE utterance: same
@@ -449,11 +538,10 @@ extern "C" int la_viterbi_core(const float *em, int64_t em_row_stride, const int
                                int32_t n_frames_host, const int32_t *n_labels, const int32_t *n_frames, double *dp,
                                long long *bt, int32_t *scratch_i32, double *scratch_f64, void *workspace,
                                size_t workspace_bytes, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     LA_CHECK_ARG(em && labels && n_labels && n_frames && dp && bt && scratch_i32 && scratch_f64, "viterbi_core: null pointer");
     LA_CHECK_ARG(n_labels_host > 0 && n_frames_host > 0 && em_row_stride >= n_labels_host + 1, "viterbi_core: bad sizes");
     VitPlan pl;
-    if (!plan_viterbi(1, n_frames_host, n_labels_host, &pl) || pl.strip) {
+    if (!plan_viterbi(1, n_frames_host, n_labels_host, false, &pl) || pl.strip) {
         la::set_error("viterbi_core: more than 511 labels (the dp / bt dump face is one lane per state)");
         return LA_EUNSUPPORTED;
     }
@@ -461,21 +549,6 @@ extern "C" int la_viterbi_core(const float *em, int64_t em_row_stride, const int
     // scratch_i32: onset[L] | offset[L] | status[1]
     VitParams p{em, 0, em_row_stride, labels, n_labels_host, n_labels, n_frames, n_frames_host, n_labels_host,
                 scratch_i32, scratch_i32 + n_labels_host, n_labels_host, scratch_f64, scratch_i32 + 2 * n_labels_host,
-                reinterpret_cast<unsigned long long *>(workspace), pl.bt_in_lds ? 1 : 0, dp, bt};
-#define LA_CORE_CASE(NWV)                                                                                           \
-    case NWV: {                                                                                                     \
-        auto kern = viterbi_kernel<NWV, false, true>;                                                               \
-        if (pl.lds_bytes > 48 * 1024)                                                                               \
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       (int)pl.lds_bytes));                                                         \
-        hipLaunchKernelGGL(kern, dim3(1), dim3(NWV * 64), pl.lds_bytes, stream, p);                                 \
-        break;                                                                                                      \
-    }
-    switch (pl.nw) {
-        LA_CORE_CASE(1) LA_CORE_CASE(2) LA_CORE_CASE(4) LA_CORE_CASE(8) LA_CORE_CASE(16)
-        default: return LA_EUNSUPPORTED;
-    }
-#undef LA_CORE_CASE
-    LA_LAUNCH_CHECK();
-    return LA_OK;
+                nullptr, 0, 0.0, reinterpret_cast<unsigned long long *>(workspace), pl.bt_in_lds ? 1 : 0, dp, bt};
+    return launch_lanes<false, true>("viterbi", p, pl, 1, (hipStream_t)stream_);
 }

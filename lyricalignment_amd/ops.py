@@ -35,29 +35,44 @@ def _capacity(t: torch.Tensor) -> int:
 # --------------------------------------------------------------------------- #
 # alignment DP                                                                  #
 # --------------------------------------------------------------------------- #
+def _lattice_inputs(who: str, em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor, **more_i32):
+    """The checks every lattice entry point makes of em [B,T,E] / labels [B,Lmax] / n_labels [B] / n_frames [B] (and that the
+    entry's further int32 device tensors are such) -> B, T, Lmax and the contiguous count tensors."""
+    _dev(em, "em", torch.float32); _dev(labels, "labels", torch.int32)
+    _dev(n_labels, "n_labels", torch.int32); _dev(n_frames, "n_frames", torch.int32)
+    for name, t in more_i32.items():
+        _dev(t, name, torch.int32)
+    if em.dim() != 3 or labels.dim() != 2 or em.stride(2) != 1 or labels.stride(1) != 1:
+        raise ValueError(f"{who}: em [B,T,E] / labels [B,Lmax] with unit inner stride expected")
+    B, T, E = em.shape
+    Lmax = labels.shape[1]
+    if labels.shape[0] != B or n_labels.shape != (B,) or n_frames.shape != (B,) or E < Lmax + 1:
+        raise ValueError(f"{who}: inconsistent shapes")
+    return B, T, Lmax, n_labels.contiguous(), n_frames.contiguous()
+
+
+def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device) -> Tuple[torch.Tensor, int]:
+    """lib().la_<query>(B, T, Lmax) -> a device byte buffer of max(need, 16) bytes and `need`."""
+    need = ctypes.c_size_t(0)
+    check(getattr(lib(), "la_" + query)(B, T, Lmax, ctypes.byref(need)), query)
+    return torch.empty((max(need.value, 16),), dtype=torch.uint8, device=device), need.value
+
+
+def _viterbi_outputs(B: int, Lmax: int, device):
+    return (torch.empty((B, Lmax), dtype=torch.int32, device=device), torch.empty((B, Lmax), dtype=torch.int32, device=device),
+            torch.empty((B,), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.int32, device=device))
+
+
 def viterbi_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """em [B,T,E] f32 (E >= Lmax+1), labels [B,Lmax] i32, n_labels [B] i32, n_frames [B] i32 (device).
     -> onset [B,Lmax] i32, offset [B,Lmax] i32, final_score [B] f64, status [B] i32 (device)."""
-    _dev(em, "em", torch.float32); _dev(labels, "labels", torch.int32)
-    _dev(n_labels, "n_labels", torch.int32); _dev(n_frames, "n_frames", torch.int32)
-    if em.dim() != 3 or labels.dim() != 2 or em.stride(2) != 1 or labels.stride(1) != 1:
-        raise ValueError("viterbi_batch: em [B,T,E] / labels [B,Lmax] with unit inner stride expected")
-    B, T, E = em.shape
-    Lmax = labels.shape[1]
-    if labels.shape[0] != B or n_labels.shape != (B,) or n_frames.shape != (B,) or E < Lmax + 1:
-        raise ValueError("viterbi_batch: inconsistent shapes")
-    n_labels = n_labels.contiguous(); n_frames = n_frames.contiguous()
-    onset = torch.empty((B, Lmax), dtype=torch.int32, device=em.device)
-    offset = torch.empty((B, Lmax), dtype=torch.int32, device=em.device)
-    score = torch.empty((B,), dtype=torch.float64, device=em.device)
-    status = torch.empty((B,), dtype=torch.int32, device=em.device)
-    need = ctypes.c_size_t(0)
-    check(lib().la_viterbi_workspace_bytes(B, T, Lmax, ctypes.byref(need)), "viterbi_workspace_bytes")
-    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=em.device)
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs("viterbi_batch", em, labels, n_labels, n_frames)
+    onset, offset, score, status = _viterbi_outputs(B, Lmax, em.device)
+    ws, need = _lattice_workspace("viterbi_workspace_bytes", B, T, Lmax, em.device)
     check(lib().la_viterbi_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
                                  ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
-                                 ptr(ws), need.value, stream_ptr()), "viterbi_batch")
+                                 ptr(ws), need, stream_ptr()), "viterbi_batch")
     return onset, offset, score, status
 
 
@@ -67,30 +82,17 @@ def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.
     """la_viterbi_spans_batch: viterbi_batch on the lattice with optional label spans.  skip_from [B, >= Lmax+1] i32 (device):
     skip_from[b, n] = a (0 <= a < n) makes labels a..n-1 of clip b optional, anything else = no span ends at n.
     -> the tuple of viterbi_batch; labels inside a taken jump have onset = offset = -1 under status LA_OK."""
-    _dev(em, "em", torch.float32); _dev(labels, "labels", torch.int32)
-    _dev(n_labels, "n_labels", torch.int32); _dev(n_frames, "n_frames", torch.int32); _dev(skip_from, "skip_from", torch.int32)
-    if em.dim() != 3 or labels.dim() != 2 or em.stride(2) != 1 or labels.stride(1) != 1:
-        raise ValueError("viterbi_spans_batch: em [B,T,E] / labels [B,Lmax] with unit inner stride expected")
-    B, T, E = em.shape
-    Lmax = labels.shape[1]
-    if labels.shape[0] != B or n_labels.shape != (B,) or n_frames.shape != (B,) or E < Lmax + 1:
-        raise ValueError("viterbi_spans_batch: inconsistent shapes")
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs("viterbi_spans_batch", em, labels, n_labels, n_frames, skip_from=skip_from)
     if skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1:
         raise ValueError("viterbi_spans_batch: skip_from [B, >= Lmax+1] with unit inner stride expected")
     skip_penalty = float(skip_penalty)
     if not skip_penalty >= 0.0:
         raise ValueError("viterbi_spans_batch: skip_penalty must be >= 0")
-    n_labels = n_labels.contiguous(); n_frames = n_frames.contiguous()
-    onset = torch.empty((B, Lmax), dtype=torch.int32, device=em.device)
-    offset = torch.empty((B, Lmax), dtype=torch.int32, device=em.device)
-    score = torch.empty((B,), dtype=torch.float64, device=em.device)
-    status = torch.empty((B,), dtype=torch.int32, device=em.device)
-    need = ctypes.c_size_t(0)
-    check(lib().la_viterbi_spans_workspace_bytes(B, T, Lmax, ctypes.byref(need)), "viterbi_spans_workspace_bytes")
-    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=em.device)
+    onset, offset, score, status = _viterbi_outputs(B, Lmax, em.device)
+    ws, need = _lattice_workspace("viterbi_spans_workspace_bytes", B, T, Lmax, em.device)
     check(lib().la_viterbi_spans_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
                                        ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
-                                       ptr(skip_from), skip_from.stride(0), skip_penalty, ptr(ws), need.value, stream_ptr()),
+                                       ptr(skip_from), skip_from.stride(0), skip_penalty, ptr(ws), need, stream_ptr()),
           "viterbi_spans_batch")
     return onset, offset, score, status
 
@@ -100,20 +102,11 @@ def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,
     onset / offset [B,Lmax] i32 = viterbi_batch's (or align_head_forward's) outputs for the same emissions.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32 [, gamma [B,T,2*Lmax+1] f32] (device)."""
-    _dev(em, "em", torch.float32); _dev(labels, "labels", torch.int32)
-    _dev(n_labels, "n_labels", torch.int32); _dev(n_frames, "n_frames", torch.int32)
-    _dev(onset, "onset", torch.int32); _dev(offset, "offset", torch.int32)
-    if em.dim() != 3 or labels.dim() != 2 or em.stride(2) != 1 or labels.stride(1) != 1:
-        raise ValueError("alignment_posteriors: em [B,T,E] / labels [B,Lmax] with unit inner stride expected")
-    B, T, E = em.shape
-    Lmax = labels.shape[1]
-    if labels.shape[0] != B or n_labels.shape != (B,) or n_frames.shape != (B,) or E < Lmax + 1:
-        raise ValueError("alignment_posteriors: inconsistent shapes")
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs("alignment_posteriors", em, labels, n_labels, n_frames, onset=onset, offset=offset)
     if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
         raise ValueError("alignment_posteriors: onset / offset must be [B,Lmax]")
     if int(boundary_window) < 0:
         raise ValueError("alignment_posteriors: boundary_window must be >= 0")
-    n_labels = n_labels.contiguous(); n_frames = n_frames.contiguous()
     onset = onset.contiguous(); offset = offset.contiguous()
     dev = em.device
     occupancy = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
@@ -122,14 +115,12 @@ def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch
     log_z = torch.empty((B,), dtype=torch.float64, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    need = ctypes.c_size_t(0)
-    check(lib().la_alignment_posteriors_workspace_bytes(B, T, Lmax, ctypes.byref(need)), "alignment_posteriors_workspace_bytes")
-    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
+    ws, need = _lattice_workspace("alignment_posteriors_workspace_bytes", B, T, Lmax, dev)
     check(lib().la_alignment_posteriors(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
                                         ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
                                         ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(log_z), ptr(status), ptr(gamma),
                                         gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
-                                        ptr(ws), need.value, stream_ptr()), "alignment_posteriors")
+                                        ptr(ws), need, stream_ptr()), "alignment_posteriors")
     res = (occupancy, onset_prob, offset_prob, log_z, status)
     return res + (gamma,) if want_gamma else res
 

@@ -265,3 +265,50 @@ def test_random_ragged_batches_bit_exact(seed):
         else:
             n_bad += 1
     assert n_bad < 48
+
+
+# (batch, max_frames, max_labels) -> bytes from la_viterbi_workspace_bytes, la_viterbi_spans_workspace_bytes and
+# la_alignment_posteriors_workspace_bytes; None = LA_EUNSUPPORTED.  Literals recorded from the library as it stood before the
+# plain and the optional-span DP became one kernel with one planner: callers size their buffers by these numbers.
+# Covered: 1 / 2 / 4 / 8 / 16 waves, the strip kernel's range (plain DP only), and both sides of the backpointers-fit-in-LDS
+# edge for two (plain) and three (spans) mask words per wave and frame, at one wave and at four.
+_WORKSPACE_BYTES = {
+    (32, 1500, 26): (0, 0, 24576000),
+    (1, 1, 1): (0, 0, 512),
+    (1, 10096, 26): (0, 242304, 5169152),
+    (1, 10097, 26): (161552, 242328, 5169664),
+    (1, 6720, 26): (0, 0, 3440640),
+    (2, 6721, 26): (0, 322608, 6882304),
+    (3, 700, 40): (0, 0, 2150400),
+    (2, 1800, 100): (0, 345600, 7372800),
+    (1, 2467, 100): (0, 236832, 5052416),
+    (1, 2468, 100): (157952, 236928, 5054464),
+    (1, 1634, 100): (0, 0, 3346432),
+    (3, 1635, 100): (0, 470880, 10045440),
+    (1, 5389, 171): (689792, 1034688, 22073344),
+    (1, 9000, 238): (1152000, 1728000, 36864000),
+    (4, 600, 500): (614400, 921600, 19660800),
+    (1, 2000, 511): (512000, 768000, 16384000),
+    (1, 100, 512): (51200, None, None),
+    (1, 100, 600): (51200, None, None),
+    (2, 300, 1100): (614400, None, None),
+    (1, 50, 2100): (102400, None, None),
+    (2, 100, 4095): (409600, None, None),
+    (1, 100, 4096): (None, None, None),
+}
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    """The sizing contract of the three lattice entry points: same bytes, same label limits (4095 / 511 / 511)."""
+    import ctypes
+    from lyricalignment_amd import _lib
+    L = _lib.lib()
+    queries = (L.la_viterbi_workspace_bytes, L.la_viterbi_spans_workspace_bytes, L.la_alignment_posteriors_workspace_bytes)
+    for shape, want in _WORKSPACE_BYTES.items():
+        for query, expected in zip(queries, want):
+            need = ctypes.c_size_t(12345)
+            rc = query(*shape, ctypes.byref(need))
+            if expected is None:
+                assert rc == _lib.LA_EUNSUPPORTED, (shape, rc)
+            else:
+                assert rc == _lib.LA_OK and need.value == expected, (shape, rc, need.value, expected)

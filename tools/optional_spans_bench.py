@@ -1,11 +1,12 @@
-"""Cost of the alignment DP with optional lyric lines (la_viterbi_spans_batch, csrc/la_viterbi_spans.hip) beside la_viterbi_batch.
+"""Cost of the alignment DP with optional lyric lines (la_viterbi_spans_batch) beside la_viterbi_batch; both are
+instantiations of one kernel in csrc/la_viterbi.hip, without and with the span code.
 
     python tools/optional_spans_bench.py [--runs 30] [--out profiles/optional_spans.txt]
 
 On the same synthetic emissions at 32 clips x 1500 frames x 26 labels (caller-owned buffers, device events around one call, a
 synchronise after each, the three calls alternated call by call):
-  * la_viterbi_batch                          -- unchanged by this feature: the baseline;
-  * la_viterbi_spans_batch with no spans      -- every skip_from entry -1: what a span-free clip pays for the span kernel;
+  * la_viterbi_batch                          -- the instantiation without any span code: the baseline;
+  * la_viterbi_spans_batch with no spans      -- every skip_from entry -1: what a span-free clip pays for the span instantiation;
   * la_viterbi_spans_batch with every line optional -- the 26 labels as four lines of 6 / 7 / 6 / 7 characters, each optional; the emissions
     plant lines 1, 2 and 4, so the jump over line 3 is taken.
 Every number is the median of `runs` calls after a warm-up; min .. max is printed next to it.  The no-span outputs are checked bit for
