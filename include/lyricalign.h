@@ -260,6 +260,46 @@ int la_alignment_posteriors(const float *em, int64_t em_batch_stride, int64_t em
                             float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Confidence on the lattice with OPTIONAL SPANS: the sum-product sweep of la_viterbi_spans_batch's lattice (same skip_from /
+ * skip_penalty; no counterpart in the reference).  S = 2L+1 states, start states 0 and 1, end states S-1 and S-2; into state
+ * s from s, s-1 and (odd s >= 3, differing neighbour labels) s-2; and, for skip_from[n] = a with 0 <= a < n, into the two
+ * states at position n (2n, and 2n+1 when n < L) also from J = 2a and from J-1 (a >= 1; into the odd target only if
+ * labels[n] != labels[a-1]).  A jump arc multiplies the path weight by exp(-skip_penalty).  No arc arises twice from these
+ * rules, so every path counts once.  With alpha / beta including e_t(k) as above:
+ *   log_z, gamma_t(k), entry_t(n), exit_t(n), occupancy, onset_prob, offset_prob: as la_alignment_posteriors, the jump arcs
+ *                       being part of the incoming sums (entry) and of the outgoing sums (exit)
+ *   present_prob[b][n]   = sum over t of entry_t(n): probability that label n is on the path at all ("was it sung")
+ *   span_skip_prob[b][n] = sum over t >= 1, destination in {2n, 2n+1} and source in {J, J-1 where allowed} of
+ *                          exp(alpha_{t-1}(source) - skip_penalty + beta_t(destination) - log_z): probability that the path
+ *                          takes the jump of the span that ENDS at position n; 0 where no span ends
+ * A path is monotone and leaves label n out only by one jump that covers it: for every label,
+ *   present_prob[n] + sum over spans (a, e) with a <= n < e of span_skip_prob[e] = 1.
+ * onset / offset are la_viterbi_spans_batch's outputs for the same skip_from and skip_penalty: labels with onset -1 (inside a
+ * taken jump) get occupancy = onset_prob = offset_prob = 0, their present_prob is still written.  present_prob
+ * [batch][out_stride], span_skip_prob [batch][skip_stride] (entries 0 .. max_labels of a row are written), float32.  A clip
+ * without any span gets present_prob = 1 for its labels (identically true there, not summed) and its other outputs are
+ * la_alignment_posteriors' bit for bit.  Statuses, zeroing of failed rows (present_prob and span_skip_prob rows too) and of
+ * rows n >= L_b, gamma_out, the workspace (same size formula) and the limit max_labels <= 511 as la_alignment_posteriors.
+ * The jump terms are folded in float64, in a fixed order (no atomics: a clip's result does not depend on its batch mates):
+ * the error bound 8 T 2^-23 holds unchanged.  Argument errors (a negative or NaN skip_penalty, skip_stride < max_labels + 1
+ * included) are answered on the host before anything is enqueued.
+ */
+int la_alignment_posteriors_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors_spans(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                  const int32_t *labels, int32_t labels_stride,
+                                  const int32_t *n_labels, const int32_t *n_frames,
+                                  int32_t batch, int32_t max_frames, int32_t max_labels,
+                                  const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                                  int32_t boundary_window,
+                                  const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                  float *occupancy, float *onset_prob, float *offset_prob, float *present_prob,
+                                  float *span_skip_prob,
+                                  double *log_z, int32_t *status,
+                                  float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* emission prep from materialised logits                                     */
 /*   (replaces utils/alignment.py:123-134 [CTC] and :14-20 [plain])           */

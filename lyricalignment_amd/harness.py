@@ -166,11 +166,14 @@ def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, 
 
 
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
-                       use_ctc_loss: bool = True, skip_penalty: float = 0.0) -> List[Optional[list]]:
+                       use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
-    [[onset, offset, char], ...] (AlignModel.align(optional_spans=...), skip_penalty >= 0 per skipped line)."""
+    [[onset, offset, char], ...] (AlignModel.align(optional_spans=...), skip_penalty >= 0 per skipped line).
+    with_confidence: -> (lines_out, sung), sung[i] = the probability under the model that line i was sung (a Python float: present_prob
+    of the line's first character, AlignModel.align(return_span_confidence=True)); 1 for a mandatory line, and 1 - span_skip_prob of an
+    optional line's span."""
     from .utils.alignment import spans_from_lines
     lines = list(lines)
     ids = [list(tokenize(line)) for line in lines]
@@ -181,12 +184,20 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     spans = [(a, n) for n, a in enumerate(skip_from) if a >= 0]
     labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
     with torch.no_grad():
-        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)[0]
+        if with_confidence:
+            res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                      return_span_confidence=True)
+            res, present = res[0], scores[0]["sung_prob"]
+        else:
+            res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)[0]
     out: List[Optional[list]] = []
+    sung: List[float] = []
     pos = 0
     for line in lines:
         part = res[pos: pos + len(line)]
+        if with_confidence:
+            sung.append(float(present[pos]))
         pos += len(line)
         # a span is taken or left as a whole: its characters are None together
         out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
-    return out
+    return (out, sung) if with_confidence else out

@@ -330,7 +330,7 @@ class AlignModel(torch.nn.Module):
     def align(self, audios: Optional[Sequence[np.ndarray]] = None, labels=None, *, mel: Optional[torch.Tensor] = None,
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
-              skip_penalty: float = 0.0):
+              skip_penalty: float = 0.0, return_span_confidence: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -347,7 +347,13 @@ class AlignModel(torch.nn.Module):
         optional_spans (addition): optional_spans[b] = list of (a, n) pairs -- labels a .. n-1 of clip b (a lyric line that may not be sung)
         may be left out by the path; the head's emissions go through the DP on the lattice with optional spans (ops.viterbi_spans_batch,
         skip_penalty >= 0 per taken jump) and skipped characters come back as None (onset = offset = -1 with return_frames).  None or
-        all-empty: the call as it was.  Not with return_confidence (ValueError: no posteriors over that lattice); at most 511 labels."""
+        all-empty: the call as it was.  Not with return_confidence (ValueError; return_span_confidence is the keyword); at most 511 labels.
+        return_span_confidence (addition): -> (seconds, scores) on the lattice with optional spans (ops.alignment_posteriors_spans):
+        return_confidence's dicts (skipped characters: None in seconds, their three scores 0) plus "sung_prob": [L], the probability that
+        the character is on the path at all, and "span_skip_prob": the probability that the span was left out, one value per span of
+        optional_spans[b] in the order given.  With return_frames the device tensors (onset, offset, score, status, occupancy, onset_prob,
+        offset_prob, log_z, present_prob [B,Lmax], span_skip_prob [B,Lmax+1], indexed by the span's end position).  Without any span:
+        return_confidence's numbers, sung_prob 1 and an empty span_skip_prob."""
         from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames, _skip_from_of_spans
         eng = self.engine()
         kw = {}
@@ -363,9 +369,26 @@ class AlignModel(torch.nn.Module):
             feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
         skip_from = _skip_from_of_spans(optional_spans, lab_lists)
+        if skip_from is not None and return_confidence:
+            raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice by that "
+                             "keyword: return_span_confidence=True gives them)")
+        if return_span_confidence:
+            variant = _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN
+            onset, offset, score, status, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, variant, want_emissions=True, **kw)
+            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
+            if skip_from is None:            # the plain DP's frames are the span DP's bit for bit when no span exists
+                skip_dev = torch.full((B, lab_dev.shape[1] + 1), -1, dtype=torch.int32, device=eng.device)
+            else:
+                skip_dev = skip_from.to(eng.device)
+                onset, offset, score, status = ops.viterbi_spans_batch(em, lab_dev, n_lab, nf, skip_dev, skip_penalty)
+            occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_spans(em, lab_dev, n_lab, nf, onset, offset, skip_dev, skip_penalty,
+                                                                                 boundary_window)
+            if return_frames:
+                return onset, offset, score, status, occ, onp, offp, log_z, pres, skp
+            seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=True)
+            spans = optional_spans if optional_spans is not None else [[] for _ in lab_lists]
+            return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists, pres, skp, spans)
         if skip_from is not None:
-            if return_confidence:
-                raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice)")
             *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
                                              want_emissions=True, **kw)
             nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)

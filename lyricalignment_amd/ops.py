@@ -125,6 +125,42 @@ def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch
     return res + (gamma,) if want_gamma else res
 
 
+def alignment_posteriors_spans(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                               onset: torch.Tensor, offset: torch.Tensor, skip_from: torch.Tensor, skip_penalty: float = 0.0,
+                               boundary_window: int = 2, want_gamma: bool = False):
+    """la_alignment_posteriors_spans: forward-backward on the lattice with optional label spans.  Inputs as alignment_posteriors, onset /
+    offset = viterbi_spans_batch's outputs for the same skip_from [B, >= Lmax+1] i32 and skip_penalty.
+    -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, present_prob [B,Lmax] f32 (label n is on the path),
+    span_skip_prob [B,Lmax+1] f32 (the span ending at position n is jumped) [, gamma [B,T,2*Lmax+1] f32] (device)."""
+    who = "alignment_posteriors_spans"
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, onset=onset, offset=offset, skip_from=skip_from)
+    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
+        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
+    if skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1:
+        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
+    if int(boundary_window) < 0:
+        raise ValueError(f"{who}: boundary_window must be >= 0")
+    skip_penalty = float(skip_penalty)
+    if not skip_penalty >= 0.0:
+        raise ValueError(f"{who}: skip_penalty must be >= 0")
+    onset = onset.contiguous(); offset = offset.contiguous()
+    dev = em.device
+    occupancy, onset_prob, offset_prob, present_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(4))
+    span_skip_prob = torch.empty((B, Lmax + 1), dtype=torch.float32, device=dev)
+    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
+    ws, need = _lattice_workspace("alignment_posteriors_spans_workspace_bytes", B, T, Lmax, dev)
+    check(lib().la_alignment_posteriors_spans(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
+                                              ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
+                                              ptr(skip_from), skip_from.stride(0), skip_penalty, ptr(occupancy), ptr(onset_prob),
+                                              ptr(offset_prob), ptr(present_prob), ptr(span_skip_prob), ptr(log_z), ptr(status), ptr(gamma),
+                                              gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
+                                              ptr(ws), need, stream_ptr()), who)
+    res = (occupancy, onset_prob, offset_prob, log_z, status, present_prob, span_skip_prob)
+    return res + (gamma,) if want_gamma else res
+
+
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:
     """logits [B,T,V] f32 device -> compact emissions [B,T,Lmax+1] f32."""
     _dev(logits, "logits", torch.float32); _dev(labels, "labels", torch.int32); _dev(n_labels, "n_labels", torch.int32)

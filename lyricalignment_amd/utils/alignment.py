@@ -98,15 +98,24 @@ def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second, sk
     return result
 
 
-def _scores_from_posteriors(occupancy, onset_prob, offset_prob, log_z, final_score, label_lists):
+def _scores_from_posteriors(occupancy, onset_prob, offset_prob, log_z, final_score, label_lists, present_prob=None, span_skip_prob=None,
+                            optional_spans=None):
     """Device outputs of ops.alignment_posteriors -> per-utterance dicts of Python floats (after _seconds_from_frames
-    has raised for failed utterances).  path_log_posterior = final_score - log_z <= 0: log-probability of the reported path."""
+    has raised for failed utterances).  path_log_posterior = final_score - log_z <= 0: log-probability of the reported path.
+    With present_prob / span_skip_prob (ops.alignment_posteriors_spans) each dict also holds "sung_prob": [L] and "span_skip_prob":
+    one value per span of optional_spans[b], in the order given."""
     occ, onp, offp = occupancy.cpu().numpy(), onset_prob.cpu().numpy(), offset_prob.cpu().numpy()
     lz, fs = log_z.cpu().numpy(), final_score.cpu().numpy()
-    return [{"occupancy": [float(v) for v in occ[b, : len(labs)]],
-             "onset_prob": [float(v) for v in onp[b, : len(labs)]],
-             "offset_prob": [float(v) for v in offp[b, : len(labs)]],
-             "path_log_posterior": float(fs[b] - lz[b])} for b, labs in enumerate(label_lists)]
+    out = [{"occupancy": [float(v) for v in occ[b, : len(labs)]],
+            "onset_prob": [float(v) for v in onp[b, : len(labs)]],
+            "offset_prob": [float(v) for v in offp[b, : len(labs)]],
+            "path_log_posterior": float(fs[b] - lz[b])} for b, labs in enumerate(label_lists)]
+    if present_prob is not None:
+        pres, skp = present_prob.cpu().numpy(), span_skip_prob.cpu().numpy()
+        for b, labs in enumerate(label_lists):
+            out[b]["sung_prob"] = [float(v) for v in pres[b, : len(labs)]]
+            out[b]["span_skip_prob"] = [float(skp[b, int(n)]) for _, n in ((optional_spans[b] or ()) if optional_spans is not None else ())]
+    return out
 
 
 def _device_of(prediction) -> torch.device:
@@ -135,10 +144,14 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         nf = torch.tensor(counts, dtype=torch.int32).to(dev)
     skip_from = _skip_from_of_spans(optional_spans, lists)
     if skip_from is not None:                # (addition) the lattice with optional spans; None / all-empty takes the path below unchanged
-        if boundary_window is not None:
-            raise ValueError("posteriors over the lattice with optional spans are not defined: optional_spans goes without confidence")
-        onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_from.to(dev), skip_penalty)
-        return _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=True)
+        skip_dev = skip_from.to(dev)
+        onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
+        seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=True)
+        if boundary_window is None:
+            return seconds
+        occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty,
+                                                                             boundary_window)
+        return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists, pres, skp, optional_spans)
     onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
     seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second)
     if boundary_window is None:
@@ -162,16 +175,22 @@ def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None,
                     skip_penalty=skip_penalty)
 
 
-def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None):
+def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0):
     """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
     scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
-    sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi."""
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames)
+    sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi.
+    optional_spans / skip_penalty as perform_viterbi: skipped characters are None (their three scores 0), and each dict additionally holds
+    "sung_prob": [L] (probability that the character is on the path at all) and "span_skip_prob": one value per span, in the order given
+    (probability that the span was left out) -- la_alignment_posteriors_spans.  Without a span the dicts are as before, without these keys."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty)
 
 
-def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None):
+def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                               skip_penalty=0.0):
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
-    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames)
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty)
 
 
 def run_viterbi_core(dp_matrix, backtrace_dp_matrix, cur_log_prediction, cur_log_silence_prediction, cur_label):
