@@ -219,6 +219,39 @@ int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, int64_t em_
                            void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same DP with a FRAME WINDOW per lattice state (no counterpart in the reference): what the caller knows about time -- the
+ * line start times of an LRC sheet, a boundary corrected by hand -- narrows the lattice.  Every argument of
+ * la_viterbi_spans_batch up to skip_penalty in the same order (skip_from may be NULL: no span anywhere), then win_lo / win_hi
+ * [batch][win_stride] int32 (device, win_stride >= 2 * max_labels + 1; entries 0 .. 2 L_b of row b are read).  State s of clip
+ * b (0 = leading silence, 2n+1 = label n, 2n+2 = the silence after it) may hold the path at frame t only if
+ * win_lo[b][s] <= t < win_hi[b][s]; any pair of int32 values is legal, lo >= hi closes the state, nothing is validated on the
+ * device.  dp[t][s] is computed by la_viterbi_spans_batch's rule (comparison order, tie rules, span arcs, emission added last)
+ * and then set to float64 -inf when the cell lies outside its window; row 0 likewise.  Termination is unchanged.  If the winning
+ * final score is -inf no path lies inside the windows: status LA_EINFEASIBLE, final_score -inf, every onset and offset -1.
+ * Otherwise backtrace, outputs and status are la_viterbi_spans_batch's (as for a clip too short for its labels, the -1e7
+ * initial value of the states >= 2 at frame 0 can carry a finite score to the end when only later frames are closed: the
+ * path then misses a label and the status is LA_EINFEASIBLE).  With every window [0, T_b) the outputs are
+ * la_viterbi_batch's (no spans) and la_viterbi_spans_batch's (spans) bit for bit.
+ * Windows are per STATE, not per label, because a bound on a label's onset from above is a bound on the states before it: a
+ * window on the label alone lets the silence before it stretch past the bound.
+ * Limit, workspace (la_viterbi_windows_workspace_bytes() = la_viterbi_spans_workspace_bytes()) and option viterbi_dpp as
+ * la_viterbi_spans_batch.  Argument errors (null win_lo / win_hi, a win_stride below 2 * max_labels + 1, a negative or NaN
+ * skip_penalty, more than 511 labels: LA_EUNSUPPORTED) are answered on the host before anything is enqueued; never
+ * synchronises, allocates or frees.
+ */
+int la_viterbi_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                             const int32_t *labels, int32_t labels_stride,
+                             const int32_t *n_labels, const int32_t *n_frames,
+                             int32_t batch, int32_t max_frames, int32_t max_labels,
+                             int32_t *onset, int32_t *offset, int32_t out_stride,
+                             double *final_score, int32_t *status,
+                             const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                             const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
  * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
  * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable

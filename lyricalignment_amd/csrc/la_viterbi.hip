@@ -27,6 +27,14 @@
 // jump code.  Backpointers are then five outcomes {stay, advance, skip, jump from J, jump from J-1}: three ballot masks per wave
 // per frame (T * 24 B per wave; the third is written and read only where spans exist), and J(s) stays in an LDS int array for
 // the backtrace thread.
+//
+// Frame windows (the WIN instantiations, la_viterbi_windows_batch): state s may hold the path at frame t only if lo[s] <= t < hi[s];
+// a cell outside its window is -inf.  Each lane keeps its state's lo / hi in two registers.  The test depends on the frame index
+// alone, so it is applied to the EMISSION as it leaves the prefetch registers (e = inside ? e : -inf, and likewise to row 0):
+// best + (double)e is then -inf without an instruction on the loop-carried chain (best is never +inf or NaN).  WIN exists only
+// together with SPANS (a null skip_from = no span anywhere; the once-per-clip has_span test still sends a span-free clip through the
+// plain loop).  A winning final score of -inf is LA_EINFEASIBLE with every onset / offset -1; otherwise backtrace and status are
+// unchanged.
 #include <type_traits>
 
 #include "la_lattice.h"
@@ -60,12 +68,16 @@ struct VitParams {
     // run_viterbi_core face (DUMP instantiation only, batch 1): row 0 of dp is READ, rows >= 1 of dp / bt are written
     double *dp_dump;    // [T][S]
     long long *bt_dump; // [T][S]
+    // per-state frame windows (WIN instantiations only): [batch][win_stride], entries 0 .. 2 L_b of row b are read
+    const int32_t *win_lo, *win_hi;
+    int32_t win_stride;
 };
 
-template <int NW, bool DPP, bool SPANS, bool DUMP = false>
+template <int NW, bool DPP, bool SPANS, bool DUMP = false, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     static_assert(!DPP || NW == 1, "DPP neighbour exchange is single-wave only");
     static_assert(!DUMP || (!DPP && !SPANS), "the dp / bt dump is a face of the plain LDS-exchange form");
+    static_assert(!WIN || (SPANS && !DUMP), "frame windows are a face of the optional-span forms");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = NW * 64;
     constexpr int MW = SPANS ? 3 : 2;  // backpointer mask words per wave per frame
@@ -113,7 +125,7 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     int J = -1;
     bool jm1_ok = false;
     if constexpr (SPANS) {
-        if (valid && n >= 1) {
+        if (valid && n >= 1 && (!WIN || p.skip_from)) {   // (windows: a null skip_from = no span anywhere)
             const int a = p.skip_from[(int64_t)b * p.skip_stride + n];
             if (a >= 0 && a < n) {
                 J = 2 * a;
@@ -124,10 +136,22 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     }
     const double pen = p.penalty;
     const float *emb = p.em + (int64_t)b * p.em_bs + col;
+    // this state's frame window; lanes without a state keep the open one (nothing is read past 2 L_b <= win_stride - 1)
+    int wlo = 0, whi = 0x7fffffff;
+    if constexpr (WIN) {
+        if (valid) {
+            wlo = p.win_lo[(int64_t)b * p.win_stride + k];
+            whi = p.win_hi[(int64_t)b * p.win_stride + k];
+        }
+    }
+    auto gated = [&](float e, int j) { return (j >= wlo && j < whi) ? e : -INFINITY; };
 
     // row 0 (:144-152); the run_viterbi_core face takes row 0 from the caller like the reference does (:73-76)
     double cur = (k <= 1) ? (double)emb[0] : kNeg;
     if (DUMP) cur = valid ? p.dp_dump[k] : kNeg;
+    if constexpr (WIN) {
+        if (!(0 >= wlo && 0 < whi)) cur = -INFINITY;
+    }
 
     if (!DPP) {
         if (k < 2) { rowbuf[k] = kNeg; rowbuf[NT + 2 + k] = kNeg; }  // slots for k-1, k-2 of states 0,1
@@ -148,7 +172,10 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         for (int j0 = 1; j0 < T; j0 += PF) {
             float e_cur[PF];
 #pragma unroll
-            for (int i = 0; i < PF; ++i) e_cur[i] = e_buf[i];
+            for (int i = 0; i < PF; ++i) {
+                if constexpr (WIN) e_cur[i] = gated(e_buf[i], j0 + i);   // the window's gate: off the dependent chain
+                else e_cur[i] = e_buf[i];
+            }
 #pragma unroll
             for (int i = 0; i < PF; ++i) {
                 const int jj = j0 + PF + i;
@@ -222,7 +249,8 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         int kk = (fin[S - 1] > fin[S - 2]) ? (S - 1) : (S - 2);  // strict '>' (:157)
         p.final_score[b] = fin[kk];
         int knext = -1;
-        for (int j = T - 1; j >= 0; --j) {
+        const bool no_path = WIN && fin[kk] == -INFINITY;   // no path inside the windows: on_s / off_s stay -1, no backtrace
+        for (int j = no_path ? -1 : T - 1; j >= 0; --j) {
             if (kk & 1) {
                 const int nn = kk >> 1;
                 if (kk != knext) off_s[nn] = j + 1;  // last frame in this state + 1
@@ -251,7 +279,7 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
             if (SPANS && off_s[nn] == kSkipped) off_s[nn] = -1;
             else if (on_s[nn] < 0) st = LA_EINFEASIBLE;  // reference: ValueError from list.index (:183)
         }
-        p.status[b] = st;
+        p.status[b] = st;   // (no path inside the windows: every on_s is -1, so LA_EINFEASIBLE)
     }
     __syncthreads();
     for (int nn = k; nn < L; nn += NT) {
@@ -441,25 +469,26 @@ int launch(const char *timer, int threads, const VitParams &p, const VitPlan &pl
 }
 
 // the lane-per-state forms; the single wave takes its neighbours by DPP unless the option is off or dp / bt are dumped
-template <bool SPANS, bool DUMP>
+template <bool SPANS, bool DUMP, bool WIN = false>
 int launch_lanes(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
     switch (pl.nw) {
         case 1:
-            if (!DUMP && la::opts().viterbi_dpp) return launch<viterbi_kernel<1, true, SPANS>>(timer, 64, p, pl, batch, stream);
-            return launch<viterbi_kernel<1, false, SPANS, DUMP>>(timer, 64, p, pl, batch, stream);
-        case 2: return launch<viterbi_kernel<2, false, SPANS, DUMP>>(timer, 128, p, pl, batch, stream);
-        case 4: return launch<viterbi_kernel<4, false, SPANS, DUMP>>(timer, 256, p, pl, batch, stream);
-        case 8: return launch<viterbi_kernel<8, false, SPANS, DUMP>>(timer, 512, p, pl, batch, stream);
-        case 16: return launch<viterbi_kernel<16, false, SPANS, DUMP>>(timer, 1024, p, pl, batch, stream);
+            if (!DUMP && la::opts().viterbi_dpp) return launch<viterbi_kernel<1, true, SPANS, false, WIN>>(timer, 64, p, pl, batch, stream);
+            return launch<viterbi_kernel<1, false, SPANS, DUMP, WIN>>(timer, 64, p, pl, batch, stream);
+        case 2: return launch<viterbi_kernel<2, false, SPANS, DUMP, WIN>>(timer, 128, p, pl, batch, stream);
+        case 4: return launch<viterbi_kernel<4, false, SPANS, DUMP, WIN>>(timer, 256, p, pl, batch, stream);
+        case 8: return launch<viterbi_kernel<8, false, SPANS, DUMP, WIN>>(timer, 512, p, pl, batch, stream);
+        case 16: return launch<viterbi_kernel<16, false, SPANS, DUMP, WIN>>(timer, 1024, p, pl, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
 
-int query_workspace(bool spans, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", spans ? "viterbi_spans" : "viterbi");
+// who: "viterbi", "viterbi_spans" or "viterbi_windows" (the last two share the planner: three masks, one lane per state)
+int query_workspace(const char *who, bool spans, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", who);
     VitPlan pl;
     if (!plan_viterbi(batch, max_frames, max_labels, spans, &pl)) {
-        if (spans) la::set_error("viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)", max_labels);
+        if (spans) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", who, max_labels);
         else la::set_error("viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
         return LA_EUNSUPPORTED;
     }
@@ -467,22 +496,25 @@ int query_workspace(bool spans, int32_t batch, int32_t max_frames, int32_t max_l
     return LA_OK;
 }
 
-// la_viterbi_batch (p.skip_from unused) and la_viterbi_spans_batch: p holds the caller's arguments, the workspace fields are set here
-int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    const char *who = spans ? "viterbi_spans_batch" : "viterbi_batch";
+// la_viterbi_batch (p.skip_from unused), la_viterbi_spans_batch and la_viterbi_windows_batch (win: spans is set too, p.skip_from may be
+// null): p holds the caller's arguments, the workspace fields are set here
+int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream, bool win = false) {
+    const char *who = win ? "viterbi_windows_batch" : spans ? "viterbi_spans_batch" : "viterbi_batch";
     if (batch == 0) return LA_OK;
-    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && p.final_score && p.status && (!spans || p.skip_from),
+    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && p.final_score && p.status &&
+                     (!spans || win || p.skip_from) && (!win || (p.win_lo && p.win_hi)),
                  "%s: null pointer", who);
     LA_CHECK_ARG(batch > 0 && p.max_frames > 0 && p.max_labels > 0, "%s: bad sizes", who);
     LA_CHECK_ARG(!spans || p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
     const bool strides_ok = p.em_rs >= p.max_labels + 1 && p.out_stride >= p.max_labels && p.labels_stride >= p.max_labels &&
-                            (!spans || p.skip_stride >= p.max_labels + 1);
+                            (!spans || !p.skip_from || p.skip_stride >= p.max_labels + 1) &&
+                            (!win || p.win_stride >= 2 * p.max_labels + 1);
     VitPlan pl;
     const bool planned = plan_viterbi(batch, p.max_frames, p.max_labels, spans, &pl);
     // the label limit is reported after the strides by la_viterbi_batch and before them by la_viterbi_spans_batch
     LA_CHECK_ARG(strides_ok || (spans && !planned), "%s: strides smaller than max_labels", who);
     if (!planned) {
-        if (spans) la::set_error("viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)", p.max_labels);
+        if (spans) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", win ? "viterbi_windows" : "viterbi_spans", p.max_labels);
         else la::set_error("viterbi: max_labels %d exceeds 4095", p.max_labels);
         return LA_EUNSUPPORTED;
     }
@@ -491,6 +523,7 @@ int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t wo
     LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
     p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
     p.bt_in_lds = pl.bt_in_lds ? 1 : 0;
+    if (win) return launch_lanes<true, false, true>("viterbi_windows", p, pl, batch, stream);
     if (spans) return launch_lanes<true, false>("viterbi_spans", p, pl, batch, stream);
     switch (pl.strip) {
         case 0: return launch_lanes<false, false>("viterbi", p, pl, batch, stream);
@@ -504,11 +537,15 @@ int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t wo
 }  // namespace
 
 extern "C" int la_viterbi_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace(false, batch, max_frames, max_labels, bytes);
+    return query_workspace("viterbi", false, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace(true, batch, max_frames, max_labels, bytes);
+    return query_workspace("viterbi_spans", true, batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_viterbi_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace("viterbi_windows", true, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -530,6 +567,21 @@ extern "C" int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, 
     VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
                 max_labels, onset, offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty};
     return run_batch(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                        const int32_t *labels, int32_t labels_stride, const int32_t *n_labels,
+                                        const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
+                                        int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
+                                        int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                        const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                        void *workspace, size_t workspace_bytes, void *stream_) {
+    VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
+                max_labels, onset, offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty};
+    p.win_lo = win_lo;
+    p.win_hi = win_hi;
+    p.win_stride = win_stride;
+    return run_batch(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_, true);
 }
 
 // run_viterbi_core(dp, bt, lp, ls, label) of the reference (utils/alignment.py:73-119) for ONE utterance: same

@@ -10,6 +10,7 @@ drop-in frame_manual_forward + perform_viterbi(_ctc) pair exactly like the refer
 """
 from __future__ import annotations
 
+import re
 from typing import Any, Iterable, List, Optional, Sequence
 
 import numpy as np
@@ -201,3 +202,65 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
         # a span is taken or left as a whole: its characters are None together
         out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
     return (out, sung) if with_confidence else out
+
+
+_LRC_TAG = re.compile(r"\[([^\[\]]*)\]")
+_LRC_TIME = re.compile(r"^(\d+):(\d{1,2})(?:[.:](\d{1,3}))?$")
+
+
+def parse_lrc(text: str) -> List[tuple]:
+    """LRC lyric sheet -> [(start_seconds, line), ...] sorted by time (a stable sort: equal times keep the file's order).  Time tags are
+    [mm:ss], [mm:ss.xx] and [mm:ss.xxx]; several tags in front of one line repeat the line; metadata tags ([ar:...], [ti:...], [offset:...])
+    and lines without text are dropped."""
+    out = []
+    for raw in str(text).splitlines():
+        rest, times = raw.strip(), []
+        while True:
+            m = _LRC_TAG.match(rest)
+            if m is None:
+                break
+            t = _LRC_TIME.match(m.group(1).strip())
+            if t is not None:
+                frac = t.group(3) or ""
+                times.append(60.0 * int(t.group(1)) + int(t.group(2)) + (int(frac) / 10.0 ** len(frac) if frac else 0.0))
+            rest = rest[m.end():].lstrip()
+        if rest and times:
+            out += [(s, rest) for s in times]
+    out.sort(key=lambda v: v[0])
+    return out
+
+
+def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
+                     use_ctc_loss: bool = True, skip_penalty: float = 0.0):
+    """One recording against an LRC sheet (addition): per-character timing from per-line start times.  `lrc` is LRC text (parse_lrc) or a
+    list of (start_seconds, line) pairs; the first character of every line gets an onset anchor at the line's start time with tolerance_s
+    (AlignModel.align(onset_anchors=...): the line starts within tolerance_s of its tag, and everything before it has ended by then).
+    optional[i] marks lines that may be absent, as in align_record_lines (default: none).  `tokenize(line)` as in align_records, one class per
+    character.  -> one entry per line: None for a line the alignment left out, otherwise [[onset, offset, char], ...].  ValueError when no
+    path lies inside the anchors' windows (a tag further from its line than tolerance_s)."""
+    from .utils.alignment import spans_from_lines
+    pairs = parse_lrc(lrc) if isinstance(lrc, str) else [(float(s), str(line)) for s, line in lrc]
+    if not pairs:
+        raise ValueError("align_record_lrc: no timed line in the sheet")
+    lines = [line for _, line in pairs]
+    optional = [False] * len(lines) if optional is None else list(optional)
+    ids = [list(tokenize(line)) for line in lines]
+    for line, tok in zip(lines, ids):
+        if len(tok) != len(line):
+            raise ValueError(f"align_record_lrc: {len(tok)} tokens for the {len(line)} characters of {line!r}")
+    skip_from = spans_from_lines([len(t) for t in ids], optional)
+    spans = [(a, n) for n, a in enumerate(skip_from) if a >= 0]
+    anchors, pos = [], 0
+    for (start, _), tok in zip(pairs, ids):
+        anchors.append((pos, start, float(tolerance_s)))
+        pos += len(tok)
+    labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
+    with torch.no_grad():
+        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty, onset_anchors=[anchors])[0]
+    out: List[Optional[list]] = []
+    pos = 0
+    for line in lines:
+        part = res[pos: pos + len(line)]
+        pos += len(line)
+        out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
+    return out

@@ -330,7 +330,7 @@ class AlignModel(torch.nn.Module):
     def align(self, audios: Optional[Sequence[np.ndarray]] = None, labels=None, *, mel: Optional[torch.Tensor] = None,
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
-              skip_penalty: float = 0.0, return_span_confidence: bool = False):
+              skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -353,22 +353,42 @@ class AlignModel(torch.nn.Module):
         the character is on the path at all, and "span_skip_prob": the probability that the span was left out, one value per span of
         optional_spans[b] in the order given.  With return_frames the device tensors (onset, offset, score, status, occupancy, onset_prob,
         offset_prob, log_z, present_prob [B,Lmax], span_skip_prob [B,Lmax+1], indexed by the span's end position).  Without any span:
-        return_confidence's numbers, sung_prob 1 and an empty span_skip_prob."""
-        from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames, _skip_from_of_spans
+        return_confidence's numbers, sung_prob 1 and an empty span_skip_prob.
+        char_windows / onset_anchors (addition): what is known about time, per clip a list in utils.alignment.windows_from_anchors' form
+        -- char_windows[b] = [(n, lo_s, hi_s), ...], onset_anchors[b] = [(n, t_s, tol_s), ...], seconds in the clip's own frames (per_clip and
+        the long form included).  The head's emissions go through the DP with a frame window per lattice state (ops.viterbi_windows_batch),
+        with or without optional_spans.  None or all-empty: the call as it was.  A clip without a path inside its windows raises like a clip
+        too short for its labels (status LA_EINFEASIBLE with return_frames).  Not with return_confidence / return_span_confidence
+        (ValueError: no posteriors on the windowed lattice); at most 511 labels."""
+        from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames, _skip_from_of_spans, _windows_of
         eng = self.engine()
         kw = {}
         if per_clip:
             if mel is not None or not get_orig_len:
                 raise ValueError("align(per_clip=True) takes waveforms (audios=) and get_orig_len=True")
-            feats, B, T, nf_clip, _ = self._features_per_clip(audios)
+            feats, B, T, nf_clip, frame_counts = self._features_per_clip(audios)
             stride = N_CTX
             kw["n_frames"] = nf_clip
         else:
             if mel is None:
                 mel = self._mel_of(audios)
             feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
+            frame_counts = [T] * B
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
         skip_from = _skip_from_of_spans(optional_spans, lab_lists)
+        windows = _windows_of(char_windows, onset_anchors, lab_lists, frame_counts, hop_size_second)
+        if windows is not None:
+            if return_confidence or return_span_confidence:
+                raise ValueError("align: char_windows / onset_anchors do not go with return_confidence / return_span_confidence (no posteriors "
+                                 "on the windowed lattice)")
+            *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
+                                             want_emissions=True, **kw)
+            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
+            onset, offset, score, status = ops.viterbi_windows_batch(em, lab_dev, n_lab, nf, windows[0].to(eng.device), windows[1].to(eng.device),
+                                                                     None if skip_from is None else skip_from.to(eng.device), skip_penalty)
+            if return_frames:
+                return onset, offset, score, status
+            return _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=skip_from is not None)
         if skip_from is not None and return_confidence:
             raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice by that "
                              "keyword: return_span_confidence=True gives them)")

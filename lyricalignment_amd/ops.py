@@ -97,6 +97,33 @@ def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.
     return onset, offset, score, status
 
 
+def viterbi_windows_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                          win_lo: torch.Tensor, win_hi: torch.Tensor, skip_from: Optional[torch.Tensor] = None, skip_penalty: float = 0.0
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """la_viterbi_windows_batch: viterbi_spans_batch (skip_from None: viterbi_batch) on the lattice with a frame window per state.
+    win_lo / win_hi [B, >= 2*Lmax+1] i32 (device, one row pitch): state s of clip b may hold the path at frame t only if
+    win_lo[b, s] <= t < win_hi[b, s].  -> the tuple of viterbi_batch; a clip without a path inside its windows has status
+    LA_EINFEASIBLE, score -inf and every onset / offset -1."""
+    who = "viterbi_windows_batch"
+    more = dict(win_lo=win_lo, win_hi=win_hi) if skip_from is None else dict(win_lo=win_lo, win_hi=win_hi, skip_from=skip_from)
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
+    for t in (win_lo, win_hi):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != win_lo.stride(0):
+            raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
+    if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
+        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
+    skip_penalty = float(skip_penalty)
+    if not skip_penalty >= 0.0:
+        raise ValueError(f"{who}: skip_penalty must be >= 0")
+    onset, offset, score, status = _viterbi_outputs(B, Lmax, em.device)
+    ws, need = _lattice_workspace("viterbi_windows_workspace_bytes", B, T, Lmax, em.device)
+    check(lib().la_viterbi_windows_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
+                                         ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
+                                         ptr(skip_from), skip_from.stride(0) if skip_from is not None else 0, skip_penalty,
+                                         ptr(win_lo), ptr(win_hi), win_lo.stride(0), ptr(ws), need, stream_ptr()), who)
+    return onset, offset, score, status
+
+
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
                          onset: torch.Tensor, offset: torch.Tensor, boundary_window: int = 2, want_gamma: bool = False):
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,

@@ -11,6 +11,7 @@ reference's per-utterance loop.  No CPU fallback: the HIP library is required.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -80,6 +81,82 @@ def _skip_from_of_spans(optional_spans, label_lists: List[List[int]]):
     return rows if any_span else None
 
 
+def _frame_bound(seconds: float, hop: float, n_frames: int, up: bool) -> int:
+    """ceil (up) or floor of seconds / hop with a 1e-9 guard against the division's rounding, clamped to -1 .. n_frames + 1."""
+    x = min(max(float(seconds) / hop, -1.0), float(n_frames) + 1.0)
+    return int(math.ceil(x - 1e-9)) if up else int(math.floor(x + 1e-9))
+
+
+def windows_from_anchors(n_labels: int, n_frames: int, char_windows=None, onset_anchors=None,
+                         hop_size_second: float = 0.02) -> Tuple[List[int], List[int]]:
+    """One clip's per-state frame windows (include/lyricalign.h la_viterbi_windows_batch) from what is known about time: -> (lo, hi), two
+    lists of 2 * n_labels + 1 ints; state s (0 = leading silence, 2n+1 = character n, 2n+2 = the silence after it) may hold the path at
+    frame t only if lo[s] <= t < hi[s].  Without constraints every window is [0, n_frames).  Host only.
+    char_windows = [(n, lo_s, hi_s), ...]: character n's segment lies inside [lo_s, hi_s] seconds (either side None = open): state 2n+1
+    gets lo = ceil(lo_s / hop), hi = floor(hi_s / hop) (exclusive, as the reported offset is the last frame + 1).
+    onset_anchors = [(n, t_s, tol_s), ...]: if character n is on the path its onset lies within tol_s of t_s.  With [f_lo, f_hi] the
+    frames f with |f * hop - t_s| <= tol_s, widened to hold round(t_s / hop): state 2n+1 gets lo = f_lo and EVERY state below 2n+1 gets
+    hi = f_hi, so that the path has reached state 2n+1 (or passed it) by frame f_hi -- the bound a window on the character alone cannot
+    give, as the silence before it could stretch past it.
+    Several constraints on one state intersect.  ValueError for an index outside 0 .. n_labels-1, a negative tolerance, or a NaN."""
+    L, T, hop = int(n_labels), int(n_frames), float(hop_size_second)
+    if L < 0 or T < 0 or not hop > 0.0:
+        raise ValueError("windows_from_anchors: n_labels >= 0, n_frames >= 0 and hop_size_second > 0 expected")
+    lo, hi = [0] * (2 * L + 1), [T] * (2 * L + 1)
+
+    def index(n, what):
+        if isinstance(n, float) and n != n:
+            raise ValueError(f"windows_from_anchors: {what}: NaN")
+        if int(n) != n or not 0 <= int(n) < L:
+            raise ValueError(f"windows_from_anchors: {what}: character index {n} outside 0..{L - 1}")
+        return int(n)
+
+    def number(v, what):
+        v = float(v)
+        if v != v:
+            raise ValueError(f"windows_from_anchors: {what}: NaN")
+        return v
+
+    for n, lo_s, hi_s in (char_windows or ()):
+        s = 2 * index(n, "char_windows") + 1
+        if lo_s is not None:
+            lo[s] = max(lo[s], _frame_bound(number(lo_s, "char_windows"), hop, T, True))
+        if hi_s is not None:
+            hi[s] = min(hi[s], _frame_bound(number(hi_s, "char_windows"), hop, T, False))
+    for n, t_s, tol_s in (onset_anchors or ()):
+        s = 2 * index(n, "onset_anchors") + 1
+        t_s, tol_s = number(t_s, "onset_anchors"), number(tol_s, "onset_anchors")
+        if tol_s < 0.0:
+            raise ValueError(f"windows_from_anchors: onset_anchors: negative tolerance {tol_s}")
+        nearest = int(math.floor(min(max(t_s / hop, -1.0), T + 1.0) + 0.5))
+        f_lo = min(_frame_bound(t_s - tol_s, hop, T, True), nearest)
+        f_hi = max(_frame_bound(t_s + tol_s, hop, T, False), nearest)
+        lo[s] = max(lo[s], f_lo)
+        for below in range(s):
+            hi[below] = min(hi[below], f_hi)
+    return lo, hi
+
+
+def _windows_of(char_windows, onset_anchors, label_lists: List[List[int]], frame_counts: Sequence[int], hop_size_second: float):
+    """char_windows / onset_anchors: per utterance a list in windows_from_anchors' form (or None) -> host int32 tensors (win_lo, win_hi)
+    [B, 2 * Lmax + 1] in each utterance's own frames, or None when no utterance has a constraint (None or all-empty keywords)."""
+    B = len(label_lists)
+    for name, per in (("char_windows", char_windows), ("onset_anchors", onset_anchors)):
+        if per is not None and len(per) != B:
+            raise ValueError(f"{name}: {B} lists expected, one per utterance")
+    if not any(per is not None and any(len(v or ()) for v in per) for per in (char_windows, onset_anchors)):
+        return None
+    Lmax = max(1, max((len(l) for l in label_lists), default=1))
+    win_lo = torch.zeros((B, 2 * Lmax + 1), dtype=torch.int32)
+    win_hi = torch.zeros((B, 2 * Lmax + 1), dtype=torch.int32)
+    for b, labs in enumerate(label_lists):
+        lo, hi = windows_from_anchors(len(labs), int(frame_counts[b]), char_windows[b] if char_windows is not None else None,
+                                      onset_anchors[b] if onset_anchors is not None else None, hop_size_second)
+        win_lo[b, : len(lo)] = torch.tensor(lo, dtype=torch.int32)
+        win_hi[b, : len(hi)] = torch.tensor(hi, dtype=torch.int32)
+    return win_lo, win_hi
+
+
 def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second, skipped_as_none: bool = False):
     """skipped_as_none (the span lattice): a label with onset -1 under LA_OK was inside a taken jump -> None in place of [onset, offset]."""
     on, off, st = onset.cpu().numpy(), offset.cpu().numpy(), status.cpu().numpy()
@@ -125,7 +202,8 @@ def _device_of(prediction) -> torch.device:
     return torch.device(f"cuda:{torch.cuda.current_device()}")
 
 
-def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0):
+def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
+             char_windows=None, onset_anchors=None):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -143,6 +221,13 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
             raise ValueError(f"n_frames: {B} frame counts in 0..{T} expected")
         nf = torch.tensor(counts, dtype=torch.int32).to(dev)
     skip_from = _skip_from_of_spans(optional_spans, lists)
+    windows = _windows_of(char_windows, onset_anchors, lists, [T] * B if n_frames is None else counts, hop_size_second)
+    if windows is not None:                  # (addition) per-state frame windows; None / all-empty takes the paths below unchanged
+        if boundary_window is not None:
+            raise ValueError("char_windows / onset_anchors: no posteriors on the windowed lattice (use the functions without _scored)")
+        onset, offset, score, status = ops.viterbi_windows_batch(em, lab, n_lab, nf, windows[0].to(dev), windows[1].to(dev),
+                                                                 None if skip_from is None else skip_from.to(dev), skip_penalty)
+        return _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=skip_from is not None)
     if skip_from is not None:                # (addition) the lattice with optional spans; None / all-empty takes the path below unchanged
         skip_dev = skip_from.to(dev)
         onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
@@ -160,37 +245,44 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists)
 
 
-def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0):
+def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
+                    char_windows=None, onset_anchors=None):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
     aligned over its first n_frames[b] rows, as if it had been handed over alone.
     optional_spans (addition): optional_spans[b] = list of (a, n) pairs, labels a .. n-1 of utterance b may be left out by the path
     (la_viterbi_spans_batch; skip_penalty >= 0 per taken jump); skipped characters come back as None in place of [onset, offset].
-    None or all-empty: today's DP.  ValueError for a < 0, a >= n, n > L or two spans with one end."""
+    None or all-empty: today's DP.  ValueError for a < 0, a >= n, n > L or two spans with one end.
+    char_windows / onset_anchors (addition): per utterance a list in windows_from_anchors' form (seconds, in the utterance's own frames):
+    the DP runs on the lattice with per-state frame windows (la_viterbi_windows_batch), with or without optional_spans.  None or
+    all-empty: the call as it was.  An utterance without a path inside its windows raises like one too short for its labels."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
-                    skip_penalty=skip_penalty)
+                    skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
 
-def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0):
+def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
+                        char_windows=None, onset_anchors=None):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
-                    skip_penalty=skip_penalty)
+                    skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
 
-def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0):
+def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0,
+                           char_windows=None, onset_anchors=None):
     """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
     scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
     sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi.
     optional_spans / skip_penalty as perform_viterbi: skipped characters are None (their three scores 0), and each dict additionally holds
     "sung_prob": [L] (probability that the character is on the path at all) and "span_skip_prob": one value per span, in the order given
-    (probability that the span was left out) -- la_alignment_posteriors_spans.  Without a span the dicts are as before, without these keys."""
+    (probability that the span was left out) -- la_alignment_posteriors_spans.  Without a span the dicts are as before, without these keys.
+    char_windows / onset_anchors: ValueError unless None or all-empty (no posteriors on the windowed lattice)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
-                    optional_spans=optional_spans, skip_penalty=skip_penalty)
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
 
 def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                               skip_penalty=0.0):
+                               skip_penalty=0.0, char_windows=None, onset_anchors=None):
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
-                    optional_spans=optional_spans, skip_penalty=skip_penalty)
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
 
 def run_viterbi_core(dp_matrix, backtrace_dp_matrix, cur_log_prediction, cur_log_silence_prediction, cur_label):
