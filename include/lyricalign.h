@@ -333,6 +333,46 @@ int la_alignment_posteriors_spans(const float *em, int64_t em_batch_stride, int6
                                   float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Confidence GIVEN what the caller knows about time: the sum-product sweep of la_viterbi_windows_batch's lattice (no counterpart
+ * in the reference).  Every argument of la_alignment_posteriors_spans up to skip_penalty in the same order (skip_from may be
+ * NULL: no span anywhere; skip_stride is also the row pitch of span_skip_prob and must be >= max_labels + 1 either way), then
+ * win_lo / win_hi [batch][win_stride] int32 as la_viterbi_windows_batch (device, win_stride >= 2 * max_labels + 1; entries
+ * 0 .. 2 L_b of row b are read; any pair of int32 values is legal, lo >= hi closes the state), then the outputs and the
+ * workspace of la_alignment_posteriors_spans, unchanged.  A cell (t, s) weighs zero unless win_lo[b][s] <= t < win_hi[b][s]:
+ * the sweep runs over exactly the paths la_viterbi_windows_batch maximises over, and log_z is the log-sum over THOSE paths, so
+ *   gamma, occupancy, onset_prob, offset_prob, present_prob, span_skip_prob are posteriors given the windows (gamma_t(s) is
+ *   exactly 0 outside the window of s; rows of gamma still sum to 1; the coverage identity of la_alignment_posteriors_spans
+ *   holds), and final_score[b] of la_viterbi_windows_batch - log_z[b] <= 0 is the log-posterior of its path given the windows;
+ *   log_z[b] - (log_z[b] of la_alignment_posteriors_spans / la_alignment_posteriors on the same emissions) <= 0 is the
+ *   log-probability the unanchored model gives to "the path lies inside the windows": near 0 when the windows agree with the
+ *   audio, strongly negative when one of them fights it.
+ * onset / offset are la_viterbi_windows_batch's outputs for the same windows, skip_from and skip_penalty.  No path inside the
+ * windows: status LA_EINFEASIBLE, log_z -inf, every output row and gamma 0 (as for a clip too short for its labels).  Other
+ * statuses, zeroing, gamma_out, the limit max_labels <= 511, option viterbi_dpp and the error bound 8 T 2^-23 as
+ * la_alignment_posteriors_spans (a closed cell is exactly -inf and adds no rounding); a clip without a span gets
+ * present_prob = 1 for its labels and span_skip_prob = 0.  With every window [0, T_b) the outputs are
+ * la_alignment_posteriors_spans' bit for bit (with a NULL or all -1 skip_from the shared ones are la_alignment_posteriors').
+ * la_alignment_posteriors_windows_workspace_bytes() = la_alignment_posteriors_spans_workspace_bytes().  Argument errors (null
+ * win_lo / win_hi, a win_stride below 2 * max_labels + 1, la_alignment_posteriors_spans' other checks; more than 511 labels:
+ * LA_EUNSUPPORTED) are answered on the host before anything is enqueued; never synchronises, allocates or frees.
+ */
+int la_alignment_posteriors_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors_windows(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                    const int32_t *labels, int32_t labels_stride,
+                                    const int32_t *n_labels, const int32_t *n_frames,
+                                    int32_t batch, int32_t max_frames, int32_t max_labels,
+                                    const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                                    int32_t boundary_window,
+                                    const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                    const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                    float *occupancy, float *onset_prob, float *offset_prob, float *present_prob,
+                                    float *span_skip_prob,
+                                    double *log_z, int32_t *status,
+                                    float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* emission prep from materialised logits                                     */
 /*   (replaces utils/alignment.py:123-134 [CTC] and :14-20 [plain])           */

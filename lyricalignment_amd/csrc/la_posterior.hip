@@ -32,6 +32,16 @@
 // lanes, which hold beta_t and read alpha_{t-1}(J), alpha_{t-1}(J-1) from the stored alpha rows; lanes 2n and 2n+1 are added at the
 // end.  "This clip has a span" is a workgroup-uniform test taken once: a span-free clip runs the loops of the plain kernel (its
 // present_prob is written as 1: without a jump every path visits every label).
+//
+// Frame windows (the WIN instantiations, la_alignment_posteriors_windows): the lattice of la_viterbi_windows_batch swept sum-product.  A
+// cell (t, s) outside win_lo[s] <= t < win_hi[s] weighs zero.  Each lane keeps its state's lo / hi in two registers and the gate acts on
+// the EMISSION, off the loop-carried chain, as in the DP: sum + (double)(-inf) is -inf (sum is never +inf or NaN).  Forward, the block of
+// prefetched emissions is gated as it is copied; backward, a step needs the emission twice -- gated in beta_t = sum + e, UNGATED in
+// gamma = exp(alpha + beta - e - log_z), where alpha and beta are already -inf outside the window and the gated value would give
+// -inf - (-inf) = NaN -- so the gated value is selected beside the ungated one, from the frame index alone.  Entry, exit, present and
+// span-skip terms all carry a beta_t or alpha_t factor of the gated cell and need nothing more.  log_z is the windowed one: every output
+// is a posterior GIVEN the windows; log_z = -inf (no path inside them) is the existing LA_EINFEASIBLE exit.  WIN exists only together
+// with SPANS (a null skip_from = no span anywhere; the once-per-clip has_span test still sends a span-free clip through the plain loops).
 #include <type_traits>
 
 #include "la_lattice.h"
@@ -70,11 +80,15 @@ struct PostParams {
     int32_t skip_stride;
     double penalty;
     float *present_prob, *span_skip_prob;  // [batch][out_stride], [batch][skip_stride]
+    // per-state frame windows (WIN instantiations only): [batch][win_stride], entries 0 .. 2 L_b of row b are read
+    const int32_t *win_lo, *win_hi;
+    int32_t win_stride;
 };
 
-template <int NW, bool DPP, bool SPANS>
+template <int NW, bool DPP, bool SPANS, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     static_assert(!DPP || NW == 1, "DPP neighbour exchange is single-wave only");
+    static_assert(!WIN || SPANS, "frame windows are a face of the optional-span forms");
     constexpr int NT = NW * 64;
     // steps per prefetch block: 8; 4 in the multi-wave form, which also prefetches two neighbour alpha columns (1024 threads leave 128
     // VGPRs).  A clip with spans in the multi-wave form prefetches alpha(J) and alpha(J-1) as well, and its steps are several times
@@ -145,7 +159,8 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     bool jm1_ok = false;
     if constexpr (SPANS) {
         if (k <= L) {  // (L + 1 <= NT / 2 + 1)
-            const int a = p.skip_from[(int64_t)b * p.skip_stride + k];
+            int a = -1;
+            if (!WIN || p.skip_from) a = p.skip_from[(int64_t)b * p.skip_stride + k];   // (windows: a null skip_from = no span anywhere)
             skip_s[k] = (a >= 0 && a < k) ? a : -1;
         }
         __syncthreads();
@@ -193,8 +208,18 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
         }
     }
 
+    // this state's frame window; lanes without a state keep the open one (nothing is read past 2 L_b <= win_stride - 1)
+    int wlo = 0, whi = 0x7fffffff;
+    if constexpr (WIN) {
+        if (valid) {
+            wlo = p.win_lo[(int64_t)b * p.win_stride + k];
+            whi = p.win_hi[(int64_t)b * p.win_stride + k];
+        }
+    }
+    auto gated = [&](float e, int t) { return (t >= wlo && t < whi) ? e : -INFINITY; };
+
     // ---- forward: alpha_t(k) = e_t(k) + logsumexp(alpha_{t-1}(k), alpha_{t-1}(k-1), [alpha_{t-1}(k-2)]) ----
-    double a = k <= 1 ? (double)emb[0] : NEG;
+    double a = k <= 1 ? (double)(WIN ? gated(emb[0], 0) : emb[0]) : NEG;
     aw[0] = a;
     auto forward = [&](auto has_c) {
         constexpr bool HAS = decltype(has_c)::value;  // this clip has a span
@@ -208,7 +233,7 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
         for (int t0 = 1; t0 < T; t0 += U) {
             float ec[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) ec[u] = ev[u];
+            for (int u = 0; u < U; ++u) ec[u] = WIN ? gated(ev[u], t0 + u) : ev[u];   // the window's gate: off the dependent chain
             if (t0 + U < T) fetch(t0 + U);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -307,11 +332,13 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                 const int t = t0 - u;
                 if (t >= 0) {  // workgroup-uniform
                     const double e = (double)ec[u];
+                    // gated in the sums, UNGATED in gamma's subtraction (depends on t and the prefetched value alone: off the chain)
+                    const double eg = WIN ? (double)gated(ec[u], t) : e;
                     const double at = ac[u];
                     double out = NEG;  // log weight of leaving state k after frame t: beta_{t+1}(k+1), [beta_{t+1}(k+2)]
                     double js = NEG;   // with spans: the same over the jump arcs that leave state k
                     if (t == T - 1) {
-                        be = (k == S - 1 || k == S - 2) ? e : NEG;
+                        be = (k == S - 1 || k == S - 2) ? eg : NEG;
                     } else {
                         double b1, b2;
                         if (DPP) {
@@ -338,7 +365,7 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                         out = log_add2(b1, b2);
                         double sum = log_add3(be, b1, b2);
                         if (HAS) sum = log_add_jump(sum, js);
-                        be = valid ? sum + e : NEG;
+                        be = valid ? sum + eg : NEG;
                     }
                     double am1, am2;  // alpha_{t-1}(k-1), alpha_{t-1}(k-2)
                     if (DPP) {
@@ -360,7 +387,7 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                         }
                         if (J >= 0 && t > 0) jin = log_add_jump(aj - pen, jm1_ok ? ajm - pen : NEG);
                     }
-                    const float g = __expf((float)(at + be - e - log_z));  // alpha and beta both include e_t(k)
+                    const float g = __expf((float)(at + be - e - log_z));  // alpha and beta both include e_t(k); outside a window both are -inf
                     if (gam && k < Sg) gam[(int64_t)t * p.gamma_rs + k] = g;
                     if (HAS) {
                         if (J >= 0 && t > 0) s_skip += (double)__expf((float)(jin + be - log_z));
@@ -421,22 +448,24 @@ bool plan_posterior(int max_labels, int *nw_out) {
     return *nw_out <= 16;
 }
 
-template <int NW, bool DPP, bool SPANS>
+template <int NW, bool DPP, bool SPANS, bool WIN>
 int launch_posterior(const PostParams &p, int batch, hipStream_t stream) {
-    la::TimerScope ts(SPANS ? "posterior_spans" : "posterior", stream);
-    hipLaunchKernelGGL((posterior_kernel<NW, DPP, SPANS>), dim3(batch), dim3(NW * 64), 0, stream, p);
+    la::TimerScope ts(WIN ? "posterior_windows" : SPANS ? "posterior_spans" : "posterior", stream);
+    hipLaunchKernelGGL((posterior_kernel<NW, DPP, SPANS, WIN>), dim3(batch), dim3(NW * 64), 0, stream, p);
     LA_LAUNCH_CHECK();
     return LA_OK;
 }
 
-template <bool SPANS>
+template <bool SPANS, bool WIN = false>
 int launch_waves(int nw, const PostParams &p, int batch, hipStream_t stream) {
     switch (nw) {
-        case 1: return la::opts().viterbi_dpp ? launch_posterior<1, true, SPANS>(p, batch, stream) : launch_posterior<1, false, SPANS>(p, batch, stream);
-        case 2: return launch_posterior<2, false, SPANS>(p, batch, stream);
-        case 4: return launch_posterior<4, false, SPANS>(p, batch, stream);
-        case 8: return launch_posterior<8, false, SPANS>(p, batch, stream);
-        case 16: return launch_posterior<16, false, SPANS>(p, batch, stream);
+        case 1:
+            return la::opts().viterbi_dpp ? launch_posterior<1, true, SPANS, WIN>(p, batch, stream)
+                                          : launch_posterior<1, false, SPANS, WIN>(p, batch, stream);
+        case 2: return launch_posterior<2, false, SPANS, WIN>(p, batch, stream);
+        case 4: return launch_posterior<4, false, SPANS, WIN>(p, batch, stream);
+        case 8: return launch_posterior<8, false, SPANS, WIN>(p, batch, stream);
+        case 16: return launch_posterior<16, false, SPANS, WIN>(p, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
@@ -452,18 +481,21 @@ int query_workspace(const char *who, int32_t batch, int32_t max_frames, int32_t 
     return LA_OK;
 }
 
-// la_alignment_posteriors (the span fields of p unused) and la_alignment_posteriors_spans: p holds the caller's arguments
-int run_posteriors(bool spans, PostParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    const char *who = spans ? "alignment_posteriors_spans" : "alignment_posteriors";
+// la_alignment_posteriors (the span fields of p unused), la_alignment_posteriors_spans and la_alignment_posteriors_windows (win: spans is
+// set too, p.skip_from may be null; skip_stride stays the row pitch of span_skip_prob): p holds the caller's arguments
+int run_posteriors(bool spans, PostParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream, bool win = false) {
+    const char *who = win ? "alignment_posteriors_windows" : spans ? "alignment_posteriors_spans" : "alignment_posteriors";
     if (batch == 0) return LA_OK;
-    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && (!spans || p.skip_from), "%s: null input pointer", who);
+    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && (!spans || win || p.skip_from) &&
+                     (!win || (p.win_lo && p.win_hi)),
+                 "%s: null input pointer", who);
     LA_CHECK_ARG(p.occupancy && p.onset_prob && p.offset_prob && p.log_z && p.status && (!spans || (p.present_prob && p.span_skip_prob)),
                  "%s: null output pointer", who);
     LA_CHECK_ARG(batch > 0 && p.max_frames > 0 && p.max_labels > 0, "%s: bad sizes", who);
     LA_CHECK_ARG(p.window >= 0, "%s: negative boundary_window", who);
     LA_CHECK_ARG(!spans || p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
     LA_CHECK_ARG(p.em_rs >= p.max_labels + 1 && p.out_stride >= p.max_labels && p.labels_stride >= p.max_labels &&
-                     (!spans || p.skip_stride >= p.max_labels + 1),
+                     (!spans || p.skip_stride >= p.max_labels + 1) && (!win || p.win_stride >= 2 * p.max_labels + 1),
                  "%s: strides smaller than max_labels", who);
     LA_CHECK_ARG(!p.gamma || (p.gamma_rs >= 2 * (int64_t)p.max_labels + 1 && (batch == 1 || p.gamma_bs >= (int64_t)p.max_frames * p.gamma_rs)),
                  "%s: gamma strides smaller than [max_frames][2 max_labels + 1]", who);
@@ -476,6 +508,7 @@ int run_posteriors(bool spans, PostParams p, int32_t batch, void *workspace, siz
     LA_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
     LA_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
     p.alpha_ws = reinterpret_cast<double *>(workspace);
+    if (win) return launch_waves<true, true>(nw, p, batch, stream);
     return spans ? launch_waves<true>(nw, p, batch, stream) : launch_waves<false>(nw, p, batch, stream);
 }
 
@@ -487,6 +520,10 @@ extern "C" int la_alignment_posteriors_workspace_bytes(int32_t batch, int32_t ma
 
 extern "C" int la_alignment_posteriors_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     return query_workspace("alignment_posteriors_spans", batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_alignment_posteriors_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace("alignment_posteriors_windows", batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_alignment_posteriors(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
@@ -515,4 +552,20 @@ extern "C" int la_alignment_posteriors_spans(const float *em, int64_t em_batch_s
                  gamma_out, gamma_batch_stride, gamma_row_stride, nullptr, skip_from, skip_stride, skip_penalty, present_prob,
                  span_skip_prob};
     return run_posteriors(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int la_alignment_posteriors_windows(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
+                                               int32_t labels_stride, const int32_t *n_labels, const int32_t *n_frames, int32_t batch,
+                                               int32_t max_frames, int32_t max_labels, const int32_t *onset, const int32_t *offset,
+                                               int32_t out_stride, int32_t boundary_window, const int32_t *skip_from, int32_t skip_stride,
+                                               double skip_penalty, const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                               float *occupancy, float *onset_prob, float *offset_prob, float *present_prob,
+                                               float *span_skip_prob, double *log_z, int32_t *status, float *gamma_out,
+                                               int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
+                                               size_t workspace_bytes, void *stream_) {
+    PostParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
+                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
+                 gamma_out, gamma_batch_stride, gamma_row_stride, nullptr, skip_from, skip_stride, skip_penalty, present_prob,
+                 span_skip_prob, win_lo, win_hi, win_stride};
+    return run_posteriors(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_, true);
 }

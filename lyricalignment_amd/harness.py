@@ -231,13 +231,19 @@ def parse_lrc(text: str) -> List[tuple]:
 
 
 def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
-                     use_ctc_loss: bool = True, skip_penalty: float = 0.0):
+                     use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False):
     """One recording against an LRC sheet (addition): per-character timing from per-line start times.  `lrc` is LRC text (parse_lrc) or a
     list of (start_seconds, line) pairs; the first character of every line gets an onset anchor at the line's start time with tolerance_s
     (AlignModel.align(onset_anchors=...): the line starts within tolerance_s of its tag, and everything before it has ended by then).
     optional[i] marks lines that may be absent, as in align_record_lines (default: none).  `tokenize(line)` as in align_records, one class per
     character.  -> one entry per line: None for a line the alignment left out, otherwise [[onset, offset, char], ...].  ValueError when no
-    path lies inside the anchors' windows (a tag further from its line than tolerance_s)."""
+    path lies inside the anchors' windows (a tag further from its line than tolerance_s).
+    with_confidence: -> (lines_out, conf) with the posteriors GIVEN the tags (AlignModel.align(return_anchored_confidence=True)):
+    conf = {"sung": [per line, as align_record_lines: the probability that the line was sung, 1 for a mandatory line],
+            "line_onset_prob": [per line: the probability that the line's first character starts within boundary_window = 2 frames of
+                                the reported onset, None for a line that was left out],
+            "window_log_prob": float <= 0, the log-probability the unanchored model gives to "the path respects every tag" -- near 0
+                               when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}."""
     from .utils.alignment import spans_from_lines
     pairs = parse_lrc(lrc) if isinstance(lrc, str) else [(float(s), str(line)) for s, line in lrc]
     if not pairs:
@@ -255,12 +261,25 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
         anchors.append((pos, start, float(tolerance_s)))
         pos += len(tok)
     labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
+    scores = None
     with torch.no_grad():
-        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty, onset_anchors=[anchors])[0]
+        if with_confidence:
+            res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                      onset_anchors=[anchors], return_anchored_confidence=True)
+            res, scores = res[0], scores[0]
+        else:
+            res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty, onset_anchors=[anchors])[0]
     out: List[Optional[list]] = []
+    sung: List[float] = []
+    line_onset: List[Optional[float]] = []
     pos = 0
     for line in lines:
         part = res[pos: pos + len(line)]
+        if with_confidence:
+            sung.append(float(scores["sung_prob"][pos]))
+            line_onset.append(None if part[0] is None else float(scores["onset_prob"][pos]))
         pos += len(line)
         out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
+    if with_confidence:
+        return out, {"sung": sung, "line_onset_prob": line_onset, "window_log_prob": float(scores["window_log_prob"])}
     return out

@@ -330,7 +330,8 @@ class AlignModel(torch.nn.Module):
     def align(self, audios: Optional[Sequence[np.ndarray]] = None, labels=None, *, mel: Optional[torch.Tensor] = None,
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
-              skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None):
+              skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
+              return_anchored_confidence: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -359,8 +360,20 @@ class AlignModel(torch.nn.Module):
         the long form included).  The head's emissions go through the DP with a frame window per lattice state (ops.viterbi_windows_batch),
         with or without optional_spans.  None or all-empty: the call as it was.  A clip without a path inside its windows raises like a clip
         too short for its labels (status LA_EINFEASIBLE with return_frames).  Not with return_confidence / return_span_confidence
-        (ValueError: no posteriors on the windowed lattice); at most 511 labels."""
-        from ..utils.alignment import _labels_to_device, _scores_from_posteriors, _seconds_from_frames, _skip_from_of_spans, _windows_of
+        (ValueError: return_anchored_confidence is the keyword); at most 511 labels.
+        return_anchored_confidence (addition): -> (seconds, scores) on the lattice with the frame windows of char_windows / onset_anchors
+        (ops.alignment_posteriors_windows), with or without optional_spans, per_clip and the long form: return_span_confidence's dicts,
+        every number a posterior GIVEN the windows, plus "window_log_prob" = log_z(windowed) - log_z(same lattice, no windows) <= 0, the
+        log-probability the unanchored model gives to "the path lies inside the windows" (near 0: the anchors agree with the audio;
+        strongly negative: one of them fights it; the second log_z is one more launch of the existing sweep).  None or all-empty windows:
+        return_span_confidence's dicts and window_log_prob 0.0.  With return_frames the windowed DP's four tensors, then (occupancy,
+        onset_prob, offset_prob, log_z, present_prob, span_skip_prob, log_z_free).  A clip without a path inside its windows raises as
+        above.  Not together with return_confidence / return_span_confidence (ValueError)."""
+        from ..utils.alignment import (_anchored_posteriors, _labels_to_device, _scores_from_posteriors, _seconds_from_frames,
+                                       _skip_from_of_spans, _windows_of)
+        if return_anchored_confidence and (return_confidence or return_span_confidence):
+            raise ValueError("align: return_anchored_confidence does not go with return_confidence / return_span_confidence (it returns "
+                             "their numbers on the windowed lattice)")
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -377,10 +390,21 @@ class AlignModel(torch.nn.Module):
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
         skip_from = _skip_from_of_spans(optional_spans, lab_lists)
         windows = _windows_of(char_windows, onset_anchors, lab_lists, frame_counts, hop_size_second)
+        if return_anchored_confidence:
+            *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
+                                             want_emissions=True, **kw)
+            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
+            onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free = _anchored_posteriors(
+                em, lab_dev, n_lab, nf, windows, skip_from, skip_penalty, boundary_window)
+            if return_frames:
+                return onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free
+            seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=True)
+            spans = optional_spans if optional_spans is not None else [[] for _ in lab_lists]
+            return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists, pres, skp, spans, log_z_free)
         if windows is not None:
             if return_confidence or return_span_confidence:
-                raise ValueError("align: char_windows / onset_anchors do not go with return_confidence / return_span_confidence (no posteriors "
-                                 "on the windowed lattice)")
+                raise ValueError("align: char_windows / onset_anchors do not go with return_confidence / return_span_confidence "
+                                 "(return_anchored_confidence=True gives the posteriors on the windowed lattice)")
             *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
                                              want_emissions=True, **kw)
             nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)

@@ -188,6 +188,52 @@ def alignment_posteriors_spans(em: torch.Tensor, labels: torch.Tensor, n_labels:
     return res + (gamma,) if want_gamma else res
 
 
+def alignment_posteriors_windows(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                                 onset: torch.Tensor, offset: torch.Tensor, win_lo: torch.Tensor, win_hi: torch.Tensor,
+                                 skip_from: Optional[torch.Tensor] = None, skip_penalty: float = 0.0, boundary_window: int = 2,
+                                 want_gamma: bool = False):
+    """la_alignment_posteriors_windows: alignment_posteriors_spans (skip_from None: no span anywhere) on the lattice with a frame window
+    per state, the lattice of viterbi_windows_batch; onset / offset = its outputs for the same windows, skip_from and skip_penalty.
+    win_lo / win_hi as viterbi_windows_batch.  Every output is a posterior GIVEN the windows (normalised by the windowed log_z).
+    -> the tuple of alignment_posteriors_spans (skip_from None: present_prob 1 on reported labels, span_skip_prob 0); a clip without a
+    path inside its windows has status LA_EINFEASIBLE, log_z -inf and every output 0."""
+    who = "alignment_posteriors_windows"
+    more = dict(onset=onset, offset=offset, win_lo=win_lo, win_hi=win_hi)
+    if skip_from is not None:
+        more["skip_from"] = skip_from
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
+    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
+        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
+    for t in (win_lo, win_hi):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != win_lo.stride(0):
+            raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
+    if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
+        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
+    if int(boundary_window) < 0:
+        raise ValueError(f"{who}: boundary_window must be >= 0")
+    skip_penalty = float(skip_penalty)
+    if not skip_penalty >= 0.0:
+        raise ValueError(f"{who}: skip_penalty must be >= 0")
+    onset = onset.contiguous(); offset = offset.contiguous()
+    dev = em.device
+    occupancy, onset_prob, offset_prob, present_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(4))
+    skip_stride = skip_from.stride(0) if skip_from is not None else Lmax + 1    # the row pitch of span_skip_prob as well
+    span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
+    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
+    ws, need = _lattice_workspace("alignment_posteriors_windows_workspace_bytes", B, T, Lmax, dev)
+    check(lib().la_alignment_posteriors_windows(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
+                                                ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
+                                                ptr(skip_from), skip_stride, skip_penalty,
+                                                ptr(win_lo), ptr(win_hi), win_lo.stride(0), ptr(occupancy), ptr(onset_prob),
+                                                ptr(offset_prob), ptr(present_prob), ptr(span_skip_prob), ptr(log_z), ptr(status), ptr(gamma),
+                                                gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
+                                                ptr(ws), need, stream_ptr()), who)
+    res = (occupancy, onset_prob, offset_prob, log_z, status, present_prob, span_skip_prob)
+    return res + (gamma,) if want_gamma else res
+
+
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:
     """logits [B,T,V] f32 device -> compact emissions [B,T,Lmax+1] f32."""
     _dev(logits, "logits", torch.float32); _dev(labels, "labels", torch.int32); _dev(n_labels, "n_labels", torch.int32)

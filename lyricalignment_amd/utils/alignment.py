@@ -176,11 +176,12 @@ def _seconds_from_frames(onset, offset, status, label_lists, hop_size_second, sk
 
 
 def _scores_from_posteriors(occupancy, onset_prob, offset_prob, log_z, final_score, label_lists, present_prob=None, span_skip_prob=None,
-                            optional_spans=None):
+                            optional_spans=None, log_z_free=None):
     """Device outputs of ops.alignment_posteriors -> per-utterance dicts of Python floats (after _seconds_from_frames
     has raised for failed utterances).  path_log_posterior = final_score - log_z <= 0: log-probability of the reported path.
     With present_prob / span_skip_prob (ops.alignment_posteriors_spans) each dict also holds "sung_prob": [L] and "span_skip_prob":
-    one value per span of optional_spans[b], in the order given."""
+    one value per span of optional_spans[b], in the order given.  With log_z_free (the same lattice without frame windows) also
+    "window_log_prob" = log_z - log_z_free <= 0: the log-probability the unanchored model gives to "the path lies inside the windows"."""
     occ, onp, offp = occupancy.cpu().numpy(), onset_prob.cpu().numpy(), offset_prob.cpu().numpy()
     lz, fs = log_z.cpu().numpy(), final_score.cpu().numpy()
     out = [{"occupancy": [float(v) for v in occ[b, : len(labs)]],
@@ -192,7 +193,38 @@ def _scores_from_posteriors(occupancy, onset_prob, offset_prob, log_z, final_sco
         for b, labs in enumerate(label_lists):
             out[b]["sung_prob"] = [float(v) for v in pres[b, : len(labs)]]
             out[b]["span_skip_prob"] = [float(skp[b, int(n)]) for _, n in ((optional_spans[b] or ()) if optional_spans is not None else ())]
+    if log_z_free is not None:
+        lzf = log_z_free.cpu().numpy()
+        for b in range(len(label_lists)):
+            out[b]["window_log_prob"] = float(lz[b] - lzf[b])
     return out
+
+
+def _anchored_posteriors(em, lab, n_lab, nf, windows, skip_from, skip_penalty, boundary_window):
+    """DP and posteriors GIVEN the frame windows (host tensors (win_lo, win_hi), or None: no window at all) on the lattice with the
+    optional spans of skip_from (host tensor or None) -> device tensors (onset, offset, score, status, occupancy, onset_prob,
+    offset_prob, log_z, present_prob, span_skip_prob, log_z_free); log_z_free is log_z of the same lattice without windows (one more
+    launch of the existing sweep; without windows it IS log_z)."""
+    dev = em.device
+    skip_dev = None if skip_from is None else skip_from.to(dev)
+    if windows is None:
+        if skip_dev is None:                 # the plain DP's frames are the span DP's bit for bit when no span exists
+            onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
+            skip_dev = torch.full((em.shape[0], lab.shape[1] + 1), -1, dtype=torch.int32, device=dev)
+        else:
+            onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
+        occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty,
+                                                                             boundary_window)
+        return onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z
+    win_lo, win_hi = windows[0].to(dev), windows[1].to(dev)
+    onset, offset, score, status = ops.viterbi_windows_batch(em, lab, n_lab, nf, win_lo, win_hi, skip_dev, skip_penalty)
+    occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_windows(em, lab, n_lab, nf, onset, offset, win_lo, win_hi, skip_dev,
+                                                                           skip_penalty, boundary_window)
+    if skip_dev is None:
+        log_z_free = ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[3]
+    else:
+        log_z_free = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, boundary_window)[3]
+    return onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free
 
 
 def _device_of(prediction) -> torch.device:
@@ -203,7 +235,7 @@ def _device_of(prediction) -> torch.device:
 
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
-             char_windows=None, onset_anchors=None):
+             char_windows=None, onset_anchors=None, anchored=False):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -222,9 +254,16 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         nf = torch.tensor(counts, dtype=torch.int32).to(dev)
     skip_from = _skip_from_of_spans(optional_spans, lists)
     windows = _windows_of(char_windows, onset_anchors, lists, [T] * B if n_frames is None else counts, hop_size_second)
+    if anchored:                             # (addition) posteriors GIVEN the windows, and what the unanchored model thinks of them
+        onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free = _anchored_posteriors(
+            em, lab, n_lab, nf, windows, skip_from, skip_penalty, boundary_window)
+        seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=True)
+        spans = optional_spans if optional_spans is not None else [[] for _ in lists]
+        return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists, pres, skp, spans, log_z_free)
     if windows is not None:                  # (addition) per-state frame windows; None / all-empty takes the paths below unchanged
         if boundary_window is not None:
-            raise ValueError("char_windows / onset_anchors: no posteriors on the windowed lattice (use the functions without _scored)")
+            raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
+                             "(perform_viterbi(_ctc)_anchored_scored give them)")
         onset, offset, score, status = ops.viterbi_windows_batch(em, lab, n_lab, nf, windows[0].to(dev), windows[1].to(dev),
                                                                  None if skip_from is None else skip_from.to(dev), skip_penalty)
         return _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=skip_from is not None)
@@ -273,7 +312,7 @@ def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_wi
     optional_spans / skip_penalty as perform_viterbi: skipped characters are None (their three scores 0), and each dict additionally holds
     "sung_prob": [L] (probability that the character is on the path at all) and "span_skip_prob": one value per span, in the order given
     (probability that the span was left out) -- la_alignment_posteriors_spans.  Without a span the dicts are as before, without these keys.
-    char_windows / onset_anchors: ValueError unless None or all-empty (no posteriors on the windowed lattice)."""
+    char_windows / onset_anchors: ValueError unless None or all-empty (perform_viterbi_anchored_scored is the function for them)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
@@ -283,6 +322,29 @@ def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundar
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
+
+
+def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                    skip_penalty=0.0, char_windows=None, onset_anchors=None):
+    """perform_viterbi with char_windows / onset_anchors plus the confidence GIVEN them (addition): -> (predicted_onset_offset, scores).
+    The DP and the forward-backward sweep run on the lattice with per-state frame windows (la_viterbi_windows_batch,
+    la_alignment_posteriors_windows), with or without optional_spans.  scores[b] holds perform_viterbi_scored's keys with optional_spans
+    ("occupancy", "onset_prob", "offset_prob", "path_log_posterior", "sung_prob", "span_skip_prob"; without a span sung_prob is 1 and
+    span_skip_prob empty), every one a posterior given the windows, and "window_log_prob" = log_z(windowed) - log_z(same lattice, no
+    windows) <= 0: the log-probability the unanchored model gives to "the path lies inside the windows" -- near 0 when the anchors agree
+    with the audio, strongly negative when one of them fights it.  None or all-empty windows: the unanchored numbers and
+    window_log_prob 0.0.  An utterance without a path inside its windows raises as in perform_viterbi."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    anchored=True)
+
+
+def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                        skip_penalty=0.0, char_windows=None, onset_anchors=None):
+    """perform_viterbi_ctc plus the confidence given the windows: see perform_viterbi_anchored_scored."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    anchored=True)
 
 
 def run_viterbi_core(dp_matrix, backtrace_dp_matrix, cur_log_prediction, cur_log_silence_prediction, cur_label):
