@@ -1,6 +1,7 @@
 // la_lattice.h -- what the kernels that sweep the alignment lattice (S = 2L+1 states, one lane per state, row by row) have in
 // common: la_viterbi.hip (max-product), la_posterior.hip and the CTC lattice of la_loss.hip (sum-product).  Device helpers for
-// the neighbour exchange inside one wave64 and for the log-sum-exp of a step, and the host's wave count of a label count.
+// the neighbour exchange inside one wave64 and for the log-sum-exp of a step; on the host the wave count of a label count, the face of
+// an entry point (plain, optional spans, frame windows) with its names, and the description of the lattice with its argument checks.
 #pragma once
 
 #include "la_common.h"
@@ -17,6 +18,72 @@ inline int waves_for_labels(int max_labels) {
     while (nw * 64 < S) nw *= 2;
     return nw;
 }
+
+// ---- host side: what the entry points of la_viterbi.hip and la_posterior.hip share ------------------------------------------------
+// The face of a call: which lattice it sweeps.  Windows is Spans plus a frame window per state (a null skip_from = no span anywhere);
+// both run the SPANS instantiations.  Decided by the extern "C" entry point, nowhere else.
+enum class Face { Plain, Spans, Windows };
+enum class Sweep { Dp, Posteriors };
+
+// entry: the "who" of an entry point's messages; query: of its workspace query (and of the label-limit message); timer: its TimerScope
+struct FaceNames {
+    const char *entry, *query, *timer;
+};
+inline const FaceNames &face_names(Sweep sweep, Face face) {
+    static const FaceNames table[2][3] = {
+        {{"viterbi_batch", "viterbi", "viterbi"},
+         {"viterbi_spans_batch", "viterbi_spans", "viterbi_spans"},
+         {"viterbi_windows_batch", "viterbi_windows", "viterbi_windows"}},
+        {{"alignment_posteriors", "alignment_posteriors", "posterior"},
+         {"alignment_posteriors_spans", "alignment_posteriors_spans", "posterior_spans"},
+         {"alignment_posteriors_windows", "alignment_posteriors_windows", "posterior_windows"}}};
+    return table[(int)sweep][(int)face];
+}
+
+// The caller's description of the lattice, read by every kernel that sweeps it.  VitParams and PostParams derive from it (the kernels
+// write p.em, p.skip_from, ...) and add their outputs and workspace.  Filled by name: what a face does not have stays zero.
+struct LatticeIn {
+    const float *em;
+    int64_t em_bs, em_rs;
+    const int32_t *labels;
+    int32_t labels_stride;
+    const int32_t *n_labels;
+    const int32_t *n_frames;
+    int32_t max_frames, max_labels;
+    // optional spans (SPANS instantiations only)
+    const int32_t *skip_from;
+    int32_t skip_stride;
+    double penalty;
+    // per-state frame windows (WIN instantiations only): [batch][win_stride], entries 0 .. 2 L_b of row b are read
+    const int32_t *win_lo, *win_hi;
+    int32_t win_stride;
+
+    void set_inputs(const float *em_, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels_, int32_t labels_stride_,
+                    const int32_t *n_labels_, const int32_t *n_frames_, int32_t max_frames_, int32_t max_labels_) {
+        em = em_, em_bs = em_batch_stride, em_rs = em_row_stride;
+        labels = labels_, labels_stride = labels_stride_;
+        n_labels = n_labels_, n_frames = n_frames_;
+        max_frames = max_frames_, max_labels = max_labels_;
+    }
+    void set_spans(const int32_t *skip_from_, int32_t skip_stride_, double skip_penalty) {
+        skip_from = skip_from_, skip_stride = skip_stride_, penalty = skip_penalty;
+    }
+    void set_windows(const int32_t *lo, const int32_t *hi, int32_t stride) { win_lo = lo, win_hi = hi, win_stride = stride; }
+
+    // the argument checks of a face, for the entry points to report under their own names and in their own order
+    bool inputs_present(Face face) const {
+        return em && labels && n_labels && n_frames && (face != Face::Spans || skip_from) && (face != Face::Windows || (win_lo && win_hi));
+    }
+    bool sizes_ok(int32_t batch) const { return batch > 0 && max_frames > 0 && max_labels > 0; }
+    bool penalty_ok(Face face) const { return face == Face::Plain || penalty >= 0.0; }  // false for NaN
+    // out_stride: the row pitch of the entry's [batch][max_labels] arrays.  skip_stride counts where a skip_from is read, and for the
+    // posteriors with a null one too (pitch_of_output: it is the row pitch of span_skip_prob).
+    bool strides_ok(Face face, int32_t out_stride, bool pitch_of_output) const {
+        return em_rs >= max_labels + 1 && out_stride >= max_labels && labels_stride >= max_labels &&
+               (face == Face::Plain || !(skip_from || pitch_of_output) || skip_stride >= max_labels + 1) &&
+               (face != Face::Windows || win_stride >= 2 * max_labels + 1);
+    }
+};
 
 // DPP wave_shr:1 / wave_shl:1 -- across the whole wave64 (gfx9 family); the lane without a neighbour receives `fill`
 __device__ __forceinline__ double wave_shr1(double x, double fill) {  // lane i <- lane i-1, lane 0 <- fill

@@ -58,32 +58,18 @@ __device__ __forceinline__ double log_add_jump(double a, double b) {
     return log_add(a, b);
 }
 
-struct PostParams {
-    const float *em;
-    int64_t em_bs, em_rs;
-    const int32_t *labels;
-    int32_t labels_stride;
-    const int32_t *n_labels;
-    const int32_t *n_frames;
-    int32_t max_frames, max_labels;
+struct PostParams : LatticeIn {
     const int32_t *onset, *offset;
     int32_t out_stride;
     int32_t window;
     float *occupancy, *onset_prob, *offset_prob;
     double *log_z;
     int32_t *status;
+    float *present_prob, *span_skip_prob;  // SPANS instantiations only: [batch][out_stride], [batch][skip_stride]
     float *gamma;
     int64_t gamma_bs, gamma_rs;
     double *alpha_ws;  // [batch][max_frames][NT]
-    // optional spans (SPANS instantiations only)
-    const int32_t *skip_from;
-    int32_t skip_stride;
-    double penalty;
-    float *present_prob, *span_skip_prob;  // [batch][out_stride], [batch][skip_stride]
-    // per-state frame windows (WIN instantiations only): [batch][win_stride], entries 0 .. 2 L_b of row b are read
-    const int32_t *win_lo, *win_hi;
-    int32_t win_stride;
-};
+};  // (the order of the fields decides how the kernel-argument loads pair up: profiles/lattice_host_refactor.txt section 1)
 
 template <int NW, bool DPP, bool SPANS, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
@@ -449,28 +435,29 @@ bool plan_posterior(int max_labels, int *nw_out) {
 }
 
 template <int NW, bool DPP, bool SPANS, bool WIN>
-int launch_posterior(const PostParams &p, int batch, hipStream_t stream) {
-    la::TimerScope ts(WIN ? "posterior_windows" : SPANS ? "posterior_spans" : "posterior", stream);
+int launch_posterior(const char *timer, const PostParams &p, int batch, hipStream_t stream) {
+    la::TimerScope ts(timer, stream);
     hipLaunchKernelGGL((posterior_kernel<NW, DPP, SPANS, WIN>), dim3(batch), dim3(NW * 64), 0, stream, p);
     LA_LAUNCH_CHECK();
     return LA_OK;
 }
 
 template <bool SPANS, bool WIN = false>
-int launch_waves(int nw, const PostParams &p, int batch, hipStream_t stream) {
+int launch_waves(const char *timer, int nw, const PostParams &p, int batch, hipStream_t stream) {
     switch (nw) {
         case 1:
-            return la::opts().viterbi_dpp ? launch_posterior<1, true, SPANS, WIN>(p, batch, stream)
-                                          : launch_posterior<1, false, SPANS, WIN>(p, batch, stream);
-        case 2: return launch_posterior<2, false, SPANS, WIN>(p, batch, stream);
-        case 4: return launch_posterior<4, false, SPANS, WIN>(p, batch, stream);
-        case 8: return launch_posterior<8, false, SPANS, WIN>(p, batch, stream);
-        case 16: return launch_posterior<16, false, SPANS, WIN>(p, batch, stream);
+            return la::opts().viterbi_dpp ? launch_posterior<1, true, SPANS, WIN>(timer, p, batch, stream)
+                                          : launch_posterior<1, false, SPANS, WIN>(timer, p, batch, stream);
+        case 2: return launch_posterior<2, false, SPANS, WIN>(timer, p, batch, stream);
+        case 4: return launch_posterior<4, false, SPANS, WIN>(timer, p, batch, stream);
+        case 8: return launch_posterior<8, false, SPANS, WIN>(timer, p, batch, stream);
+        case 16: return launch_posterior<16, false, SPANS, WIN>(timer, p, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
 
-int query_workspace(const char *who, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+int query_workspace(Face face, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    const char *who = face_names(Sweep::Posteriors, face).query;
     LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", who);
     int nw;
     if (!plan_posterior(max_labels, &nw)) {
@@ -481,22 +468,35 @@ int query_workspace(const char *who, int32_t batch, int32_t max_frames, int32_t 
     return LA_OK;
 }
 
-// la_alignment_posteriors (the span fields of p unused), la_alignment_posteriors_spans and la_alignment_posteriors_windows (win: spans is
-// set too, p.skip_from may be null; skip_stride stays the row pitch of span_skip_prob): p holds the caller's arguments
-int run_posteriors(bool spans, PostParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream, bool win = false) {
-    const char *who = win ? "alignment_posteriors_windows" : spans ? "alignment_posteriors_spans" : "alignment_posteriors";
+// the arguments the three la_alignment_posteriors* entry points share, by name; the span outputs stay null on the plain face
+PostParams shared_params(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels, int32_t labels_stride,
+                         const int32_t *n_labels, const int32_t *n_frames, int32_t max_frames, int32_t max_labels, const int32_t *onset,
+                         const int32_t *offset, int32_t out_stride, int32_t boundary_window, float *occupancy, float *onset_prob,
+                         float *offset_prob, double *log_z, int32_t *status, float *gamma_out, int64_t gamma_batch_stride,
+                         int64_t gamma_row_stride) {
+    PostParams p{};
+    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
+    p.onset = onset, p.offset = offset, p.out_stride = out_stride, p.window = boundary_window;
+    p.occupancy = occupancy, p.onset_prob = onset_prob, p.offset_prob = offset_prob;
+    p.log_z = log_z, p.status = status;
+    p.gamma = gamma_out, p.gamma_bs = gamma_batch_stride, p.gamma_rs = gamma_row_stride;
+    return p;
+}
+
+// the three entry points: p holds the caller's arguments (Windows: skip_from may be null, skip_stride stays the row pitch of
+// span_skip_prob), the workspace field is set here
+int run_posteriors(Face face, PostParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    const FaceNames &names = face_names(Sweep::Posteriors, face);
+    const char *who = names.entry;
     if (batch == 0) return LA_OK;
-    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && (!spans || win || p.skip_from) &&
-                     (!win || (p.win_lo && p.win_hi)),
-                 "%s: null input pointer", who);
-    LA_CHECK_ARG(p.occupancy && p.onset_prob && p.offset_prob && p.log_z && p.status && (!spans || (p.present_prob && p.span_skip_prob)),
+    LA_CHECK_ARG(p.inputs_present(face) && p.onset && p.offset, "%s: null input pointer", who);
+    LA_CHECK_ARG(p.occupancy && p.onset_prob && p.offset_prob && p.log_z && p.status &&
+                     (face == Face::Plain || (p.present_prob && p.span_skip_prob)),
                  "%s: null output pointer", who);
-    LA_CHECK_ARG(batch > 0 && p.max_frames > 0 && p.max_labels > 0, "%s: bad sizes", who);
+    LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
     LA_CHECK_ARG(p.window >= 0, "%s: negative boundary_window", who);
-    LA_CHECK_ARG(!spans || p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
-    LA_CHECK_ARG(p.em_rs >= p.max_labels + 1 && p.out_stride >= p.max_labels && p.labels_stride >= p.max_labels &&
-                     (!spans || p.skip_stride >= p.max_labels + 1) && (!win || p.win_stride >= 2 * p.max_labels + 1),
-                 "%s: strides smaller than max_labels", who);
+    LA_CHECK_ARG(p.penalty_ok(face), "%s: skip_penalty must be >= 0 (and not NaN)", who);
+    LA_CHECK_ARG(p.strides_ok(face, p.out_stride, true), "%s: strides smaller than max_labels", who);
     LA_CHECK_ARG(!p.gamma || (p.gamma_rs >= 2 * (int64_t)p.max_labels + 1 && (batch == 1 || p.gamma_bs >= (int64_t)p.max_frames * p.gamma_rs)),
                  "%s: gamma strides smaller than [max_frames][2 max_labels + 1]", who);
     int nw;
@@ -508,22 +508,26 @@ int run_posteriors(bool spans, PostParams p, int32_t batch, void *workspace, siz
     LA_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
     LA_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
     p.alpha_ws = reinterpret_cast<double *>(workspace);
-    if (win) return launch_waves<true, true>(nw, p, batch, stream);
-    return spans ? launch_waves<true>(nw, p, batch, stream) : launch_waves<false>(nw, p, batch, stream);
+    switch (face) {
+        case Face::Plain: return launch_waves<false>(names.timer, nw, p, batch, stream);
+        case Face::Spans: return launch_waves<true>(names.timer, nw, p, batch, stream);
+        case Face::Windows: return launch_waves<true, true>(names.timer, nw, p, batch, stream);
+    }
+    return LA_EUNSUPPORTED;
 }
 
 }  // namespace
 
 extern "C" int la_alignment_posteriors_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace("alignment_posteriors", batch, max_frames, max_labels, bytes);
+    return query_workspace(Face::Plain, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_alignment_posteriors_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace("alignment_posteriors_spans", batch, max_frames, max_labels, bytes);
+    return query_workspace(Face::Spans, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_alignment_posteriors_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace("alignment_posteriors_windows", batch, max_frames, max_labels, bytes);
+    return query_workspace(Face::Windows, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_alignment_posteriors(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
@@ -533,10 +537,10 @@ extern "C" int la_alignment_posteriors(const float *em, int64_t em_batch_stride,
                                        float *offset_prob, double *log_z, int32_t *status, float *gamma_out,
                                        int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
                                        size_t workspace_bytes, void *stream_) {
-    PostParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
-                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
-                 gamma_out, gamma_batch_stride, gamma_row_stride, nullptr, nullptr, 0, 0.0, nullptr, nullptr};
-    return run_posteriors(false, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    PostParams p = shared_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
+                                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
+                                 gamma_out, gamma_batch_stride, gamma_row_stride);
+    return run_posteriors(Face::Plain, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_alignment_posteriors_spans(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
@@ -547,11 +551,12 @@ extern "C" int la_alignment_posteriors_spans(const float *em, int64_t em_batch_s
                                              float *present_prob, float *span_skip_prob, double *log_z, int32_t *status, float *gamma_out,
                                              int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
                                              size_t workspace_bytes, void *stream_) {
-    PostParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
-                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
-                 gamma_out, gamma_batch_stride, gamma_row_stride, nullptr, skip_from, skip_stride, skip_penalty, present_prob,
-                 span_skip_prob};
-    return run_posteriors(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    PostParams p = shared_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
+                                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
+                                 gamma_out, gamma_batch_stride, gamma_row_stride);
+    p.set_spans(skip_from, skip_stride, skip_penalty);
+    p.present_prob = present_prob, p.span_skip_prob = span_skip_prob;
+    return run_posteriors(Face::Spans, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_alignment_posteriors_windows(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
@@ -563,9 +568,11 @@ extern "C" int la_alignment_posteriors_windows(const float *em, int64_t em_batch
                                                float *span_skip_prob, double *log_z, int32_t *status, float *gamma_out,
                                                int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
                                                size_t workspace_bytes, void *stream_) {
-    PostParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
-                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
-                 gamma_out, gamma_batch_stride, gamma_row_stride, nullptr, skip_from, skip_stride, skip_penalty, present_prob,
-                 span_skip_prob, win_lo, win_hi, win_stride};
-    return run_posteriors(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_, true);
+    PostParams p = shared_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels,
+                                 onset, offset, out_stride, boundary_window, occupancy, onset_prob, offset_prob, log_z, status,
+                                 gamma_out, gamma_batch_stride, gamma_row_stride);
+    p.set_spans(skip_from, skip_stride, skip_penalty);
+    p.set_windows(win_lo, win_hi, win_stride);
+    p.present_prob = present_prob, p.span_skip_prob = span_skip_prob;
+    return run_posteriors(Face::Windows, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }

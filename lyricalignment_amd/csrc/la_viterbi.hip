@@ -47,30 +47,20 @@ constexpr double kNeg = -10000000.0;  // utils/alignment.py:144
 constexpr int PF = 8;                 // emission prefetch depth (frames)
 constexpr int kSkipped = -2;          // off_s marker of a label inside a taken jump (written out as -1)
 
-struct VitParams {
-    const float *em;
-    int64_t em_bs, em_rs;
-    const int32_t *labels;
-    int32_t labels_stride;
-    const int32_t *n_labels;
-    const int32_t *n_frames;
-    int32_t max_frames, max_labels;
+struct VitParams : LatticeIn {
     int32_t *onset, *offset;
     int32_t out_stride;
     double *final_score;
     int32_t *status;
-    // optional spans (SPANS instantiations only)
-    const int32_t *skip_from;
-    int32_t skip_stride;
-    double penalty;
     unsigned long long *bt_global;  // [batch][max_frames][NW][2, with spans 3] when !bt_in_lds
     int32_t bt_in_lds;
     // run_viterbi_core face (DUMP instantiation only, batch 1): row 0 of dp is READ, rows >= 1 of dp / bt are written
     double *dp_dump;    // [T][S]
     long long *bt_dump; // [T][S]
-    // per-state frame windows (WIN instantiations only): [batch][win_stride], entries 0 .. 2 L_b of row b are read
-    const int32_t *win_lo, *win_hi;
-    int32_t win_stride;
+
+    void set_outputs(int32_t *onset_, int32_t *offset_, int32_t out_stride_, double *final_score_, int32_t *status_) {
+        onset = onset_, offset = offset_, out_stride = out_stride_, final_score = final_score_, status = status_;
+    }
 };
 
 template <int NW, bool DPP, bool SPANS, bool DUMP = false, bool WIN = false>
@@ -483,12 +473,12 @@ int launch_lanes(const char *timer, const VitParams &p, const VitPlan &pl, int b
     return LA_EUNSUPPORTED;
 }
 
-// who: "viterbi", "viterbi_spans" or "viterbi_windows" (the last two share the planner: three masks, one lane per state)
-int query_workspace(const char *who, bool spans, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+int query_workspace(Face face, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    const char *who = face_names(Sweep::Dp, face).query;
     LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", who);
     VitPlan pl;
-    if (!plan_viterbi(batch, max_frames, max_labels, spans, &pl)) {
-        if (spans) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", who, max_labels);
+    if (!plan_viterbi(batch, max_frames, max_labels, face != Face::Plain, &pl)) {
+        if (face != Face::Plain) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", who, max_labels);
         else la::set_error("viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
         return LA_EUNSUPPORTED;
     }
@@ -496,25 +486,23 @@ int query_workspace(const char *who, bool spans, int32_t batch, int32_t max_fram
     return LA_OK;
 }
 
-// la_viterbi_batch (p.skip_from unused), la_viterbi_spans_batch and la_viterbi_windows_batch (win: spans is set too, p.skip_from may be
-// null): p holds the caller's arguments, the workspace fields are set here
-int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream, bool win = false) {
-    const char *who = win ? "viterbi_windows_batch" : spans ? "viterbi_spans_batch" : "viterbi_batch";
+// the three la_viterbi*_batch entry points: p holds the caller's arguments, the workspace fields are set here.  Spans and Windows share
+// the planner (three masks, one lane per state)
+int run_batch(Face face, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    const FaceNames &names = face_names(Sweep::Dp, face);
+    const char *who = names.entry;
+    const bool spans = face != Face::Plain;
     if (batch == 0) return LA_OK;
-    LA_CHECK_ARG(p.em && p.labels && p.n_labels && p.n_frames && p.onset && p.offset && p.final_score && p.status &&
-                     (!spans || win || p.skip_from) && (!win || (p.win_lo && p.win_hi)),
-                 "%s: null pointer", who);
-    LA_CHECK_ARG(batch > 0 && p.max_frames > 0 && p.max_labels > 0, "%s: bad sizes", who);
-    LA_CHECK_ARG(!spans || p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
-    const bool strides_ok = p.em_rs >= p.max_labels + 1 && p.out_stride >= p.max_labels && p.labels_stride >= p.max_labels &&
-                            (!spans || !p.skip_from || p.skip_stride >= p.max_labels + 1) &&
-                            (!win || p.win_stride >= 2 * p.max_labels + 1);
+    LA_CHECK_ARG(p.inputs_present(face) && p.onset && p.offset && p.final_score && p.status, "%s: null pointer", who);
+    LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
+    LA_CHECK_ARG(p.penalty_ok(face), "%s: skip_penalty must be >= 0 (and not NaN)", who);
+    const bool strides_ok = p.strides_ok(face, p.out_stride, false);
     VitPlan pl;
     const bool planned = plan_viterbi(batch, p.max_frames, p.max_labels, spans, &pl);
     // the label limit is reported after the strides by la_viterbi_batch and before them by la_viterbi_spans_batch
     LA_CHECK_ARG(strides_ok || (spans && !planned), "%s: strides smaller than max_labels", who);
     if (!planned) {
-        if (spans) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", win ? "viterbi_windows" : "viterbi_spans", p.max_labels);
+        if (spans) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", names.query, p.max_labels);
         else la::set_error("viterbi: max_labels %d exceeds 4095", p.max_labels);
         return LA_EUNSUPPORTED;
     }
@@ -523,13 +511,13 @@ int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t wo
     LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
     p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
     p.bt_in_lds = pl.bt_in_lds ? 1 : 0;
-    if (win) return launch_lanes<true, false, true>("viterbi_windows", p, pl, batch, stream);
-    if (spans) return launch_lanes<true, false>("viterbi_spans", p, pl, batch, stream);
+    if (face == Face::Windows) return launch_lanes<true, false, true>(names.timer, p, pl, batch, stream);
+    if (face == Face::Spans) return launch_lanes<true, false>(names.timer, p, pl, batch, stream);
     switch (pl.strip) {
-        case 0: return launch_lanes<false, false>("viterbi", p, pl, batch, stream);
-        case 2: return launch<viterbi_strip_kernel<2>>("viterbi", 1024, p, pl, batch, stream);
-        case 4: return launch<viterbi_strip_kernel<4>>("viterbi", 1024, p, pl, batch, stream);
-        case 8: return launch<viterbi_strip_kernel<8>>("viterbi", 1024, p, pl, batch, stream);
+        case 0: return launch_lanes<false, false>(names.timer, p, pl, batch, stream);
+        case 2: return launch<viterbi_strip_kernel<2>>(names.timer, 1024, p, pl, batch, stream);
+        case 4: return launch<viterbi_strip_kernel<4>>(names.timer, 1024, p, pl, batch, stream);
+        case 8: return launch<viterbi_strip_kernel<8>>(names.timer, 1024, p, pl, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
@@ -537,15 +525,15 @@ int run_batch(bool spans, VitParams p, int32_t batch, void *workspace, size_t wo
 }  // namespace
 
 extern "C" int la_viterbi_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace("viterbi", false, batch, max_frames, max_labels, bytes);
+    return query_workspace(Face::Plain, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace("viterbi_spans", true, batch, max_frames, max_labels, bytes);
+    return query_workspace(Face::Spans, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace("viterbi_windows", true, batch, max_frames, max_labels, bytes);
+    return query_workspace(Face::Windows, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -553,9 +541,10 @@ extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_
                                 const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
                                 int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
-                max_labels, onset, offset, out_stride, final_score, status};
-    return run_batch(false, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    VitParams p{};
+    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
+    p.set_outputs(onset, offset, out_stride, final_score, status);
+    return run_batch(Face::Plain, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -564,9 +553,11 @@ extern "C" int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, 
                                       int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
                                       int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
                                       void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
-                max_labels, onset, offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty};
-    return run_batch(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    VitParams p{};
+    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
+    p.set_spans(skip_from, skip_stride, skip_penalty);
+    p.set_outputs(onset, offset, out_stride, final_score, status);
+    return run_batch(Face::Spans, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -576,12 +567,12 @@ extern "C" int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride
                                         int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
                                         const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
                                         void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames,
-                max_labels, onset, offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty};
-    p.win_lo = win_lo;
-    p.win_hi = win_hi;
-    p.win_stride = win_stride;
-    return run_batch(true, p, batch, workspace, workspace_bytes, (hipStream_t)stream_, true);
+    VitParams p{};
+    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
+    p.set_spans(skip_from, skip_stride, skip_penalty);
+    p.set_windows(win_lo, win_hi, win_stride);
+    p.set_outputs(onset, offset, out_stride, final_score, status);
+    return run_batch(Face::Windows, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // run_viterbi_core(dp, bt, lp, ls, label) of the reference (utils/alignment.py:73-119) for ONE utterance: same
@@ -598,9 +589,13 @@ extern "C" int la_viterbi_core(const float *em, int64_t em_row_stride, const int
         return LA_EUNSUPPORTED;
     }
     LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes), "viterbi_core: workspace too small");
+    VitParams p{};
+    p.set_inputs(em, 0, em_row_stride, labels, n_labels_host, n_labels, n_frames, n_frames_host, n_labels_host);
     // scratch_i32: onset[L] | offset[L] | status[1]
-    VitParams p{em, 0, em_row_stride, labels, n_labels_host, n_labels, n_frames, n_frames_host, n_labels_host,
-                scratch_i32, scratch_i32 + n_labels_host, n_labels_host, scratch_f64, scratch_i32 + 2 * n_labels_host,
-                nullptr, 0, 0.0, reinterpret_cast<unsigned long long *>(workspace), pl.bt_in_lds ? 1 : 0, dp, bt};
-    return launch_lanes<false, true>("viterbi", p, pl, 1, (hipStream_t)stream_);
+    p.set_outputs(scratch_i32, scratch_i32 + n_labels_host, n_labels_host, scratch_f64, scratch_i32 + 2 * n_labels_host);
+    p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
+    p.bt_in_lds = pl.bt_in_lds ? 1 : 0;
+    p.dp_dump = dp;
+    p.bt_dump = bt;
+    return launch_lanes<false, true>(face_names(Sweep::Dp, Face::Plain).timer, p, pl, 1, (hipStream_t)stream_);
 }

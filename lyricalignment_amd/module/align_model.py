@@ -369,8 +369,7 @@ class AlignModel(torch.nn.Module):
         return_span_confidence's dicts and window_log_prob 0.0.  With return_frames the windowed DP's four tensors, then (occupancy,
         onset_prob, offset_prob, log_z, present_prob, span_skip_prob, log_z_free).  A clip without a path inside its windows raises as
         above.  Not together with return_confidence / return_span_confidence (ValueError)."""
-        from ..utils.alignment import (_anchored_posteriors, _labels_to_device, _scores_from_posteriors, _seconds_from_frames,
-                                       _skip_from_of_spans, _windows_of)
+        from ..utils.alignment import LatticeResult, _formatted, _labels_to_device, _skip_from_of_spans, _windows_of, run_lattice
         if return_anchored_confidence and (return_confidence or return_span_confidence):
             raise ValueError("align: return_anchored_confidence does not go with return_confidence / return_span_confidence (it returns "
                              "their numbers on the windowed lattice)")
@@ -379,9 +378,8 @@ class AlignModel(torch.nn.Module):
         if per_clip:
             if mel is not None or not get_orig_len:
                 raise ValueError("align(per_clip=True) takes waveforms (audios=) and get_orig_len=True")
-            feats, B, T, nf_clip, frame_counts = self._features_per_clip(audios)
+            feats, B, T, kw["n_frames"], frame_counts = self._features_per_clip(audios)
             stride = N_CTX
-            kw["n_frames"] = nf_clip
         else:
             if mel is None:
                 mel = self._mel_of(audios)
@@ -390,71 +388,28 @@ class AlignModel(torch.nn.Module):
         lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
         skip_from = _skip_from_of_spans(optional_spans, lab_lists)
         windows = _windows_of(char_windows, onset_anchors, lab_lists, frame_counts, hop_size_second)
-        if return_anchored_confidence:
-            *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
-                                             want_emissions=True, **kw)
-            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free = _anchored_posteriors(
-                em, lab_dev, n_lab, nf, windows, skip_from, skip_penalty, boundary_window)
-            if return_frames:
-                return onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free
-            seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=True)
-            spans = optional_spans if optional_spans is not None else [[] for _ in lab_lists]
-            return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists, pres, skp, spans, log_z_free)
-        if windows is not None:
-            if return_confidence or return_span_confidence:
-                raise ValueError("align: char_windows / onset_anchors do not go with return_confidence / return_span_confidence "
-                                 "(return_anchored_confidence=True gives the posteriors on the windowed lattice)")
-            *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
-                                             want_emissions=True, **kw)
-            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            onset, offset, score, status = ops.viterbi_windows_batch(em, lab_dev, n_lab, nf, windows[0].to(eng.device), windows[1].to(eng.device),
-                                                                     None if skip_from is None else skip_from.to(eng.device), skip_penalty)
-            if return_frames:
-                return onset, offset, score, status
-            return _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=skip_from is not None)
+        if windows is not None and (return_confidence or return_span_confidence):
+            raise ValueError("align: char_windows / onset_anchors do not go with return_confidence / return_span_confidence "
+                             "(return_anchored_confidence=True gives the posteriors on the windowed lattice)")
         if skip_from is not None and return_confidence:
             raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice by that "
                              "keyword: return_span_confidence=True gives them)")
-        if return_span_confidence:
-            variant = _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN
-            onset, offset, score, status, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, variant, want_emissions=True, **kw)
+        confidence = ("anchored" if return_anchored_confidence else "span" if return_span_confidence else "plain" if return_confidence
+                      else None)
+        # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
+        need_em = confidence is not None or skip_from is not None or windows is not None
+        head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
+                                       want_emissions=need_em, **kw)
+        if need_em:
             nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            if skip_from is None:            # the plain DP's frames are the span DP's bit for bit when no span exists
-                skip_dev = torch.full((B, lab_dev.shape[1] + 1), -1, dtype=torch.int32, device=eng.device)
-            else:
-                skip_dev = skip_from.to(eng.device)
-                onset, offset, score, status = ops.viterbi_spans_batch(em, lab_dev, n_lab, nf, skip_dev, skip_penalty)
-            occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_spans(em, lab_dev, n_lab, nf, onset, offset, skip_dev, skip_penalty,
-                                                                                 boundary_window)
-            if return_frames:
-                return onset, offset, score, status, occ, onp, offp, log_z, pres, skp
-            seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=True)
-            spans = optional_spans if optional_spans is not None else [[] for _ in lab_lists]
-            return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists, pres, skp, spans)
-        if skip_from is not None:
-            *_, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
-                                             want_emissions=True, **kw)
-            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            onset, offset, score, status = ops.viterbi_spans_batch(em, lab_dev, n_lab, nf, skip_from.to(eng.device), skip_penalty)
-            if return_frames:
-                return onset, offset, score, status
-            return _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second, skipped_as_none=True)
-        if return_confidence:
-            onset, offset, score, status, em = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
-                                                                       _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
-                                                                       want_emissions=True, **kw)
-            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            occ, onp, offp, log_z, _ = ops.alignment_posteriors(em, lab_dev, n_lab, nf, onset, offset, boundary_window)
-            if return_frames:
-                return onset, offset, score, status, occ, onp, offp, log_z
-            seconds = _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second)
-            return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lab_lists)
-        onset, offset, score, status = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab,
-                                                               _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN, **kw)
-        if return_frames:
-            return onset, offset, score, status
-        return _seconds_from_frames(onset, offset, status, lab_lists, hop_size_second)
+            # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same bits)
+            r = run_lattice(head[4], lab_dev, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
+                            dp=None if return_anchored_confidence else head[:4])
+        else:
+            r = LatticeResult(*head)
+        if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors
+            return tuple(t for t in r if t is not None)
+        return _formatted(r, lab_lists, hop_size_second, optional_spans)
 
 
 def encoder_only_engine(whisper_model, mel: torch.Tensor) -> torch.Tensor:

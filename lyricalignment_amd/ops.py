@@ -58,22 +58,90 @@ def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device) -> Tuple[t
     return torch.empty((max(need.value, 16),), dtype=torch.uint8, device=device), need.value
 
 
-def _viterbi_outputs(B: int, Lmax: int, device):
-    return (torch.empty((B, Lmax), dtype=torch.int32, device=device), torch.empty((B, Lmax), dtype=torch.int32, device=device),
-            torch.empty((B,), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.int32, device=device))
+# The face of a lattice call (csrc/la_lattice.h Face) is chosen by the public function: "plain", "spans" (skip_from given) or
+# "windows" (win_lo / win_hi given, skip_from may be None).  -> the stem of its C symbols, DP and posteriors
+_DP_ENTRY = {"plain": "viterbi", "spans": "viterbi_spans", "windows": "viterbi_windows"}
+_POSTERIOR_ENTRY = {"plain": "alignment_posteriors", "spans": "alignment_posteriors_spans", "windows": "alignment_posteriors_windows"}
+
+
+def _lattice_checked(who: str, face: str, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows, path=None, boundary_window=None):
+    """_lattice_inputs plus the checks of the face's own arguments (path = the (onset, offset) the posteriors are asked about)
+    -> B, T, Lmax, the contiguous count tensors and skip_penalty as a float."""
+    more = {} if path is None else dict(onset=path[0], offset=path[1])
+    if windows is not None:
+        more.update(win_lo=windows[0], win_hi=windows[1])
+    if skip_from is not None:
+        more["skip_from"] = skip_from
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
+    if path is not None and (path[0].shape != (B, Lmax) or path[1].shape != (B, Lmax)):
+        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
+    for t in windows or ():
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != windows[0].stride(0):
+            raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
+    if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
+        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
+    if boundary_window is not None and int(boundary_window) < 0:
+        raise ValueError(f"{who}: boundary_window must be >= 0")
+    skip_penalty = float(skip_penalty)
+    if face != "plain" and not skip_penalty >= 0.0:
+        raise ValueError(f"{who}: skip_penalty must be >= 0")
+    return B, T, Lmax, n_labels, n_frames, skip_penalty
+
+
+def _face_args(face: str, skip_from, skip_stride: int, skip_penalty: float, windows) -> tuple:
+    """The C arguments a face adds to the plain one's: (skip_from, skip_stride, skip_penalty) and (win_lo, win_hi, win_stride)."""
+    spans = () if face == "plain" else (ptr(skip_from), skip_stride, skip_penalty)
+    return spans + ((ptr(windows[0]), ptr(windows[1]), windows[0].stride(0)) if face == "windows" else ())
+
+
+def _viterbi(who: str, face: str, em, labels, n_labels, n_frames, skip_from=None, skip_penalty=0.0, windows=None):
+    """The alignment DP of one face: checks, outputs, workspace and the C call -> onset, offset, final_score, status."""
+    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, face, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows)
+    dev = em.device
+    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
+    score = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws, need = _lattice_workspace(_DP_ENTRY[face] + "_workspace_bytes", B, T, Lmax, dev)
+    skip_stride = skip_from.stride(0) if skip_from is not None else 0
+    check(getattr(lib(), "la_" + _DP_ENTRY[face] + "_batch")(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), *_face_args(face, skip_from, skip_stride, skip_penalty, windows),
+        ptr(ws), need, stream_ptr()), who)
+    return onset, offset, score, status
+
+
+def _posteriors(who: str, face: str, em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                skip_from=None, skip_penalty=0.0, windows=None):
+    """The forward-backward sweep of one face: checks, outputs, workspace and the C call -> occupancy, onset_prob, offset_prob, log_z,
+    status [, present_prob, span_skip_prob unless plain] [, gamma]."""
+    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, face, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows,
+                                                                    (onset, offset), boundary_window)
+    onset = onset.contiguous(); offset = offset.contiguous()
+    dev = em.device
+    occupancy, onset_prob, offset_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(3))
+    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
+    res, span_out = (occupancy, onset_prob, offset_prob, log_z, status), ()
+    skip_stride = skip_from.stride(0) if skip_from is not None else Lmax + 1
+    if face != "plain":                     # skip_stride is the row pitch the kernel is told for skip_from AND for span_skip_prob
+        present_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+        span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
+        res, span_out = res + (present_prob, span_skip_prob), (ptr(present_prob), ptr(span_skip_prob))
+    ws, need = _lattice_workspace(_POSTERIOR_ENTRY[face] + "_workspace_bytes", B, T, Lmax, dev)
+    check(getattr(lib(), "la_" + _POSTERIOR_ENTRY[face])(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, int(boundary_window), *_face_args(face, skip_from, skip_stride, skip_penalty, windows),
+        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), *span_out, ptr(log_z), ptr(status), ptr(gamma),
+        gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0, ptr(ws), need, stream_ptr()), who)
+    return res + (gamma,) if want_gamma else res
 
 
 def viterbi_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """em [B,T,E] f32 (E >= Lmax+1), labels [B,Lmax] i32, n_labels [B] i32, n_frames [B] i32 (device).
     -> onset [B,Lmax] i32, offset [B,Lmax] i32, final_score [B] f64, status [B] i32 (device)."""
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs("viterbi_batch", em, labels, n_labels, n_frames)
-    onset, offset, score, status = _viterbi_outputs(B, Lmax, em.device)
-    ws, need = _lattice_workspace("viterbi_workspace_bytes", B, T, Lmax, em.device)
-    check(lib().la_viterbi_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
-                                 ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
-                                 ptr(ws), need, stream_ptr()), "viterbi_batch")
-    return onset, offset, score, status
+    return _viterbi("viterbi_batch", "plain", em, labels, n_labels, n_frames)
 
 
 def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -82,19 +150,7 @@ def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.
     """la_viterbi_spans_batch: viterbi_batch on the lattice with optional label spans.  skip_from [B, >= Lmax+1] i32 (device):
     skip_from[b, n] = a (0 <= a < n) makes labels a..n-1 of clip b optional, anything else = no span ends at n.
     -> the tuple of viterbi_batch; labels inside a taken jump have onset = offset = -1 under status LA_OK."""
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs("viterbi_spans_batch", em, labels, n_labels, n_frames, skip_from=skip_from)
-    if skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1:
-        raise ValueError("viterbi_spans_batch: skip_from [B, >= Lmax+1] with unit inner stride expected")
-    skip_penalty = float(skip_penalty)
-    if not skip_penalty >= 0.0:
-        raise ValueError("viterbi_spans_batch: skip_penalty must be >= 0")
-    onset, offset, score, status = _viterbi_outputs(B, Lmax, em.device)
-    ws, need = _lattice_workspace("viterbi_spans_workspace_bytes", B, T, Lmax, em.device)
-    check(lib().la_viterbi_spans_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
-                                       ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
-                                       ptr(skip_from), skip_from.stride(0), skip_penalty, ptr(ws), need, stream_ptr()),
-          "viterbi_spans_batch")
-    return onset, offset, score, status
+    return _viterbi("viterbi_spans_batch", "spans", em, labels, n_labels, n_frames, skip_from, skip_penalty)
 
 
 def viterbi_windows_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -104,24 +160,7 @@ def viterbi_windows_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     win_lo / win_hi [B, >= 2*Lmax+1] i32 (device, one row pitch): state s of clip b may hold the path at frame t only if
     win_lo[b, s] <= t < win_hi[b, s].  -> the tuple of viterbi_batch; a clip without a path inside its windows has status
     LA_EINFEASIBLE, score -inf and every onset / offset -1."""
-    who = "viterbi_windows_batch"
-    more = dict(win_lo=win_lo, win_hi=win_hi) if skip_from is None else dict(win_lo=win_lo, win_hi=win_hi, skip_from=skip_from)
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
-    for t in (win_lo, win_hi):
-        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != win_lo.stride(0):
-            raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
-    if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
-        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
-    skip_penalty = float(skip_penalty)
-    if not skip_penalty >= 0.0:
-        raise ValueError(f"{who}: skip_penalty must be >= 0")
-    onset, offset, score, status = _viterbi_outputs(B, Lmax, em.device)
-    ws, need = _lattice_workspace("viterbi_windows_workspace_bytes", B, T, Lmax, em.device)
-    check(lib().la_viterbi_windows_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
-                                         ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
-                                         ptr(skip_from), skip_from.stride(0) if skip_from is not None else 0, skip_penalty,
-                                         ptr(win_lo), ptr(win_hi), win_lo.stride(0), ptr(ws), need, stream_ptr()), who)
-    return onset, offset, score, status
+    return _viterbi("viterbi_windows_batch", "windows", em, labels, n_labels, n_frames, skip_from, skip_penalty, (win_lo, win_hi))
 
 
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -129,27 +168,7 @@ def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,
     onset / offset [B,Lmax] i32 = viterbi_batch's (or align_head_forward's) outputs for the same emissions.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32 [, gamma [B,T,2*Lmax+1] f32] (device)."""
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs("alignment_posteriors", em, labels, n_labels, n_frames, onset=onset, offset=offset)
-    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
-        raise ValueError("alignment_posteriors: onset / offset must be [B,Lmax]")
-    if int(boundary_window) < 0:
-        raise ValueError("alignment_posteriors: boundary_window must be >= 0")
-    onset = onset.contiguous(); offset = offset.contiguous()
-    dev = em.device
-    occupancy = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
-    onset_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
-    offset_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
-    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    ws, need = _lattice_workspace("alignment_posteriors_workspace_bytes", B, T, Lmax, dev)
-    check(lib().la_alignment_posteriors(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
-                                        ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
-                                        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(log_z), ptr(status), ptr(gamma),
-                                        gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
-                                        ptr(ws), need, stream_ptr()), "alignment_posteriors")
-    res = (occupancy, onset_prob, offset_prob, log_z, status)
-    return res + (gamma,) if want_gamma else res
+    return _posteriors("alignment_posteriors", "plain", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma)
 
 
 def alignment_posteriors_spans(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -159,33 +178,8 @@ def alignment_posteriors_spans(em: torch.Tensor, labels: torch.Tensor, n_labels:
     offset = viterbi_spans_batch's outputs for the same skip_from [B, >= Lmax+1] i32 and skip_penalty.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, present_prob [B,Lmax] f32 (label n is on the path),
     span_skip_prob [B,Lmax+1] f32 (the span ending at position n is jumped) [, gamma [B,T,2*Lmax+1] f32] (device)."""
-    who = "alignment_posteriors_spans"
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, onset=onset, offset=offset, skip_from=skip_from)
-    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
-        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
-    if skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1:
-        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
-    if int(boundary_window) < 0:
-        raise ValueError(f"{who}: boundary_window must be >= 0")
-    skip_penalty = float(skip_penalty)
-    if not skip_penalty >= 0.0:
-        raise ValueError(f"{who}: skip_penalty must be >= 0")
-    onset = onset.contiguous(); offset = offset.contiguous()
-    dev = em.device
-    occupancy, onset_prob, offset_prob, present_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(4))
-    span_skip_prob = torch.empty((B, Lmax + 1), dtype=torch.float32, device=dev)
-    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    ws, need = _lattice_workspace("alignment_posteriors_spans_workspace_bytes", B, T, Lmax, dev)
-    check(lib().la_alignment_posteriors_spans(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
-                                              ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
-                                              ptr(skip_from), skip_from.stride(0), skip_penalty, ptr(occupancy), ptr(onset_prob),
-                                              ptr(offset_prob), ptr(present_prob), ptr(span_skip_prob), ptr(log_z), ptr(status), ptr(gamma),
-                                              gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
-                                              ptr(ws), need, stream_ptr()), who)
-    res = (occupancy, onset_prob, offset_prob, log_z, status, present_prob, span_skip_prob)
-    return res + (gamma,) if want_gamma else res
+    return _posteriors("alignment_posteriors_spans", "spans", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty)
 
 
 def alignment_posteriors_windows(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -197,41 +191,8 @@ def alignment_posteriors_windows(em: torch.Tensor, labels: torch.Tensor, n_label
     win_lo / win_hi as viterbi_windows_batch.  Every output is a posterior GIVEN the windows (normalised by the windowed log_z).
     -> the tuple of alignment_posteriors_spans (skip_from None: present_prob 1 on reported labels, span_skip_prob 0); a clip without a
     path inside its windows has status LA_EINFEASIBLE, log_z -inf and every output 0."""
-    who = "alignment_posteriors_windows"
-    more = dict(onset=onset, offset=offset, win_lo=win_lo, win_hi=win_hi)
-    if skip_from is not None:
-        more["skip_from"] = skip_from
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
-    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
-        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
-    for t in (win_lo, win_hi):
-        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != win_lo.stride(0):
-            raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
-    if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
-        raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
-    if int(boundary_window) < 0:
-        raise ValueError(f"{who}: boundary_window must be >= 0")
-    skip_penalty = float(skip_penalty)
-    if not skip_penalty >= 0.0:
-        raise ValueError(f"{who}: skip_penalty must be >= 0")
-    onset = onset.contiguous(); offset = offset.contiguous()
-    dev = em.device
-    occupancy, onset_prob, offset_prob, present_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(4))
-    skip_stride = skip_from.stride(0) if skip_from is not None else Lmax + 1    # the row pitch of span_skip_prob as well
-    span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
-    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    ws, need = _lattice_workspace("alignment_posteriors_windows_workspace_bytes", B, T, Lmax, dev)
-    check(lib().la_alignment_posteriors_windows(ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels),
-                                                ptr(n_frames), B, T, Lmax, ptr(onset), ptr(offset), Lmax, int(boundary_window),
-                                                ptr(skip_from), skip_stride, skip_penalty,
-                                                ptr(win_lo), ptr(win_hi), win_lo.stride(0), ptr(occupancy), ptr(onset_prob),
-                                                ptr(offset_prob), ptr(present_prob), ptr(span_skip_prob), ptr(log_z), ptr(status), ptr(gamma),
-                                                gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
-                                                ptr(ws), need, stream_ptr()), who)
-    res = (occupancy, onset_prob, offset_prob, log_z, status, present_prob, span_skip_prob)
-    return res + (gamma,) if want_gamma else res
+    return _posteriors("alignment_posteriors_windows", "windows", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty, (win_lo, win_hi))
 
 
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:

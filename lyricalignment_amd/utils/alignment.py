@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -200,31 +200,68 @@ def _scores_from_posteriors(occupancy, onset_prob, offset_prob, log_z, final_sco
     return out
 
 
-def _anchored_posteriors(em, lab, n_lab, nf, windows, skip_from, skip_penalty, boundary_window):
-    """DP and posteriors GIVEN the frame windows (host tensors (win_lo, win_hi), or None: no window at all) on the lattice with the
-    optional spans of skip_from (host tensor or None) -> device tensors (onset, offset, score, status, occupancy, onset_prob,
-    offset_prob, log_z, present_prob, span_skip_prob, log_z_free); log_z_free is log_z of the same lattice without windows (one more
-    launch of the existing sweep; without windows it IS log_z)."""
+class LatticeResult(NamedTuple):
+    """Device tensors of one run_lattice call, in the order of AlignModel.align(return_frames=True); what was not asked for is None."""
+    onset: torch.Tensor
+    offset: torch.Tensor
+    score: torch.Tensor
+    status: torch.Tensor
+    occupancy: Optional[torch.Tensor] = None
+    onset_prob: Optional[torch.Tensor] = None
+    offset_prob: Optional[torch.Tensor] = None
+    log_z: Optional[torch.Tensor] = None
+    present_prob: Optional[torch.Tensor] = None
+    span_skip_prob: Optional[torch.Tensor] = None
+    log_z_free: Optional[torch.Tensor] = None
+
+
+def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0.0, confidence=None, boundary_window=2, dp=None) -> LatticeResult:
+    """The one place where the face of an alignment is decided (csrc/la_lattice.h Face, through the ops wrappers): the DP and, if asked
+    for, the posteriors on the lattice that skip_from (host rows of _skip_from_of_spans, or None) and windows (host (win_lo, win_hi)
+    of _windows_of, or None) describe.  em / lab / n_lab / nf are device tensors.
+    confidence: None | "plain" (ops.alignment_posteriors; no spans, no windows) | "span" (the span lattice's; no windows; without a
+    span the plain DP's frames, which are the span DP's bit for bit, and an all -1 skip_from) | "anchored" (posteriors GIVEN the windows,
+    plus log_z_free = log_z of the same lattice without windows: one more launch of the free sweep, and log_z itself without windows).
+    dp: the (onset, offset, score, status) of the plain lattice where they exist already (the fused head's)."""
     dev = em.device
     skip_dev = None if skip_from is None else skip_from.to(dev)
-    if windows is None:
-        if skip_dev is None:                 # the plain DP's frames are the span DP's bit for bit when no span exists
-            onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
-            skip_dev = torch.full((em.shape[0], lab.shape[1] + 1), -1, dtype=torch.int32, device=dev)
-        else:
-            onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
-        occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty,
-                                                                             boundary_window)
-        return onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z
-    win_lo, win_hi = windows[0].to(dev), windows[1].to(dev)
-    onset, offset, score, status = ops.viterbi_windows_batch(em, lab, n_lab, nf, win_lo, win_hi, skip_dev, skip_penalty)
-    occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_windows(em, lab, n_lab, nf, onset, offset, win_lo, win_hi, skip_dev,
-                                                                           skip_penalty, boundary_window)
-    if skip_dev is None:
-        log_z_free = ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[3]
+    win = None if windows is None else (windows[0].to(dev), windows[1].to(dev))
+    if win is not None:
+        dp = ops.viterbi_windows_batch(em, lab, n_lab, nf, win[0], win[1], skip_dev, skip_penalty)
+    elif skip_dev is not None:
+        dp = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
+    elif dp is None:
+        dp = ops.viterbi_batch(em, lab, n_lab, nf)
+    onset, offset = dp[0], dp[1]
+    if confidence is None:
+        return LatticeResult(*dp)
+    if confidence == "plain":
+        return LatticeResult(*dp, *ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[:4])
+    span_free = skip_dev is None
+    if win is None:
+        if span_free:
+            skip_dev = torch.full((lab.shape[0], lab.shape[1] + 1), -1, dtype=torch.int32, device=dev)
+        post = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, boundary_window)
+        log_z_free = post[3]
     else:
-        log_z_free = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, boundary_window)[3]
-    return onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free
+        post = ops.alignment_posteriors_windows(em, lab, n_lab, nf, onset, offset, win[0], win[1], skip_dev, skip_penalty, boundary_window)
+        if span_free:
+            log_z_free = ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[3]
+        else:
+            log_z_free = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, boundary_window)[3]
+    return LatticeResult(*dp, *post[:4], *post[5:7], log_z_free if confidence == "anchored" else None)
+
+
+def _formatted(r: LatticeResult, label_lists, hop_size_second, optional_spans):
+    """What the public functions return for r: seconds, or (seconds, scores) when r holds posteriors.  The dicts of the span lattice
+    (present_prob computed) name every span of optional_spans, or none where the caller gave no span.  A label with onset -1 under LA_OK
+    was inside a taken jump (the lattice without spans has none) and comes back as None."""
+    seconds = _seconds_from_frames(r.onset, r.offset, r.status, label_lists, hop_size_second, skipped_as_none=True)
+    if r.occupancy is None:
+        return seconds
+    spans = None if r.present_prob is None else optional_spans if optional_spans is not None else [[] for _ in label_lists]
+    return seconds, _scores_from_posteriors(r.occupancy, r.onset_prob, r.offset_prob, r.log_z, r.score, label_lists, r.present_prob,
+                                            r.span_skip_prob, spans, r.log_z_free)
 
 
 def _device_of(prediction) -> torch.device:
@@ -244,44 +281,22 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         pred = pred.contiguous()
     B, T, V = pred.shape
     lab, n_lab, lists = _labels_to_device(labels, B, dev)
-    em = ops.emissions_from_logits(pred, lab, n_lab, variant)
-    if n_frames is None:
-        nf = torch.full((B,), T, dtype=torch.int32, device=dev)
-    else:                                    # (addition) utterance b owns the first n_frames[b] rows of a zero-padded [B, Tmax, V] prediction
+    counts = [T] * B
+    if n_frames is not None:                 # (addition) utterance b owns the first n_frames[b] rows of a zero-padded [B, Tmax, V] prediction
         counts = [int(v) for v in (n_frames.tolist() if torch.is_tensor(n_frames) else n_frames)]
         if len(counts) != B or any(v < 0 or v > T for v in counts):
             raise ValueError(f"n_frames: {B} frame counts in 0..{T} expected")
-        nf = torch.tensor(counts, dtype=torch.int32).to(dev)
+    # (additions) optional spans and per-state frame windows; None / all-empty keywords take the reference's lattice unchanged
     skip_from = _skip_from_of_spans(optional_spans, lists)
-    windows = _windows_of(char_windows, onset_anchors, lists, [T] * B if n_frames is None else counts, hop_size_second)
-    if anchored:                             # (addition) posteriors GIVEN the windows, and what the unanchored model thinks of them
-        onset, offset, score, status, occ, onp, offp, log_z, pres, skp, log_z_free = _anchored_posteriors(
-            em, lab, n_lab, nf, windows, skip_from, skip_penalty, boundary_window)
-        seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=True)
-        spans = optional_spans if optional_spans is not None else [[] for _ in lists]
-        return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists, pres, skp, spans, log_z_free)
-    if windows is not None:                  # (addition) per-state frame windows; None / all-empty takes the paths below unchanged
-        if boundary_window is not None:
-            raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
-                             "(perform_viterbi(_ctc)_anchored_scored give them)")
-        onset, offset, score, status = ops.viterbi_windows_batch(em, lab, n_lab, nf, windows[0].to(dev), windows[1].to(dev),
-                                                                 None if skip_from is None else skip_from.to(dev), skip_penalty)
-        return _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=skip_from is not None)
-    if skip_from is not None:                # (addition) the lattice with optional spans; None / all-empty takes the path below unchanged
-        skip_dev = skip_from.to(dev)
-        onset, offset, score, status = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
-        seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second, skipped_as_none=True)
-        if boundary_window is None:
-            return seconds
-        occ, onp, offp, log_z, _, pres, skp = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty,
-                                                                             boundary_window)
-        return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists, pres, skp, optional_spans)
-    onset, offset, score, status = ops.viterbi_batch(em, lab, n_lab, nf)
-    seconds = _seconds_from_frames(onset, offset, status, lists, hop_size_second)
-    if boundary_window is None:
-        return seconds
-    occ, onp, offp, log_z, _ = ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)
-    return seconds, _scores_from_posteriors(occ, onp, offp, log_z, score, lists)
+    windows = _windows_of(char_windows, onset_anchors, lists, counts, hop_size_second)
+    if windows is not None and boundary_window is not None and not anchored:
+        raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
+                         "(perform_viterbi(_ctc)_anchored_scored give them)")
+    confidence = "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
+    em = ops.emissions_from_logits(pred, lab, n_lab, variant)
+    nf = torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
+    r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window)
+    return _formatted(r, lists, hop_size_second, optional_spans)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
