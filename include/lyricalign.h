@@ -613,6 +613,40 @@ int la_multitask_loss(const float *logits, int64_t batch_stride, int64_t row_str
                       void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Training from line times (addition; the reference has none): the negative log-partition of the lattice with per-state frame
+ * windows as a loss on the align logits, forward and gradient with respect to the logits.  logits as in la_multitask_loss
+ * ([batch][frames][row_stride >= vocab+1] f32, column `vocab` the silence logit); labels, n_labels, n_frames (NULL: every clip
+ * has `frames` rows), skip_from / skip_stride / skip_penalty (skip_from may be NULL: no span anywhere), win_lo / win_hi /
+ * win_stride and the 511-label limit as in la_alignment_posteriors_windows.
+ *   em      = the CTC-variant compact emissions of la_emissions_from_logits (bit for bit):
+ *             em[t][0] = logsigmoid(x[t][V]), em[t][1+n] = x[t][c_n] - lse_{1..V-1}(x[t]) + logsigmoid(-x[t][V]),  V = vocab
+ *   nll[b]  = -log_z[b], the windowed log-partition of la_alignment_posteriors_windows on em
+ *   loss[0] = (1 / batch) * sum over feasible b of nll[b] / n_frames[b]
+ *   dlogits (optional) = scale * d loss / d logits: with gamma_t(s) the windowed posterior, g_sil = sum over even s of gamma_t(s),
+ *             g_n = gamma_t(2n+1), g_voiced = sum_n g_n, w = scale / (batch * n_frames[b]):
+ *               d[t][0] = 0
+ *               d[t][c] = w * (g_voiced * softmax_{1..V-1}(x[t])[c] - sum over n with c_n = c of g_n),   1 <= c < V
+ *               d[t][V] = w * (sigmoid(x[t][V]) - g_sil)
+ *             rows t >= n_frames[b] are exact zeros; columns past V are not written.  The -1000 clip of the emission prep is
+ *             treated as inactive (an emission that reaches it takes the gradient of the unclipped expression); a label whose
+ *             class lies outside 1..V-1 (constant emission -1000) takes no part in the gradient.  Jump arcs of optional spans
+ *             weigh a constant: they change gamma, not the formula.
+ * status[b]: LA_OK; LA_EINFEASIBLE (no path inside the windows, or too few frames for the labels) and LA_EEMPTY (no label):
+ * nll[b] = +inf, zero gradient rows, and the clip is left out of the sum, which is still divided by `batch`.
+ * Deterministic: no float atomics, classes that occur at several label positions are summed in ascending position; a clip's
+ * rows do not depend on its batch mates.  Argument errors (null pointers, strides, vocab < 3, a negative or NaN penalty; more
+ * than 511 labels: LA_EUNSUPPORTED) are answered before anything is enqueued.  Never synchronises, allocates or frees.
+ * workspace: 256-byte aligned.
+ */
+int la_anchored_alignment_loss_workspace_bytes(int32_t batch, int32_t frames, int32_t max_labels, size_t *bytes);
+int la_anchored_alignment_loss(const float *logits, int64_t batch_stride, int64_t row_stride, int32_t batch, int32_t frames,
+                               int32_t vocab, const int32_t *labels, int32_t labels_stride, const int32_t *n_labels,
+                               const int32_t *n_frames, int32_t max_labels, const int32_t *skip_from, int32_t skip_stride,
+                               double skip_penalty, const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride, float scale,
+                               float *loss, double *nll, int32_t *status, float *dlogits, int64_t d_batch_stride,
+                               int64_t d_row_stride, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * clip_grad_norm_(params, max_norm) + AdamW on flat f32 buffers (train_multitask.py:337-340,683-686).
  * la_grad_sqnorm_f32 ADDS sum(grad^2) into *sum_sq (device double; zero it once, call it per bucket, all-reduce is the
  * caller's: gradients are already averaged over ranks before this).  la_adamw_step_f32 applies

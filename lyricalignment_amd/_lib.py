@@ -88,6 +88,9 @@ SYMBOLS = {
     "la_fc_emissions": (c_int32, [_I32, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I64, _I64, _P, _SZ, _P]),
     "la_multitask_loss_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_multitask_loss": (c_int32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, ctypes.c_float, _P, _P, _I64, _I64, _P, _SZ, _P]),
+    "la_anchored_alignment_loss_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
+    "la_anchored_alignment_loss": (c_int32, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _I32, c_double, _P, _P, _I32,
+                                             ctypes.c_float, _P, _P, _P, _P, _I64, _I64, _P, _SZ, _P]),
     "la_grad_sqnorm_f32": (c_int32, [_P, _I64, _P, _P]),
     "la_adamw_step_f32": (c_int32, [_P, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _I32, _P, ctypes.c_float, ctypes.c_float, _P]),
     "la_gru_layer_train_fwd": (c_int32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P]),

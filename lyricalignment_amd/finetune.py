@@ -64,6 +64,62 @@ def multitask_loss(logits: torch.Tensor, frame_labels: Optional[torch.Tensor], c
     return losses, dlogits
 
 
+def anchored_alignment_loss(logits: torch.Tensor, labels: torch.Tensor, win_lo: torch.Tensor, win_hi: torch.Tensor,
+                            n_frames: Optional[torch.Tensor] = None, skip_from: Optional[torch.Tensor] = None, skip_penalty: float = 0.0,
+                            vocab_size: int = 21128, scale: float = 1.0, want_grad: bool = True):
+    """la_anchored_alignment_loss (include/lyricalign.h): the negative log-partition of the lattice with per-state frame windows on the
+    CTC-variant emissions of the logits -- the frame CE + silence BCE marginalised over every alignment the windows allow.
+    logits [B,T,>=vocab_size+1] f32 contiguous (device); labels [B,Lmax] class ids with -100 padding; win_lo / win_hi [B, 2*Lmax+1]
+    int32 (utils.alignment.windows_from_anchors; [0, T) = open); n_frames [B] int32 or None (every clip has T rows); skip_from
+    [B, Lmax+1] int32 or None (utils.alignment.spans_from_lines).
+    -> (loss f32[1] = mean_b nll_b / T_b over the feasible clips, nll f64[B] (+inf: infeasible), status i32[B], dlogits or None), all on
+    the device: nothing here synchronises.  dlogits = scale * d loss / d logits; rows past a clip's end, the rows of an infeasible clip
+    and the columns past vocab_size of wider logits are exact zeros."""
+    _lib.require_gpu()
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 3 or not logits.is_contiguous():
+        raise ValueError("anchored_alignment_loss: logits must be a contiguous float32 device tensor [B,T,V+1]")
+    B, T, W = logits.shape
+    if W < vocab_size + 1:
+        raise ValueError("anchored_alignment_loss: logits need vocab_size + 1 columns (word classes + silence)")
+    dev = logits.device
+    if labels.dim() != 2 or labels.shape[0] != B:
+        raise ValueError(f"anchored_alignment_loss: labels must be [{B}, Lmax]")
+    cl = labels.to(dev)
+    if cl.shape[1] == 0:
+        cl = torch.full((B, 1), -100, dtype=cl.dtype, device=dev)
+    Lmax = cl.shape[1]
+    nl = (cl != -100).sum(dim=1).to(torch.int32).contiguous()
+    lab = torch.where(cl == -100, torch.zeros_like(cl), cl).to(torch.int32).contiguous()
+
+    def rows(t, width, what):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < width:
+            raise ValueError(f"anchored_alignment_loss: {what} must be int32 [{B}, >= {width}]")
+        return t.to(dev).contiguous()
+
+    lo, hi = rows(win_lo, 2 * Lmax + 1, "win_lo"), rows(win_hi, 2 * Lmax + 1, "win_hi")
+    if lo.shape != hi.shape:
+        raise ValueError("anchored_alignment_loss: win_lo and win_hi must have one shape")
+    skip = None if skip_from is None else rows(skip_from, Lmax + 1, "skip_from")
+    nf = None
+    if n_frames is not None:
+        if n_frames.dim() != 1 or n_frames.shape[0] != B:
+            raise ValueError(f"anchored_alignment_loss: n_frames must be [{B}]")
+        nf = n_frames.to(device=dev, dtype=torch.int32).contiguous()
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    nll = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    dlogits = (torch.zeros_like(logits) if W > vocab_size + 1 else torch.empty_like(logits)) if want_grad else None
+    need = ctypes.c_size_t(0)
+    check(lib().la_anchored_alignment_loss_workspace_bytes(B, T, Lmax, ctypes.byref(need)), "anchored_alignment_loss_workspace_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+    check(lib().la_anchored_alignment_loss(ptr(logits), logits.stride(0), logits.stride(1), B, T, vocab_size, ptr(lab), lab.stride(0), ptr(nl),
+                                           ptr(nf), Lmax, ptr(skip), skip.stride(0) if skip is not None else 0, float(skip_penalty), ptr(lo),
+                                           ptr(hi), lo.stride(0), float(scale), ptr(loss), ptr(nll), ptr(status), ptr(dlogits),
+                                           dlogits.stride(0) if want_grad else 0, dlogits.stride(1) if want_grad else 0, ptr(ws), need.value,
+                                           stream_ptr()), "anchored_alignment_loss")
+    return loss, nll, status, dlogits
+
+
 class FlatAdamW:
     """clip_grad_norm_(all params, max_norm) + AdamW over flat f32 buckets, one bucket per parameter group
     (reference: head lr 5e-3, backbone lr 5e-6, weight_decay 1e-5, betas (0.9, 0.999), eps 1e-8)."""
@@ -424,6 +480,40 @@ class FineTuner:
             head_train.check_deferred_flags()                     # GRU time-out flags of a head that ran beside the decoder
         self._check_grad_views()
         return out
+
+    def micro_step_anchored(self, audios, labels, onset_anchors=None, char_windows=None, optional_spans=None, skip_penalty: float = 0.0,
+                            accum_grad_steps: int = 1, last: bool = False) -> torch.Tensor:
+        """One micro-batch trained from what is known about time instead of frame labels (addition): clips of at most 30 s, labels
+        [B, Lmax] class ids with -100 padding, onset_anchors / char_windows / optional_spans per clip as AlignModel.align takes them
+        (seconds from the clip's start; harness.lrc_training_clips cuts an LRC sheet into such clips).  The loss is
+        anchored_alignment_loss above on the align logits of frame_manual_forward(get_orig_len=False): it trains the word columns and
+        the silence logit, the columns the aligner reads.  Gradients accumulate into the flat buckets like micro_step's (divided by
+        accum_grad_steps); step() follows as usual.  -> the un-scaled loss, a device scalar.
+        ValueError: a model without the silence logit (use_ctc_loss False: the plain variant has no such loss), and -- after the backward,
+        where the GRU flags are read anyway; the clip's gradient rows were zero -- a clip without a path inside its windows."""
+        from .utils.alignment import anchored_loss_inputs, raise_for_loss_status
+        m = self.model
+        if not self.use_ctc_loss or not m.train_alignment:
+            raise ValueError("micro_step_anchored: the anchored alignment loss exists for the CTC variant only (word columns + silence logit, "
+                             "use_ctc_loss=True) and needs train_alignment")
+        m.train()
+        B = len(audios)
+        if last and self.overlap is not None:
+            self.overlap.arm()
+        align_logit, _ = m.frame_manual_forward(audios, None, get_orig_len=False)
+        T, W = int(align_logit.shape[1]), int(align_logit.shape[2])
+        if W < self.vocab_size + 1:
+            raise ValueError(f"micro_step_anchored: the align logits have {W} columns, vocab_size + 1 = {self.vocab_size + 1} expected")
+        dev = align_logit.device
+        lab, windows, skip = anchored_loss_inputs(labels, [T] * B, onset_anchors, char_windows, optional_spans, 0.02)
+        loss, _nll, status, dlog = anchored_alignment_loss(align_logit.detach().contiguous(), lab.to(dev), windows[0].to(dev), windows[1].to(dev),
+                                                           None, None if skip is None else skip.to(dev), skip_penalty,
+                                                           vocab_size=self.vocab_size, scale=1.0 / float(accum_grad_steps))
+        self._backward([align_logit], [dlog])
+        head_train.check_deferred_flags()                         # GRU time-out flags of the head; the host waits for the device here
+        raise_for_loss_status(status)
+        self._check_grad_views()
+        return loss.view(())
 
     def accumulate(self, micro_batches, accum_grad_steps: Optional[int] = None, get_orig_len: bool = False, fused: bool = True,
                    decoder_pad_id: int = 0):

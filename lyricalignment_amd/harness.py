@@ -283,3 +283,56 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
     if with_confidence:
         return out, {"sung": sung, "line_onset_prob": line_onset, "window_log_prob": float(scores["window_log_prob"])}
     return out
+
+
+def lrc_training_clips(audio, lrc, tokenize, max_seconds: float = 30.0, tolerance_s: float = 1.0, sample_rate: int = 16000) -> List[dict]:
+    """One recording and its LRC sheet -> training clips for FineTuner.micro_step_anchored / utils.alignment.anchored_alignment_loss
+    (addition; host only): [{"audio": samples of the clip, "lines": [line, ...], "onset_anchors": [(first character index of the line,
+    tag - clip start in seconds, tolerance_s), ...]}, ...].  `lrc` is LRC text (parse_lrc) or a list of (start_seconds, line) pairs;
+    `tokenize(line)` as in align_records, one class per character (used for the character counts).
+    Consecutive lines are packed greedily: a clip starts tolerance_s before its first line's tag (not before 0) and ends where the next clip
+    starts (the last one where the audio ends), capped at max_seconds; the next line joins a clip as long as the clip, ending where the line
+    after it would start a clip of its own, stays within max_seconds.  A gap longer than max_seconds after a line therefore ends the clip at
+    the cap, and the next clip starts tolerance_s before the next tag.  ValueError for a line that cannot fit: more characters than its clip
+    has 20 ms frames, or a tag that lies at or behind the end of its clip (of the audio)."""
+    pairs = parse_lrc(lrc) if isinstance(lrc, str) else sorted(((float(s), str(line)) for s, line in lrc), key=lambda v: v[0])
+    if not pairs:
+        raise ValueError("lrc_training_clips: no timed line in the sheet")
+    max_seconds, tol = float(max_seconds), float(tolerance_s)
+    if not max_seconds > 0.0 or tol < 0.0:
+        raise ValueError("lrc_training_clips: max_seconds > 0 and tolerance_s >= 0 expected")
+    total = len(audio) / float(sample_rate)
+    counts = []
+    for _, line in pairs:
+        n = len(list(tokenize(line)))
+        if n != len(line):
+            raise ValueError(f"lrc_training_clips: {n} tokens for the {len(line)} characters of {line!r}")
+        counts.append(n)
+    own_start = [max(0.0, s - tol) for s, _ in pairs]       # where a clip that begins with line i starts
+
+    def end_after(j, start):                                # end of a clip from `start` whose last line is j
+        nxt = own_start[j + 1] if j + 1 < len(pairs) else total
+        return min(nxt, total, start + max_seconds)
+
+    clips = []
+    i = 0
+    while i < len(pairs):
+        start = own_start[i]
+        j = i
+        while j + 1 < len(pairs) and (own_start[j + 2] if j + 2 < len(pairs) else total) <= start + max_seconds and pairs[j + 1][0] < total:
+            j += 1
+        end = end_after(j, start)
+        frames = int((end - start) / 0.02 + 1e-9)
+        anchors, pos = [], 0
+        for k in range(i, j + 1):
+            tag, line = pairs[k]
+            if tag - start >= end - start:
+                raise ValueError(f"lrc_training_clips: line {k} ({line!r}) is tagged at {tag:.2f} s, at or behind the end of its clip ({end:.2f} s)")
+            anchors.append((pos, tag - start, tol))
+            pos += counts[k]
+        if pos > frames:
+            raise ValueError(f"lrc_training_clips: lines {i}..{j} hold {pos} characters, their clip of {end - start:.2f} s only {frames} frames")
+        clips.append({"audio": audio[int(round(start * sample_rate)): int(round(end * sample_rate))], "lines": [pairs[k][1] for k in range(i, j + 1)],
+                      "onset_anchors": anchors})
+        i = j + 1
+    return clips

@@ -362,6 +362,94 @@ def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02
                     anchored=True)
 
 
+class _AnchoredAlignmentLoss(torch.autograd.Function):
+    """finetune.anchored_alignment_loss under autograd: the loss kernels write d loss / d logits in the forward, backward hands it on
+    (times the incoming scalar: the chain rule's factor, 1 for a plain loss.backward())."""
+
+    @staticmethod
+    def forward(ctx, align_logit, lab, lo, hi, nf, skip, skip_penalty, vocab_size):
+        from ..finetune import anchored_alignment_loss as loss_kernels
+        want = align_logit.requires_grad
+        loss, nll, status, dlogits = loss_kernels(align_logit.detach().contiguous(), lab, lo, hi, nf, skip, skip_penalty,
+                                                  vocab_size=vocab_size, scale=1.0, want_grad=want)
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(nll, status)
+        return loss.view(()), nll, status
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_nll, _grad_status):
+        (dlogits,) = ctx.saved_tensors
+        return (None if dlogits is None else dlogits * grad_loss, None, None, None, None, None, None, None)
+
+
+def anchored_loss_inputs(labels, frame_counts: Sequence[int], onset_anchors=None, char_windows=None, optional_spans=None,
+                         hop_size_second: float = 0.02):
+    """What finetune.anchored_alignment_loss takes beside the logits, from the keywords of AlignModel.align (host only): labels [B, Lmax]
+    (tensor / array / lists, -100 padding) -> (labels int64 [B, Lmax] with -100 padding, (win_lo, win_hi) int32 [B, 2 Lmax + 1] by
+    _windows_of -- every window open when nothing is known about time --, skip_from int32 [B, Lmax + 1] by _skip_from_of_spans or None)."""
+    B = len(frame_counts)
+    lab_t = torch.as_tensor(labels)
+    lists = _label_lists(lab_t.cpu() if torch.is_tensor(lab_t) else lab_t, B)
+    Lmax = max(1, max((len(l) for l in lists), default=1))
+    lab = torch.full((B, Lmax), -100, dtype=torch.int64)
+    for b, l in enumerate(lists):
+        if l:
+            lab[b, : len(l)] = torch.tensor(l, dtype=torch.int64)
+    skip = _skip_from_of_spans(optional_spans, lists)
+    windows = _windows_of(char_windows, onset_anchors, lists, frame_counts, hop_size_second)
+    if windows is None:                       # nothing known about time: every window is open
+        windows = (torch.zeros((B, 2 * Lmax + 1), dtype=torch.int32),
+                   torch.tensor([int(v) for v in frame_counts], dtype=torch.int32)[:, None].repeat(1, 2 * Lmax + 1))
+    return lab, windows, skip
+
+
+def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_windows=None, optional_spans=None, skip_penalty=0.0,
+                            hop_size_second=0.02, n_frames=None, on_infeasible="raise"):
+    """Training from line times (addition; the reference's losses need a label for every frame): -log of the total weight of the alignments
+    that char_windows / onset_anchors (per utterance, in windows_from_anchors' form, seconds in the utterance's own frames) and
+    optional_spans (as perform_viterbi) allow, per frame and averaged over the batch -- include/lyricalign.h la_anchored_alignment_loss.
+    With every frame pinned to one state this is the frame CE + silence BCE of train_multitask.py:587-614 with hard targets; with looser
+    windows it is that loss marginalised over the alignments.  No constraint at all is legal: every window is open.
+    align_logit [B, T, V+1] float32 on the device (AlignModel.frame_manual_forward in .train(); column V = the silence logit: the CTC
+    variant, the only one); labels [B, Lmax] class ids with -100 padding; n_frames as perform_viterbi.
+    -> a device scalar with a grad_fn: `loss.backward(); optimizer.step()` works with it.
+    on_infeasible: "raise" reads the per-clip status once (ONE host synchronisation per call) and raises ValueError naming the first clip
+    without a path inside its windows (or without labels); "skip" does not read it: such a clip adds nothing to the loss (still divided by
+    B) and gets a zero gradient."""
+    if on_infeasible not in ("raise", "skip"):
+        raise ValueError('anchored_alignment_loss: on_infeasible must be "raise" or "skip"')
+    if not torch.is_tensor(align_logit) or align_logit.dim() != 3 or not align_logit.is_cuda or align_logit.dtype != torch.float32:
+        raise ValueError("anchored_alignment_loss: align_logit must be a float32 device tensor [B, T, V+1]")
+    B, T, W = align_logit.shape
+    if W < 4:
+        raise ValueError("anchored_alignment_loss: align_logit needs the silence logit behind at least three word columns (the CTC variant)")
+    dev = align_logit.device
+    counts = [T] * B
+    nf = None
+    if n_frames is not None:
+        counts = [int(v) for v in (n_frames.tolist() if torch.is_tensor(n_frames) else n_frames)]
+        if len(counts) != B or any(v < 0 or v > T for v in counts):
+            raise ValueError(f"n_frames: {B} frame counts in 0..{T} expected")
+        nf = torch.tensor(counts, dtype=torch.int32).to(dev)
+    lab, windows, skip = anchored_loss_inputs(labels, counts, onset_anchors, char_windows, optional_spans, hop_size_second)
+    loss, _nll, status = _AnchoredAlignmentLoss.apply(align_logit, lab.to(dev), windows[0].to(dev), windows[1].to(dev), nf,
+                                                      None if skip is None else skip.to(dev), float(skip_penalty), W - 1)
+    if on_infeasible == "raise":
+        raise_for_loss_status(status)
+    return loss
+
+
+def raise_for_loss_status(status) -> None:
+    """status [B] of la_anchored_alignment_loss (reads it: a host synchronisation) -> ValueError naming the first clip that is not LA_OK."""
+    for b, st in enumerate(status.tolist()):
+        if st == LA_EINFEASIBLE:
+            raise ValueError(f"anchored_alignment_loss: clip {b} has no alignment inside its windows (or too few frames for its labels)")
+        if st == LA_EEMPTY:
+            raise ValueError(f"anchored_alignment_loss: clip {b} has no labels")
+        if st != LA_OK:
+            raise ValueError(f"anchored_alignment_loss: clip {b}: status {int(st)}")
+
+
 def run_viterbi_core(dp_matrix, backtrace_dp_matrix, cur_log_prediction, cur_log_silence_prediction, cur_label):
     """In place on the caller's numpy arrays and returned, like the reference (dp float64 [T,S], bt int64 [T,S],
     lp float32 [T,V'], ls float32 [T,1], label int64 [L]); row 0 of dp is taken as initialised by the caller."""
