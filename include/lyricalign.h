@@ -252,6 +252,35 @@ int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride, int64_t e
                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The general DP entry: the lattice of la_viterbi_windows_batch for up to 4095 labels (whole songs against whole lyric sheets).
+ * Every argument of la_viterbi_windows_batch in the same order.  skip_from may be NULL (no span anywhere); win_lo / win_hi may BOTH be
+ * NULL (no windows; one of them null and the other not is LA_EINVAL).  The lattice, the comparison order, the tie rules, the float64
+ * arithmetic and the window gate are la_viterbi_windows_batch's; outputs and status likewise.
+ * max_labels <= 511: the call runs the kernels of the matching entry and its outputs are that entry's bit for bit --
+ * la_viterbi_windows_batch with windows, la_viterbi_spans_batch with spans and no windows, la_viterbi_batch with neither.
+ * 512 <= max_labels <= 4095: 1024 threads sweep 2 / 4 / 8 consecutive states each, as in la_viterbi_batch (which is what runs when
+ * neither spans nor windows are given); with spans or windows every thread exchanges all its states through the LDS row where the
+ * clip has a span, and the backpointers are three 64-bit masks per (frame, state slot, wave).  LA_EUNSUPPORTED above 4095.
+ * la_viterbi_lattice_workspace_bytes(): la_viterbi_spans_workspace_bytes()' answer up to 511 labels, above that
+ * batch * max_frames * R * 16 * 3 * 8 bytes with R = 2, 4, 8 the states per thread (2 * max_labels + 1 <= 1024 R); `workspace` is
+ * 8-byte aligned.  Argument errors (la_viterbi_windows_batch's, for the pointers that are present: a skip_stride below
+ * max_labels + 1 with a skip_from, a win_stride below 2 * max_labels + 1 with windows, a negative or NaN skip_penalty) are answered
+ * on the host before anything is enqueued; never synchronises, allocates or frees.
+ * The posterior sweeps (la_alignment_posteriors*) and la_anchored_alignment_loss keep their limit of 511 labels.
+ */
+int la_viterbi_lattice_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                             const int32_t *labels, int32_t labels_stride,
+                             const int32_t *n_labels, const int32_t *n_frames,
+                             int32_t batch, int32_t max_frames, int32_t max_labels,
+                             int32_t *onset, int32_t *offset, int32_t out_stride,
+                             double *final_score, int32_t *status,
+                             const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                             const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
  * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
  * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable

@@ -35,6 +35,8 @@
 // together with SPANS (a null skip_from = no span anywhere; the once-per-clip has_span test still sends a span-free clip through the
 // plain loop).  A winning final score of -inf is LA_EINFEASIBLE with every onset / offset -1; otherwise backtrace and status are
 // unchanged.
+//
+// More than 511 labels (la_viterbi_lattice_batch): the span and window faces of viterbi_strip_kernel, described there.
 #include <type_traits>
 
 #include "la_lattice.h"
@@ -283,10 +285,22 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
 // labels).  Same recurrence, same comparison order, float64; the previous row goes through a double-buffered f64 row in
 // LDS (one barrier per frame).  Backpointer masks: [frame][r][wave][2] 64-bit ballots in the caller's workspace.
 // Onset / offset go straight to the outputs (no LDS copies: the row buffers take the LDS at R = 8).
-template <int R>
+// The SPANS and SPANS + WIN faces (la_viterbi_lattice_batch beyond 511 labels) are viterbi_kernel's on this form.  A jump source J
+// or J-1 can be any state of any thread, one of the reading thread's own included, so where the clip has a span (workgroup-uniform,
+// tested once outside the frame loop) every thread writes ALL R of its states into the row of the current parity and reads dp[J] /
+// dp[J-1] from that row after the barrier -- never from cur[], which the same r loop is overwriting.  A span-free clip runs the
+// plain loop: two row states, two mask words, no jump code.  J, jm1_ok and the window pair of each owned state stay in registers
+// (the two rows take 131,104 B of LDS at R = 8: no room for a J array); the backtrace thread recomputes J(kk) from skip_from.
+// Masks are then [frame][r][wave][3], the third word written and read only where the clip has a span.  The window's gate is applied
+// to the emission as it leaves the prefetch registers, off the loop-carried chain, as in viterbi_kernel.
+template <int R, bool SPANS = false, bool WIN = false>
 __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
+    static_assert(!WIN || SPANS, "frame windows are a face of the optional-span forms");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NT = 1024, NS = NT * R, SPF = 4;
+    // (R = 8 with spans: J, the window pairs and two generations of 4 x 8 prefetched emissions do not fit 128 VGPRs; the face waits on
+    // the barrier, not on the loads, so its prefetch is two frames deep, and one frame deep with the 16 window registers)
+    constexpr int NT = 1024, NS = NT * R, SPF = R < 8 || !SPANS ? 4 : WIN ? 1 : 2;
+    constexpr int MW = SPANS ? 3 : 2;  // backpointer mask words per (frame, r, wave)
     double *rowbuf = reinterpret_cast<double *>(smem);      // [2][NS + 2]
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -304,7 +318,7 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
         if (tid == 0) { p.status[b] = LA_EINVAL; p.final_score[b] = 0.0; }
         return;
     }
-    unsigned long long *bt = p.bt_global + (int64_t)b * p.max_frames * R * 32;
+    unsigned long long *bt = p.bt_global + (int64_t)b * p.max_frames * R * (16 * MW);
     const int32_t *lab = p.labels + (int64_t)b * p.labels_stride;
     const int k0 = tid * R;
     int col[R];
@@ -318,9 +332,50 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
         col[r] = (odd && valid[r]) ? 1 + n : 0;
         can_skip[r] = odd && valid[r] && k >= 3 && lab[n] != lab[n - 1];
     }
+    // the span that ends at each owned state's position, and each owned state's frame window (states >= S: none, the open window)
+    [[maybe_unused]] const int32_t *skip_b = nullptr;
+    [[maybe_unused]] int J[SPANS ? R : 1];
+    [[maybe_unused]] bool jm1_ok[SPANS ? R : 1];
+    [[maybe_unused]] int wlo[WIN ? R : 1], whi[WIN ? R : 1];
+    [[maybe_unused]] bool has_span = false;
+    if constexpr (SPANS) {
+        if (!WIN || p.skip_from) skip_b = p.skip_from + (int64_t)b * p.skip_stride;   // (windows: a null skip_from = no span anywhere)
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int k = k0 + r, n = k >> 1;
+            J[r] = -1;
+            jm1_ok[r] = false;
+            if (skip_b && valid[r] && n >= 1) {
+                const int a = skip_b[n];
+                if (a >= 0 && a < n) {
+                    J[r] = 2 * a;
+                    jm1_ok[r] = a >= 1 && (!(k & 1) || lab[n] != lab[a - 1]);
+                    any = true;
+                }
+            }
+        }
+        has_span = __syncthreads_or(any) != 0;   // workgroup-uniform: a clip without a span runs the plain loop
+    }
+    if constexpr (WIN) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            wlo[r] = 0, whi[r] = 0x7fffffff;
+            if (valid[r]) {
+                wlo[r] = p.win_lo[(int64_t)b * p.win_stride + k0 + r];
+                whi[r] = p.win_hi[(int64_t)b * p.win_stride + k0 + r];
+            }
+        }
+    }
+    [[maybe_unused]] const double pen = p.penalty;
     const float *emb = p.em + (int64_t)b * p.em_bs;
 #pragma unroll
-    for (int r = 0; r < R; ++r) cur[r] = (k0 + r <= 1) ? (double)emb[col[r]] : kNeg;
+    for (int r = 0; r < R; ++r) {
+        cur[r] = (k0 + r <= 1) ? (double)emb[col[r]] : kNeg;
+        if constexpr (WIN) {
+            if (!(0 >= wlo[r] && 0 < whi[r])) cur[r] = -INFINITY;
+        }
+    }
     if (tid == 0) { rowbuf[0] = kNeg; rowbuf[1] = kNeg; rowbuf[NS + 2] = kNeg; rowbuf[NS + 3] = kNeg; }
 
     float e_buf[SPF][R];
@@ -329,49 +384,137 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
 #pragma unroll
         for (int r = 0; r < R; ++r) e_buf[i][r] = (1 + i) < T ? emb[(int64_t)(1 + i) * p.em_rs + col[r]] : 0.0f;
     int parity = 0;
-    for (int j0 = 1; j0 < T; j0 += SPF) {
-        float e_cur[SPF][R];
+    auto sweep = [&](auto has_c) {
+        constexpr bool HAS = decltype(has_c)::value;  // this clip has a span
+        for (int j0 = 1; j0 < T; j0 += SPF) {
+            float e_cur[SPF][R];
 #pragma unroll
-        for (int i = 0; i < SPF; ++i)
+            for (int i = 0; i < SPF; ++i)
 #pragma unroll
-            for (int r = 0; r < R; ++r) e_cur[i][r] = e_buf[i][r];
+                for (int r = 0; r < R; ++r) {
+                    if constexpr (WIN) e_cur[i][r] = (j0 + i >= wlo[r] && j0 + i < whi[r]) ? e_buf[i][r] : -INFINITY;   // the window's gate
+                    else e_cur[i][r] = e_buf[i][r];
+                }
 #pragma unroll
-        for (int i = 0; i < SPF; ++i)
+            for (int i = 0; i < SPF; ++i)
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int jj = j0 + SPF + i;
-                e_buf[i][r] = jj < T ? emb[(int64_t)jj * p.em_rs + col[r]] : 0.0f;
+                for (int r = 0; r < R; ++r) {
+                    const int jj = j0 + SPF + i;
+                    e_buf[i][r] = jj < T ? emb[(int64_t)jj * p.em_rs + col[r]] : 0.0f;
+                }
+#pragma unroll
+            for (int i = 0; i < SPF; ++i) {
+                const int j = j0 + i;
+                if (j >= T) break;
+                double *rb = rowbuf + parity * (NS + 2);
+                if constexpr (HAS) {
+                    // any state can be a jump source: the whole row goes through LDS
+#pragma unroll
+                    for (int r = 0; r < R; ++r) rb[k0 + 2 + r] = cur[r];
+                } else {
+                    // the two rightmost states of this thread are the k-1 / k-2 neighbours of the next thread's first states
+                    rb[k0 + 2 + R - 1] = cur[R - 1];
+                    rb[k0 + 2 + R - 2] = cur[R - 2];
+                }
+                __syncthreads();
+                double prev[R + 2];
+                prev[0] = rb[k0];
+                prev[1] = rb[k0 + 1];
+#pragma unroll
+                for (int r = 0; r < R; ++r) prev[r + 2] = cur[r];
+                parity ^= 1;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double p0 = prev[r + 2], p1 = prev[r + 1], p2 = prev[r];
+                    const bool stay = p0 > p1;
+                    const bool skip = can_skip[r] && (p2 >= p1) && (p2 >= p0);
+                    int code = skip ? 2 : (stay ? 0 : 1);
+                    double best = skip ? p2 : (stay ? p0 : p1);
+                    if (k0 + r == 0) { code = 0; best = p0; }
+                    if constexpr (HAS) {
+                        if (J[r] >= 0) {
+                            const double vj = rb[J[r] + 2] - pen;                 // from the row, never from cur[]
+                            if (vj > best) { best = vj; code = 3; }             // strict, J before J-1
+                            if (jm1_ok[r]) {
+                                const double vm = rb[J[r] + 1] - pen;
+                                if (vm > best) { best = vm; code = 4; }
+                            }
+                        }
+                    }
+                    cur[r] = best + (double)e_cur[i][r];
+                    if constexpr (HAS) {
+                        const unsigned long long m0 = __ballot(code & 1);
+                        const unsigned long long m1 = __ballot((code >> 1) & 1);
+                        const unsigned long long m2 = __ballot(code >> 2);
+                        if (lane == 0) {
+                            unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * MW;
+                            row[0] = m0;
+                            row[1] = m1;
+                            row[2] = m2;
+                        }
+                    } else {
+                        const unsigned long long lo = __ballot(code & 1);
+                        const unsigned long long hi = __ballot(code >> 1);
+                        if (lane == 0) {
+                            unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * MW;
+                            row[0] = lo;
+                            row[1] = hi;
+                        }
+                    }
+                }
             }
+        }
+    };
+    if constexpr (SPANS) {
+        if (has_span) sweep(std::true_type{});
+        else sweep(std::false_type{});
+    } else {
+        // the plain DP's loop, kept as written (not routed through the lambda: the compiler allocates it differently there, and the plain
+        // instantiations keep their code); sweep(std::false_type) above is this loop with three mask words of pitch
+        for (int j0 = 1; j0 < T; j0 += SPF) {
+            float e_cur[SPF][R];
 #pragma unroll
-        for (int i = 0; i < SPF; ++i) {
-            const int j = j0 + i;
-            if (j >= T) break;
-            double *rb = rowbuf + parity * (NS + 2);
-            // the two rightmost states of this thread are the k-1 / k-2 neighbours of the next thread's first states
-            rb[k0 + 2 + R - 1] = cur[R - 1];
-            rb[k0 + 2 + R - 2] = cur[R - 2];
-            __syncthreads();
-            double prev[R + 2];
-            prev[0] = rb[k0];
-            prev[1] = rb[k0 + 1];
+            for (int i = 0; i < SPF; ++i)
 #pragma unroll
-            for (int r = 0; r < R; ++r) prev[r + 2] = cur[r];
-            parity ^= 1;
+                for (int r = 0; r < R; ++r) e_cur[i][r] = e_buf[i][r];
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const double p0 = prev[r + 2], p1 = prev[r + 1], p2 = prev[r];
-                const bool stay = p0 > p1;
-                const bool skip = can_skip[r] && (p2 >= p1) && (p2 >= p0);
-                int code = skip ? 2 : (stay ? 0 : 1);
-                double best = skip ? p2 : (stay ? p0 : p1);
-                if (k0 + r == 0) { code = 0; best = p0; }
-                cur[r] = best + (double)e_cur[i][r];
-                const unsigned long long lo = __ballot(code & 1);
-                const unsigned long long hi = __ballot(code >> 1);
-                if (lane == 0) {
-                    unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * 2;
-                    row[0] = lo;
-                    row[1] = hi;
+            for (int i = 0; i < SPF; ++i)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int jj = j0 + SPF + i;
+                    e_buf[i][r] = jj < T ? emb[(int64_t)jj * p.em_rs + col[r]] : 0.0f;
+                }
+#pragma unroll
+            for (int i = 0; i < SPF; ++i) {
+                const int j = j0 + i;
+                if (j >= T) break;
+                double *rb = rowbuf + parity * (NS + 2);
+                // the two rightmost states of this thread are the k-1 / k-2 neighbours of the next thread's first states
+                rb[k0 + 2 + R - 1] = cur[R - 1];
+                rb[k0 + 2 + R - 2] = cur[R - 2];
+                __syncthreads();
+                double prev[R + 2];
+                prev[0] = rb[k0];
+                prev[1] = rb[k0 + 1];
+#pragma unroll
+                for (int r = 0; r < R; ++r) prev[r + 2] = cur[r];
+                parity ^= 1;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double p0 = prev[r + 2], p1 = prev[r + 1], p2 = prev[r];
+                    const bool stay = p0 > p1;
+                    const bool skip = can_skip[r] && (p2 >= p1) && (p2 >= p0);
+                    int code = skip ? 2 : (stay ? 0 : 1);
+                    double best = skip ? p2 : (stay ? p0 : p1);
+                    if (k0 + r == 0) { code = 0; best = p0; }
+                    cur[r] = best + (double)e_cur[i][r];
+                    const unsigned long long lo = __ballot(code & 1);
+                    const unsigned long long hi = __ballot(code >> 1);
+                    if (lane == 0) {
+                        unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * 2;
+                        row[0] = lo;
+                        row[1] = hi;
+                    }
                 }
             }
         }
@@ -386,8 +529,9 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
     if (tid == 0) {
         int kk = (fin[S - 1] > fin[S - 2]) ? (S - 1) : (S - 2);
         p.final_score[b] = fin[kk];
-        int knext = -1, entered = 0;
-        for (int j = T - 1; j >= 0; --j) {
+        int knext = -1, entered = 0, skipped = 0;
+        const bool no_path = WIN && fin[kk] == -INFINITY;   // no path inside the windows: every onset / offset stays -1, no backtrace
+        for (int j = no_path ? -1 : T - 1; j >= 0; --j) {
             if (kk & 1) {
                 const int nn = kk >> 1;
                 if (kk != knext) { off_g[nn] = j + 1; ++entered; }
@@ -396,17 +540,31 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
             int knew = kk;
             if (j > 0) {
                 const int t2 = kk / R, r = kk - t2 * R;
-                const unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + (t2 >> 6)) * 2;
+                const unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + (t2 >> 6)) * MW;
                 const int sh = t2 & 63;
-                const int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
+                int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
+                if constexpr (SPANS) {
+                    if (has_span) {                          // (uniform: a span-free clip's backtrace is the plain DP's)
+                        const int nn = kk >> 1;
+                        const int a = nn >= 1 ? skip_b[nn] : -1;     // J(kk), as the sweep computed it
+                        if (a >= 0 && a < nn) {                      // the third mask is meaningful only for states with a span
+                            code |= (int)((row[2] >> sh) & 1ull) << 2;
+                            if (code >= 3) {                         // labels a .. nn-1 lie inside the taken jump: they stay -1
+                                skipped += nn - a;
+                                code = kk - (2 * a - (code - 3));
+                            }
+                        }
+                    }
+                }
                 knew = kk - code;
                 if ((kk & 1) && knew != kk) on_g[kk >> 1] = j;   // frame j is the first one in this state
             }
             knext = kk;
             kk = knew;
         }
-        // the path is monotone in k, so every odd state is entered at most once: all L labels visited <=> L entries
-        p.status[b] = entered == L ? LA_OK : LA_EINFEASIBLE;   // reference: ValueError from list.index (:183)
+        // the path is monotone in k, so every odd state is entered at most once and taken jumps do not overlap:
+        // every label visited or inside a taken jump <=> entered + skipped == L
+        p.status[b] = entered + skipped == L ? LA_OK : LA_EINFEASIBLE;   // reference: ValueError from list.index (:183)
     }
 }
 
@@ -418,20 +576,21 @@ struct VitPlan {
     size_t ws_bytes;
 };
 
-// false: more labels than a workgroup holds -- 4095 for the plain DP (strip kernel, R = 8), 511 with spans (one lane per state)
-bool plan_viterbi(int batch, int max_frames, int max_labels, bool spans, VitPlan *pl) {
+// false: more labels than a workgroup holds -- 4095 for the plain DP (strip kernel, R = 8), 511 with spans (one lane per state) unless
+// `wide` (la_viterbi_lattice_batch: the strip kernel's span and window faces, three mask words)
+bool plan_viterbi(int batch, int max_frames, int max_labels, bool spans, VitPlan *pl, bool wide = false) {
     const int nw = waves_for_labels(max_labels);
     pl->strip = 0;
     if (nw > 16) {
         const int S = 2 * max_labels + 1;
         int R = 2;
         while (1024 * R < S) R *= 2;
-        if (spans || R > 8) return false;
+        if ((spans && !wide) || R > 8) return false;
         pl->strip = R;
         pl->nw = 16;
         pl->bt_in_lds = false;
         pl->lds_bytes = 2 * (size_t)(1024 * R + 2) * sizeof(double);
-        pl->ws_bytes = (size_t)batch * max_frames * R * 32 * sizeof(unsigned long long);
+        pl->ws_bytes = (size_t)batch * max_frames * R * 16 * (spans ? 3 : 2) * sizeof(unsigned long long);
         return true;
     }
     const size_t fixed = 2 * (size_t)(nw * 64 + 2) * sizeof(double) + 2 * (size_t)((max_labels + 3) & ~3) * sizeof(int32_t) +
@@ -522,6 +681,52 @@ int run_batch(Face face, VitParams p, int32_t batch, void *workspace, size_t wor
     return LA_EUNSUPPORTED;
 }
 
+// la_viterbi_lattice_batch: the face follows from the pointers that are present.  Every argument error is answered here, under this
+// entry's name; up to 511 labels (and for the plain lattice at any size) the call then IS the matching entry's, above that the strip
+// kernel's span / window faces.  One planner for the workspace whatever the face: the span planner's, three mask words.
+constexpr const char *kLatticeWho = "viterbi_lattice_batch";
+
+bool plan_lattice(int batch, int max_frames, int max_labels, VitPlan *pl) {
+    if (plan_viterbi(batch, max_frames, max_labels, true, pl, true)) return true;
+    la::set_error("viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
+    return false;
+}
+
+int run_lattice_batch(VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    const char *who = kLatticeWho;
+    if (batch == 0) return LA_OK;
+    LA_CHECK_ARG((p.win_lo == nullptr) == (p.win_hi == nullptr), "%s: win_lo and win_hi go together (both null: no windows)", who);
+    const Face face = p.win_lo ? Face::Windows : p.skip_from ? Face::Spans : Face::Plain;
+    LA_CHECK_ARG(p.inputs_present(face) && p.onset && p.offset && p.final_score && p.status, "%s: null pointer", who);
+    LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
+    LA_CHECK_ARG(p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
+    VitPlan pl;
+    if (!plan_lattice(batch, p.max_frames, p.max_labels, &pl)) return LA_EUNSUPPORTED;
+    LA_CHECK_ARG(p.strides_ok(face, p.out_stride, false), "%s: strides smaller than max_labels", who);
+    LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes), "%s: workspace too small (%zu < %zu)", who,
+                 workspace_bytes, pl.ws_bytes);
+    LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+    // (the matching entry's own need never exceeds the span planner's: fewer mask words, no J array)
+    if (!pl.strip || face == Face::Plain) return run_batch(face, p, batch, workspace, workspace_bytes, stream);
+    p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
+    p.bt_in_lds = 0;
+    const char *timer = "viterbi_lattice";
+    if (face == Face::Windows) {
+        switch (pl.strip) {
+            case 2: return launch<viterbi_strip_kernel<2, true, true>>(timer, 1024, p, pl, batch, stream);
+            case 4: return launch<viterbi_strip_kernel<4, true, true>>(timer, 1024, p, pl, batch, stream);
+            case 8: return launch<viterbi_strip_kernel<8, true, true>>(timer, 1024, p, pl, batch, stream);
+        }
+    } else {
+        switch (pl.strip) {
+            case 2: return launch<viterbi_strip_kernel<2, true>>(timer, 1024, p, pl, batch, stream);
+            case 4: return launch<viterbi_strip_kernel<4, true>>(timer, 1024, p, pl, batch, stream);
+            case 8: return launch<viterbi_strip_kernel<8, true>>(timer, 1024, p, pl, batch, stream);
+        }
+    }
+    return LA_EUNSUPPORTED;
+}
+
 }  // namespace
 
 extern "C" int la_viterbi_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
@@ -573,6 +778,29 @@ extern "C" int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride
     p.set_windows(win_lo, win_hi, win_stride);
     p.set_outputs(onset, offset, out_stride, final_score, status);
     return run_batch(Face::Windows, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int la_viterbi_lattice_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "viterbi_lattice_workspace_bytes: bad arguments");
+    VitPlan pl;
+    if (!plan_lattice(batch, max_frames, max_labels, &pl)) return LA_EUNSUPPORTED;
+    *bytes = pl.ws_bytes;
+    return LA_OK;
+}
+
+extern "C" int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                        const int32_t *labels, int32_t labels_stride, const int32_t *n_labels,
+                                        const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
+                                        int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
+                                        int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                        const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                        void *workspace, size_t workspace_bytes, void *stream_) {
+    VitParams p{};
+    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
+    p.set_spans(skip_from, skip_stride, skip_penalty);
+    p.set_windows(win_lo, win_hi, win_stride);
+    p.set_outputs(onset, offset, out_stride, final_score, status);
+    return run_lattice_batch(p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // run_viterbi_core(dp, bt, lp, ls, label) of the reference (utils/alignment.py:73-119) for ONE utterance: same

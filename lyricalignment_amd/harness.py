@@ -174,7 +174,8 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     [[onset, offset, char], ...] (AlignModel.align(optional_spans=...), skip_penalty >= 0 per skipped line).
     with_confidence: -> (lines_out, sung), sung[i] = the probability under the model that line i was sung (a Python float: present_prob
     of the line's first character, AlignModel.align(return_span_confidence=True)); 1 for a mandatory line, and 1 - span_skip_prob of an
-    optional line's span."""
+    optional line's span.
+    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError)."""
     from .utils.alignment import spans_from_lines
     lines = list(lines)
     ids = [list(tokenize(line)) for line in lines]
@@ -243,7 +244,8 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
             "line_onset_prob": [per line: the probability that the line's first character starts within boundary_window = 2 frames of
                                 the reported onset, None for a line that was left out],
             "window_log_prob": float <= 0, the log-probability the unanchored model gives to "the path respects every tag" -- near 0
-                               when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}."""
+                               when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}.
+    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError)."""
     from .utils.alignment import spans_from_lines
     pairs = parse_lrc(lrc) if isinstance(lrc, str) else [(float(s), str(line)) for s, line in lrc]
     if not pairs:

@@ -348,7 +348,8 @@ class AlignModel(torch.nn.Module):
         optional_spans (addition): optional_spans[b] = list of (a, n) pairs -- labels a .. n-1 of clip b (a lyric line that may not be sung)
         may be left out by the path; the head's emissions go through the DP on the lattice with optional spans (ops.viterbi_spans_batch,
         skip_penalty >= 0 per taken jump) and skipped characters come back as None (onset = offset = -1 with return_frames).  None or
-        all-empty: the call as it was.  Not with return_confidence (ValueError; return_span_confidence is the keyword); at most 511 labels.
+        all-empty: the call as it was.  Not with return_confidence (ValueError; return_span_confidence is the keyword).  Up to 4095 labels
+        (beyond 511: ops.viterbi_lattice_batch); the confidence keywords at most 511 (NotImplementedError).
         return_span_confidence (addition): -> (seconds, scores) on the lattice with optional spans (ops.alignment_posteriors_spans):
         return_confidence's dicts (skipped characters: None in seconds, their three scores 0) plus "sung_prob": [L], the probability that
         the character is on the path at all, and "span_skip_prob": the probability that the span was left out, one value per span of
@@ -360,7 +361,8 @@ class AlignModel(torch.nn.Module):
         the long form included).  The head's emissions go through the DP with a frame window per lattice state (ops.viterbi_windows_batch),
         with or without optional_spans.  None or all-empty: the call as it was.  A clip without a path inside its windows raises like a clip
         too short for its labels (status LA_EINFEASIBLE with return_frames).  Not with return_confidence / return_span_confidence
-        (ValueError: return_anchored_confidence is the keyword); at most 511 labels.
+        (ValueError: return_anchored_confidence is the keyword).  Up to 4095 labels (beyond 511: ops.viterbi_lattice_batch);
+        return_anchored_confidence at most 511 (NotImplementedError).
         return_anchored_confidence (addition): -> (seconds, scores) on the lattice with the frame windows of char_windows / onset_anchors
         (ops.alignment_posteriors_windows), with or without optional_spans, per_clip and the long form: return_span_confidence's dicts,
         every number a posterior GIVEN the windows, plus "window_log_prob" = log_z(windowed) - log_z(same lattice, no windows) <= 0, the

@@ -59,8 +59,9 @@ def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device) -> Tuple[t
 
 
 # The face of a lattice call (csrc/la_lattice.h Face) is chosen by the public function: "plain", "spans" (skip_from given) or
-# "windows" (win_lo / win_hi given, skip_from may be None).  -> the stem of its C symbols, DP and posteriors
-_DP_ENTRY = {"plain": "viterbi", "spans": "viterbi_spans", "windows": "viterbi_windows"}
+# "windows" (win_lo / win_hi given, skip_from may be None); "lattice" is the general DP entry (la_viterbi_lattice_batch: skip_from and
+# the windows may each be None, up to 4095 labels).  -> the stem of its C symbols, DP and posteriors
+_DP_ENTRY = {"plain": "viterbi", "spans": "viterbi_spans", "windows": "viterbi_windows", "lattice": "viterbi_lattice"}
 _POSTERIOR_ENTRY = {"plain": "alignment_posteriors", "spans": "alignment_posteriors_spans", "windows": "alignment_posteriors_windows"}
 
 
@@ -91,7 +92,9 @@ def _lattice_checked(who: str, face: str, em, labels, n_labels, n_frames, skip_f
 def _face_args(face: str, skip_from, skip_stride: int, skip_penalty: float, windows) -> tuple:
     """The C arguments a face adds to the plain one's: (skip_from, skip_stride, skip_penalty) and (win_lo, win_hi, win_stride)."""
     spans = () if face == "plain" else (ptr(skip_from), skip_stride, skip_penalty)
-    return spans + ((ptr(windows[0]), ptr(windows[1]), windows[0].stride(0)) if face == "windows" else ())
+    if face == "lattice" and windows is None:                # the general entry always takes the window arguments: null = no windows
+        return spans + (0, 0, 0)
+    return spans + ((ptr(windows[0]), ptr(windows[1]), windows[0].stride(0)) if face in ("windows", "lattice") else ())
 
 
 def _viterbi(who: str, face: str, em, labels, n_labels, n_frames, skip_from=None, skip_penalty=0.0, windows=None):
@@ -161,6 +164,18 @@ def viterbi_windows_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     win_lo[b, s] <= t < win_hi[b, s].  -> the tuple of viterbi_batch; a clip without a path inside its windows has status
     LA_EINFEASIBLE, score -inf and every onset / offset -1."""
     return _viterbi("viterbi_windows_batch", "windows", em, labels, n_labels, n_frames, skip_from, skip_penalty, (win_lo, win_hi))
+
+
+def viterbi_lattice_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                          skip_from: Optional[torch.Tensor] = None, skip_penalty: float = 0.0, win_lo: Optional[torch.Tensor] = None,
+                          win_hi: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """la_viterbi_lattice_batch: the DP on the lattice that skip_from (None: no span) and win_lo / win_hi (both None: no windows)
+    describe, for up to 4095 labels.  Up to 511 labels the outputs are viterbi_windows_batch's, viterbi_spans_batch's or viterbi_batch's
+    bit for bit, according to what is given.  -> the tuple of viterbi_batch."""
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError("viterbi_lattice_batch: win_lo and win_hi go together")
+    return _viterbi("viterbi_lattice_batch", "lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty,
+                    None if win_lo is None else (win_lo, win_hi))
 
 
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,

@@ -215,6 +215,9 @@ class LatticeResult(NamedTuple):
     log_z_free: Optional[torch.Tensor] = None
 
 
+POSTERIOR_MAX_LABELS = 511      # one lane per lattice state in the sum-product sweeps and in the span / window entries of the DP
+
+
 def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0.0, confidence=None, boundary_window=2, dp=None) -> LatticeResult:
     """The one place where the face of an alignment is decided (csrc/la_lattice.h Face, through the ops wrappers): the DP and, if asked
     for, the posteriors on the lattice that skip_from (host rows of _skip_from_of_spans, or None) and windows (host (win_lo, win_hi)
@@ -222,11 +225,19 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     confidence: None | "plain" (ops.alignment_posteriors; no spans, no windows) | "span" (the span lattice's; no windows; without a
     span the plain DP's frames, which are the span DP's bit for bit, and an all -1 skip_from) | "anchored" (posteriors GIVEN the windows,
     plus log_z_free = log_z of the same lattice without windows: one more launch of the free sweep, and log_z itself without windows).
-    dp: the (onset, offset, score, status) of the plain lattice where they exist already (the fused head's)."""
+    dp: the (onset, offset, score, status) of the plain lattice where they exist already (the fused head's).
+    More than 511 labels (up to 4095): the DP with spans or windows is ops.viterbi_lattice_batch; the posterior sweeps stop at 511, so any
+    confidence raises NotImplementedError before anything is launched."""
+    wide = lab.shape[1] > POSTERIOR_MAX_LABELS
+    if wide and confidence is not None:
+        raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posterior sweeps "
+                                  "(the alignment itself, without the confidence keywords, takes up to 4095)")
     dev = em.device
     skip_dev = None if skip_from is None else skip_from.to(dev)
     win = None if windows is None else (windows[0].to(dev), windows[1].to(dev))
-    if win is not None:
+    if wide and (win is not None or skip_dev is not None):
+        dp = ops.viterbi_lattice_batch(em, lab, n_lab, nf, skip_dev, skip_penalty, *(win or (None, None)))
+    elif win is not None:
         dp = ops.viterbi_windows_batch(em, lab, n_lab, nf, win[0], win[1], skip_dev, skip_penalty)
     elif skip_dev is not None:
         dp = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
@@ -308,7 +319,8 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     None or all-empty: today's DP.  ValueError for a < 0, a >= n, n > L or two spans with one end.
     char_windows / onset_anchors (addition): per utterance a list in windows_from_anchors' form (seconds, in the utterance's own frames):
     the DP runs on the lattice with per-state frame windows (la_viterbi_windows_batch), with or without optional_spans.  None or
-    all-empty: the call as it was.  An utterance without a path inside its windows raises like one too short for its labels."""
+    all-empty: the call as it was.  An utterance without a path inside its windows raises like one too short for its labels.
+    Up to 4095 labels with any of these keywords (beyond 511 the DP is la_viterbi_lattice_batch); the _scored functions at most 511."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
