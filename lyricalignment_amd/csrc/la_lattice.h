@@ -1,6 +1,6 @@
 // la_lattice.h -- what the kernels that sweep the alignment lattice (S = 2L+1 states, one lane per state, row by row) have in
 // common: la_viterbi.hip (max-product), la_posterior.hip and the CTC lattice of la_loss.hip (sum-product).  Device helpers for
-// the neighbour exchange inside one wave64 and for the log-sum-exp of a step; on the host the wave count of a label count, the face of
+// the neighbour exchange inside one wave64, the span-source rule and the log-sum-exp of a step; on the host the wave count of a label count, the face of
 // an entry point (plain, optional spans, frame windows) with its names, and the description of the lattice with its argument checks.
 #pragma once
 
@@ -103,6 +103,31 @@ __device__ __forceinline__ double wave_gather(double x, int byte_addr) {
     const int lo = __builtin_amdgcn_ds_bpermute(byte_addr, __double2loint(x));
     const int hi = __builtin_amdgcn_ds_bpermute(byte_addr, __double2hiint(x));
     return __hiloint2double(hi, lo);
+}
+
+// The span that ends at position n (optional spans, la_viterbi.hip): skip_row[n] = a with 0 <= a < n declares labels a .. n-1 optional.
+// span_first: a, or -1 for none (position 0, or a outside 0 <= a < n); skip_row is not null.
+__device__ __forceinline__ int span_first(const int32_t *skip_row, int n) {
+    if (n < 1) return -1;
+    const int a = skip_row[n];
+    return a >= 0 && a < n ? a : -1;
+}
+// What the span gives state k at its position n = k >> 1: the jump sources J = 2a (the silence before the span) and, where jm1_ok, J-1
+// (the label before it: a >= 1, and for an odd target only when labels[n] != labels[a-1]).  J = -1: none -- a null skip_row, a state
+// past the clip's last, or no span at n.
+struct SpanSource {
+    int J;
+    bool jm1_ok;
+};
+__device__ __forceinline__ SpanSource span_source(const int32_t *skip_row, const int32_t *lab, int k, bool valid) {
+    SpanSource s{-1, false};
+    const int n = k >> 1;
+    const int a = skip_row && valid ? span_first(skip_row, n) : -1;
+    if (a >= 0) {
+        s.J = 2 * a;
+        s.jm1_ok = a >= 1 && (!(k & 1) || lab[n] != lab[a - 1]);
+    }
+    return s;
 }
 
 // log(exp(a) + exp(b) [+ exp(c)]), -inf safe: float64 maximum, float32 correction.  The correction log(sum exp(x - max)) lies

@@ -65,6 +65,32 @@ struct VitParams : LatticeIn {
     }
 };
 
+// The recurrence cell, for both kernels: the winner among a state's predecessors and its backpointer code.
+struct Cell {
+    int code;      // 0 stay, 1 advance, 2 skip: the offset back to the predecessor; 3 jump from J, 4 jump from J-1
+    double best;
+};
+// p0, p1, p2: dp[j-1][k], [k-1], [k-2]; the reference's comparisons in the reference's order
+__device__ __forceinline__ Cell choose_neighbour(double p0, double p1, double p2, bool can_skip, bool state0) {
+    const bool stay = p0 > p1;                                   // strict (:85,:94,:110)
+    const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);      // (:104-105)
+    int code = skip ? 2 : (stay ? 0 : 1);
+    double best = skip ? p2 : (stay ? p0 : p1);
+    if (state0) { code = 0; best = p0; }                         // (:78-82)
+    return {code, best};
+}
+// The two arcs of the span that ends at this state (J >= 0): each is charged pen and must beat the winner so far STRICTLY, J before J-1.
+// dp_jm1 is dereferenced only where that arc exists.
+__device__ __forceinline__ Cell jump_step(Cell c, const double *dp_j, const double *dp_jm1, bool jm1_ok, double pen) {
+    const double vj = *dp_j - pen;
+    if (vj > c.best) c = {3, vj};
+    if (jm1_ok) {
+        const double vm = *dp_jm1 - pen;
+        if (vm > c.best) c = {4, vm};
+    }
+    return c;
+}
+
 template <int NW, bool DPP, bool SPANS, bool DUMP = false, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     static_assert(!DPP || NW == 1, "DPP neighbour exchange is single-wave only");
@@ -117,13 +143,10 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
     int J = -1;
     bool jm1_ok = false;
     if constexpr (SPANS) {
-        if (valid && n >= 1 && (!WIN || p.skip_from)) {   // (windows: a null skip_from = no span anywhere)
-            const int a = p.skip_from[(int64_t)b * p.skip_stride + n];
-            if (a >= 0 && a < n) {
-                J = 2 * a;
-                jm1_ok = a >= 1 && (!odd || lab[n] != lab[a - 1]);
-            }
-        }
+        // (windows: a null skip_from = no span anywhere)
+        const SpanSource src = span_source(!WIN || p.skip_from ? p.skip_from + (int64_t)b * p.skip_stride : nullptr, lab, k, valid);
+        J = src.J;
+        jm1_ok = src.jm1_ok;
         j_s[k] = J;
     }
     const double pen = p.penalty;
@@ -197,20 +220,10 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
                     }
                     parity ^= 1;
                 }
-                const bool stay = p0 > p1;                                   // strict (:85,:94,:110)
-                const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);      // (:104-105)
-                int code = skip ? 2 : (stay ? 0 : 1);
-                double best = skip ? p2 : (stay ? p0 : p1);
-                if (k == 0) { code = 0; best = p0; }                         // (:78-82)
-                if (HAS && J >= 0) {
-                    const double vj = pj - pen;
-                    if (vj > best) { best = vj; code = 3; }                  // strict, J before J-1
-                    if (jm1_ok) {
-                        const double vm = pjm1 - pen;
-                        if (vm > best) { best = vm; code = 4; }
-                    }
-                }
-                cur = best + (double)e_cur[i];
+                Cell c = choose_neighbour(p0, p1, p2, can_skip, k == 0);
+                if (HAS && J >= 0) c = jump_step(c, &pj, &pjm1, jm1_ok, pen);
+                const int code = c.code;
+                cur = c.best + (double)e_cur[i];
                 if (DUMP && valid) {
                     p.dp_dump[(int64_t)j * S + k] = cur;
                     p.bt_dump[(int64_t)j * S + k] = k - code;
@@ -343,17 +356,10 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
         bool any = false;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int k = k0 + r, n = k >> 1;
-            J[r] = -1;
-            jm1_ok[r] = false;
-            if (skip_b && valid[r] && n >= 1) {
-                const int a = skip_b[n];
-                if (a >= 0 && a < n) {
-                    J[r] = 2 * a;
-                    jm1_ok[r] = a >= 1 && (!(k & 1) || lab[n] != lab[a - 1]);
-                    any = true;
-                }
-            }
+            const SpanSource src = span_source(skip_b, lab, k0 + r, valid[r]);
+            J[r] = src.J;
+            jm1_ok[r] = src.jm1_ok;
+            any |= src.J >= 0;
         }
         has_span = __syncthreads_or(any) != 0;   // workgroup-uniform: a clip without a span runs the plain loop
     }
@@ -425,100 +431,29 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
                 parity ^= 1;
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    const double p0 = prev[r + 2], p1 = prev[r + 1], p2 = prev[r];
-                    const bool stay = p0 > p1;
-                    const bool skip = can_skip[r] && (p2 >= p1) && (p2 >= p0);
-                    int code = skip ? 2 : (stay ? 0 : 1);
-                    double best = skip ? p2 : (stay ? p0 : p1);
-                    if (k0 + r == 0) { code = 0; best = p0; }
+                    Cell c = choose_neighbour(prev[r + 2], prev[r + 1], prev[r], can_skip[r], k0 + r == 0);
                     if constexpr (HAS) {
-                        if (J[r] >= 0) {
-                            const double vj = rb[J[r] + 2] - pen;                 // from the row, never from cur[]
-                            if (vj > best) { best = vj; code = 3; }             // strict, J before J-1
-                            if (jm1_ok[r]) {
-                                const double vm = rb[J[r] + 1] - pen;
-                                if (vm > best) { best = vm; code = 4; }
-                            }
-                        }
+                        if (J[r] >= 0) c = jump_step(c, rb + J[r] + 2, rb + J[r] + 1, jm1_ok[r], pen);   // from the row, never from cur[]
                     }
-                    cur[r] = best + (double)e_cur[i][r];
-                    if constexpr (HAS) {
-                        const unsigned long long m0 = __ballot(code & 1);
-                        const unsigned long long m1 = __ballot((code >> 1) & 1);
-                        const unsigned long long m2 = __ballot(code >> 2);
-                        if (lane == 0) {
-                            unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * MW;
-                            row[0] = m0;
-                            row[1] = m1;
-                            row[2] = m2;
-                        }
-                    } else {
-                        const unsigned long long lo = __ballot(code & 1);
-                        const unsigned long long hi = __ballot(code >> 1);
-                        if (lane == 0) {
-                            unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * MW;
-                            row[0] = lo;
-                            row[1] = hi;
-                        }
+                    const int code = c.code;
+                    cur[r] = c.best + (double)e_cur[i][r];
+                    const unsigned long long m0 = __ballot(code & 1);
+                    const unsigned long long m1 = __ballot((code >> 1) & 1);
+                    [[maybe_unused]] unsigned long long m2 = 0ull;
+                    if constexpr (HAS) m2 = __ballot(code >> 2);
+                    if (lane == 0) {
+                        unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * MW;
+                        row[0] = m0;
+                        row[1] = m1;
+                        if constexpr (HAS) row[2] = m2;                                 // (read back only for states with a span)
                     }
                 }
             }
         }
     };
-    if constexpr (SPANS) {
-        if (has_span) sweep(std::true_type{});
-        else sweep(std::false_type{});
-    } else {
-        // the plain DP's loop, kept as written (not routed through the lambda: the compiler allocates it differently there, and the plain
-        // instantiations keep their code); sweep(std::false_type) above is this loop with three mask words of pitch
-        for (int j0 = 1; j0 < T; j0 += SPF) {
-            float e_cur[SPF][R];
-#pragma unroll
-            for (int i = 0; i < SPF; ++i)
-#pragma unroll
-                for (int r = 0; r < R; ++r) e_cur[i][r] = e_buf[i][r];
-#pragma unroll
-            for (int i = 0; i < SPF; ++i)
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int jj = j0 + SPF + i;
-                    e_buf[i][r] = jj < T ? emb[(int64_t)jj * p.em_rs + col[r]] : 0.0f;
-                }
-#pragma unroll
-            for (int i = 0; i < SPF; ++i) {
-                const int j = j0 + i;
-                if (j >= T) break;
-                double *rb = rowbuf + parity * (NS + 2);
-                // the two rightmost states of this thread are the k-1 / k-2 neighbours of the next thread's first states
-                rb[k0 + 2 + R - 1] = cur[R - 1];
-                rb[k0 + 2 + R - 2] = cur[R - 2];
-                __syncthreads();
-                double prev[R + 2];
-                prev[0] = rb[k0];
-                prev[1] = rb[k0 + 1];
-#pragma unroll
-                for (int r = 0; r < R; ++r) prev[r + 2] = cur[r];
-                parity ^= 1;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double p0 = prev[r + 2], p1 = prev[r + 1], p2 = prev[r];
-                    const bool stay = p0 > p1;
-                    const bool skip = can_skip[r] && (p2 >= p1) && (p2 >= p0);
-                    int code = skip ? 2 : (stay ? 0 : 1);
-                    double best = skip ? p2 : (stay ? p0 : p1);
-                    if (k0 + r == 0) { code = 0; best = p0; }
-                    cur[r] = best + (double)e_cur[i][r];
-                    const unsigned long long lo = __ballot(code & 1);
-                    const unsigned long long hi = __ballot(code >> 1);
-                    if (lane == 0) {
-                        unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + wave) * 2;
-                        row[0] = lo;
-                        row[1] = hi;
-                    }
-                }
-            }
-        }
-    }
+    // (MW is this instantiation's: the plain kernels run sweep(false) at two mask words of pitch, a span-free clip of the span faces at three)
+    if (has_span) sweep(std::bool_constant<SPANS>{});
+    else sweep(std::false_type{});
     // termination + backtrace by one thread; the masks were written by other waves of this workgroup: drain + barrier first
     __syncthreads();
     double *fin = rowbuf;
@@ -544,14 +479,13 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
                 const int sh = t2 & 63;
                 int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
                 if constexpr (SPANS) {
-                    if (has_span) {                          // (uniform: a span-free clip's backtrace is the plain DP's)
-                        const int nn = kk >> 1;
-                        const int a = nn >= 1 ? skip_b[nn] : -1;     // J(kk), as the sweep computed it
-                        if (a >= 0 && a < nn) {                      // the third mask is meaningful only for states with a span
+                    if (has_span) {                          // (uniform: a span-free clip's backtrace is the plain DP's; skip_b is not null)
+                        const int ak = span_first(skip_b, kk >> 1);      // J(kk) = 2 ak, as the sweep computed it
+                        if (ak >= 0) {                               // the third mask is meaningful only for states with a span
                             code |= (int)((row[2] >> sh) & 1ull) << 2;
-                            if (code >= 3) {                         // labels a .. nn-1 lie inside the taken jump: they stay -1
-                                skipped += nn - a;
-                                code = kk - (2 * a - (code - 3));
+                            if (code >= 3) {                         // labels ak .. kk / 2 - 1 lie inside the taken jump: they stay -1
+                                skipped += (kk >> 1) - ak;
+                                code = kk - (2 * ak - (code - 3));
                             }
                         }
                     }
@@ -576,27 +510,27 @@ struct VitPlan {
     size_t ws_bytes;
 };
 
-// false: more labels than a workgroup holds -- 4095 for the plain DP (strip kernel, R = 8), 511 with spans (one lane per state) unless
-// `wide` (la_viterbi_lattice_batch: the strip kernel's span and window faces, three mask words)
-bool plan_viterbi(int batch, int max_frames, int max_labels, bool spans, VitPlan *pl, bool wide = false) {
+// mask_words: 2, or 3 with spans (then the lane-per-state forms also keep J in LDS).  label_limit: 511 = one lane per state only,
+// 4095 = the strip kernel beyond that (R = 8 holds 8192 states).  false: more labels than the limit
+bool plan_viterbi(int batch, int max_frames, int max_labels, int mask_words, int label_limit, VitPlan *pl) {
+    if (max_labels > label_limit) return false;
     const int nw = waves_for_labels(max_labels);
     pl->strip = 0;
     if (nw > 16) {
         const int S = 2 * max_labels + 1;
         int R = 2;
         while (1024 * R < S) R *= 2;
-        if ((spans && !wide) || R > 8) return false;
         pl->strip = R;
         pl->nw = 16;
         pl->bt_in_lds = false;
         pl->lds_bytes = 2 * (size_t)(1024 * R + 2) * sizeof(double);
-        pl->ws_bytes = (size_t)batch * max_frames * R * 16 * (spans ? 3 : 2) * sizeof(unsigned long long);
+        pl->ws_bytes = (size_t)batch * max_frames * R * 16 * mask_words * sizeof(unsigned long long);
         return true;
     }
     const size_t fixed = 2 * (size_t)(nw * 64 + 2) * sizeof(double) + 2 * (size_t)((max_labels + 3) & ~3) * sizeof(int32_t) +
-                         (spans ? (size_t)nw * 64 * sizeof(int32_t) : 0);
+                         (mask_words == 3 ? (size_t)nw * 64 * sizeof(int32_t) : 0);
     const size_t fixed_al = (fixed + 15) & ~(size_t)15;
-    const size_t bt_bytes = (size_t)max_frames * nw * (spans ? 3 : 2) * sizeof(unsigned long long);
+    const size_t bt_bytes = (size_t)max_frames * nw * mask_words * sizeof(unsigned long long);
     pl->nw = nw;
     pl->bt_in_lds = fixed_al + bt_bytes <= kLdsBudget;
     pl->lds_bytes = pl->bt_in_lds ? fixed_al + bt_bytes : fixed_al;
@@ -632,97 +566,106 @@ int launch_lanes(const char *timer, const VitParams &p, const VitPlan &pl, int b
     return LA_EUNSUPPORTED;
 }
 
-int query_workspace(Face face, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    const char *who = face_names(Sweep::Dp, face).query;
-    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", who);
+// the strip forms, R states per thread
+template <bool SPANS, bool WIN>
+int launch_strip(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
+    switch (pl.strip) {
+        case 2: return launch<viterbi_strip_kernel<2, SPANS, WIN>>(timer, 1024, p, pl, batch, stream);
+        case 4: return launch<viterbi_strip_kernel<4, SPANS, WIN>>(timer, 1024, p, pl, batch, stream);
+        case 8: return launch<viterbi_strip_kernel<8, SPANS, WIN>>(timer, 1024, p, pl, batch, stream);
+    }
+    return LA_EUNSUPPORTED;
+}
+
+template <bool SPANS, bool WIN>
+int launch_face(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
+    return pl.strip ? launch_strip<SPANS, WIN>(timer, p, pl, batch, stream) : launch_lanes<SPANS, false, WIN>(timer, p, pl, batch, stream);
+}
+
+// What the four batch entries (and their workspace queries) differ in.  la_viterbi_lattice_batch takes its face from the pointers that
+// are present and answers every argument error under its own name; its workspace is the span planner's (three mask words) whatever
+// the face.  Up to 511 labels, and for the plain lattice at any size, its call then IS the matching entry's: that entry's plan (whose
+// need is never larger: fewer mask words) and timer; above that the strip kernel's span / window faces under its own timer.
+struct Entry {
+    FaceNames names;
+    int mask_words, label_limit;
+    bool limit_first;                      // the label limit is reported before the stride check (la_viterbi_batch: after it)
+    const char *over_batch, *over_query;   // the label-limit message of the batch call and of the workspace query
+};
+enum EntryId { kPlain, kSpans, kWindows, kLattice };   // the first three are (int)Face of the entry's fixed face; kLattice: decided per call
+static_assert(kPlain == (int)Face::Plain && kSpans == (int)Face::Spans && kWindows == (int)Face::Windows, "kEntries rows follow Face");
+const Entry kEntries[4] = {
+    {face_names(Sweep::Dp, Face::Plain), 2, 4095, false, "viterbi: max_labels %d exceeds 4095",
+     "viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)"},
+    {face_names(Sweep::Dp, Face::Spans), 3, 511, true, "viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)",
+     "viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)"},
+    {face_names(Sweep::Dp, Face::Windows), 3, 511, true, "viterbi_windows: max_labels %d exceeds 511 (one lane per lattice state)",
+     "viterbi_windows: max_labels %d exceeds 511 (one lane per lattice state)"},
+    {{"viterbi_lattice_batch", "viterbi_lattice", "viterbi_lattice"}, 3, 4095, true,
+     "viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)",
+     "viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)"}};
+
+int query_workspace(EntryId id, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    const Entry &e = kEntries[id];
+    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", e.names.query);
     VitPlan pl;
-    if (!plan_viterbi(batch, max_frames, max_labels, face != Face::Plain, &pl)) {
-        if (face != Face::Plain) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", who, max_labels);
-        else la::set_error("viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
+    if (!plan_viterbi(batch, max_frames, max_labels, e.mask_words, e.label_limit, &pl)) {
+        la::set_error(e.over_query, max_labels);
         return LA_EUNSUPPORTED;
     }
     *bytes = pl.ws_bytes;
     return LA_OK;
 }
 
-// the three la_viterbi*_batch entry points: p holds the caller's arguments, the workspace fields are set here.  Spans and Windows share
-// the planner (three masks, one lane per state)
-int run_batch(Face face, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    const FaceNames &names = face_names(Sweep::Dp, face);
-    const char *who = names.entry;
-    const bool spans = face != Face::Plain;
+// the caller's arguments of a batch entry; null / zero stands in for what the entry does not have
+VitParams batch_params(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels, int32_t labels_stride,
+                       const int32_t *n_labels, const int32_t *n_frames, int32_t max_frames, int32_t max_labels, int32_t *onset,
+                       int32_t *offset, int32_t out_stride, double *final_score, int32_t *status, const int32_t *skip_from,
+                       int32_t skip_stride, double skip_penalty, const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride) {
+    VitParams p{};
+    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
+    p.set_spans(skip_from, skip_stride, skip_penalty);
+    p.set_windows(win_lo, win_hi, win_stride);
+    p.set_outputs(onset, offset, out_stride, final_score, status);
+    return p;
+}
+
+// the four la_viterbi*_batch entry points: p holds the caller's arguments, the workspace fields are set here
+int run_batch(EntryId id, VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    const Entry &e = kEntries[id];
+    const char *who = e.names.entry;
     if (batch == 0) return LA_OK;
+    Face face = id == kLattice ? Face::Plain : (Face)id;
+    if (id == kLattice) {
+        LA_CHECK_ARG((p.win_lo == nullptr) == (p.win_hi == nullptr), "%s: win_lo and win_hi go together (both null: no windows)", who);
+        face = p.win_lo ? Face::Windows : p.skip_from ? Face::Spans : Face::Plain;
+    }
     LA_CHECK_ARG(p.inputs_present(face) && p.onset && p.offset && p.final_score && p.status, "%s: null pointer", who);
     LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
-    LA_CHECK_ARG(p.penalty_ok(face), "%s: skip_penalty must be >= 0 (and not NaN)", who);
-    const bool strides_ok = p.strides_ok(face, p.out_stride, false);
+    // (la_viterbi_batch has no penalty: 0.  The lattice entry checks the one it was given whatever the face)
+    LA_CHECK_ARG(p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
     VitPlan pl;
-    const bool planned = plan_viterbi(batch, p.max_frames, p.max_labels, spans, &pl);
-    // the label limit is reported after the strides by la_viterbi_batch and before them by la_viterbi_spans_batch
-    LA_CHECK_ARG(strides_ok || (spans && !planned), "%s: strides smaller than max_labels", who);
+    const bool planned = plan_viterbi(batch, p.max_frames, p.max_labels, e.mask_words, e.label_limit, &pl);
+    LA_CHECK_ARG(p.strides_ok(face, p.out_stride, false) || (e.limit_first && !planned), "%s: strides smaller than max_labels", who);
     if (!planned) {
-        if (spans) la::set_error("%s: max_labels %d exceeds 511 (one lane per lattice state)", names.query, p.max_labels);
-        else la::set_error("viterbi: max_labels %d exceeds 4095", p.max_labels);
+        la::set_error(e.over_batch, p.max_labels);
         return LA_EUNSUPPORTED;
     }
     LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes), "%s: workspace too small (%zu < %zu)", who,
                  workspace_bytes, pl.ws_bytes);
     LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+    const char *timer = e.names.timer;
+    if (id == kLattice && (face == Face::Plain || !pl.strip)) {
+        const Entry &own = kEntries[(int)face];
+        plan_viterbi(batch, p.max_frames, p.max_labels, own.mask_words, own.label_limit, &pl);
+        timer = own.names.timer;
+    }
     p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
     p.bt_in_lds = pl.bt_in_lds ? 1 : 0;
-    if (face == Face::Windows) return launch_lanes<true, false, true>(names.timer, p, pl, batch, stream);
-    if (face == Face::Spans) return launch_lanes<true, false>(names.timer, p, pl, batch, stream);
-    switch (pl.strip) {
-        case 0: return launch_lanes<false, false>(names.timer, p, pl, batch, stream);
-        case 2: return launch<viterbi_strip_kernel<2>>(names.timer, 1024, p, pl, batch, stream);
-        case 4: return launch<viterbi_strip_kernel<4>>(names.timer, 1024, p, pl, batch, stream);
-        case 8: return launch<viterbi_strip_kernel<8>>(names.timer, 1024, p, pl, batch, stream);
-    }
-    return LA_EUNSUPPORTED;
-}
-
-// la_viterbi_lattice_batch: the face follows from the pointers that are present.  Every argument error is answered here, under this
-// entry's name; up to 511 labels (and for the plain lattice at any size) the call then IS the matching entry's, above that the strip
-// kernel's span / window faces.  One planner for the workspace whatever the face: the span planner's, three mask words.
-constexpr const char *kLatticeWho = "viterbi_lattice_batch";
-
-bool plan_lattice(int batch, int max_frames, int max_labels, VitPlan *pl) {
-    if (plan_viterbi(batch, max_frames, max_labels, true, pl, true)) return true;
-    la::set_error("viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
-    return false;
-}
-
-int run_lattice_batch(VitParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    const char *who = kLatticeWho;
-    if (batch == 0) return LA_OK;
-    LA_CHECK_ARG((p.win_lo == nullptr) == (p.win_hi == nullptr), "%s: win_lo and win_hi go together (both null: no windows)", who);
-    const Face face = p.win_lo ? Face::Windows : p.skip_from ? Face::Spans : Face::Plain;
-    LA_CHECK_ARG(p.inputs_present(face) && p.onset && p.offset && p.final_score && p.status, "%s: null pointer", who);
-    LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
-    LA_CHECK_ARG(p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
-    VitPlan pl;
-    if (!plan_lattice(batch, p.max_frames, p.max_labels, &pl)) return LA_EUNSUPPORTED;
-    LA_CHECK_ARG(p.strides_ok(face, p.out_stride, false), "%s: strides smaller than max_labels", who);
-    LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes), "%s: workspace too small (%zu < %zu)", who,
-                 workspace_bytes, pl.ws_bytes);
-    LA_CHECK_ARG(pl.ws_bytes == 0 || (uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
-    // (the matching entry's own need never exceeds the span planner's: fewer mask words, no J array)
-    if (!pl.strip || face == Face::Plain) return run_batch(face, p, batch, workspace, workspace_bytes, stream);
-    p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
-    p.bt_in_lds = 0;
-    const char *timer = "viterbi_lattice";
-    if (face == Face::Windows) {
-        switch (pl.strip) {
-            case 2: return launch<viterbi_strip_kernel<2, true, true>>(timer, 1024, p, pl, batch, stream);
-            case 4: return launch<viterbi_strip_kernel<4, true, true>>(timer, 1024, p, pl, batch, stream);
-            case 8: return launch<viterbi_strip_kernel<8, true, true>>(timer, 1024, p, pl, batch, stream);
-        }
-    } else {
-        switch (pl.strip) {
-            case 2: return launch<viterbi_strip_kernel<2, true>>(timer, 1024, p, pl, batch, stream);
-            case 4: return launch<viterbi_strip_kernel<4, true>>(timer, 1024, p, pl, batch, stream);
-            case 8: return launch<viterbi_strip_kernel<8, true>>(timer, 1024, p, pl, batch, stream);
-        }
+    switch (face) {
+        case Face::Plain: return launch_face<false, false>(timer, p, pl, batch, stream);
+        case Face::Spans: return launch_face<true, false>(timer, p, pl, batch, stream);
+        case Face::Windows: return launch_face<true, true>(timer, p, pl, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
@@ -730,15 +673,19 @@ int run_lattice_batch(VitParams p, int32_t batch, void *workspace, size_t worksp
 }  // namespace
 
 extern "C" int la_viterbi_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace(Face::Plain, batch, max_frames, max_labels, bytes);
+    return query_workspace(kPlain, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_spans_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace(Face::Spans, batch, max_frames, max_labels, bytes);
+    return query_workspace(kSpans, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_windows_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    return query_workspace(Face::Windows, batch, max_frames, max_labels, bytes);
+    return query_workspace(kWindows, batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_viterbi_lattice_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace(kLattice, batch, max_frames, max_labels, bytes);
 }
 
 extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -746,10 +693,10 @@ extern "C" int la_viterbi_batch(const float *em, int64_t em_batch_stride, int64_
                                 const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
                                 int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{};
-    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
-    p.set_outputs(onset, offset, out_stride, final_score, status);
-    return run_batch(Face::Plain, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    return run_batch(kPlain,
+                     batch_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset,
+                                  offset, out_stride, final_score, status, nullptr, 0, 0.0, nullptr, nullptr, 0),
+                     batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -758,11 +705,10 @@ extern "C" int la_viterbi_spans_batch(const float *em, int64_t em_batch_stride, 
                                       int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
                                       int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
                                       void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{};
-    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
-    p.set_spans(skip_from, skip_stride, skip_penalty);
-    p.set_outputs(onset, offset, out_stride, final_score, status);
-    return run_batch(Face::Spans, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    return run_batch(kSpans,
+                     batch_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset,
+                                  offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty, nullptr, nullptr, 0),
+                     batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -772,20 +718,10 @@ extern "C" int la_viterbi_windows_batch(const float *em, int64_t em_batch_stride
                                         int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
                                         const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
                                         void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{};
-    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
-    p.set_spans(skip_from, skip_stride, skip_penalty);
-    p.set_windows(win_lo, win_hi, win_stride);
-    p.set_outputs(onset, offset, out_stride, final_score, status);
-    return run_batch(Face::Windows, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
-}
-
-extern "C" int la_viterbi_lattice_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
-    LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "viterbi_lattice_workspace_bytes: bad arguments");
-    VitPlan pl;
-    if (!plan_lattice(batch, max_frames, max_labels, &pl)) return LA_EUNSUPPORTED;
-    *bytes = pl.ws_bytes;
-    return LA_OK;
+    return run_batch(kWindows,
+                     batch_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset,
+                                  offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride),
+                     batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
@@ -795,12 +731,10 @@ extern "C" int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride
                                         int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
                                         const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
                                         void *workspace, size_t workspace_bytes, void *stream_) {
-    VitParams p{};
-    p.set_inputs(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels);
-    p.set_spans(skip_from, skip_stride, skip_penalty);
-    p.set_windows(win_lo, win_hi, win_stride);
-    p.set_outputs(onset, offset, out_stride, final_score, status);
-    return run_lattice_batch(p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    return run_batch(kLattice,
+                     batch_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset,
+                                  offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride),
+                     batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // run_viterbi_core(dp, bt, lp, ls, label) of the reference (utils/alignment.py:73-119) for ONE utterance: same
@@ -812,7 +746,7 @@ extern "C" int la_viterbi_core(const float *em, int64_t em_row_stride, const int
     LA_CHECK_ARG(em && labels && n_labels && n_frames && dp && bt && scratch_i32 && scratch_f64, "viterbi_core: null pointer");
     LA_CHECK_ARG(n_labels_host > 0 && n_frames_host > 0 && em_row_stride >= n_labels_host + 1, "viterbi_core: bad sizes");
     VitPlan pl;
-    if (!plan_viterbi(1, n_frames_host, n_labels_host, false, &pl) || pl.strip) {
+    if (!plan_viterbi(1, n_frames_host, n_labels_host, 2, 511, &pl)) {
         la::set_error("viterbi_core: more than 511 labels (the dp / bt dump face is one lane per state)");
         return LA_EUNSUPPORTED;
     }

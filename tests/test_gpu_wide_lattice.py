@@ -147,6 +147,25 @@ def test_few_frames_around_the_prefetch_depth(T):
     _assert_equals_reference(_launch([em], [lab], [skip], 0.5), 0, ref, L, ("no windows", T))
 
 
+@pytest.mark.parametrize("L", [512, 1024, 2048])
+@pytest.mark.parametrize("T", [1, 2, 3, 4, 5, 6, 9])
+def test_plain_strip_loop_at_few_frames(T, L):
+    """The span-free frame loop of the strip kernel (the plain DP's loop for every song over 511 labels) at the first label counts of 2, 4
+    and 8 states per thread, T around the prefetch depth of 4 and two blocks plus one, through la_viterbi_batch and through
+    la_viterbi_lattice_batch with nothing given.  L > T: no such lattice has a path, so this pins the tie rules on rows of equal kNeg cells
+    and the tail of a partial prefetch block."""
+    from lyricalignment_amd import ops
+    lab = [int(v) for v in np.random.RandomState(11 * T + L).randint(1, 4, size=L)]     # three classes: equal neighbours everywhere
+    em = _emissions(60 + T, T, lab, 0.0)
+    ref = wr.viterbi_windows(em, lab, *wr.open_windows(L, T), None, 0.0, rows=True)
+    assert ref[3] == wr.LA_EINFEASIBLE
+    _assert_equals_reference(_launch([em], [lab], None, 0.0), 0, ref, L, ("lattice, nothing given", T, L))
+    got = ops.viterbi_batch(torch.from_numpy(em)[None].cuda(), torch.tensor([lab], dtype=torch.int32).cuda(),
+                            torch.tensor([L], dtype=torch.int32).cuda(), torch.tensor([T], dtype=torch.int32).cuda())
+    torch.cuda.synchronize()
+    _assert_equals_reference(tuple(g.cpu().numpy() for g in got), 0, ref, L, ("viterbi_batch", T, L))
+
+
 # ------------------------------------------------------------------------------------------------ 3. nothing given and all open
 def _dev_inputs(ems, lab):
     B, T, L = len(ems), ems[0].shape[0], len(lab)

@@ -11,9 +11,9 @@ Legs, alternated call by call (caller-owned buffers, device events around one ca
   * la_viterbi_lattice_batch with every window [0, T) and a null skip_from: what the window face costs when nothing is known;
   * la_viterbi_lattice_batch with one onset anchor per line (the line's first character within 1 s of where the unanchored DP put it);
   * la_viterbi_lattice_batch with anchors (around the sheet-only DP's result) and every fourth line optional.
-With --parent-lib the parent commit's la_viterbi_batch runs in the same alternation, and at 32 clips x 1500 frames x 26 labels the parent's
-la_viterbi_batch, span-free la_viterbi_spans_batch and all-open la_viterbi_windows_batch run beside this build's: the existing entries'
-medians are reported against the parent's min .. max.
+With --parent-lib the parent commit's five legs run in the same alternation (outputs checked bit for bit against this build's), and at
+32 clips x 1500 frames x 26 labels the parent's la_viterbi_batch, span-free la_viterbi_spans_batch and all-open la_viterbi_windows_batch
+run beside this build's: every leg's median is reported against the parent's min .. max of the same leg.
 Every number is the median of `runs` calls after a warm-up; min .. max is printed next to it.  The nothing-given and all-open outputs are
 checked bit for bit against la_viterbi_batch's, and every leg's status is LA_OK, before anything is timed.
 """
@@ -26,6 +26,8 @@ import statistics
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+SONG_LEGS = ("la_viterbi_batch", "la_viterbi_lattice_batch, nothing given", "la_viterbi_lattice_batch, all windows open",
+             "la_viterbi_lattice_batch, one onset anchor per line, +-1 s", "la_viterbi_lattice_batch, anchors + every fourth line optional")
 SONGS = [("1 song x 12000 frames x 800 labels (2 states per thread)", 12000, 800),
          ("1 song x 12000 frames x 2500 labels (8 states per thread)", 12000, 2500)]
 LINE = 10
@@ -67,7 +69,8 @@ def main():
     if args.parent_lib:
         parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
         for name in ("la_viterbi_workspace_bytes", "la_viterbi_batch", "la_viterbi_spans_workspace_bytes", "la_viterbi_spans_batch",
-                     "la_viterbi_windows_workspace_bytes", "la_viterbi_windows_batch"):
+                     "la_viterbi_windows_workspace_bytes", "la_viterbi_windows_batch", "la_viterbi_lattice_workspace_bytes",
+                     "la_viterbi_lattice_batch"):
             fn = getattr(parent, name)
             fn.restype, fn.argtypes = SYMBOLS[name]
 
@@ -115,7 +118,7 @@ def main():
                 more += (ptr(windows[0]), ptr(windows[1]), 2 * L + 1) if windows is not None else (0, 0, 0)
             entry = getattr(L_, f"la_{stem}_batch")
 
-            def fn():
+            def fn(_held=(skip, windows)):      # `more` holds bare addresses: the leg keeps their tensors alive
                 assert entry(*self._head(out), *more, ptr(ws), need, stream_ptr()) == 0, _lib.last_error()
             return fn, out
 
@@ -149,7 +152,12 @@ def main():
         say(f"{name}: {m:.3f} against the parent's {pm:.3f} ({plo:.3f} .. {phi:.3f}): {where} its min .. max "
             f"({100 * (m / pm - 1):+.1f} % of its median)")
 
-    same = lambda a, b: all(torch.equal(x, y) for x, y in zip(a, b))     # noqa: E731
+    def same(a, b):
+        diff = [f"{name}: {int((x != y).sum())} of {x.numel()}" for name, x, y in zip(("onset", "offset", "score", "status"), a, b) if not torch.equal(x, y)]
+        if diff:
+            print("outputs differ -- " + "; ".join(diff), flush=True)
+        return not diff
+
     say(f"# whole-song alignment lattices on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up of 3, "
         f"legs alternated call by call, device events around one call, ms")
     for title, T, L in SONGS:
@@ -176,17 +184,21 @@ def main():
         torch.cuda.synchronize()
         assert int(plain[1][3][0]) == 0 and int(sheet_only[1][3][0]) == 0
         win_a, win_s = anchored(plain[1][0][0].cpu()), anchored(sheet_only[1][0][0].cpu())
-        legs = [("la_viterbi_batch", plain), ("la_viterbi_lattice_batch, nothing given", sh.leg(lib(), "viterbi_lattice")),
-                ("la_viterbi_lattice_batch, all windows open", sh.leg(lib(), "viterbi_lattice", None, sh.open_windows())),
-                ("la_viterbi_lattice_batch, one onset anchor per line, +-1 s", sh.leg(lib(), "viterbi_lattice", None, win_a)),
-                ("la_viterbi_lattice_batch, anchors + every fourth line optional", sh.leg(lib(), "viterbi_lattice", skip, win_s))]
+
+        def song_legs(L_, first):
+            return [first, sh.leg(L_, "viterbi_lattice"), sh.leg(L_, "viterbi_lattice", None, sh.open_windows()),
+                    sh.leg(L_, "viterbi_lattice", None, win_a), sh.leg(L_, "viterbi_lattice", skip, win_s)]
+
+        legs = list(zip(SONG_LEGS, song_legs(lib(), plain)))
         if parent is not None:
-            legs.append(("parent commit: la_viterbi_batch", sh.leg(parent, "viterbi")))
+            legs += [("parent commit: " + name, leg) for name, leg in zip(SONG_LEGS, song_legs(parent, sh.leg(parent, "viterbi")))]
         for _, (fn, _) in legs:
             fn()
         torch.cuda.synchronize()
-        for i in (1, 2) + ((5,) if parent is not None else ()):
+        for i in (1, 2) + ((5, 6, 7) if parent is not None else ()):
             assert same(legs[0][1][1], legs[i][1][1]), f"{legs[i][0]}: outputs differ from la_viterbi_batch"
+        for i in (3, 4) if parent is not None else ():
+            assert same(legs[i][1][1], legs[5 + i][1][1]), f"{legs[i][0]}: outputs differ from the parent commit's"
         kept = same(legs[0][1][1], legs[3][1][1]), same(sheet_only[1], legs[4][1][1])      # the anchors lie around each DP's own result
         stats = measure(title, legs)
         left = int((legs[4][1][1][0][0] < 0).sum())
@@ -195,7 +207,8 @@ def main():
             f"every status LA_OK; the sheet leaves {left} of {L} labels out; anchored result equals the unanchored one: {kept[0]}, with the "
             f"sheet: {kept[1]}")
         if parent is not None:
-            against_parent(stats, "la_viterbi_batch")
+            for name in SONG_LEGS:
+                against_parent(stats, name)
         del sh, legs, plain, sheet_only
         torch.cuda.empty_cache()
 
