@@ -232,17 +232,20 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float *s, int64_t ld,
     for (int c = lane; c < cols; c += 64) r[c] *= inv;
     for (int c = cols + lane; c < ld; c += 64) r[c] = 0.f;
 }
-// dS = P * (dP - sum_c dP P), written over dP
+// dS = P * (dP - sum_c dP P), written over dP.  The row's dot product and the difference are taken in double: on a confident row (one
+// p close to 1) dP - dot cancels to a small number at that column, and a float32 dot would leave half an ulp OF THE DOT as the absolute
+// error of that entry.
 __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float *p, float *dp, int64_t ld, int64_t rows, int cols) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     const float *pr = p + row * ld;
     float *dr = dp + row * ld;
-    float dot = 0.f;
-    for (int c = lane; c < cols; c += 64) dot += pr[c] * dr[c];
-    dot = wsum(dot);
-    for (int c = lane; c < cols; c += 64) dr[c] = pr[c] * (dr[c] - dot);
+    double dot = 0.0;
+    for (int c = lane; c < cols; c += 64) dot += (double)pr[c] * (double)dr[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+    for (int c = lane; c < cols; c += 64) dr[c] = pr[c] * (float)((double)dr[c] - dot);
     for (int c = cols + lane; c < ld; c += 64) dr[c] = 0.f;
 }
 
@@ -286,9 +289,10 @@ __global__ void embed_bwd_kernel(const float *dx, const int64_t *tokens, int B, 
     }
 }
 
-// F.cross_entropy(logits [R][V], target [R], ignore_index = -100, reduction = 'mean') -- three small passes
-__global__ __launch_bounds__(256) void ce_row_kernel(const float *logits, int64_t ld, int V, const int64_t *target, float *row_lse,
-                                                      float *row_loss) {
+// F.cross_entropy(logits [R][V], target [R], ignore_index = -100, reduction = 'mean') -- three small passes.
+// A row keeps its maximum m and log sum_c exp(l[c] - m) apart, and every later use takes (l - m) - logsum like torch's log_softmax:
+// m + logsum rounded to one float costs an ulp OF m, which for logits with a large common offset (1e4: 5e-4) is the whole loss.
+__global__ __launch_bounds__(256) void ce_row_kernel(const float *logits, int64_t ld, int V, float *row_max, float *row_logsum) {
     __shared__ float red[4];
     const int r = blockIdx.x;
     const float *l = logits + (int64_t)r * ld;
@@ -305,18 +309,17 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float *logits, int64_
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float lse = m + logf(red[0] + red[1] + red[2] + red[3]);
-        row_lse[r] = lse;
-        const int64_t t = target[r];
-        row_loss[r] = (t >= 0 && t < V) ? lse - l[t] : 0.f;
+        row_max[r] = m;
+        row_logsum[r] = logf(red[0] + red[1] + red[2] + red[3]);
     }
 }
-__global__ __launch_bounds__(64) void ce_reduce_kernel(const float *row_loss, const int64_t *target, int R, int V, float *out2) {
+__global__ __launch_bounds__(64) void ce_reduce_kernel(const float *logits, int64_t ld, const float *row_max, const float *row_logsum,
+                                                       const int64_t *target, int R, int V, float *out2) {
     double s = 0.0;
     int cnt = 0;
     for (int r = threadIdx.x; r < R; r += 64) {
         const int64_t t = target[r];
-        if (t >= 0 && t < V) { s += (double)row_loss[r]; ++cnt; }
+        if (t >= 0 && t < V) { s += (double)(row_logsum[r] - (logits[(int64_t)r * ld + t] - row_max[r])); ++cnt; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); cnt += __shfl_xor(cnt, o); }
@@ -325,15 +328,15 @@ __global__ __launch_bounds__(64) void ce_reduce_kernel(const float *row_loss, co
         out2[1] = cnt > 0 ? 1.0f / (float)cnt : 0.f;
     }
 }
-__global__ void ce_grad_kernel(const float *logits, int64_t ld, int V, const int64_t *target, const float *row_lse, const float *out2,
-                               float scale, float *dlogits, int64_t ld_d, int64_t n) {
+__global__ void ce_grad_kernel(const float *logits, int64_t ld, int V, const int64_t *target, const float *row_max, const float *row_logsum,
+                               const float *out2, float scale, float *dlogits, int64_t ld_d, int64_t n) {
     const float k = out2[1] * scale;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % V);
         const int64_t r = i / V;
         const int64_t t = target[r];
         float g = 0.f;
-        if (t >= 0 && t < V) g = (expf(logits[r * ld + c] - row_lse[r]) - (c == t ? 1.f : 0.f)) * k;
+        if (t >= 0 && t < V) g = (expf((logits[r * ld + c] - row_max[r]) - row_logsum[r]) - (c == t ? 1.f : 0.f)) * k;
         dlogits[r * ld_d + c] = g;
     }
 }
@@ -510,12 +513,13 @@ extern "C" int la_cross_entropy_f32(const float *logits, int64_t ld, int32_t row
     LA_CHECK_ARG(logits && target && loss2 && row_ws && rows > 0 && vocab > 0 && ld >= vocab && (!dlogits || ld_d >= vocab),
                  "cross_entropy: bad arguments");
     hipStream_t st = (hipStream_t)stream_;
-    float *row_lse = row_ws, *row_loss = row_ws + rows;
-    hipLaunchKernelGGL(ce_row_kernel, dim3(rows), dim3(256), 0, st, logits, ld, vocab, target, row_lse, row_loss);
-    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(64), 0, st, row_loss, target, rows, vocab, loss2);
+    float *row_max = row_ws, *row_logsum = row_ws + rows;
+    hipLaunchKernelGGL(ce_row_kernel, dim3(rows), dim3(256), 0, st, logits, ld, vocab, row_max, row_logsum);
+    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(64), 0, st, logits, ld, row_max, row_logsum, target, rows, vocab, loss2);
     if (dlogits) {
         const int64_t n = (int64_t)rows * vocab;
-        hipLaunchKernelGGL(ce_grad_kernel, dim3(ew_grid(n)), dim3(256), 0, st, logits, ld, vocab, target, row_lse, loss2, scale, dlogits, ld_d, n);
+        hipLaunchKernelGGL(ce_grad_kernel, dim3(ew_grid(n)), dim3(256), 0, st, logits, ld, vocab, target, row_max, row_logsum, loss2, scale, dlogits,
+                           ld_d, n);
     }
     LA_LAUNCH_CHECK();
     return LA_OK;
