@@ -402,6 +402,42 @@ int la_alignment_posteriors_windows(const float *em, int64_t em_batch_stride, in
                                     float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
                                     void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Whole-song confidence: the sum-product sweep on any face of the lattice at any size up to 4095 labels -- the posteriors'
+ * counterpart of la_viterbi_lattice_batch.  The arguments are la_alignment_posteriors_windows' in the same order, with skip_from
+ * and the pair win_lo / win_hi each optional (NULL): both NULL sweeps the plain lattice, skip_from alone the optional-span lattice,
+ * windows (with or without skip_from) the windowed one.  win_lo without win_hi (or the reverse) is LA_EINVAL.  present_prob and
+ * span_skip_prob are always written (skip_stride is the row pitch of span_skip_prob and must be >= max_labels + 1 whatever the
+ * face): on a lattice without a span present_prob is 1 on the labels n < L_b of an LA_OK clip and 0 elsewhere, span_skip_prob is 0.
+ *   max_labels <= 511: the call IS the matching entry above (la_alignment_posteriors_windows / _spans; with nothing given
+ *     la_alignment_posteriors for the five common outputs), bit for bit, and the workspace query returns that entry's answer.
+ *   512 <= max_labels <= 4095: one workgroup of 1024 threads per clip, R = 2 / 4 / 8 consecutive states per thread for up to
+ *     2048 / 4096 / 8192 states.  Every cell is computed by the same expression sequence as in the entries above, so the outputs
+ *     of a clip do not depend on max_labels, on its batch mates or on which of the two forms ran it, and the bound 8 T 2^-23
+ *     carries over.  The workspace is batch * max_frames * 1024 R * 8 bytes of alpha rows plus batch * 1024 R * 28 bytes (the
+ *     sparse per-label sums and the jump arcs by source): one clip of 12000 frames takes 197 MB at 800 labels and 786 MB at
+ *     2500 .. 4095.  It must be 16-byte aligned.
+ *   max_labels > 4095: LA_EUNSUPPORTED.
+ * onset / offset are la_viterbi_lattice_batch's outputs for the same lattice.  Statuses, zeroing, gamma_out and its strides as in
+ * la_alignment_posteriors_windows.  Every argument error is answered on the host under this entry's name before anything is
+ * enqueued; never synchronises, allocates or frees.
+ */
+int la_alignment_posteriors_lattice_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors_lattice(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                    const int32_t *labels, int32_t labels_stride,
+                                    const int32_t *n_labels, const int32_t *n_frames,
+                                    int32_t batch, int32_t max_frames, int32_t max_labels,
+                                    const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                                    int32_t boundary_window,
+                                    const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                    const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                    float *occupancy, float *onset_prob, float *offset_prob, float *present_prob,
+                                    float *span_skip_prob,
+                                    double *log_z, int32_t *status,
+                                    float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* emission prep from materialised logits                                     */
 /*   (replaces utils/alignment.py:123-134 [CTC] and :14-20 [plain])           */

@@ -50,14 +50,6 @@ namespace {
 
 using namespace la::lattice;
 
-// la_lattice.h's all-float64 log_add with its trivial cases taken first -- the same values to the bit (log1p(exp(-inf)) = 0) -- so that a
-// wave in which no lane has two finite operands (no jump arc at this call site) skips the float64 exp / log1p
-__device__ __forceinline__ double log_add_jump(double a, double b) {
-    if (b == -INFINITY) return a;
-    if (a == -INFINITY) return b;
-    return log_add(a, b);
-}
-
 struct PostParams : LatticeIn {
     const int32_t *onset, *offset;
     int32_t out_stride;

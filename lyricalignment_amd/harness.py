@@ -166,6 +166,57 @@ def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, 
     return out
 
 
+def _sheet_inputs(who: str, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize):
+    """What the sheet functions hand to AlignModel.align: -> (token ids per line, optional_spans of the one clip, class-id labels [1, L])."""
+    from .utils.alignment import spans_from_lines
+    ids = [list(tokenize(line)) for line in lines]
+    for line, tok in zip(lines, ids):
+        if len(tok) != len(line):
+            raise ValueError(f"{who}: {len(tok)} tokens for the {len(line)} characters of {line!r}")
+    skip_from = spans_from_lines([len(t) for t in ids], optional)
+    spans = [(a, n) for n, a in enumerate(skip_from) if a >= 0]
+    labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
+    return ids, spans, labels
+
+
+def _line_anchors(starts: Sequence[float], ids, tolerance_s: float) -> list:
+    """One onset anchor per line: (index of the line's first character, the line's start time, tolerance_s)."""
+    anchors, pos = [], 0
+    for start, tok in zip(starts, ids):
+        anchors.append((pos, start, float(tolerance_s)))
+        pos += len(tok)
+    return anchors
+
+
+def _sheet_lines_out(res, lines: Sequence[str], per_line=()):
+    """One clip's per-character result -> one entry per line (None for a line left out: a span is taken or left as a whole, its characters
+    are None together), and for every f of per_line the list of f(position of the line's first character, its result)."""
+    out: List[Optional[list]] = []
+    extra = [[] for _ in per_line]
+    pos = 0
+    for line in lines:
+        part = res[pos: pos + len(line)]
+        for values, f in zip(extra, per_line):
+            values.append(f(pos, part[0]))
+        pos += len(line)
+        out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
+    return (out, *extra)
+
+
+def _timed_lines(who: str, lrc) -> List[tuple]:
+    pairs = parse_lrc(lrc) if isinstance(lrc, str) else [(float(s), str(line)) for s, line in lrc]
+    if not pairs:
+        raise ValueError(f"{who}: no timed line in the sheet")
+    return pairs
+
+
+def _sheet_confidence(res, scores, lines: Sequence[str]):
+    """-> (lines_out, conf) of align_record_lrc(with_confidence=True) from one clip's seconds and its anchored / sheet score dict."""
+    out, sung, line_onset = _sheet_lines_out(res, lines, (lambda pos, first: float(scores["sung_prob"][pos]),
+                                                          lambda pos, first: None if first is None else float(scores["onset_prob"][pos])))
+    return out, {"sung": sung, "line_onset_prob": line_onset, "window_log_prob": float(scores["window_log_prob"])}
+
+
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
@@ -175,34 +226,17 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     with_confidence: -> (lines_out, sung), sung[i] = the probability under the model that line i was sung (a Python float: present_prob
     of the line's first character, AlignModel.align(return_span_confidence=True)); 1 for a mandatory line, and 1 - span_skip_prob of an
     optional line's span.
-    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError)."""
-    from .utils.alignment import spans_from_lines
+    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song)."""
     lines = list(lines)
-    ids = [list(tokenize(line)) for line in lines]
-    for line, tok in zip(lines, ids):
-        if len(tok) != len(line):
-            raise ValueError(f"align_record_lines: {len(tok)} tokens for the {len(line)} characters of {line!r}")
-    skip_from = spans_from_lines([len(t) for t in ids], optional)
-    spans = [(a, n) for n, a in enumerate(skip_from) if a >= 0]
-    labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
+    ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
     with torch.no_grad():
         if with_confidence:
             res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                       return_span_confidence=True)
-            res, present = res[0], scores[0]["sung_prob"]
-        else:
-            res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)[0]
-    out: List[Optional[list]] = []
-    sung: List[float] = []
-    pos = 0
-    for line in lines:
-        part = res[pos: pos + len(line)]
-        if with_confidence:
-            sung.append(float(present[pos]))
-        pos += len(line)
-        # a span is taken or left as a whole: its characters are None together
-        out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
-    return (out, sung) if with_confidence else out
+            present = scores[0]["sung_prob"]
+            return _sheet_lines_out(res[0], lines, (lambda pos, first: float(present[pos]),))
+        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)[0]
+    return _sheet_lines_out(res, lines)[0]
 
 
 _LRC_TAG = re.compile(r"\[([^\[\]]*)\]")
@@ -245,46 +279,45 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
                                 the reported onset, None for a line that was left out],
             "window_log_prob": float <= 0, the log-probability the unanchored model gives to "the path respects every tag" -- near 0
                                when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}.
-    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError)."""
-    from .utils.alignment import spans_from_lines
-    pairs = parse_lrc(lrc) if isinstance(lrc, str) else [(float(s), str(line)) for s, line in lrc]
-    if not pairs:
-        raise ValueError("align_record_lrc: no timed line in the sheet")
+    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song)."""
+    pairs = _timed_lines("align_record_lrc", lrc)
     lines = [line for _, line in pairs]
     optional = [False] * len(lines) if optional is None else list(optional)
-    ids = [list(tokenize(line)) for line in lines]
-    for line, tok in zip(lines, ids):
-        if len(tok) != len(line):
-            raise ValueError(f"align_record_lrc: {len(tok)} tokens for the {len(line)} characters of {line!r}")
-    skip_from = spans_from_lines([len(t) for t in ids], optional)
-    spans = [(a, n) for n, a in enumerate(skip_from) if a >= 0]
-    anchors, pos = [], 0
-    for (start, _), tok in zip(pairs, ids):
-        anchors.append((pos, start, float(tolerance_s)))
-        pos += len(tok)
-    labels = lut(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long))
-    scores = None
+    ids, spans, labels = _sheet_inputs("align_record_lrc", lines, optional, lut, tokenize)
+    anchors = _line_anchors([start for start, _ in pairs], ids, tolerance_s)
     with torch.no_grad():
         if with_confidence:
             res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                       onset_anchors=[anchors], return_anchored_confidence=True)
-            res, scores = res[0], scores[0]
-        else:
-            res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty, onset_anchors=[anchors])[0]
-    out: List[Optional[list]] = []
-    sung: List[float] = []
-    line_onset: List[Optional[float]] = []
-    pos = 0
-    for line in lines:
-        part = res[pos: pos + len(line)]
-        if with_confidence:
-            sung.append(float(scores["sung_prob"][pos]))
-            line_onset.append(None if part[0] is None else float(scores["onset_prob"][pos]))
-        pos += len(line)
-        out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
-    if with_confidence:
-        return out, {"sung": sung, "line_onset_prob": line_onset, "window_log_prob": float(scores["window_log_prob"])}
-    return out
+            return _sheet_confidence(res[0], scores[0], lines)
+        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty, onset_anchors=[anchors])[0]
+    return _sheet_lines_out(res, lines)[0]
+
+
+def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
+               use_ctc_loss: bool = True, skip_penalty: float = 0.0):
+    """A whole song against its whole sheet, timing and confidences in one call (addition): up to 4095 characters.  `sheet` is LRC text
+    (parse_lrc), a list of (start_seconds, line) pairs -- every line's first character anchored at its start time with tolerance_s, as in
+    align_record_lrc -- or a list of plain lines (no times: no anchors, as in align_record_lines).  optional[i] marks lines that may be
+    absent from the audio (default: none).  -> (lines_out, conf) in align_record_lrc(with_confidence=True)'s form, from
+    AlignModel.align(return_sheet_confidence=True): lines_out has one entry per line (None for a line left out), conf = {"sung": [per line],
+    "line_onset_prob": [per line, None for a line left out], "window_log_prob": float <= 0 (0.0 for a sheet without times)}.  Up to 511
+    characters the numbers are align_record_lrc's exactly.  The posterior sweep keeps every alpha row on the device: frames * 1024 R * 8
+    bytes beyond 511 characters (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095): 197 MB for a four-minute song of 800 characters."""
+    if isinstance(sheet, str) or (len(sheet) > 0 and not isinstance(sheet[0], str)):
+        pairs = _timed_lines("align_song", sheet)
+        lines, starts = [line for _, line in pairs], [start for start, _ in pairs]
+    else:
+        lines, starts = [str(line) for line in sheet], None
+        if not lines:
+            raise ValueError("align_song: no line in the sheet")
+    optional = [False] * len(lines) if optional is None else list(optional)
+    ids, spans, labels = _sheet_inputs("align_song", lines, optional, lut, tokenize)
+    kw = {} if starts is None else {"onset_anchors": [_line_anchors(starts, ids, tolerance_s)]}
+    with torch.no_grad():
+        res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                  return_sheet_confidence=True, **kw)
+    return _sheet_confidence(res[0], scores[0], lines)
 
 
 def lrc_training_clips(audio, lrc, tokenize, max_seconds: float = 30.0, tolerance_s: float = 1.0, sample_rate: int = 16000) -> List[dict]:

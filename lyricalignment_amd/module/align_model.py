@@ -331,7 +331,7 @@ class AlignModel(torch.nn.Module):
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
               skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
-              return_anchored_confidence: bool = False):
+              return_anchored_confidence: bool = False, return_sheet_confidence: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -349,7 +349,7 @@ class AlignModel(torch.nn.Module):
         may be left out by the path; the head's emissions go through the DP on the lattice with optional spans (ops.viterbi_spans_batch,
         skip_penalty >= 0 per taken jump) and skipped characters come back as None (onset = offset = -1 with return_frames).  None or
         all-empty: the call as it was.  Not with return_confidence (ValueError; return_span_confidence is the keyword).  Up to 4095 labels
-        (beyond 511: ops.viterbi_lattice_batch); the confidence keywords at most 511 (NotImplementedError).
+        (beyond 511: ops.viterbi_lattice_batch); the confidence keywords at most 511 (NotImplementedError), return_sheet_confidence excepted.
         return_span_confidence (addition): -> (seconds, scores) on the lattice with optional spans (ops.alignment_posteriors_spans):
         return_confidence's dicts (skipped characters: None in seconds, their three scores 0) plus "sung_prob": [L], the probability that
         the character is on the path at all, and "span_skip_prob": the probability that the span was left out, one value per span of
@@ -362,7 +362,7 @@ class AlignModel(torch.nn.Module):
         with or without optional_spans.  None or all-empty: the call as it was.  A clip without a path inside its windows raises like a clip
         too short for its labels (status LA_EINFEASIBLE with return_frames).  Not with return_confidence / return_span_confidence
         (ValueError: return_anchored_confidence is the keyword).  Up to 4095 labels (beyond 511: ops.viterbi_lattice_batch);
-        return_anchored_confidence at most 511 (NotImplementedError).
+        return_anchored_confidence at most 511 (NotImplementedError; return_sheet_confidence takes up to 4095).
         return_anchored_confidence (addition): -> (seconds, scores) on the lattice with the frame windows of char_windows / onset_anchors
         (ops.alignment_posteriors_windows), with or without optional_spans, per_clip and the long form: return_span_confidence's dicts,
         every number a posterior GIVEN the windows, plus "window_log_prob" = log_z(windowed) - log_z(same lattice, no windows) <= 0, the
@@ -370,11 +370,19 @@ class AlignModel(torch.nn.Module):
         strongly negative: one of them fights it; the second log_z is one more launch of the existing sweep).  None or all-empty windows:
         return_span_confidence's dicts and window_log_prob 0.0.  With return_frames the windowed DP's four tensors, then (occupancy,
         onset_prob, offset_prob, log_z, present_prob, span_skip_prob, log_z_free).  A clip without a path inside its windows raises as
-        above.  Not together with return_confidence / return_span_confidence (ValueError)."""
+        above.  Not together with return_confidence / return_span_confidence (ValueError).
+        return_sheet_confidence (addition): whole songs -- return_anchored_confidence's dicts (and, with return_frames, its 11 tensors) for up
+        to 4095 labels, with or without optional_spans, onset_anchors / char_windows, per_clip and the long form
+        (ops.alignment_posteriors_lattice on the lattice the DP ran on); window_log_prob is 0.0 without windows.  Up to 511 labels the numbers
+        are return_anchored_confidence's exactly.  The sweep keeps every alpha row: T * 1024 R * 8 bytes per clip beyond 511 labels (R = 2 /
+        4 / 8 for up to 1023 / 2047 / 4095 labels).  Not together with any of the three older confidence keywords (ValueError)."""
         from ..utils.alignment import LatticeResult, _formatted, _labels_to_device, _skip_from_of_spans, _windows_of, run_lattice
         if return_anchored_confidence and (return_confidence or return_span_confidence):
             raise ValueError("align: return_anchored_confidence does not go with return_confidence / return_span_confidence (it returns "
                              "their numbers on the windowed lattice)")
+        if return_sheet_confidence and (return_confidence or return_span_confidence or return_anchored_confidence):
+            raise ValueError("align: return_sheet_confidence does not go with return_confidence / return_span_confidence / "
+                             "return_anchored_confidence (it returns their numbers at any size up to 4095 labels)")
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -396,15 +404,16 @@ class AlignModel(torch.nn.Module):
         if skip_from is not None and return_confidence:
             raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice by that "
                              "keyword: return_span_confidence=True gives them)")
-        confidence = ("anchored" if return_anchored_confidence else "span" if return_span_confidence else "plain" if return_confidence
-                      else None)
+        confidence = ("sheet" if return_sheet_confidence else "anchored" if return_anchored_confidence else "span" if return_span_confidence
+                      else "plain" if return_confidence else None)
         # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
         need_em = confidence is not None or skip_from is not None or windows is not None
         head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
                                        want_emissions=need_em, **kw)
         if need_em:
             nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same bits)
+            # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same bits;
+            # the sheet confidence keeps the fused head's, which run_lattice uses only where there is neither a span nor a window)
             r = run_lattice(head[4], lab_dev, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
                             dp=None if return_anchored_confidence else head[:4])
         else:

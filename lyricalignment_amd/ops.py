@@ -59,10 +59,11 @@ def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device) -> Tuple[t
 
 
 # The face of a lattice call (csrc/la_lattice.h Face) is chosen by the public function: "plain", "spans" (skip_from given) or
-# "windows" (win_lo / win_hi given, skip_from may be None); "lattice" is the general DP entry (la_viterbi_lattice_batch: skip_from and
-# the windows may each be None, up to 4095 labels).  -> the stem of its C symbols, DP and posteriors
+# "windows" (win_lo / win_hi given, skip_from may be None); "lattice" is the general entry (la_viterbi_lattice_batch and
+# la_alignment_posteriors_lattice: skip_from and the windows may each be None, up to 4095 labels).  -> the stem of its C symbols, DP and posteriors
 _DP_ENTRY = {"plain": "viterbi", "spans": "viterbi_spans", "windows": "viterbi_windows", "lattice": "viterbi_lattice"}
-_POSTERIOR_ENTRY = {"plain": "alignment_posteriors", "spans": "alignment_posteriors_spans", "windows": "alignment_posteriors_windows"}
+_POSTERIOR_ENTRY = {"plain": "alignment_posteriors", "spans": "alignment_posteriors_spans", "windows": "alignment_posteriors_windows",
+                    "lattice": "alignment_posteriors_lattice"}
 
 
 def _lattice_checked(who: str, face: str, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows, path=None, boundary_window=None):
@@ -208,6 +209,22 @@ def alignment_posteriors_windows(em: torch.Tensor, labels: torch.Tensor, n_label
     path inside its windows has status LA_EINFEASIBLE, log_z -inf and every output 0."""
     return _posteriors("alignment_posteriors_windows", "windows", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
                        skip_from, skip_penalty, (win_lo, win_hi))
+
+
+def alignment_posteriors_lattice(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                                 onset: torch.Tensor, offset: torch.Tensor, skip_from: Optional[torch.Tensor] = None,
+                                 skip_penalty: float = 0.0, win_lo: Optional[torch.Tensor] = None, win_hi: Optional[torch.Tensor] = None,
+                                 boundary_window: int = 2, want_gamma: bool = False):
+    """la_alignment_posteriors_lattice: forward-backward on the lattice that skip_from (None: no span) and win_lo / win_hi (both None: no
+    windows) describe, for up to 4095 labels; onset / offset = viterbi_lattice_batch's outputs for the same lattice.  Up to 511 labels the
+    outputs are alignment_posteriors_windows', alignment_posteriors_spans' or (the five common ones) alignment_posteriors' bit for bit,
+    according to what is given.  The workspace holds every alpha row: B * T * 1024 R * 8 bytes beyond 511 labels (R = 2 / 4 / 8 for up to
+    1023 / 2047 / 4095 labels).  -> the tuple of alignment_posteriors_spans (no span: present_prob 1 on the labels of an LA_OK clip,
+    span_skip_prob 0)."""
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError("alignment_posteriors_lattice: win_lo and win_hi go together")
+    return _posteriors("alignment_posteriors_lattice", "lattice", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty, None if win_lo is None else (win_lo, win_hi))
 
 
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:

@@ -226,12 +226,17 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     span the plain DP's frames, which are the span DP's bit for bit, and an all -1 skip_from) | "anchored" (posteriors GIVEN the windows,
     plus log_z_free = log_z of the same lattice without windows: one more launch of the free sweep, and log_z itself without windows).
     dp: the (onset, offset, score, status) of the plain lattice where they exist already (the fused head's).
-    More than 511 labels (up to 4095): the DP with spans or windows is ops.viterbi_lattice_batch; the posterior sweeps stop at 511, so any
-    confidence raises NotImplementedError before anything is launched."""
+    "sheet" (whole songs): any face at any size up to 4095 labels.  The DP runs by the routing below; the posteriors come from ONE call of
+    ops.alignment_posteriors_lattice on the lattice given, log_z_free from a second call without windows where windows were given, else
+    from log_z itself; the result is filled exactly as for "anchored".
+    More than 511 labels (up to 4095): the DP with spans or windows is ops.viterbi_lattice_batch; the three older kinds of confidence
+    stop at 511 and raise NotImplementedError before anything is launched ("sheet" is the kind for whole songs)."""
+    if confidence not in (None, "plain", "span", "anchored", "sheet"):
+        raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
     wide = lab.shape[1] > POSTERIOR_MAX_LABELS
-    if wide and confidence is not None:
+    if wide and confidence not in (None, "sheet"):
         raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posterior sweeps "
-                                  "(the alignment itself, without the confidence keywords, takes up to 4095)")
+                                  "(the alignment itself and the sheet confidence take up to 4095)")
     dev = em.device
     skip_dev = None if skip_from is None else skip_from.to(dev)
     win = None if windows is None else (windows[0].to(dev), windows[1].to(dev))
@@ -246,6 +251,14 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     onset, offset = dp[0], dp[1]
     if confidence is None:
         return LatticeResult(*dp)
+    if confidence == "sheet":
+        post = ops.alignment_posteriors_lattice(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, *(win or (None, None)),
+                                                boundary_window=boundary_window)
+        log_z_free = post[3]
+        if win is not None:
+            log_z_free = ops.alignment_posteriors_lattice(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty,
+                                                          boundary_window=boundary_window)[3]
+        return LatticeResult(*dp, *post[:4], *post[5:7], log_z_free)
     if confidence == "plain":
         return LatticeResult(*dp, *ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[:4])
     span_free = skip_dev is None
@@ -283,7 +296,7 @@ def _device_of(prediction) -> torch.device:
 
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
-             char_windows=None, onset_anchors=None, anchored=False):
+             char_windows=None, onset_anchors=None, anchored=False, sheet=False):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -300,10 +313,10 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     # (additions) optional spans and per-state frame windows; None / all-empty keywords take the reference's lattice unchanged
     skip_from = _skip_from_of_spans(optional_spans, lists)
     windows = _windows_of(char_windows, onset_anchors, lists, counts, hop_size_second)
-    if windows is not None and boundary_window is not None and not anchored:
+    if windows is not None and boundary_window is not None and not (anchored or sheet):
         raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
                          "(perform_viterbi(_ctc)_anchored_scored give them)")
-    confidence = "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
+    confidence = "sheet" if sheet else "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
     em = ops.emissions_from_logits(pred, lab, n_lab, variant)
     nf = torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
     r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window)
@@ -320,7 +333,8 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     char_windows / onset_anchors (addition): per utterance a list in windows_from_anchors' form (seconds, in the utterance's own frames):
     the DP runs on the lattice with per-state frame windows (la_viterbi_windows_batch), with or without optional_spans.  None or
     all-empty: the call as it was.  An utterance without a path inside its windows raises like one too short for its labels.
-    Up to 4095 labels with any of these keywords (beyond 511 the DP is la_viterbi_lattice_batch); the _scored functions at most 511."""
+    Up to 4095 labels with any of these keywords (beyond 511 the DP is la_viterbi_lattice_batch); the _scored functions at most 511,
+    except perform_viterbi(_ctc)_sheet_scored, which take whole songs (up to 4095)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
 
@@ -372,6 +386,26 @@ def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     anchored=True)
+
+
+def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                 skip_penalty=0.0, char_windows=None, onset_anchors=None):
+    """Whole-song timing with its confidences (addition): perform_viterbi_anchored_scored's (predicted_onset_offset, scores) for up to 4095
+    labels, with or without optional_spans and char_windows / onset_anchors (la_viterbi_lattice_batch's routing for the DP,
+    la_alignment_posteriors_lattice for the posteriors).  window_log_prob is 0.0 without windows.  Up to 511 labels the numbers are
+    perform_viterbi_anchored_scored's exactly.  The sweep's workspace holds every alpha row: T * 1024 R * 8 bytes per utterance beyond
+    511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    sheet=True)
+
+
+def perform_viterbi_ctc_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                     skip_penalty=0.0, char_windows=None, onset_anchors=None):
+    """perform_viterbi_ctc plus the whole-song confidences: see perform_viterbi_sheet_scored."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    sheet=True)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
