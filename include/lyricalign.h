@@ -669,6 +669,17 @@ int la_fc_emissions_x2(const float *act, int64_t ld_act, const float *w_fc, cons
  * losses[2] = CTC (mean over the batch of nll_b / n_labels[b]; +inf if an utterance is infeasible).
  * dlogits (optional, same layout) receives scale * d(losses[0]+losses[1]+losses[2]) / dlogits, restricted to the
  * requested terms (use_ce / use_ctc).  The alpha/beta lattice runs one workgroup per utterance, one lane per state.
+ * The losses of a term that was not requested are not meaningful.
+ *   - A clip with n_labels[b] = 0 contributes 0 to losses[2] and nothing to the gradient; the sum is still divided by `batch`.
+ *   - A frame label outside 1..vocab-1 other than -100 is ignored by the word CE (not counted, no gradient); for the silence BCE it
+ *     is a frame with a label (target 0).  With no frame label in 1..vocab-1 at all, losses[0] is NaN and the word-CE gradient zero.
+ *   - A CTC label whose class lies outside 0..vocab-1 can be emitted by no frame: the clip is infeasible, like one with fewer frames
+ *     than labels plus adjacent repeats (losses[2] = +inf; the clip's CTC gradient rows are exact zeros, its batch mates unaffected).
+ *   - n_labels[b] <= max_labels is the caller's duty (it is not checked: the labels live on the device); max_labels <= 511.
+ *   - The CTC gradient of a class that occurs at several label positions is summed with float atomics: where a class repeats,
+ *     dlogits is not bit-reproducible from call to call.
+ * Each row's normaliser is kept as its maximum and the log of the sum apart, (x - m) - log s, so a common offset on a row costs nothing.
+ * workspace: la_multitask_loss_workspace_bytes, 256-byte aligned.  Argument errors are answered before anything is enqueued.
  */
 int la_multitask_loss_workspace_bytes(int32_t batch, int32_t frames, int32_t max_labels, size_t *bytes);
 int la_multitask_loss(const float *logits, int64_t batch_stride, int64_t row_stride, int32_t batch, int32_t frames,

@@ -7,8 +7,8 @@
 // logits are [B][T][ldl >= V+1] f32 (V = 21128 word columns incl. blank, column V = silence logit).
 //
 // Kernels (all HBM- or latency-bound, none GEMM-shaped):
-//   row_stats        one workgroup per (b,t) row: max / sum-exp over [0,V) and over [1,V)  -> 2 log-normalisers, and the
-//                    CE / BCE loss terms of the row (block-reduced, one atomic per workgroup)
+//   row_stats        one workgroup per (b,t) row: max / sum-exp over [0,V) and over [1,V)  -> 2 normalisers (maximum m and
+//                    log s = log sum exp(x - m), kept apart), and the CE / BCE loss terms of the row (one atomic per workgroup)
 //   ctc_lattice      one workgroup per utterance, one lane per extended-label state s (S = 2L+1): alpha sweep forward
 //                    (stored), beta sweep backward, nll, and the per-(t,s) occupancy exp(alpha+beta+nll-lp) which is
 //                    scattered into the gradient (the alpha/beta lattice north_star names; same row-by-row wave sweep
@@ -31,13 +31,21 @@ __device__ __forceinline__ float wave_sum_f(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// A row's normaliser: its maximum and the log of sum_c exp(x[c] - m), kept APART.  Every use takes (x - m) - log_s like torch's
+// log_softmax (and la_cross_entropy_f32, la_anchor_loss.hip): m + log_s rounded to one float costs an ulp OF m, which for logits with a
+// large common offset (1e4: 5e-4 per frame) is larger than the losses' own resolution and adds up over the frames of the lattice.
+struct RowNorm {
+    float m, log_s;
+};
+__device__ __forceinline__ double log_prob(float x, RowNorm n) { return ((double)x - (double)n.m) - (double)n.log_s; }
+
 struct LossAcc {  // device accumulators (double): [0] sum CE, [1] #valid frames, [2] sum BCE, [3] sum_b nll_b / L_b, [4] #inf
     double v[8];
 };
 
 // ---- row statistics + CE / BCE terms --------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void row_stats_kernel(const float *logits, int64_t ldl, int rows, int V,
-                                                        const int32_t *frame_labels, float *lse_all, float *lse_ce,
+                                                        const int32_t *frame_labels, RowNorm *norm_all, RowNorm *norm_ce,
                                                         LossAcc *acc) {
     __shared__ float red[12];
     const int row = blockIdx.x;
@@ -58,10 +66,9 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float *logits, int
     __syncthreads();
     if (tid == 0) {
         const float s1 = (red[4] + red[5]) + (red[6] + red[7]);
-        const float l_ce = m1 + logf(s1);
-        const float l_all = m0 + logf(s1 * expf(m1 - m0) + expf(x0 - m0));
-        lse_ce[row] = l_ce;
-        lse_all[row] = l_all;
+        const float ls1 = logf(s1);
+        norm_ce[row] = RowNorm{m1, ls1};
+        norm_all[row] = RowNorm{m0, logf(s1 * expf(m1 - m0) + expf(x0 - m0))};
         if (frame_labels) {
             const int lab = frame_labels[row];
             const float xs = x[V];
@@ -71,7 +78,7 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float *logits, int
             if (lab != -100) {
                 const int c = lab;  // class id k (>= 1): reference shifts labels by -1 and slices columns 1.., i.e. column k
                 if (c >= 1 && c < V) {
-                    atomicAdd(&acc->v[0], (double)(l_ce - x[c]));
+                    atomicAdd(&acc->v[0], (double)(ls1 - (x[c] - m1)));
                     atomicAdd(&acc->v[1], 1.0);
                 }
             }
@@ -80,11 +87,11 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float *logits, int
 }
 
 // ---- CTC alpha / beta lattice -----------------------------------------------------------------------------------
-// One workgroup (NT threads, NT >= S) per utterance.  lp_t(s) = logits[t][ext(s)] - lse_all[t], ext(s) = 0 for even s,
+// One workgroup (NT threads, NT >= S) per utterance.  lp_t(s) = (logits[t][ext(s)] - m[t]) - log_s[t], ext(s) = 0 for even s,
 // label[s/2] for odd s.  alpha rows are stored in the workspace for the backward sweep.
 template <int NT>
 __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, int64_t ld_b, int64_t ldl, int T, int V,
-                                                         const float *lse_all, const int32_t *labels, int labels_stride,
+                                                         const RowNorm *norm_all, const int32_t *labels, int labels_stride,
                                                          const int32_t *n_labels, double *alpha_ws, int S_pad,
                                                          float *dlogits, int64_t ldd_b, int64_t ldd, float scale,
                                                          int batch, LossAcc *acc, float *nll_out, int reuse_alpha) {
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, in
     // backward-direction skip: state s may go to s+2 iff ext(s+2) != blank and != ext(s)
     const bool can_skip_fwd_from = valid && (s & 1) && (s + 2 < S) && lab[(s >> 1) + 1] != lab[s >> 1];
     const float *xb = logits + (int64_t)b * ld_b;
-    const float *lseb = lse_all + (int64_t)b * T;
+    const RowNorm *nb = norm_all + (int64_t)b * T;
     double *aw = alpha_ws + (int64_t)b * T * S_pad;
     const bool cls_ok = cls >= 0 && cls < V;
     if (L <= 0 || S > NT) {  // torch: zero-length targets give nll = -sum lp(blank); not used by the reference's data
@@ -119,7 +126,7 @@ __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, in
         // ---- alpha ----
         double a = -INFINITY;
         {
-            const double lp = valid && cls_ok ? (double)xb[cls] - (double)lseb[0] : -INFINITY;
+            const double lp = valid && cls_ok ? log_prob(xb[cls], nb[0]) : -INFINITY;
             if (s <= 1 && valid) a = lp;
             if (valid) aw[s] = a;
         }
@@ -130,7 +137,7 @@ __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, in
             par ^= 1;
             double acc3 = log_add(a, a1);
             if (can_skip) acc3 = log_add(acc3, a2);
-            const double lp = valid && cls_ok ? (double)xb[(int64_t)t * ldl + cls] - (double)lseb[t] : -INFINITY;
+            const double lp = valid && cls_ok ? log_prob(xb[(int64_t)t * ldl + cls], nb[t]) : -INFINITY;
             a = valid ? acc3 + lp : -INFINITY;
             if (valid) aw[(int64_t)t * S_pad + s] = a;
         }
@@ -158,7 +165,7 @@ __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, in
     double be = -INFINITY;
     par = 0;
     for (int t = T - 1; t >= 0; --t) {
-        const double lp = valid && cls_ok ? (double)xb[(int64_t)t * ldl + cls] - (double)lseb[t] : -INFINITY;
+        const double lp = valid && cls_ok ? log_prob(xb[(int64_t)t * ldl + cls], nb[t]) : -INFINITY;
         if (t == T - 1) {
             be = (valid && (s == S - 1 || s == S - 2)) ? lp : -INFINITY;
         } else {
@@ -186,7 +193,7 @@ __global__ __launch_bounds__(NT) void ctc_lattice_kernel(const float *logits, in
 // float32 rounding is <= 1e-7 ABSOLUTE per step (the path scores themselves, ~ -1e4, stay float64: the reason the lattice is float64 at
 // all) -- and the emissions / stored alpha rows prefetched a block of 8 steps ahead of the chain.
 // (la_lattice.h: wave_shr1 / wave_shl1 and log_add3.)
-__global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logits, int64_t ld_b, int64_t ldl, int T, int V, const float *lse_all,
+__global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logits, int64_t ld_b, int64_t ldl, int T, int V, const RowNorm *norm_all,
                                                               const int32_t *labels, int labels_stride, const int32_t *n_labels, double *alpha_ws,
                                                               int S_pad, float *dlogits, int64_t ldd_b, int64_t ldd, float scale, int batch,
                                                               LossAcc *acc, float *nll_out, int reuse_alpha) {
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logit
     const bool can_skip_fwd_from = valid && (s & 1) && (s + 2 < S) && lab[(s >> 1) + 1] != lab[s >> 1];
     const bool live = valid && cls >= 0 && cls < V;        // lanes with an emission; the others carry -inf
     const float *xb = logits + (int64_t)b * ld_b + (live ? cls : 0);
-    const float *lseb = lse_all + (int64_t)b * T;
+    const RowNorm *nb = norm_all + (int64_t)b * T;
     double *aw = alpha_ws + (int64_t)b * T * S_pad + (valid ? s : 0);
     const double NEG = -INFINITY;
     double nll;
@@ -215,20 +222,22 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logit
         nll = -log_add(f0, f1);
     } else {
         // ---- alpha ----
-        double a = (s <= 1 && live) ? (double)xb[0] - (double)lseb[0] : NEG;
+        double a = (s <= 1 && live) ? log_prob(xb[0], nb[0]) : NEG;
         if (valid) aw[0] = a;
-        float xv[U], lv[U];
+        float xv[U];
+        RowNorm lv[U];
         auto fetch = [&](int t0) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int t = min(t0 + u, T - 1);
                 xv[u] = xb[(int64_t)t * ldl];
-                lv[u] = lseb[t];
+                lv[u] = nb[t];
             }
         };
         fetch(1);
         for (int t0 = 1; t0 < T; t0 += U) {
-            float xc[U], lc[U];
+            float xc[U];
+            RowNorm lc[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) { xc[u] = xv[u]; lc[u] = lv[u]; }
             if (t0 + U < T) fetch(t0 + U);
@@ -239,7 +248,7 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logit
                     const double a1 = wave_shr1(a, NEG);
                     double a2 = wave_shr1(a1, NEG);
                     if (!can_skip) a2 = NEG;
-                    const double lp = (double)xc[u] - (double)lc[u];
+                    const double lp = log_prob(xc[u], lc[u]);
                     a = live ? log_add3(a, a1, a2) + lp : NEG;
                     if (valid) aw[(int64_t)t * S_pad] = a;
                 }
@@ -259,20 +268,22 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logit
     float *db = dlogits + (int64_t)b * ldd_b + (live ? cls : 0);
     const bool scatter = live && !isinf(nll);
     double be = NEG;
-    float xv[U], lv[U];
+    float xv[U];
+    RowNorm lv[U];
     double av[U];
     auto fetch = [&](int t0) {                                        // steps t0, t0 - 1, ..., t0 - U + 1
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = max(t0 - u, 0);
             xv[u] = xb[(int64_t)t * ldl];
-            lv[u] = lseb[t];
+            lv[u] = nb[t];
             av[u] = aw[(int64_t)t * S_pad];
         }
     };
     fetch(T - 1);
     for (int t0 = T - 1; t0 >= 0; t0 -= U) {
-        float xc[U], lc[U];
+        float xc[U];
+        RowNorm lc[U];
         double ac[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) { xc[u] = xv[u]; lc[u] = lv[u]; ac[u] = av[u]; }
@@ -281,7 +292,7 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logit
         for (int u = 0; u < U; ++u) {
             const int t = t0 - u;
             if (t >= 0) {                                             // wave-uniform
-                const double lp = (double)xc[u] - (double)lc[u];
+                const double lp = log_prob(xc[u], lc[u]);
                 if (t == T - 1) {
                     be = (live && (s == S - 1 || s == S - 2)) ? lp : NEG;
                 } else {
@@ -301,7 +312,7 @@ __global__ __launch_bounds__(64) void ctc_lattice_wave_kernel(const float *logit
 
 // ---- dense gradient ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dense_grad_kernel(const float *logits, int64_t ldl, int rows, int T, int V,
-                                                         const float *lse_all, const float *lse_ce,
+                                                         const RowNorm *norm_all, const RowNorm *norm_ce,
                                                          const int32_t *frame_labels, const int32_t *n_labels,
                                                          const float *nll, const LossAcc *acc, int use_ce, int use_ctc,
                                                          float scale, int batch, float *dlogits, int64_t ldd) {
@@ -309,7 +320,7 @@ __global__ __launch_bounds__(256) void dense_grad_kernel(const float *logits, in
     const int b = row / T;
     const float *x = logits + (int64_t)row * ldl;
     float *d = dlogits + (int64_t)row * ldd;
-    const float la = lse_all[row], lc = lse_ce[row];
+    const RowNorm na = norm_all[row], nc = norm_ce[row];
     float w_ctc = 0.f;
     if (use_ctc) {
         const int L = n_labels[b];
@@ -324,9 +335,9 @@ __global__ __launch_bounds__(256) void dense_grad_kernel(const float *logits, in
     }
     for (int c = threadIdx.x; c < V; c += 256) {
         const float xc = x[c];
-        float g = w_ctc * expf(xc - la);
+        float g = w_ctc * expf((xc - na.m) - na.log_s);
         if (c >= 1) {
-            g += w_ce * expf(xc - lc);
+            g += w_ce * expf((xc - nc.m) - nc.log_s);
             if (c == lab) g -= w_ce;
         }
         d[c] = g;
@@ -355,7 +366,7 @@ extern "C" int la_multitask_loss_workspace_bytes(int32_t batch, int32_t frames, 
     LA_CHECK_ARG(bytes && batch > 0 && frames > 0 && max_labels > 0, "multitask_loss_workspace_bytes: bad arguments");
     const int64_t rows = (int64_t)batch * frames;
     const int S_pad = (2 * max_labels + 1 + 3) & ~3;
-    *bytes = (size_t)(256 + la::round_up(rows * 4, 256) * 2 + la::round_up((int64_t)batch * 4, 256) + la::round_up(rows * S_pad * 8, 256));
+    *bytes = (size_t)(256 + la::round_up(rows * 8, 256) * 2 + la::round_up((int64_t)batch * 4, 256) + la::round_up(rows * S_pad * 8, 256));
     return LA_OK;
 }
 
@@ -379,14 +390,15 @@ extern "C" int la_multitask_loss(const float *logits, int64_t batch_stride, int6
     const int S_pad = (2 * max_labels + 1 + 3) & ~3;
     unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
     LossAcc *acc = reinterpret_cast<LossAcc *>(ws);
-    float *lse_all = reinterpret_cast<float *>(ws + 256);
-    float *lse_ce = lse_all + la::round_up(rows, 64);
-    float *nll = lse_ce + la::round_up(rows, 64);
+    // the carve-up la_multitask_loss_workspace_bytes counts: accumulators, the two normalisers of every row, nll per clip, alpha rows
+    RowNorm *norm_all = reinterpret_cast<RowNorm *>(ws + 256);
+    RowNorm *norm_ce = norm_all + la::round_up(rows, 32);
+    float *nll = reinterpret_cast<float *>(norm_ce + la::round_up(rows, 32));
     double *alpha_ws = reinterpret_cast<double *>(nll + la::round_up(batch, 64));
     LA_HIP(hipMemsetAsync(acc, 0, 256, stream));
     la::TimerScope ts("multitask_loss", stream);
     hipLaunchKernelGGL(row_stats_kernel, dim3(rows), dim3(256), 0, stream, logits, row_stride, rows, vocab,
-                       use_ce ? frame_labels : nullptr, lse_all, lse_ce, acc);
+                       use_ce ? frame_labels : nullptr, norm_all, norm_ce, acc);
     LA_LAUNCH_CHECK();
     if (dlogits) {
         // dense part first (it needs nll only to zero the CTC weight of infeasible utterances -> run the lattice's alpha
@@ -398,10 +410,10 @@ extern "C" int la_multitask_loss(const float *logits, int64_t batch_stride, int6
         if (!use_ctc) return;
 #define LA_CTC_CASE(NTV)                                                                                                   \
     hipLaunchKernelGGL((ctc_lattice_kernel<NTV>), dim3(batch), dim3(NTV), 0, stream, logits, batch_stride, row_stride, frames,  \
-                       vocab, lse_all, ctc_labels, labels_stride, n_labels, alpha_ws, S_pad, dl, d_batch_stride, d_row_stride,   \
+                       vocab, norm_all, ctc_labels, labels_stride, n_labels, alpha_ws, S_pad, dl, d_batch_stride, d_row_stride,  \
                        scale, batch, dl ? acc + 1 : acc, nll, dl ? 1 : 0)
         if (S <= 64)
-            hipLaunchKernelGGL(ctc_lattice_wave_kernel, dim3(batch), dim3(64), 0, stream, logits, batch_stride, row_stride, frames, vocab, lse_all,
+            hipLaunchKernelGGL(ctc_lattice_wave_kernel, dim3(batch), dim3(64), 0, stream, logits, batch_stride, row_stride, frames, vocab, norm_all,
                                ctc_labels, labels_stride, n_labels, alpha_ws, S_pad, dl, d_batch_stride, d_row_stride, scale, batch,
                                dl ? acc + 1 : acc, nll, dl ? 1 : 0);
         else if (S <= 128) LA_CTC_CASE(128);
@@ -417,8 +429,8 @@ extern "C" int la_multitask_loss(const float *logits, int64_t batch_stride, int6
         LA_HIP(hipMemsetAsync(nll, 0, (size_t)batch * 4, stream));
     }
     if (dlogits) {
-        hipLaunchKernelGGL(dense_grad_kernel, dim3(rows), dim3(256), 0, stream, logits, row_stride, rows, frames, vocab, lse_all,
-                           lse_ce, frame_labels, n_labels, nll, acc, use_ce, use_ctc, scale, batch, dlogits, d_row_stride);
+        hipLaunchKernelGGL(dense_grad_kernel, dim3(rows), dim3(256), 0, stream, logits, row_stride, rows, frames, vocab, norm_all,
+                           norm_ce, frame_labels, n_labels, nll, acc, use_ce, use_ctc, scale, batch, dlogits, d_row_stride);
         LA_LAUNCH_CHECK();
         if (use_ctc) {
             launch_lattice(dlogits);   // beta sweep on the stored alpha rows, occupancies subtracted from the dense softmax part

@@ -99,6 +99,13 @@ def test_loss_and_gradient_match_the_float64_yardstick(T, L, V):
             with _lib.option("viterbi_dpp", form):
                 out = _run(clips, V, c["penalty"], scale=0.25)
             _compare(f"variant {variant} dpp {form}", clips, V, *out, scale=0.25)
+    if (T, L, V) == (40, 5, 12):
+        # a common offset of +1e4 on the word columns 1..V-1: the emissions keep a row's maximum and log-sum apart, so nothing is lost
+        base = alr.gpu_case(T, L, V)
+        x = base["x"].copy()
+        x[:, 1:V] += np.float32(1e4)
+        c = dict(base, x=x, ref=alr.clip(x, base["labels"], V, base["lo"], base["hi"]))
+        _compare("word columns + 1e4", [c], V, *_run([c], V, scale=0.25), scale=0.25)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the real row width
