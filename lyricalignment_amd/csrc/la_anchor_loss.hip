@@ -21,7 +21,7 @@
 //   emissions   one 256-thread workgroup per (b, t) row, the row held in registers between the maximum and the sum (ONE read): the
 //               reduction order of emissions_from_logits_kernel (la_elementwise.hip), so the same bits; keeps lse_{1..V-1} (as the row's maximum
 //               and the log of the sum, apart) and x[t][V]
-//   sweep       la_alignment_posteriors_windows (la_posterior.hip, untouched) with gamma written to the workspace; log_z and status
+//   sweep       la_alignment_posteriors_windows (la_posterior.hip, through the C ABI) with gamma written to the workspace; log_z and status
 //   gradient    one 1024-thread workgroup per (b, t) row: g_sil / g_voiced by a fixed-order reduction of the gamma row, then every lane
 //               streams its 16-byte pieces of the row from the load to the store through registers (a 21129-wide row is 21 floats per
 //               lane: one read and one write of the row).  Label columns afterwards, behind a barrier: the lane of the FIRST position of

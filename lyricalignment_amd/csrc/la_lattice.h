@@ -153,7 +153,7 @@ __device__ __forceinline__ double log_add(double a, double b) {
 }
 // log_add with its trivial cases taken first -- the same values to the bit (log1p(exp(-inf)) = 0) -- so that a wave in which no lane
 // has two finite operands (no jump arc at this call site) skips the float64 exp / log1p.  The jump terms of the posterior sweeps
-// (la_posterior.hip, la_posterior_strip.hip)
+// (la_posterior.hip)
 __device__ __forceinline__ double log_add_jump(double a, double b) {
     if (b == -INFINITY) return a;
     if (a == -INFINITY) return b;

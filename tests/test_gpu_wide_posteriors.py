@@ -1,5 +1,5 @@
-"""Whole-song posteriors on the device (la_alignment_posteriors_lattice: posterior_strip_kernel of csrc/la_posterior_strip.hip beyond 511
-labels, the lane-per-state sweeps of csrc/la_posterior.hip below) and the layers over it (ops.alignment_posteriors_lattice,
+"""Whole-song posteriors on the device (la_alignment_posteriors_lattice: posterior_strip_kernel of csrc/la_posterior.hip beyond 511
+labels, the lane-per-state posterior_kernel of the same file below) and the layers over it (ops.alignment_posteriors_lattice,
 run_lattice(confidence="sheet"), AlignModel.align(return_sheet_confidence=True), perform_viterbi(_ctc)_sheet_scored, harness.align_song).
 
 Yardstick: window_posterior_reference.posteriors plus span_posterior_reference.scores on the onset / offset of
@@ -139,6 +139,37 @@ def test_fewer_frames_than_labels():
     lo[0] = lo[1] = 1
     assert np.isneginf(wpr.posteriors(em, lab, lo, hi, skip, 0.5)[5])
     _assert_no_path(_launch([em], [lab], [skip], 0.5, [lo], [hi], [none], [none]), 0, "both start states closed")
+
+
+# ------------------------------------------------------------------------------------------------ A2b. a few frames
+@pytest.mark.parametrize("T", [1, 2, 3, 6, 7])
+@pytest.mark.parametrize("L", [512, 1100, 2100])
+def test_a_few_frames_on_the_strip_kernel(T, L):
+    """Where the cell's t == T-1 and t > 0 branches and the tail of the prefetch blocks (4, 2 and 1 frames at 2, 4 and 8 states per thread)
+    meet.  Every line optional, plus spans from label 0 to L-3 and to L; the emissions plant the last three labels at frames 1, 3 and 5.
+    One frame: no path.  Two or three: every label skipped.  Six or seven: exactly the last three labels sung, so all three sums run."""
+    lab = wpc.labels_of(3, L)
+    em = (-3 - np.random.RandomState(T + L).rand(T, L + 1) * 3).astype(np.float32)
+    for i, n in enumerate((L - 3, L - 2, L - 1)):
+        if 1 + 2 * i < T:
+            em[1 + 2 * i, 1 + n] = -0.1
+    skip = wpc.every_line_optional(L)
+    skip[L] = skip[L - 3] = 0
+    y = wpc.yardstick(em, lab, skip, 0.5)
+    assert y["status"] == (wr.LA_EINFEASIBLE if T == 1 else wr.LA_OK) and np.isneginf(y["ref"][5]) == (T == 1)
+    if T > 1:
+        sung = [n for n in range(L) if y["on"][n] >= 0]
+        assert sung == ([L - 3, L - 2, L - 1] if T >= 6 else []), sung
+    r = _launch([em], [lab], [skip], 0.5, None, None, [y["on"]], [y["off"]])
+    if T == 1:
+        _assert_no_path(r, 0, "one frame")
+        return
+    from lyricalignment_amd import _lib
+    assert r["status"][0] == _lib.LA_OK
+    r["score"] = np.array([y["score"]])
+    worst = _compare(r, 0, y["ref"], em, lab, skip, *wr.open_windows(L, T), 2)
+    _report(f"T={T} L={L} a few frames", T, worst)
+    assert all(x <= _tol(T) for x in worst.values()), worst
 
 
 # ------------------------------------------------------------------------------------------------ A3. mixed batch, bit equality

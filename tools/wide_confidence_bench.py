@@ -1,5 +1,5 @@
 """Cost of the whole-song posteriors (la_alignment_posteriors_lattice beyond 511 labels: posterior_strip_kernel,
-csrc/la_posterior_strip.hip) beside the alignment DP on the same lattice (la_viterbi_lattice_batch).
+csrc/la_posterior.hip) beside the alignment DP on the same lattice (la_viterbi_lattice_batch).
 
     python tools/wide_confidence_bench.py [--runs 30] [--parent-lib <liblyricalign_hip.so of the parent commit>] [--out profiles/wide_confidence.txt]
 
@@ -11,9 +11,11 @@ thread), both in lines of 10 labels; the emissions plant every line but each fou
   * anchors (around the sheet-only DP's result) plus every fourth line optional.
 On each lattice two legs, alternated call by call (caller-owned buffers, device events around one call, a synchronise after each):
 la_viterbi_lattice_batch, the yardstick, and la_alignment_posteriors_lattice on the DP's onset / offset (no gamma output).
-With --parent-lib the existing lane-per-state sweeps run beside the parent commit's at 32 clips x 1500 frames x 26 labels and 1 clip x
-5389 frames x 200 labels (la_alignment_posteriors, la_alignment_posteriors_spans without a span, la_alignment_posteriors_windows with
-every window open): outputs checked bit for bit, every leg's median reported against the parent's min .. max of the same leg.
+With --parent-lib every posterior leg runs beside the parent commit's, alternated with it call by call: the four
+la_alignment_posteriors_lattice legs of each song, and the lane-per-state sweeps at 32 clips x 1500 frames x 26 labels and 1 clip x 5389
+frames x 200 labels (la_alignment_posteriors, la_alignment_posteriors_spans without a span, la_alignment_posteriors_windows with every
+window open).  All seven outputs are checked bit for bit before anything is timed -- also on a song of 3000 frames x 1100 labels (4
+states per thread), which is not timed -- and every leg's median is reported against the parent's min .. max of the same leg.
 Every number is the median of `runs` calls after a warm-up; min .. max is printed next to it; every status is LA_OK before anything is timed.
 """
 from __future__ import annotations
@@ -28,6 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LATTICES = ("nothing given", "all windows open", "one onset anchor per line, +-1 s", "anchors + every fourth line optional")
 SONGS = [("1 song x 12000 frames x 800 labels (2 states per thread)", 12000, 800),
          ("1 song x 12000 frames x 2500 labels (8 states per thread)", 12000, 2500)]
+BITS_ONLY = [("1 song x 3000 frames x 1100 labels (4 states per thread)", 3000, 1100)]
 EXISTING = [("32 clips x 1500 frames x 26 labels (1 wave)", 32, 1500, 26), ("1 clip x 5389 frames x 200 labels (8 waves)", 1, 5389, 200)]
 LINE = 10
 TOL_S = 1.0
@@ -67,7 +70,7 @@ def main():
     parent = None
     if args.parent_lib:
         parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
-        for stem in ("viterbi", "alignment_posteriors", "alignment_posteriors_spans", "alignment_posteriors_windows"):
+        for stem in ("viterbi", "alignment_posteriors", "alignment_posteriors_spans", "alignment_posteriors_windows", "alignment_posteriors_lattice"):
             for name in (f"la_{stem}_workspace_bytes", f"la_{stem}_batch" if stem == "viterbi" else f"la_{stem}"):
                 fn = getattr(parent, name)
                 fn.restype, fn.argtypes = SYMBOLS[name]
@@ -160,9 +163,15 @@ def main():
     def same(a, b):
         return all(x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes() for x, y in zip(a, b))
 
+    def against_parent(name, width, stats):
+        (m, lo_t, hi_t), (pm, plo, phi) = stats[name], stats["parent commit: " + name]
+        where = "inside" if plo <= m <= phi else ("BELOW" if m < plo else "ABOVE")
+        say(f"{name:{width}s} {m:8.3f} ({lo_t:.3f} .. {hi_t:.3f}) against the parent's {pm:.3f} ({plo:.3f} .. {phi:.3f}): {where} its "
+            f"min .. max ({100 * (m / pm - 1):+.1f} % of its median); outputs bit-equal")
+
     say(f"# whole-song posteriors on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up of 3, "
         f"legs alternated call by call, device events around one call, ms")
-    for title, T, L in SONGS:
+    for title, T, L in SONGS + (BITS_ONLY if parent is not None else []):
         lengths = [LINE] * (L // LINE)
         optional = [i % 4 == 3 for i in range(len(lengths))]
         sung = [n for i in range(len(lengths)) if not optional[i] for n in range(LINE * i, LINE * i + LINE)]
@@ -186,7 +195,7 @@ def main():
         torch.cuda.synchronize()
         assert int(plain[1][3][0]) == 0 and int(sheet_only[1][3][0]) == 0
         lattices = [(None, None), (None, sh.open_windows()), (None, anchored(plain[1][0][0].cpu())), (skip, anchored(sheet_only[1][0][0].cpu()))]
-        legs = []
+        legs, beside = [], []
         for name, (sk, win) in zip(LATTICES, lattices):
             dp = sh.dp_leg(lib(), "viterbi_lattice", sk, win)
             dp[0]()
@@ -194,7 +203,16 @@ def main():
             post = sh.post_leg(lib(), "alignment_posteriors_lattice", dp[1][:2], sk, win)
             legs += [("la_viterbi_lattice_batch, " + name, dp[0], dp[1]), ("la_alignment_posteriors_lattice, " + name, post[0], post[1])]
             ws_mb = post[2] / 1e6
-        stats = measure(title, legs)
+            if parent is not None:
+                theirs = sh.post_leg(parent, "alignment_posteriors_lattice", dp[1][:2], sk, win)
+                post[0](); theirs[0]()
+                torch.cuda.synchronize()
+                assert int(post[1][6][0]) == 0 and same(post[1], theirs[1]), f"{title}, {name}: outputs differ from the parent commit's"
+                beside.append(("parent commit: la_alignment_posteriors_lattice, " + name, theirs[0], theirs[1]))
+        if (title, T, L) in BITS_ONLY:
+            say(f"## {title}: la_alignment_posteriors_lattice on the four lattices, all seven outputs equal the parent commit's bit for bit (not timed)")
+            continue
+        stats = measure(title, legs + beside)
         for i in range(0, len(legs), 2):
             (dn, (dm, dlo, dhi)), (pn, (pm, plo, phi)) = [(legs[i + j][0], stats[legs[i + j][0]]) for j in (0, 1)]
             say(f"{dn:72s} {dm:9.3f} ({dlo:.3f} .. {dhi:.3f})")
@@ -203,7 +221,9 @@ def main():
         last = legs[-1][2]
         say(f"workspace {ws_mb:.0f} MB; every status LA_OK; all-open outputs equal the nothing-given ones bit for bit: {open_same}; with the sheet "
             f"{int((last[3][0] < 0.5).sum())} of {L} labels have sung_prob < 0.5, log_z {float(last[5][0]):.3f}")
-        del sh, legs, plain, sheet_only, lattices
+        for name, _, _ in legs[1::2] if parent is not None else []:
+            against_parent(name, 72, stats)
+        del sh, legs, beside, plain, sheet_only, lattices
         torch.cuda.empty_cache()
 
     if parent is not None:
@@ -228,10 +248,7 @@ def main():
                 assert same([legs[i][2][j] for j in keep], [legs[3 + i][2][j] for j in keep]), f"{legs[i][0]}: outputs differ from the parent commit's"
             stats = measure(title + ": the existing entries beside the parent's", legs)
             for name in names:
-                (m, lo_t, hi_t), (pm, plo, phi) = stats[name], stats["parent commit: " + name]
-                where = "inside" if plo <= m <= phi else ("BELOW" if m < plo else "ABOVE")
-                say(f"{name:52s} {m:8.3f} ({lo_t:.3f} .. {hi_t:.3f}) against the parent's {pm:.3f} ({plo:.3f} .. {phi:.3f}): {where} its "
-                    f"min .. max ({100 * (m / pm - 1):+.1f} % of its median); outputs bit-equal")
+                against_parent(name, 52, stats)
             del sh, legs
             torch.cuda.empty_cache()
     if args.out:
