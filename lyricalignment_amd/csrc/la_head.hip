@@ -65,9 +65,10 @@ __global__ __launch_bounds__(C::THREADS, 2) void fc_lse_kernel(LseParams p) {
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float sum = 0.f;
         if (mx > -INFINITY) {
-            const float mb = mx * kLog2e;
+            // (v - mx) first: the maximum's own term is exactly 1.  fma(v, log2e, -fl(mx log2e)) leaves it at 2^(rounding of mx log2e),
+            // an error of ulp(mx) / 2 in the log-sum whatever V is
 #pragma unroll
-            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(fmaf(v[i], kLog2e, -mb));  // exp2(-inf) = 0 for masked columns
+            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f((v[i] - mx) * kLog2e);  // exp2(-inf) = 0 for masked columns
         }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
@@ -124,9 +125,8 @@ __global__ __launch_bounds__(PP::THREADS, 2) void fc_lse_pp_kernel(LseParams p) 
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float sum = 0.f;
         if (mx > -INFINITY) {
-            const float mb = mx * kLog2e;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(fmaf(v[i], kLog2e, -mb));
+            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f((v[i] - mx) * kLog2e);  // (as in fc_lse_kernel)
         }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
@@ -182,9 +182,8 @@ __global__ __launch_bounds__(PP::THREADS, 2) void fc_lse_x2_kernel(LseParams p) 
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float sum = 0.f;
         if (mx > -INFINITY) {
-            const float mb = mx * kLog2e;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(fmaf(v[i], kLog2e, -mb));
+            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f((v[i] - mx) * kLog2e);  // (as in fc_lse_kernel)
         }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
@@ -310,7 +309,7 @@ static int fc_emissions_impl(int32_t dtype, const void *act, int64_t ld_act, con
     if (batch == 0 || frames == 0) return LA_OK;
     LA_CHECK_ARG(act && w_fc && b_fc && labels && n_labels && em && workspace, "fc_emissions: null pointer");
     LA_CHECK_ARG(dtype == LA_F32 || dtype == LA_BF16 || dtype == LA_F16, "fc_emissions: bad dtype");
-    LA_CHECK_ARG(batch > 0 && frames > 0 && max_labels > 0, "fc_emissions: bad sizes");
+    LA_CHECK_ARG(batch > 0 && frames > 0 && in_dim > 0 && max_labels > 0, "fc_emissions: bad sizes");
     LA_CHECK_ARG(variant == LA_VARIANT_CTC ? vocab >= 3 : vocab >= 2, "fc_emissions: vocab too small");
     LA_CHECK_ARG(em_row_stride >= max_labels + 1 && labels_stride >= max_labels, "fc_emissions: strides smaller than max_labels");
     const int es = dtype == LA_F32 ? 4 : 2, ke = dtype == LA_F32 ? 32 : 64;
