@@ -611,6 +611,14 @@ int la_mel_to_rows(const float *mel, int64_t mel_batch_stride, int64_t mel_row_s
  * `timeout_flag` (device int32, optional) is set non-zero if a bounded wait (option gru_timeout_us, default 3 s) gave up: the launch set was
  * not co-resident and `out` is garbage.  Recover by calling again after hipDeviceSynchronize (alone on the device the set is co-resident);
  * INTEGRATION.md "GRU time-out and recovery".
+ * Statuses, answered on the host before anything is enqueued (the same in la_gru_layer, la_gru_layer_ragged, la_gru_layer_train_fwd and
+ * la_gru_layer_bwd): batch == 0 or frames == 0 -> LA_OK, nothing is looked at.  LA_EINVAL: a null pointer (timeout_flag and out_mish
+ * excepted), a bad dtype, a negative batch / frames or hidden <= 0, w_hh / out / workspace (backward: dgh / workspace) not 16-byte aligned,
+ * a workspace below la_gru_workspace_bytes.  LA_EUNSUPPORTED: a well-formed shape the kernels are not built for -- hidden not a multiple
+ * of 64 or beyond the type's limit (float32 384, 16-bit 512, backward 384), or more than 224 co-resident workgroups (split the batch).
+ * la_gru_workspace_bytes: [16-byte header][arrival counters [ceil(batch / 16)][2][frames] u32] padded to 256 bytes, then the granule ring,
+ * the larger of ceil(batch / 16) * 64 * hidden * 8 bytes (forward) and, for hidden % 64 == 0, ceil(batch / 16) * 64 * (hidden / 64)^2 * 512
+ * bytes (backward); LA_EINVAL for a null result or a non-positive size.
  */
 int la_gru_workspace_bytes(int32_t batch, int32_t frames, int32_t hidden, size_t *bytes);
 int la_gru_layer(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh,

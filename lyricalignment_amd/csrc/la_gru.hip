@@ -1043,7 +1043,7 @@ extern "C" int la_gru_layer_ragged(int32_t dtype, const float *gi, const void *w
 extern "C" int la_gru_layer_train_fwd(const float *gi, const float *w_hh, const float *b_hh, float *out, float *gates,
                                       int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
                                       int32_t *timeout_flag, void *stream) {
-    LA_CHECK_ARG(gates, "gru_layer_train_fwd: gates buffer missing");
+    LA_CHECK_ARG(gates || batch == 0 || frames == 0, "gru_layer_train_fwd: gates buffer missing");
     return gru_forward(LA_F32, gi, w_hh, b_hh, out, nullptr, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, gates, stream);
 }
 
@@ -1491,10 +1491,16 @@ extern "C" int la_gru_layer_bwd(const float *gates, const float *out, const floa
     hipStream_t stream = (hipStream_t)stream_;
     if (batch == 0 || frames == 0) return LA_OK;
     LA_CHECK_ARG(gates && out && dout && w_hh && dgi && dgh && workspace, "gru_layer_bwd: null pointer");
-    LA_CHECK_ARG(batch > 0 && frames > 0 && hidden > 0 && hidden % 64 == 0 && hidden <= 384, "gru_layer_bwd: hidden must be a multiple of 64, <= 384");
+    LA_CHECK_ARG(batch > 0 && frames > 0 && hidden > 0, "gru_layer_bwd: bad sizes");
+    // the exchange buffers are read with 16-byte loads: dgh by gru_bwd_kernel, the workspace ring by gru_bwd_x2_kernel
+    LA_CHECK_ARG((uintptr_t)dgh % 16 == 0 && (uintptr_t)workspace % 16 == 0, "gru_layer_bwd: alignment");
     size_t need = 0;
     la_gru_workspace_bytes(batch, frames, hidden, &need);
-    LA_CHECK_ARG(workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, "gru_layer_bwd: workspace too small");
+    LA_CHECK_ARG(workspace_bytes >= need, "gru_layer_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
+    if (hidden % 64 != 0 || hidden > 384) {                   // a valid argument outside what the kernels are built for: as in gru_forward
+        la::set_error("gru_layer_bwd: hidden=%d unsupported (multiple of 64, <= 384)", hidden);
+        return LA_EUNSUPPORTED;
+    }
     const int groups = gru_groups(batch);
     // default: the f16x2 product with the reduce-scatter granule hand-off (gru_bwd_x2_kernel); option gru_handoff = 1 keeps the
     // float32-MFMA all-gather kernel below (the A/B partner).  <= 4 clips stay on it too: its v_fma path beats a 16-row MFMA tile there.
@@ -1520,7 +1526,10 @@ extern "C" int la_gru_layer_bwd(const float *gates, const float *out, const floa
         return LA_OK;
     }
     const int nsplit = hidden / 32;
-    LA_CHECK_ARG(nsplit * 2 * groups <= 224, "gru_layer_bwd: batch too large for one co-resident launch");
+    if (nsplit * 2 * groups > 224) {
+        la::set_error("gru_layer_bwd: %d co-resident workgroups needed (batch too large for one launch; split the batch)", nsplit * 2 * groups);
+        return LA_EUNSUPPORTED;
+    }
     LA_CHECK_ARG((int64_t)batch * frames * 2 * 3 * hidden * 4 < (int64_t)2147483647, "gru_layer_bwd: dgh exceeds the 2 GiB buffer-descriptor range");
     LA_HIP(hipMemsetAsync(workspace, 0, need, stream));
     GruBwdParams p{gates, out, dout, w_hh, dgi, dgh, batch, frames, hidden,
