@@ -1,24 +1,31 @@
 // la_gru.hip -- persistent bidirectional GRU recurrence (nn.GRU, gate order r,z,n;
 // module/align_model.py:23-28,36).  The input projections W_ih x + b_ih of both directions are one
-// big GEMM (la_gemm) done beforehand; this kernel runs the T strictly sequential steps
+// big GEMM (la_gemm) done beforehand; the kernels here run the T strictly sequential steps
 //     r = sigmoid(gi_r + W_hr h + b_hr)      z = sigmoid(gi_z + W_hz h + b_hz)
 //     n = tanh(gi_n + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
-// for both directions at once.
+// for both directions at once, and the backward sweep of the same recurrence.
 //
 // Decomposition (DESIGN.md "GRU"): W_hh of one direction (3H x H) does not fit one CU, so the H
 // hidden units are split over H/(16*NW) workgroups per direction; each of a workgroup's NW waves
 // owns 16 hidden units and keeps the 48 matching rows of W_hh RESIDENT for the whole sequence
-// (bf16: in VGPRs as MFMA B-fragments; f32: in LDS), so a step costs only the h exchange.  Per step
-// a wave computes [batch x H] * [H x 48] with MFMA 16x16 tiles (batch on the rows), applies the
-// gates lane-locally (the r/z/n accumulators share one layout), writes its h slice into `out`
-// (which IS the exchange buffer: the next layer / the FC read it anyway) and signals a per-step
-// arrival counter.  Hand-off (cdna guide, Guideline 16), default = the write-through form: every
-// handed-off byte is stored sc1 -> every wave vmcnt(0) -> barrier -> lane 0 relaxed agent-scope
-// counter add; consumers poll the counter with sc1 loads, pass a barrier, then read with sc1 loads
-// only.  LA_GRU_FENCE=1 selects the release / acquire form instead (plain stores -> vmcnt(0) ->
-// barrier -> lane 0 release fence -> counter add; one lane acquires, barrier, plain loads), 1.7x
-// slower per step.  Every wait is bounded.
+// (16-bit and f16x2: in VGPRs as MFMA B-fragments; f32: in LDS), so a step costs only the h exchange.
+// Per step a wave computes [16 clips x H] * [H x 48] with MFMA 16x16 tiles (clips on the rows), applies
+// the gates lane-locally (the r/z/n accumulators share one layout) and hands its h slice on.
 // Clips are independent, so batches larger than 16 become extra workgroup groups (grid.z).
+//
+// Layout of this file:
+//   * GruFwdParams / GruBwdParams: one parameter block per sweep direction; members a kernel does not use are null / 0.  The member
+//     ORDER is part of the tuning: hipcc groups the kernel-argument loads by offset, and another order changed gru_kernel's SGPR spills
+//     and instruction counts with its text untouched (profiles/gru_refactor.txt, section 1).  Add members at the end.
+//   * five kernels, one batch tile (16 clips) per workgroup each: gru_kernel (counter hand-off; write-through by default, option
+//     gru_fence = 1 the release / acquire form), gru_granule_kernel (16-bit, the data is the flag), gru_train_x2_kernel (float32 on
+//     the f16 pipe, granules), gru_bwd_kernel (float32 MFMA, counters), gru_bwd_x2_kernel (f16 pipe, reduce-scatter granules).
+//     Every wait is bounded.  The step's arithmetic (load_gi, the cell, the epilogue stores) and the granule poll keep one text per
+//     kernel, and gru_kernel keeps its batch-tile parameter MT (only MT = 1 is instantiated): these kernels sit at 247 - 256 of 256
+//     registers per wave, and shared helper functions for those pieces changed their register use and schedules
+//     (profiles/gru_refactor.txt, section 4).
+//   * the host side: one launch table for the forward kernels (kFwdRows), gru_forward behind la_gru_layer / la_gru_layer_ragged /
+//     la_gru_layer_train_fwd, and la_gru_layer_bwd.
 #include <algorithm>
 #include <type_traits>
 
@@ -31,26 +38,48 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
-constexpr int GROUP = 16;      // clips per workgroup group = one 16-row MFMA batch tile (MT = 1).  32-clip groups (MT = 2: two batch
-                               // tiles per workgroup, kept as a template parameter) halve the workgroups but every step then does
+constexpr int GROUP = 16;      // clips per workgroup group = one 16-row MFMA batch tile.  32-clip groups (two batch tiles per workgroup,
+                               // MT = 2 of gru_kernel: never instantiated) halve the workgroups but every step then does
                                // twice the MFMAs, gates and exchange bytes on its critical path: 4.40 vs 3.62 us per step at 32
                                // clips.  More clips = more groups running side by side on other CUs, not longer steps.
 
-struct GruParams {
+struct GruFwdParams {
     const float *gi;     // [B][T][2][3H]
     const void *w_hh;    // [2][3H][H]
     const float *b_hh;   // [2][3H]
-    void *out;           // [B][T][2H]
+    void *out;           // [B][T][2H]; the counter form's exchange buffer
     void *out_mish;      // optional
     int B, T, H;
-    unsigned *counters;  // [groups][2][T] arrival counters, zeroed per call
+    union {              // the hand-off buffer behind the workspace header, zeroed per call:
+        unsigned *counters;        // counter form: [groups][2][T] arrival counters
+        unsigned long long *xch;   // granule forms: [groups][2 dirs][2 slots][16 clips][H / 2 (16-bit) or H (f16x2)] granules
+    };
     int *abort_flag;     // workspace word, zeroed per call
     int *timeout_flag;   // caller's (optional)
-    int nsplit;
+    int nsplit;          // counter form: arrivals per step
+    int poll_delay;      // 16-bit granule form: 64-clock sleeps between a step's publish and its first poll (option gru_poll_delay)
     float *gates;        // optional [B][T][2][4H] f32: r, z, n, (W_hn h + b_hn) of every step, for the backward sweep
-    unsigned long long poll_budget = 300000000ull;   // bound of one inter-workgroup wait in 100 MHz ticks (option gru_timeout_us; default 3 s)
-    int fault_step = 0;  // test hook (option gru_fault_step, one launch): workgroup (0, 0, 0) leaves at this step without publishing, as if it had never become resident
-    const int *n_frames = nullptr;   // RAGGED instantiations: [B] frames of each clip (<= T); at steps with t >= n_frames[b] clip b's h is exactly 0
+    unsigned long long poll_budget;   // bound of one inter-workgroup wait in 100 MHz ticks (option gru_timeout_us; default 3 s)
+    int fault_step;      // test hook (option gru_fault_step, one launch): workgroup (0, 0, 0) leaves at this step without publishing, as if it had never become resident
+    const int *n_frames; // RAGGED instantiations: [B] frames of each clip (<= T); at steps with t >= n_frames[b] clip b's h is exactly 0
+};
+
+struct GruBwdParams {
+    const float *gates;  // [B][T][2][4H]
+    const float *out;    // [B][T][2H]  h_t of the forward pass
+    const float *dout;   // [B][T][2H]  gradient w.r.t. the layer output
+    const float *w_hh;   // [2][3H][H]
+    float *dgi;          // [B][T][2][3H]  gradient w.r.t. the input projections (W_ih x + b_ih)
+    float *dgh;          // [B][T][2][3H]  gradient w.r.t. the recurrent projections (W_hh h + b_hh); the counter form's exchange buffer
+    int B, T, H;
+    union {              // the hand-off buffer behind the workspace header, zeroed per call:
+        unsigned *counters;        // counter form
+        unsigned long long *xch;   // granule form: [groups][2 dirs][2 slots][NS dest][NS src][16 clips][64 units] granules
+    };
+    int *abort_flag;
+    int *timeout_flag;
+    unsigned long long poll_budget;
+    int nsplit;          // counter form: arrivals per step
 };
 
 // Gate non-linearities on the hardware exponential / reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each).  The libm forms
@@ -77,7 +106,6 @@ __device__ __forceinline__ unsigned short round16(float v) {
     la::Elem<T>::store(&h, v);
     return __builtin_bit_cast(unsigned short, h);
 }
-
 // bounded wait for `*ctr >= target`; returns false on timeout / abort
 __device__ __forceinline__ bool wait_counter(unsigned *ctr, unsigned target, int *abort_flag, unsigned long long budget = 300000000ull) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
@@ -97,17 +125,14 @@ __device__ __forceinline__ bool wait_counter(unsigned *ctr, unsigned target, int
 
 template <typename T> struct GruTraits;
 template <> struct GruTraits<bf16_t> {
-    static constexpr int NW = 4;        // waves per workgroup
     static constexpr int KSTEP = 32;    // k elements per 16-byte-per-lane fragment step
     static constexpr bool W_IN_REGS = true;
 };
 template <> struct GruTraits<la::f16_t> {
-    static constexpr int NW = 4;
     static constexpr int KSTEP = 32;
     static constexpr bool W_IN_REGS = true;
 };
 template <> struct GruTraits<float> {
-    static constexpr int NW = 2;
     static constexpr int KSTEP = 16;
     static constexpr bool W_IN_REGS = false;
 };
@@ -126,12 +151,21 @@ __device__ __forceinline__ void mma_step(const uint4 &a, const uint4 &w, f32x4 &
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(w.w), acc, 0, 0, 0);
 }
 
+__device__ __forceinline__ unsigned x2_pack_hi_lo(float x) {          // x (already scaled) -> f16 hi | f16 lo << 16
+    const _Float16 h = (_Float16)x;
+    const _Float16 l = (_Float16)(x - (float)h);
+    return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
+}
+// ---------------------------------------------------------------------------------------------------------------
+// Counter hand-off form: h travels through `out` itself (the next layer / the FC read it anyway).
 // MAXKS: compile-time bound on H / KSTEP (register-resident W for bf16: H <= 512)
 // WT: write-through hand-off (cdna guide G16, valid-forms row 1): h is stored with sc1 (write-through) 4-byte stores,
 //     every storing wave drains vmcnt, one lane signals with a relaxed agent-scope add; consumers poll that counter with
 //     an sc1 load, pass a workgroup barrier and read h with sc1 16-byte buffer loads only -> no release / acquire fence
 //     (each costs ~1.7 us per step here).  WT = true is the default; LA_GRU_FENCE=1 selects the fence form (WT = false).
-// NW: waves per workgroup.  16-bit modes: 8 where hidden is a multiple of 128 (two waves per SIMD at <= 256 registers each: a
+// MT: batch tiles per workgroup.  Only MT = 1 is instantiated (see GROUP); the parameter stays in this kernel's text because without it all sixteen
+//     16-bit instantiations compile to other register use and schedules than the measured ones (profiles/gru_refactor.txt, section 4).
+// NW: waves per workgroup: 2 in float32.  16-bit modes: 4, or 8 where hidden is a multiple of 128 (two waves per SIMD at <= 256 registers each: a
 //     wave's W_hh slice is 12 * MAXKS registers, 144 at hidden <= 384) -- one (direction, 16-clip group) is then hidden / 128
 //     workgroups = CUs instead of hidden / 64: the resident recurrence takes 24 instead of 48 CUs from the encoder's GEMMs at 64
 //     clips, and a step's hand-off has 3 instead of 6 participants.  (768-thread workgroups -- 16 CUs -- do not fit: three waves
@@ -141,8 +175,8 @@ __device__ __forceinline__ void mma_step(const uint4 &a, const uint4 &w, f32x4 &
 //     whatever the inputs of those frames hold (NaN included) never reaches a frame t < n_frames[clip]: the reverse direction enters
 //     frame n_frames - 1 with h = 0 as if the clip had been launched alone; the forward direction's rows t < n_frames never read later
 //     ones.  The lengths are read once per lane before the loop.  The dense instantiations (RAGGED = false) compile to what they were.
-template <typename T, int MAXKS, bool WT, int MT, int NW = GruTraits<T>::NW, bool RAGGED = false>
-__global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruParams p) {
+template <typename T, int MAXKS, bool WT, int MT, int NW, bool RAGGED>
+__global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruFwdParams p) {
     typedef GruTraits<T> TR;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int slice = blockIdx.x, dir = blockIdx.y, group = blockIdx.z;
@@ -460,7 +494,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Granule hand-off form of the 16-bit recurrence (8-wave workgroups, MT = 1): the data IS the flag.
+// Granule hand-off form of the 16-bit recurrence (8-wave workgroups): the data IS the flag.
 // The counter form above pays four dependent memory round trips per step -- producers' write-through stores are drained
 // (vmcnt(0)), a barrier, one lane's counter add; the consumer's poll sees the add, a barrier, THEN the h loads go out.  Here
 // every pair of hidden units leaves as ONE naturally aligned 8-byte sc1 store {h[c][2j], h[c][2j+1] | tag = step + 1}
@@ -471,26 +505,11 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_kernel(GruParams p) {
 // only after it has consumed every other workgroup's step t + 1, which those produce only after they have read step t.
 // `out` (the layer's result for the next GEMM / the FC) is written with plain stores off the critical path.
 // Every wait is bounded (abort flag + 3 s).
-struct GruGranuleParams {
-    const float *gi;
-    const void *w_hh;
-    const float *b_hh;
-    void *out, *out_mish;
-    int B, T, H;
-    unsigned long long *xch;   // [groups][2 dirs][2 slots][16 clips][H / 2] granules, zeroed per call
-    int *abort_flag, *timeout_flag;
-    int nsplit;
-    int poll_delay;            // 64-clock sleeps between a step's publish and its first poll (option gru_poll_delay)
-    unsigned long long poll_budget = 300000000ull;
-    int fault_step = 0;
-    const int *n_frames = nullptr;   // RAGGED: see GruParams
-};
-
 #ifndef LA_GRU_PROBE
 #define LA_GRU_PROBE 0      // experiment build: timing-only knock-outs (1 = no gi loads after step 0, 2 = no out / out_mish stores)
 #endif
 template <typename T, int MAXKS, bool RAGGED = false>    // RAGGED: per-clip lengths, as in gru_kernel
-__global__ __launch_bounds__(512, 1) void gru_granule_kernel(GruGranuleParams p) {
+__global__ __launch_bounds__(512, 1) void gru_granule_kernel(GruFwdParams p) {
     constexpr int NW = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int slice = blockIdx.x, dir = blockIdx.y, group = blockIdx.z;
@@ -665,26 +684,10 @@ __global__ __launch_bounds__(512, 1) void gru_granule_kernel(GruGranuleParams p)
 // kernel's per-wave operand loads replaced by the granule hand-off of gru_granule_kernel: h travels as 8-byte
 // {h_hi | h_lo, step tag} granules, polled by the consumers, staged once per workgroup into LDS.
 // 4-wave workgroups (one wave per SIMD: 512 registers; the two W fragment sets are 288), 64 hidden units each.
-struct GruTrainX2Params {
-    const float *gi, *w_hh, *b_hh;
-    float *out, *gates;        // gates NULL: inference (float32 la_gru_layer on the f16x2 products), nothing but the layer output is stored
-    float *out_mish;           // optional: Mish(out), the head's last layer (module/align_model.py:36-37)
-    int B, T, H;
-    unsigned long long *xch;   // [groups][2 dirs][2 slots][16 clips][H] granules, zeroed per call
-    int *abort_flag, *timeout_flag;
-    unsigned long long poll_budget = 300000000ull;
-    int fault_step = 0;
-    const int *n_frames = nullptr;   // RAGGED: see GruParams
-};
-
-__device__ __forceinline__ unsigned x2_pack_hi_lo(float x) {          // x (already scaled) -> f16 hi | f16 lo << 16
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
-}
-
+// gates NULL: inference (float32 la_gru_layer on the f16x2 products), nothing but the layer output (and its optional Mish, the head's
+// last layer, module/align_model.py:36-37) is stored.
 template <int MAXKS, bool RAGGED = false>                // RAGGED (inference only, gates == NULL): per-clip lengths, as in gru_kernel
-__global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p) {
+__global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruFwdParams p) {
     constexpr int NW = 4;
     typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -696,7 +699,8 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p
     const int jcol = (slice * NW + wave) * 16 + r16;
     const int b0 = group * GROUP;
     const int nb = min(GROUP, p.B - b0);
-    const float *Wd = p.w_hh + (int64_t)dir * 3 * H * H;
+    const float *Wd = reinterpret_cast<const float *>(p.w_hh) + (int64_t)dir * 3 * H * H;
+    float *out = reinterpret_cast<float *>(p.out), *outm = reinterpret_cast<float *>(p.out_mish);
     const float *bh = p.b_hh + dir * 3 * H;
     const int64_t out_bs = (int64_t)T_ * 2 * H, out_ts = 2 * H;
     const int64_t gi_bs = (int64_t)T_ * 6 * H, gi_ts = 6 * H;
@@ -853,8 +857,8 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p
             const int bl = 4 * q + i;
             if (bl < nb) {
                 const int64_t o = (int64_t)(b0 + bl) * out_bs + (int64_t)t * out_ts + dir * H + jcol;
-                p.out[o] = hnew[i];
-                if (p.out_mish) p.out_mish[o] = mish_fast(hnew[i]);
+                out[o] = hnew[i];
+                if (outm) outm[o] = mish_fast(hnew[i]);
                 if (p.gates) {
                     float *gp = p.gates + (((int64_t)(b0 + bl) * T_ + t) * 2 + dir) * 4 * H + jcol;
                     gp[0] = gr[i]; gp[H] = gz[i]; gp[2 * H] = gn[i]; gp[3 * H] = ghn[i];
@@ -865,210 +869,11 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruTrainX2Params p
     if (!alive && tid == 0 && p.timeout_flag) *p.timeout_flag = 1;
 }
 
-}  // namespace
-
-static int gru_groups(int batch) { return la::cdiv(batch, GROUP); }
-static size_t gru_ctr_bytes(int batch, int frames) { return (size_t)la::round_up(16 + (int64_t)gru_groups(batch) * 2 * frames * 4, 256); }
-// granule exchange ring behind the counters: [groups][2][2 slots][16][granules per clip row] x 8 bytes
-// (sized for the largest user: the backward sweep's reduce-scatter blocks, (hidden / 64)^2 pairs of 16 x 64 granules per slot; the float32
-//  training forward uses 16 x hidden granules per slot, the 16-bit inference form half of that)
-static size_t gru_xch_fwd_bytes(int batch, int hidden) { return (size_t)gru_groups(batch) * 2 * 2 * 16 * hidden * 8; }
-static size_t gru_xch_bwd_bytes(int batch, int hidden) { return (size_t)gru_groups(batch) * 2 * 2 * (hidden / 64) * (hidden / 64) * 16 * 64 * 8; }
-static size_t gru_xch_bytes(int batch, int hidden) { return std::max(gru_xch_fwd_bytes(batch, hidden), hidden % 64 == 0 ? gru_xch_bwd_bytes(batch, hidden) : (size_t)0); }
-
-extern "C" int la_gru_workspace_bytes(int32_t batch, int32_t frames, int32_t hidden, size_t *bytes) {
-    LA_CHECK_ARG(bytes && batch > 0 && frames > 0 && hidden > 0, "gru_workspace_bytes: bad arguments");
-    // [16 B header: abort flag] + counters [groups][2][frames] u32, padded to 256 B + the granule exchange ring
-    *bytes = gru_ctr_bytes(batch, frames) + gru_xch_bytes(batch, hidden);
-    return LA_OK;
-}
-
-// gates != nullptr: the training forward (float32) also stores r, z, n and W_hn h + b_hn of every step
-static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
-                       int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
-                       int32_t *timeout_flag, float *gates, void *stream_, const int32_t *n_frames = nullptr) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (batch == 0 || frames == 0) return LA_OK;
-    LA_CHECK_ARG(gi && w_hh && b_hh && out && workspace, "gru_layer: null pointer");
-    LA_CHECK_ARG(dtype == LA_F32 || dtype == LA_BF16 || dtype == LA_F16, "gru_layer: bad dtype");
-    LA_CHECK_ARG(batch > 0 && frames > 0 && hidden > 0, "gru_layer: bad sizes");
-    LA_CHECK_ARG((uintptr_t)w_hh % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)workspace % 16 == 0, "gru_layer: alignment");
-    size_t need = 0;
-    la_gru_workspace_bytes(batch, frames, hidden, &need);
-    LA_CHECK_ARG(workspace_bytes >= need, "gru_layer: workspace too small (%zu < %zu)", workspace_bytes, need);
-    const int groups = gru_groups(batch);
-    const unsigned long long budget = la::opts().gru_timeout_us > 0 ? (unsigned long long)la::opts().gru_timeout_us * 100ull : 300000000ull;
-    const int fault = la::opts().gru_fault_step;              // one-shot test hook: the launch that reads it clears it
-    if (fault) la::opts().gru_fault_step = 0;
-    if (hidden % 64 != 0 || (dtype != LA_F32 && hidden > 512) || (dtype == LA_F32 && hidden > 384)) {
-        la::set_error("gru_layer: hidden=%d unsupported (multiple of 64; bf16 <= 512, f32 <= 384)", hidden);
-        return LA_EUNSUPPORTED;
-    }
-    // 16-bit modes: 8-wave workgroups (128 hidden units each) where hidden allows; LA_GRU_NW=4 keeps the 4-wave form (A/B)
-    const bool force_nw4 = la::opts().gru_nw == 4;
-    const bool wide = dtype != LA_F32 && hidden % 128 == 0 && hidden <= 384 && !force_nw4;   // (a 192-register W slice spills at 256)
-    const int nw = dtype == LA_F32 ? 2 : (wide ? 8 : 4);
-    const int nsplit = hidden / (16 * nw);
-    if (nsplit * 2 * groups > 224) {
-        la::set_error("gru_layer: %d co-resident workgroups needed (batch too large for one launch; split the batch)", nsplit * 2 * groups);
-        return LA_EUNSUPPORTED;
-    }
-    // float32 training forward (gates stored): recurrent product as f16x2 with the granule hand-off (gru_train_x2_kernel); option
-    // gru_handoff = 1 keeps gru_kernel<float> (float32 MFMA, counter form): the A/B partner
-    // (inference, gates == NULL: the same kernel without the gate stores where option x2_inference is on and more than 4 clips share the launch --
-    //  la_align_head_forward's float32 route; a handful of clips keeps gru_kernel<float>, whose v_fma path is faster there)
-    if (dtype == LA_F32 && (gates || (la::opts().x2_inference && batch > 4)) && hidden % 64 == 0 && hidden <= 384 && la::opts().gru_handoff == 0 &&
-        la::opts().gru_fence == 0 && (hidden / 64) * 2 * groups <= 224) {
-        unsigned char *wsb = reinterpret_cast<unsigned char *>(workspace);
-        const size_t ctrb = gru_ctr_bytes(batch, frames);
-        LA_HIP(hipMemsetAsync(wsb, 0, 16, stream));
-        LA_HIP(hipMemsetAsync(wsb + ctrb, 0, gru_xch_fwd_bytes(batch, hidden), stream));
-        GruTrainX2Params tp{gi, reinterpret_cast<const float *>(w_hh), b_hh, reinterpret_cast<float *>(out), gates, reinterpret_cast<float *>(out_mish), batch, frames, hidden,
-                            reinterpret_cast<unsigned long long *>(wsb + ctrb), reinterpret_cast<int *>(workspace), timeout_flag, budget, fault, n_frames};
-        const size_t lds_t = 16 + (size_t)2 * 2 * 16 * (hidden * 2 + 16);
-        la::TimerScope ts("gru_f32", stream);
-        if (n_frames) hipLaunchKernelGGL((gru_train_x2_kernel<12, true>), dim3(hidden / 64, 2, groups), dim3(256), lds_t, stream, tp);
-        else hipLaunchKernelGGL((gru_train_x2_kernel<12>), dim3(hidden / 64, 2, groups), dim3(256), lds_t, stream, tp);
-        LA_LAUNCH_CHECK();
-        return LA_OK;
-    }
-    // 16-bit recurrence in 8-wave workgroups: the granule hand-off (option gru_handoff = 0, default) or the counter form (1)
-    // (measured, tools/kbench.py gru: 3.28 against 3.38 us per step at 32 - 64 clips, level at 16, 2.86 against 2.64 at one clip -- the counter
-    //  form keeps the single 16-clip group; gru_handoff = 2 forces granules for every batch)
-    const bool granules = wide && !gates && la::opts().gru_fence == 0 && hidden % 128 == 0 &&
-                          (la::opts().gru_handoff == 2 || (la::opts().gru_handoff == 0 && batch > 16));
-    if (granules) {
-        LA_CHECK_ARG(frames < 0x7fffffff, "gru_layer: too many frames");
-        unsigned char *wsb = reinterpret_cast<unsigned char *>(workspace);
-        const size_t ctrb = gru_ctr_bytes(batch, frames);
-        LA_HIP(hipMemsetAsync(wsb, 0, 16, stream));
-        LA_HIP(hipMemsetAsync(wsb + ctrb, 0, gru_xch_fwd_bytes(batch, hidden), stream));
-        GruGranuleParams gp{gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, reinterpret_cast<unsigned long long *>(wsb + ctrb),
-                            reinterpret_cast<int *>(workspace), timeout_flag, nsplit, la::opts().gru_poll_delay, budget, fault, n_frames};
-        const size_t lds_g = 16 + (size_t)2 * 16 * (hidden * 2 + 16);          // flag + two h stages
-        la::TimerScope ts("gru_bf16", stream);
-        if (n_frames) {
-            if (dtype == LA_F16) hipLaunchKernelGGL((gru_granule_kernel<la::f16_t, 12, true>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
-            else hipLaunchKernelGGL((gru_granule_kernel<bf16_t, 12, true>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
-        } else
-        if (dtype == LA_F16) hipLaunchKernelGGL((gru_granule_kernel<la::f16_t, 12>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
-        else hipLaunchKernelGGL((gru_granule_kernel<bf16_t, 12>), dim3(nsplit, 2, groups), dim3(512), lds_g, stream, gp);
-        LA_LAUNCH_CHECK();
-        return LA_OK;
-    }
-    LA_HIP(hipMemsetAsync(workspace, 0, gru_ctr_bytes(batch, frames), stream));
-    GruParams p{gi, w_hh, b_hh, out, out_mish, batch, frames, hidden,
-                reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(workspace) + 16),
-                reinterpret_cast<int *>(workspace), timeout_flag, nsplit, gates, budget, fault, n_frames};
-    const dim3 grid(nsplit, 2, groups);
-    // Hand-off forms (tools/kbench.py gru, 32 clips, T=1500, H=384; tools/handoff_bench.hip for the bare protocol costs):
-    // write-through (sc1 stores, drained; relaxed counter; sc1 loads) 5.4 ms per layer, release / acquire fences 9.0 ms.
-    // The write-through form is the default; LA_GRU_FENCE=1 selects the fence form.
-    const bool use_fence = la::opts().gru_fence != 0;
-    LA_CHECK_ARG((int64_t)batch * frames * 2 * hidden * (dtype == LA_F32 ? 4 : 2) < (int64_t)2147483647, "gru_layer: out buffer exceeds the 2 GiB buffer-descriptor range");
-    if (dtype == LA_BF16 || dtype == LA_F16) {
-        la::TimerScope ts("gru_bf16", stream);
-        const int mt = (batch <= 16 || GROUP == 16) ? 1 : 2;
-        const size_t lds_b = 16 + (size_t)16 * mt * (hidden * 2 + 16);          // flag + the staged h rows of the batch tiles
-        // MAXKS = the W slice's compile-time k-steps: 12 with 8 waves (hidden <= 384, 144 registers), 16 with 4 (hidden <= 512, 192)
-#define LA_GRU_LAUNCH16_(T_, KS_, NW_)                                                                                     \
-    do {                                                                                                                   \
-        if (n_frames) {      /* per-clip lengths: one batch tile per workgroup (GROUP = 16), both hand-off forms */            \
-            if (use_fence) hipLaunchKernelGGL((gru_kernel<T_, KS_, false, 1, NW_, true>), grid, dim3(NW_ * 64), lds_b, stream, p); \
-            else hipLaunchKernelGGL((gru_kernel<T_, KS_, true, 1, NW_, true>), grid, dim3(NW_ * 64), lds_b, stream, p);    \
-        } else if (mt == 1) {                                                                                              \
-            if (use_fence) hipLaunchKernelGGL((gru_kernel<T_, KS_, false, 1, NW_>), grid, dim3(NW_ * 64), lds_b, stream, p); \
-            else hipLaunchKernelGGL((gru_kernel<T_, KS_, true, 1, NW_>), grid, dim3(NW_ * 64), lds_b, stream, p);          \
-        } else {                                                                                                           \
-            if (use_fence) hipLaunchKernelGGL((gru_kernel<T_, KS_, false, 2, NW_>), grid, dim3(NW_ * 64), lds_b, stream, p); \
-            else hipLaunchKernelGGL((gru_kernel<T_, KS_, true, 2, NW_>), grid, dim3(NW_ * 64), lds_b, stream, p);          \
-        }                                                                                                                  \
-    } while (0)
-#define LA_GRU_LAUNCH16(T_)                                                                                                \
-    do {                                                                                                                   \
-        if (wide) LA_GRU_LAUNCH16_(T_, 12, 8);                                                                             \
-        else LA_GRU_LAUNCH16_(T_, 16, 4);                                                                                  \
-    } while (0)
-        if (dtype == LA_F16) LA_GRU_LAUNCH16(la::f16_t); else LA_GRU_LAUNCH16(bf16_t);
-#undef LA_GRU_LAUNCH16
-#undef LA_GRU_LAUNCH16_
-    } else {
-        const size_t lds_bytes = 16 + (size_t)2 * 3 * 16 * hidden * 4;
-        static la::DeviceOnce attr_once;
-        if (attr_once.pending()) {
-            const int max_lds = 16 + 2 * 3 * 16 * 384 * 4;
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, false, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_kernel<float, 24, true, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            attr_once.mark();
-        }
-        la::TimerScope ts("gru_f32", stream);
-        if (n_frames) {
-            if (use_fence) hipLaunchKernelGGL((gru_kernel<float, 24, false, 1, 2, true>), grid, dim3(128), lds_bytes, stream, p);
-            else hipLaunchKernelGGL((gru_kernel<float, 24, true, 1, 2, true>), grid, dim3(128), lds_bytes, stream, p);
-        } else if (batch <= 16 || GROUP == 16) {
-            if (use_fence) hipLaunchKernelGGL((gru_kernel<float, 24, false, 1>), grid, dim3(128), lds_bytes, stream, p);
-            else hipLaunchKernelGGL((gru_kernel<float, 24, true, 1>), grid, dim3(128), lds_bytes, stream, p);
-        } else {
-            if (use_fence) hipLaunchKernelGGL((gru_kernel<float, 24, false, 2>), grid, dim3(128), lds_bytes, stream, p);
-            else hipLaunchKernelGGL((gru_kernel<float, 24, true, 2>), grid, dim3(128), lds_bytes, stream, p);
-        }
-    }
-    LA_LAUNCH_CHECK();
-    return LA_OK;
-}
-
-extern "C" int la_gru_layer(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
-                            int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
-                            int32_t *timeout_flag, void *stream) {
-    return gru_forward(dtype, gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, nullptr, stream);
-}
-
-// Per-clip lengths: n_frames [batch] (device), 1 <= n_frames[b] <= frames.  Rows t < n_frames[b] of clip b are what la_gru_layer gives for
-// that clip alone over n_frames[b] frames; rows past them are unspecified.  Every clip of the launch takes `frames` steps.
-extern "C" int la_gru_layer_ragged(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
-                                   int32_t batch, int32_t frames, const int32_t *n_frames, int32_t hidden, void *workspace,
-                                   size_t workspace_bytes, int32_t *timeout_flag, void *stream) {
-    LA_CHECK_ARG(n_frames || batch == 0 || frames == 0, "gru_layer_ragged: n_frames missing");
-    static_assert(GROUP == 16, "the ragged instantiations are the one-batch-tile forms");
-    return gru_forward(dtype, gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, nullptr, stream, n_frames);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// training face (fine-tune row, float32 like the reference): forward that also stores the gates, and the backward sweep
-// ---------------------------------------------------------------------------------------------------------------
-extern "C" int la_gru_layer_train_fwd(const float *gi, const float *w_hh, const float *b_hh, float *out, float *gates,
-                                      int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
-                                      int32_t *timeout_flag, void *stream) {
-    LA_CHECK_ARG(gates || batch == 0 || frames == 0, "gru_layer_train_fwd: gates buffer missing");
-    return gru_forward(LA_F32, gi, w_hh, b_hh, out, nullptr, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, gates, stream);
-}
-
-namespace {
-
-struct GruBwdParams {
-    const float *gates;  // [B][T][2][4H]
-    const float *out;    // [B][T][2H]  h_t of the forward pass
-    const float *dout;   // [B][T][2H]  gradient w.r.t. the layer output
-    const float *w_hh;   // [2][3H][H]
-    float *dgi;          // [B][T][2][3H]  gradient w.r.t. the input projections (W_ih x + b_ih)
-    float *dgh;          // [B][T][2][3H]  gradient w.r.t. the recurrent projections (W_hh h + b_hh); also the exchange buffer
-    int B, T, H;
-    unsigned *counters;
-    int *abort_flag;
-    int *timeout_flag;
-    int nsplit;
-    unsigned long long poll_budget = 300000000ull;
-};
-
 // Backward recurrence dh_{t-1} = dh_t * z_t + dgh_t W_hh: the contraction runs over all 3H gate units, so (as in the
 // forward kernel) the H hidden units are split over workgroups, each wave keeps its 16 columns of W_hh (as W_hh^T rows,
 // [16][3H] f32 = 72 KiB) resident in LDS, and dgh of the previous step is exchanged through HBM with the same
 // write-through (sc1) hand-off.  2 waves per workgroup, H/32 workgroups per direction.
-template <int MT>
 __global__ __launch_bounds__(128, 1) void gru_bwd_kernel(GruBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int NW = 2;
@@ -1101,35 +906,25 @@ __global__ __launch_bounds__(128, 1) void gru_bwd_kernel(GruBwdParams p) {
     const __amdgpu_buffer_rsrc_t dgh_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         p.dgh, 0, (int)((int64_t)p.B * T_ * 2 * g3 * 4), 0x00020000);
 
-    float carry[MT][4];   // dh_t * z_t of the step processed before (the direct path of the recurrence)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) carry[mt][i] = 0.f;
-    int arow[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) arow[mt] = b0 + min(mt * 16 + r16, nb - 1);
+    float carry[4] = {0.f, 0.f, 0.f, 0.f};   // dh_t * z_t of the step processed before (the direct path of the recurrence)
+    const int arow = b0 + min(r16, nb - 1);
 
     bool alive = true;
     for (int step = 0; step < T_; ++step) {
         const int t = dir == 0 ? T_ - 1 - step : step;          // reverse of the forward scan order
         const int tnext = dir == 0 ? t + 1 : t - 1;              // processed in the previous iteration
         const int tprev = dir == 0 ? t - 1 : t + 1;              // the forward pass's previous step (h_{t-1})
-        f32x4 acc[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         // this step's saved gates, h_{t-1} and upstream gradient do not depend on the hand-off: requested before the wait
-        float g_r[MT][4], g_z[MT][4], g_n[MT][4], g_hn[MT][4], g_hp[MT][4], g_do[MT][4];
+        float g_r[4], g_z[4], g_n[4], g_hn[4], g_hp[4], g_do[4];
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int b = b0 + min(mt * 16 + 4 * q + i, nb - 1);
-                const float *gp = p.gates + (((int64_t)b * T_ + t) * 2 + dir) * g4 + kcol;
-                g_r[mt][i] = gp[0]; g_z[mt][i] = gp[H]; g_n[mt][i] = gp[2 * H]; g_hn[mt][i] = gp[3 * H];
-                g_hp[mt][i] = (tprev >= 0 && tprev < T_) ? p.out[((int64_t)b * T_ + tprev) * 2 * H + dir * H + kcol] : 0.f;
-                g_do[mt][i] = p.dout[((int64_t)b * T_ + t) * 2 * H + dir * H + kcol];
-            }
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + min(4 * q + i, nb - 1);
+            const float *gp = p.gates + (((int64_t)b * T_ + t) * 2 + dir) * g4 + kcol;
+            g_r[i] = gp[0]; g_z[i] = gp[H]; g_n[i] = gp[2 * H]; g_hn[i] = gp[3 * H];
+            g_hp[i] = (tprev >= 0 && tprev < T_) ? p.out[((int64_t)b * T_ + tprev) * 2 * H + dir * H + kcol] : 0.f;
+            g_do[i] = p.dout[((int64_t)b * T_ + t) * 2 * H + dir * H + kcol];
+        }
         if (step > 0) {
             if (tid == 0) {
                 const bool ok = wait_counter(ctr + (step - 1), (unsigned)p.nsplit, p.abort_flag, p.poll_budget);
@@ -1138,12 +933,10 @@ __global__ __launch_bounds__(128, 1) void gru_bwd_kernel(GruBwdParams p) {
             __syncthreads();
             alive = *ok_s != 0;
             if (!alive) break;
-            // dgh of the step before, 12 k-steps (12 x MT fragments) requested at a time: with one fragment per iteration the
+            // dgh of the step before, 12 k-steps (12 fragments) requested at a time: with one fragment per iteration the
             // loop was 3H/16 = 72 dependent L2 round trips per step (the whole 22.7 us of it).  3H/16 = 12 (H/64).
-            int arow_off[MT];            // byte offsets into dgh
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) arow_off[mt] = (int)(((((int64_t)arow[mt] * T_ + tnext) * 2 + dir) * g3) * 4) + q * 16;
-            if (MT == 1 && nb <= 4) {
+            const int arow_off = (int)(((((int64_t)arow * T_ + tnext) * 2 + dir) * g3) * 4) + q * 16;     // byte offset into dgh
+            if (nb <= 4) {
                 // <= 4 clips: v_fma on the lane's 4-k slices instead of 16-row f32 MFMAs (see the forward kernel)
                 auto small = [&](auto nbc) {
                     constexpr int NBV = decltype(nbc)::value;
@@ -1183,7 +976,7 @@ __global__ __launch_bounds__(128, 1) void gru_bwd_kernel(GruBwdParams p) {
                         float v = part[b];
                         v += __shfl_xor(v, 16);
                         v += __shfl_xor(v, 32);
-                        acc[0][b] = v;
+                        acc[b] = v;
                     }
                 };
                 if (nb == 1) small(std::integral_constant<int, 1>{});
@@ -1192,45 +985,40 @@ __global__ __launch_bounds__(128, 1) void gru_bwd_kernel(GruBwdParams p) {
                 else small(std::integral_constant<int, 4>{});
             } else
             for (int kb = 0; kb < nks; kb += 12) {
-                uint4 a[12][MT];
+                uint4 a[12];
 #pragma unroll
-                for (int u = 0; u < 12; ++u)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-                        const u32x4 t4 = __builtin_amdgcn_raw_buffer_load_b128(dgh_rsrc, arow_off[mt] + (kb + u) * 64, 0, 16 /* sc1 */);
-                        a[u][mt] = make_uint4(t4[0], t4[1], t4[2], t4[3]);
-                    }
+                for (int u = 0; u < 12; ++u) {
+                    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+                    const u32x4 t4 = __builtin_amdgcn_raw_buffer_load_b128(dgh_rsrc, arow_off + (kb + u) * 64, 0, 16 /* sc1 */);
+                    a[u] = make_uint4(t4[0], t4[1], t4[2], t4[3]);
+                }
 #pragma unroll
                 for (int u = 0; u < 12; ++u) {
                     const int ks = kb + u;
                     const uint4 w = *reinterpret_cast<const uint4 *>(wl + (int64_t)r16 * row_bytes + (((ks * 4 + q) ^ r16) << 4));
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) mma_step(a[u][mt], w, acc[mt], 0.0f);
+                    mma_step(a[u], w, acc, 0.0f);
                 }
             }
         }
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int bl = mt * 16 + 4 * q + i;
-                const int b = b0 + min(bl, nb - 1);
-                const float r = g_r[mt][i], z = g_z[mt][i], n = g_n[mt][i], hn = g_hn[mt][i], hp = g_hp[mt][i];
-                const float dh = g_do[mt][i] + acc[mt][i] + carry[mt][i];
-                const float dn_pre = dh * (1.0f - z) * (1.0f - n * n);
-                const float dz_pre = dh * (hp - n) * z * (1.0f - z);
-                const float dr_pre = dn_pre * hn * r * (1.0f - r);
-                carry[mt][i] = dh * z;
-                if (bl < nb) {
-                    float *o1 = p.dgi + (((int64_t)b * T_ + t) * 2 + dir) * g3 + kcol;
-                    const int o2 = (int)(((((int64_t)b * T_ + t) * 2 + dir) * g3 + kcol) * 4);
-                    o1[0] = dr_pre; o1[H] = dz_pre; o1[2 * H] = dn_pre;
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dr_pre), dgh_rsrc, o2, 0, 16 /* sc1 */);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dz_pre), dgh_rsrc, o2 + H * 4, 0, 16);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dn_pre * r), dgh_rsrc, o2 + 2 * H * 4, 0, 16);
-                }
+        for (int i = 0; i < 4; ++i) {
+            const int bl = 4 * q + i;
+            const int b = b0 + min(bl, nb - 1);
+            const float r = g_r[i], z = g_z[i], n = g_n[i], hn = g_hn[i], hp = g_hp[i];
+            const float dh = g_do[i] + acc[i] + carry[i];
+            const float dn_pre = dh * (1.0f - z) * (1.0f - n * n);
+            const float dz_pre = dh * (hp - n) * z * (1.0f - z);
+            const float dr_pre = dn_pre * hn * r * (1.0f - r);
+            carry[i] = dh * z;
+            if (bl < nb) {
+                float *o1 = p.dgi + (((int64_t)b * T_ + t) * 2 + dir) * g3 + kcol;
+                const int o2 = (int)(((((int64_t)b * T_ + t) * 2 + dir) * g3 + kcol) * 4);
+                o1[0] = dr_pre; o1[H] = dz_pre; o1[2 * H] = dn_pre;
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dr_pre), dgh_rsrc, o2, 0, 16 /* sc1 */);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dz_pre), dgh_rsrc, o2 + H * 4, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dn_pre * r), dgh_rsrc, o2 + 2 * H * 4, 0, 16);
             }
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) __hip_atomic_fetch_add(ctr + step, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1247,22 +1035,13 @@ __global__ __launch_bounds__(128, 1) void gru_bwd_kernel(GruBwdParams p) {
 // it multiplies ITS OWN 192 columns of dgh (its units' dr, dz, dn r: produced in its own registers, never exchanged) with the
 // matching 192 rows of W_hh for ALL H output units k -- [16 x 192] x [192 x H], K = 192 -- and hands each partial sum to the
 // workgroup that owns unit k: 16 x 64 floats per pair of workgroups and step (40 KB received at H = 384 instead of 147 KB
-// fetched), as 8-byte {float, step tag} granules polled by the receiver (Guideline 16, R2: no counter, no drain).  The owner adds
+// fetched), as 8-byte {float, step tag} granules polled by the receiver (poll_granules).  The owner adds
 // the partials in workgroup order (deterministic).  The product runs as f16x2 (la_f32x2.hip): the W rows of a workgroup, scaled per
 // output column by powers of two, sit in registers as two half-precision fragment sets; the workgroup's dgh block is scaled per
 // clip (its largest magnitude over the 192 local columns: known locally) and split into two half planes in LDS; three MFMA
 // 16x16x32 f16 products per k-step and 16-column tile, float32 accumulate: 108 MFMAs of 16 cycles per wave and step.
-struct GruBwdX2Params {
-    const float *gates, *out, *dout, *w_hh;
-    float *dgi, *dgh;
-    int B, T, H;
-    unsigned long long *xch;   // [groups][2 dirs][2 slots][NS dest][NS src][16 clips][64 units] granules, zeroed per call
-    int *abort_flag, *timeout_flag;
-    unsigned long long poll_budget = 300000000ull;
-};
-
 template <int NS>                                               // NS = H / 64: workgroups per (group, direction) = column tiles per wave
-__global__ __launch_bounds__(256, 1) void gru_bwd_x2_kernel(GruBwdX2Params p) {
+__global__ __launch_bounds__(256, 1) void gru_bwd_x2_kernel(GruBwdParams p) {
     constexpr int NW = 4, MAXT = NS;                            // 4 waves x 16 units
     typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -1483,7 +1262,184 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_x2_kernel(GruBwdX2Params p) {
     if (!alive && tid == 0 && p.timeout_flag) *p.timeout_flag = 1;
 }
 
+// ---- the forward launch table: (dtype, waves, hand-off form, fence, ragged) -> kernel, block size, MAXKS (largest hidden / k-step the
+//      instantiation keeps resident: k-step 32, counter float32 16).  12 with 8 waves (hidden <= 384, 144 registers), 16 with 4
+//      (hidden <= 512, 192; a 192-register W slice spills at 256 registers per wave) ----
+struct FwdRow {
+    int dtype, waves;
+    bool granule, fence, ragged;
+    void (*kernel)(GruFwdParams);
+    int block, maxks;
+};
+template <typename T, int KS, int NW, bool FENCE, bool RAGGED>
+constexpr FwdRow counter_row() { return {la::Elem<T>::kDtype, NW, false, FENCE, RAGGED, gru_kernel<T, KS, !FENCE, 1, NW, RAGGED>, NW * 64, KS}; }
+template <typename T, bool RAGGED>
+constexpr FwdRow granule_row() { return {la::Elem<T>::kDtype, 8, true, false, RAGGED, gru_granule_kernel<T, 12, RAGGED>, 512, 12}; }
+template <bool RAGGED>
+constexpr FwdRow x2_row() { return {LA_F32, 4, true, false, RAGGED, gru_train_x2_kernel<12, RAGGED>, 256, 12}; }
+const FwdRow kFwdRows[] = {
+    counter_row<float, 24, 2, false, false>(),     counter_row<float, 24, 2, false, true>(),
+    counter_row<float, 24, 2, true, false>(),      counter_row<float, 24, 2, true, true>(),
+    counter_row<bf16_t, 16, 4, false, false>(),    counter_row<bf16_t, 16, 4, false, true>(),
+    counter_row<bf16_t, 16, 4, true, false>(),     counter_row<bf16_t, 16, 4, true, true>(),
+    counter_row<la::f16_t, 16, 4, false, false>(), counter_row<la::f16_t, 16, 4, false, true>(),
+    counter_row<la::f16_t, 16, 4, true, false>(),  counter_row<la::f16_t, 16, 4, true, true>(),
+    counter_row<bf16_t, 12, 8, false, false>(),    counter_row<bf16_t, 12, 8, false, true>(),
+    counter_row<bf16_t, 12, 8, true, false>(),     counter_row<bf16_t, 12, 8, true, true>(),
+    counter_row<la::f16_t, 12, 8, false, false>(), counter_row<la::f16_t, 12, 8, false, true>(),
+    counter_row<la::f16_t, 12, 8, true, false>(),  counter_row<la::f16_t, 12, 8, true, true>(),
+    x2_row<false>(),                               x2_row<true>(),
+    granule_row<bf16_t, false>(),                  granule_row<bf16_t, true>(),
+    granule_row<la::f16_t, false>(),               granule_row<la::f16_t, true>(),
+};
+
 }  // namespace
+
+static int gru_groups(int batch) { return la::cdiv(batch, GROUP); }
+static size_t gru_ctr_bytes(int batch, int frames) { return (size_t)la::round_up(16 + (int64_t)gru_groups(batch) * 2 * frames * 4, 256); }
+// granule exchange ring behind the counters: [groups][2][2 slots][16][granules per clip row] x 8 bytes
+// (sized for the largest user: the backward sweep's reduce-scatter blocks, (hidden / 64)^2 pairs of 16 x 64 granules per slot; the float32
+//  training forward uses 16 x hidden granules per slot, the 16-bit inference form half of that)
+static size_t gru_xch_fwd_bytes(int batch, int hidden) { return (size_t)gru_groups(batch) * 2 * 2 * 16 * hidden * 8; }
+static size_t gru_xch_bwd_bytes(int batch, int hidden) { return (size_t)gru_groups(batch) * 2 * 2 * (hidden / 64) * (hidden / 64) * 16 * 64 * 8; }
+static size_t gru_xch_bytes(int batch, int hidden) { return std::max(gru_xch_fwd_bytes(batch, hidden), hidden % 64 == 0 ? gru_xch_bwd_bytes(batch, hidden) : (size_t)0); }
+
+extern "C" int la_gru_workspace_bytes(int32_t batch, int32_t frames, int32_t hidden, size_t *bytes) {
+    LA_CHECK_ARG(bytes && batch > 0 && frames > 0 && hidden > 0, "gru_workspace_bytes: bad arguments");
+    // [16 B header: abort flag] + counters [groups][2][frames] u32, padded to 256 B + the granule exchange ring
+    *bytes = gru_ctr_bytes(batch, frames) + gru_xch_bytes(batch, hidden);
+    return LA_OK;
+}
+
+// option gru_timeout_us -> the bound of one inter-workgroup wait in 100 MHz ticks (default 3 s)
+static unsigned long long gru_poll_budget() {
+    return la::opts().gru_timeout_us > 0 ? (unsigned long long)la::opts().gru_timeout_us * 100ull : 300000000ull;
+}
+
+// what a granule launch needs zeroed: the 16-byte header (abort flag) and `ring_bytes` of the ring behind the counters
+static int gru_zero_header_and_ring(void *workspace, int batch, int frames, size_t ring_bytes, hipStream_t stream, unsigned long long **ring) {
+    unsigned char *wsb = reinterpret_cast<unsigned char *>(workspace);
+    const size_t ctrb = gru_ctr_bytes(batch, frames);
+    LA_HIP(hipMemsetAsync(wsb, 0, 16, stream));
+    LA_HIP(hipMemsetAsync(wsb + ctrb, 0, ring_bytes, stream));
+    *ring = reinterpret_cast<unsigned long long *>(wsb + ctrb);
+    return LA_OK;
+}
+
+// one walk of the table; the float32 counter rows keep W_hh in more dynamic LDS than the default ceiling: raised once per device
+static int gru_launch_fwd(int dtype, int waves, bool granule, bool fence, bool ragged, int kstep, dim3 grid, size_t lds_bytes,
+                          hipStream_t stream, const GruFwdParams &p) {
+    const FwdRow *row = nullptr;
+    for (const FwdRow &r : kFwdRows)
+        if (r.dtype == dtype && r.waves == waves && r.granule == granule && r.fence == fence && r.ragged == ragged) {
+            row = &r;
+            break;
+        }
+    // not reached: gru_forward's checks admit only what the table holds, at a hidden size its MAXKS covers (the message is gru_forward's)
+    if (!row || p.H > row->maxks * kstep) return LA_EUNSUPPORTED;
+    if (dtype == LA_F32 && !granule) {
+        static la::DeviceOnce attr_once;
+        if (attr_once.pending()) {
+            for (const FwdRow &r : kFwdRows)
+                if (r.dtype == LA_F32 && !r.granule)
+                    LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(r.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 16 + 2 * 3 * 16 * 384 * 4));
+            attr_once.mark();
+        }
+    }
+    la::TimerScope ts(dtype == LA_F32 ? "gru_f32" : "gru_bf16", stream);
+    hipLaunchKernelGGL(row->kernel, grid, dim3(row->block), lds_bytes, stream, p);
+    LA_LAUNCH_CHECK();
+    return LA_OK;
+}
+
+// gates != nullptr: the training forward (float32) also stores r, z, n and W_hn h + b_hn of every step
+static int gru_forward(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
+                       int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
+                       int32_t *timeout_flag, float *gates, void *stream_, const int32_t *n_frames = nullptr) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (batch == 0 || frames == 0) return LA_OK;
+    LA_CHECK_ARG(gi && w_hh && b_hh && out && workspace, "gru_layer: null pointer");
+    LA_CHECK_ARG(dtype == LA_F32 || dtype == LA_BF16 || dtype == LA_F16, "gru_layer: bad dtype");
+    LA_CHECK_ARG(batch > 0 && frames > 0 && hidden > 0, "gru_layer: bad sizes");
+    LA_CHECK_ARG((uintptr_t)w_hh % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)workspace % 16 == 0, "gru_layer: alignment");
+    size_t need = 0;
+    la_gru_workspace_bytes(batch, frames, hidden, &need);
+    LA_CHECK_ARG(workspace_bytes >= need, "gru_layer: workspace too small (%zu < %zu)", workspace_bytes, need);
+    const int groups = gru_groups(batch);
+    const int fault = la::opts().gru_fault_step;              // one-shot test hook: the launch that reads it clears it
+    if (fault) la::opts().gru_fault_step = 0;
+    if (hidden % 64 != 0 || (dtype != LA_F32 && hidden > 512) || (dtype == LA_F32 && hidden > 384)) {
+        la::set_error("gru_layer: hidden=%d unsupported (multiple of 64; bf16 <= 512, f32 <= 384)", hidden);
+        return LA_EUNSUPPORTED;
+    }
+    // 16-bit modes: 8-wave workgroups (128 hidden units each) where hidden allows; LA_GRU_NW=4 keeps the 4-wave form (A/B)
+    const bool force_nw4 = la::opts().gru_nw == 4;
+    const bool wide = dtype != LA_F32 && hidden % 128 == 0 && hidden <= 384 && !force_nw4;   // (a 192-register W slice spills at 256)
+    const int nw = dtype == LA_F32 ? 2 : (wide ? 8 : 4);
+    const int nsplit = hidden / (16 * nw);
+    if (nsplit * 2 * groups > 224) {
+        la::set_error("gru_layer: %d co-resident workgroups needed (batch too large for one launch; split the batch)", nsplit * 2 * groups);
+        return LA_EUNSUPPORTED;
+    }
+    const bool use_fence = la::opts().gru_fence != 0, ragged = n_frames != nullptr;
+    GruFwdParams p{gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, {nullptr}, reinterpret_cast<int *>(workspace), timeout_flag,
+                   nsplit, la::opts().gru_poll_delay, gates, gru_poll_budget(), fault, n_frames};
+    // float32 training forward (gates stored): recurrent product as f16x2 with the granule hand-off (gru_train_x2_kernel); option
+    // gru_handoff = 1 keeps gru_kernel<float> (float32 MFMA, counter form): the A/B partner
+    // (inference, gates == NULL: the same kernel without the gate stores where option x2_inference is on and more than 4 clips share the launch --
+    //  la_align_head_forward's float32 route; a handful of clips keeps gru_kernel<float>, whose v_fma path is faster there)
+    if (dtype == LA_F32 && (gates || (la::opts().x2_inference && batch > 4)) && hidden % 64 == 0 && hidden <= 384 && la::opts().gru_handoff == 0 &&
+        !use_fence && (hidden / 64) * 2 * groups <= 224) {
+        if (int rc = gru_zero_header_and_ring(workspace, batch, frames, gru_xch_fwd_bytes(batch, hidden), stream, &p.xch)) return rc;
+        const size_t lds_t = 16 + (size_t)2 * 2 * 16 * (hidden * 2 + 16);      // flag + two stages of two h planes
+        return gru_launch_fwd(dtype, 4, true, false, ragged, 32, dim3(hidden / 64, 2, groups), lds_t, stream, p);
+    }
+    // 16-bit recurrence in 8-wave workgroups: the granule hand-off (option gru_handoff = 0, default) or the counter form (1)
+    // (measured, tools/kbench.py gru: 3.28 against 3.38 us per step at 32 - 64 clips, level at 16, 2.86 against 2.64 at one clip -- the counter
+    //  form keeps the single 16-clip group; gru_handoff = 2 forces granules for every batch)
+    const bool granules = wide && !gates && !use_fence && hidden % 128 == 0 &&
+                          (la::opts().gru_handoff == 2 || (la::opts().gru_handoff == 0 && batch > 16));
+    if (granules) {
+        LA_CHECK_ARG(frames < 0x7fffffff, "gru_layer: too many frames");
+        if (int rc = gru_zero_header_and_ring(workspace, batch, frames, gru_xch_fwd_bytes(batch, hidden), stream, &p.xch)) return rc;
+        const size_t lds_g = 16 + (size_t)2 * 16 * (hidden * 2 + 16);          // flag + two h stages
+        return gru_launch_fwd(dtype, 8, true, false, ragged, 32, dim3(nsplit, 2, groups), lds_g, stream, p);
+    }
+    // Counter hand-off (tools/kbench.py gru, 32 clips, T=1500, H=384; tools/handoff_bench.hip for the bare protocol costs):
+    // write-through (sc1 stores, drained; relaxed counter; sc1 loads) 5.4 ms per layer, release / acquire fences 9.0 ms.
+    // The write-through form is the default; LA_GRU_FENCE=1 selects the fence form.
+    LA_HIP(hipMemsetAsync(workspace, 0, gru_ctr_bytes(batch, frames), stream));
+    p.counters = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(workspace) + 16);
+    LA_CHECK_ARG((int64_t)batch * frames * 2 * hidden * (dtype == LA_F32 ? 4 : 2) < (int64_t)2147483647, "gru_layer: out buffer exceeds the 2 GiB buffer-descriptor range");
+    // dynamic LDS: 16-bit = flag + the staged h rows of the batch tile; float32 = flag + the workgroup's W_hh rows
+    const size_t lds_c = dtype == LA_F32 ? 16 + (size_t)2 * 3 * 16 * hidden * 4 : 16 + (size_t)16 * (hidden * 2 + 16);
+    return gru_launch_fwd(dtype, nw, false, use_fence, ragged, dtype == LA_F32 ? 16 : 32, dim3(nsplit, 2, groups), lds_c, stream, p);
+}
+
+extern "C" int la_gru_layer(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
+                            int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
+                            int32_t *timeout_flag, void *stream) {
+    return gru_forward(dtype, gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, nullptr, stream);
+}
+
+// Per-clip lengths: n_frames [batch] (device), 1 <= n_frames[b] <= frames.  Rows t < n_frames[b] of clip b are what la_gru_layer gives for
+// that clip alone over n_frames[b] frames; rows past them are unspecified.  Every clip of the launch takes `frames` steps.
+extern "C" int la_gru_layer_ragged(int32_t dtype, const float *gi, const void *w_hh, const float *b_hh, void *out, void *out_mish,
+                                   int32_t batch, int32_t frames, const int32_t *n_frames, int32_t hidden, void *workspace,
+                                   size_t workspace_bytes, int32_t *timeout_flag, void *stream) {
+    LA_CHECK_ARG(n_frames || batch == 0 || frames == 0, "gru_layer_ragged: n_frames missing");
+    return gru_forward(dtype, gi, w_hh, b_hh, out, out_mish, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, nullptr, stream, n_frames);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// training face (fine-tune row, float32 like the reference): forward that also stores the gates, and the backward sweep
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int la_gru_layer_train_fwd(const float *gi, const float *w_hh, const float *b_hh, float *out, float *gates,
+                                      int32_t batch, int32_t frames, int32_t hidden, void *workspace, size_t workspace_bytes,
+                                      int32_t *timeout_flag, void *stream) {
+    LA_CHECK_ARG(gates || batch == 0 || frames == 0, "gru_layer_train_fwd: gates buffer missing");
+    return gru_forward(LA_F32, gi, w_hh, b_hh, out, nullptr, batch, frames, hidden, workspace, workspace_bytes, timeout_flag, gates, stream);
+}
 
 extern "C" int la_gru_layer_bwd(const float *gates, const float *out, const float *dout, const float *w_hh, float *dgi,
                                 float *dgh, int32_t batch, int32_t frames, int32_t hidden, void *workspace,
@@ -1502,52 +1458,36 @@ extern "C" int la_gru_layer_bwd(const float *gates, const float *out, const floa
         return LA_EUNSUPPORTED;
     }
     const int groups = gru_groups(batch);
+    GruBwdParams p{gates, out, dout, w_hh, dgi, dgh, batch, frames, hidden, {nullptr}, reinterpret_cast<int *>(workspace), timeout_flag,
+                   gru_poll_budget(), hidden / 32};
     // default: the f16x2 product with the reduce-scatter granule hand-off (gru_bwd_x2_kernel); option gru_handoff = 1 keeps the
     // float32-MFMA all-gather kernel below (the A/B partner).  <= 4 clips stay on it too: its v_fma path beats a 16-row MFMA tile there.
     if (la::opts().gru_handoff == 0 && batch > 4 && (hidden / 64) * 2 * groups <= 224) {
-        unsigned char *wsb = reinterpret_cast<unsigned char *>(workspace);
-        const size_t ctrb = gru_ctr_bytes(batch, frames);
-        LA_HIP(hipMemsetAsync(wsb, 0, 16, stream));
-        LA_HIP(hipMemsetAsync(wsb + ctrb, 0, gru_xch_bwd_bytes(batch, hidden), stream));
-        GruBwdX2Params xp{gates, out, dout, w_hh, dgi, dgh, batch, frames, hidden, reinterpret_cast<unsigned long long *>(wsb + ctrb),
-                          reinterpret_cast<int *>(workspace), timeout_flag,
-                          la::opts().gru_timeout_us > 0 ? (unsigned long long)la::opts().gru_timeout_us * 100ull : 300000000ull};
-        const size_t lds_x = 16 + 4 * 16 * 4 + (size_t)2 * 16 * (192 * 2 + 16) + (size_t)(hidden / 64) * 1024 * 4;
+        if (int rc = gru_zero_header_and_ring(workspace, batch, frames, gru_xch_bwd_bytes(batch, hidden), stream, &p.xch)) return rc;
+        const int ns = hidden / 64;
+        const size_t lds_x = 16 + 4 * 16 * 4 + (size_t)2 * 16 * (192 * 2 + 16) + (size_t)ns * 1024 * 4;
+        static void (*const kBwdX2[6])(GruBwdParams) = {gru_bwd_x2_kernel<1>, gru_bwd_x2_kernel<2>, gru_bwd_x2_kernel<3>,
+                                                        gru_bwd_x2_kernel<4>, gru_bwd_x2_kernel<5>, gru_bwd_x2_kernel<6>};
         la::TimerScope ts("gru_bwd_f32", stream);
-        switch (hidden / 64) {
-            case 1: hipLaunchKernelGGL(gru_bwd_x2_kernel<1>, dim3(1, 2, groups), dim3(256), lds_x, stream, xp); break;
-            case 2: hipLaunchKernelGGL(gru_bwd_x2_kernel<2>, dim3(2, 2, groups), dim3(256), lds_x, stream, xp); break;
-            case 3: hipLaunchKernelGGL(gru_bwd_x2_kernel<3>, dim3(3, 2, groups), dim3(256), lds_x, stream, xp); break;
-            case 4: hipLaunchKernelGGL(gru_bwd_x2_kernel<4>, dim3(4, 2, groups), dim3(256), lds_x, stream, xp); break;
-            case 5: hipLaunchKernelGGL(gru_bwd_x2_kernel<5>, dim3(5, 2, groups), dim3(256), lds_x, stream, xp); break;
-            default: hipLaunchKernelGGL(gru_bwd_x2_kernel<6>, dim3(6, 2, groups), dim3(256), lds_x, stream, xp); break;
-        }
+        hipLaunchKernelGGL(kBwdX2[ns - 1], dim3(ns, 2, groups), dim3(256), lds_x, stream, p);
         LA_LAUNCH_CHECK();
         return LA_OK;
     }
-    const int nsplit = hidden / 32;
-    if (nsplit * 2 * groups > 224) {
-        la::set_error("gru_layer_bwd: %d co-resident workgroups needed (batch too large for one launch; split the batch)", nsplit * 2 * groups);
+    if (p.nsplit * 2 * groups > 224) {
+        la::set_error("gru_layer_bwd: %d co-resident workgroups needed (batch too large for one launch; split the batch)", p.nsplit * 2 * groups);
         return LA_EUNSUPPORTED;
     }
     LA_CHECK_ARG((int64_t)batch * frames * 2 * 3 * hidden * 4 < (int64_t)2147483647, "gru_layer_bwd: dgh exceeds the 2 GiB buffer-descriptor range");
     LA_HIP(hipMemsetAsync(workspace, 0, need, stream));
-    GruBwdParams p{gates, out, dout, w_hh, dgi, dgh, batch, frames, hidden,
-                   reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(workspace) + 16),
-                   reinterpret_cast<int *>(workspace), timeout_flag, nsplit,
-                   la::opts().gru_timeout_us > 0 ? (unsigned long long)la::opts().gru_timeout_us * 100ull : 300000000ull};
+    p.counters = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(workspace) + 16);
     const size_t lds_bytes = 16 + (size_t)2 * 16 * 3 * hidden * 4;
     static la::DeviceOnce attr_once;
     if (attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_bwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   16 + 2 * 16 * 3 * 384 * 4));
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_bwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   16 + 2 * 16 * 3 * 384 * 4));
+        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 16 + 2 * 16 * 3 * 384 * 4));
         attr_once.mark();
     }
     la::TimerScope ts("gru_bwd_f32", stream);
-    if (batch <= 16 || GROUP == 16) hipLaunchKernelGGL(gru_bwd_kernel<1>, dim3(nsplit, 2, groups), dim3(128), lds_bytes, stream, p);
-    else hipLaunchKernelGGL(gru_bwd_kernel<2>, dim3(nsplit, 2, groups), dim3(128), lds_bytes, stream, p);
+    hipLaunchKernelGGL(gru_bwd_kernel, dim3(p.nsplit, 2, groups), dim3(128), lds_bytes, stream, p);
     LA_LAUNCH_CHECK();
     return LA_OK;
 }

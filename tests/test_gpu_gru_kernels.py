@@ -11,7 +11,7 @@ an exchanged h is an input of the next step and not an error of it, and each ste
     F6    gru_kernel<16-bit>, 8 waves, counters    H in {128, 256, 384}, B <= 16 or gru_handoff = 1
     F7    gru_granule_kernel                       H in {128, 256, 384}, B > 16 or gru_handoff = 2
     B1    gru_bwd_x2_kernel<H / 64>                la_gru_layer_bwd, B > 4
-    B2    gru_bwd_kernel<1>                        la_gru_layer_bwd, B <= 4 or gru_handoff = 1
+    B2    gru_bwd_kernel                           la_gru_layer_bwd, B <= 4 or gru_handoff = 1
 An option is set only where the documented dispatch would pick another form, so the boundaries B = 4 / 5 and 16 / 17 are observed.
 
 Set-up of every call: out, out_mish, gates, dgi and dgh each sit inside a sentinel-filled Guard; the workspace is exactly the queried size
