@@ -461,7 +461,9 @@ int la_emissions_from_logits(const float *logits, int64_t batch_stride, int64_t 
  * audio [batch][n_samples] float32 -> mel [batch][80][n_frames], n_frames =
  * n_samples / 160, float32.  The "-8" floor uses the max over the WHOLE batch
  * tensor, as upstream whisper does.  mel_filters is the [80][201] Slaney table
- * (device), window the 400-tap periodic Hann (device).
+ * (device), window the 400-tap periodic Hann (device).  These names are the 80-bin
+ * forms (whisper tiny .. large-v2); the *_n entries below take the bin count (80 or
+ * 128, the large-v3 generation).
  */
 int la_logmel_workspace_bytes(int32_t batch, int32_t n_samples, size_t *bytes);
 int la_logmel_f32(const float *audio, int32_t batch, int32_t n_samples,
@@ -497,6 +499,35 @@ int la_logmel_ragged_f32_prepared(const float *audio, const int32_t *n_samples, 
                                   const void *consts,
                                   float *mel, int64_t mel_batch_stride, int64_t mel_row_stride, int32_t out_frames,
                                   void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The same six with the mel bin count as their first argument (an addition: the reference calls whisper's log-mel with its default of
+ * 80 bins).  n_mels = 80 (whisper tiny .. large-v2) or 128 (large-v3, large-v3-turbo); anything else is LA_EINVAL before any launch.
+ * mel_filters is [n_mels][201], mel [batch][n_mels][frames].  With n_mels = 80 each entry IS the entry above it is named after (those
+ * are its n_mels = 80 call): the same launches, the same bits.  la_logmel_workspace_bytes_n serves the dense and the ragged form (the
+ * one-call form keeps its constants in the workspace, so the size grows with n_mels).
+ * Constants belong to ONE bin count, and the prepared entries check it on the host, by the buffer's address: la_logmel_constants_n
+ * (and la_logmel_constants) record (consts, n_mels) once their launch is accepted; a later call on the same address replaces the
+ * record.  A prepared entry with n_mels = 128 takes only an address recorded for 128.  One with n_mels = 80 refuses an address
+ * recorded for 128 and takes every other (a copy of an 80-bin buffer has no record, and la_logmel_f32_prepared has always taken it).
+ * So: build 128-bin constants in the buffer they are used from, and do not reuse that address for a copy of 80-bin constants without
+ * building them there.  The refusal is LA_EINVAL before any launch; nothing on the device is read for it.
+ */
+int la_logmel_constants_bytes_n(int32_t n_mels, size_t *bytes);
+int la_logmel_constants_n(int32_t n_mels, const float *mel_filters, const float *window,
+                          void *consts, size_t consts_bytes, void *stream);
+int la_logmel_workspace_bytes_n(int32_t n_mels, int32_t batch, int32_t n_samples, size_t *bytes);
+int la_logmel_f32_n(int32_t n_mels, const float *audio, int32_t batch, int32_t n_samples,
+                    const float *mel_filters, const float *window,
+                    float *mel, int64_t mel_batch_stride, int64_t mel_row_stride,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int la_logmel_f32_prepared_n(int32_t n_mels, const float *audio, int32_t batch, int32_t n_samples,
+                             const void *consts,
+                             float *mel, int64_t mel_batch_stride, int64_t mel_row_stride,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int la_logmel_ragged_f32_prepared_n(int32_t n_mels, const float *audio, const int32_t *n_samples, int32_t batch,
+                                    int32_t max_samples, const void *consts,
+                                    float *mel, int64_t mel_batch_stride, int64_t mel_row_stride, int32_t out_frames,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------- */
 /* building blocks of embed_audio / align_rnn                                */

@@ -148,6 +148,13 @@ SYMBOLS = {
     # clips of different lengths in one launch set (per-clip sample / frame counts on the device)
     "la_logmel_ragged_workspace_bytes": (c_int32, [_I32, _I32, POINTER(_SZ)]),
     "la_logmel_ragged_f32_prepared": (c_int32, [_P, _P, _I32, _I32, _P, _P, _I64, _I64, _I32, _P, _SZ, _P]),
+    # the log-mel entries with the bin count (80 or 128) as their first argument
+    "la_logmel_constants_bytes_n": (c_int32, [_I32, POINTER(_SZ)]),
+    "la_logmel_constants_n": (c_int32, [_I32, _P, _P, _P, _SZ, _P]),
+    "la_logmel_workspace_bytes_n": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
+    "la_logmel_f32_n": (c_int32, [_I32, _P, _I32, _I32, _P, _P, _P, _I64, _I64, _P, _SZ, _P]),
+    "la_logmel_f32_prepared_n": (c_int32, [_I32, _P, _I32, _I32, _P, _P, _I64, _I64, _P, _SZ, _P]),
+    "la_logmel_ragged_f32_prepared_n": (c_int32, [_I32, _P, _P, _I32, _I32, _P, _P, _I64, _I64, _I32, _P, _SZ, _P]),
     "la_gru_layer_ragged": (c_int32, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P, _SZ, _P, _P]),
     "la_align_head_forward_ragged": (c_int32, [_P, _P, _I64, _I64, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
 }

@@ -43,32 +43,41 @@ def mel_filter_table(n_mels: int = N_MELS) -> np.ndarray:
     return fb.astype(np.float32)
 
 
+def _check_n_mels(n_mels, what: str) -> int:
+    """The bin counts the log-mel kernel is built for: 80 (whisper tiny .. large-v2) and 128 (large-v3, large-v3-turbo)."""
+    if int(n_mels) not in (80, 128):
+        raise ValueError(f"{what}: n_mels = {n_mels}, the log-mel kernel is built for 80 or 128")
+    return int(n_mels)
+
+
 @functools.lru_cache(maxsize=None)
-def _device_tables(device_index: int):
+def _device_tables(device_index: int, n_mels: int = N_MELS):
     dev = torch.device("cuda", device_index)
-    filt = torch.from_numpy(mel_filter_table()).to(dev)
+    filt = torch.from_numpy(mel_filter_table(n_mels)).to(dev)
     win = torch.hann_window(N_FFT, periodic=True, dtype=torch.float32).to(dev)
     return filt, win
 
 
 @functools.lru_cache(maxsize=None)
-def _device_constants(device_index: int) -> torch.Tensor:
-    """The log-mel kernel's constants (windowed DFT matrix in fragment order + padded filter bank), built once per device
-    from the two tables above (la_logmel_constants) -- whisper caches its filter asset per process the same way."""
+def _device_constants(device_index: int, n_mels: int = N_MELS) -> torch.Tensor:
+    """The log-mel kernel's constants (windowed DFT matrix in fragment order + padded filter bank), built once per device and bin
+    count from the two tables above (la_logmel_constants_n) -- whisper caches its filter asset per process the same way."""
     dev = torch.device("cuda", device_index)
-    filt, win = _device_tables(device_index)
+    filt, win = _device_tables(device_index, n_mels)
     need = ctypes.c_size_t(0)
-    check(lib().la_logmel_constants_bytes(ctypes.byref(need)), "logmel_constants_bytes")
+    check(lib().la_logmel_constants_bytes_n(n_mels, ctypes.byref(need)), "logmel_constants_bytes_n")
     consts = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        check(lib().la_logmel_constants(ptr(filt), ptr(win), ptr(consts), need.value, stream_ptr()), "logmel_constants")
+        check(lib().la_logmel_constants_n(n_mels, ptr(filt), ptr(win), ptr(consts), need.value, stream_ptr()), "logmel_constants_n")
         torch.cuda.current_stream().synchronize()      # other streams may use the buffer from now on
     return consts
 
 
-def log_mel_spectrogram(audio: Union[np.ndarray, torch.Tensor], device="cuda") -> torch.Tensor:
-    """[.., N] float waveform(s) -> [.., 80, N // 160] float32 on `device` (device log-mel kernel).
-    Same contract as whisper.audio.log_mel_spectrogram incl. the whole-tensor max for the -8 floor."""
+def log_mel_spectrogram(audio: Union[np.ndarray, torch.Tensor], device="cuda", n_mels: int = N_MELS) -> torch.Tensor:
+    """[.., N] float waveform(s) -> [.., n_mels, N // 160] float32 on `device` (device log-mel kernel); n_mels = 80 or 128
+    (whisper large-v3 and large-v3-turbo).  Same contract as whisper.audio.log_mel_spectrogram incl. the whole-tensor max for the
+    -8 floor."""
+    n_mels = _check_n_mels(n_mels, "log_mel_spectrogram")
     _lib.require_gpu()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -79,22 +88,24 @@ def log_mel_spectrogram(audio: Union[np.ndarray, torch.Tensor], device="cuda") -
     a = audio.reshape(-1, audio.shape[-1]).to(device=dev, dtype=torch.float32).contiguous()
     B, N = a.shape
     frames = N // HOP_LENGTH
-    consts = _device_constants(dev.index if dev.index is not None else torch.cuda.current_device())
-    mel = torch.empty((B, N_MELS, frames), dtype=torch.float32, device=dev)
+    consts = _device_constants(dev.index if dev.index is not None else torch.cuda.current_device(), n_mels)
+    mel = torch.empty((B, n_mels, frames), dtype=torch.float32, device=dev)
     need = ctypes.c_size_t(0)
-    check(lib().la_logmel_workspace_bytes(B, N, ctypes.byref(need)), "logmel_workspace_bytes")
+    check(lib().la_logmel_workspace_bytes_n(n_mels, B, N, ctypes.byref(need)), "logmel_workspace_bytes_n")
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
-    check(lib().la_logmel_f32_prepared(ptr(a), B, N, ptr(consts), ptr(mel), mel.stride(0), mel.stride(1), ptr(ws), need.value,
-                                       stream_ptr()), "logmel_f32_prepared")
-    return mel[0] if squeeze else mel.reshape(*audio.shape[:-1], N_MELS, frames)
+    check(lib().la_logmel_f32_prepared_n(n_mels, ptr(a), B, N, ptr(consts), ptr(mel), mel.stride(0), mel.stride(1), ptr(ws), need.value,
+                                         stream_ptr()), "logmel_f32_prepared_n")
+    return mel[0] if squeeze else mel.reshape(*audio.shape[:-1], n_mels, frames)
 
 
-def log_mel_spectrogram_per_clip(audios: Sequence[np.ndarray], device="cuda", out_frames: int = 3000) -> Tuple[torch.Tensor, List[int]]:
+def log_mel_spectrogram_per_clip(audios: Sequence[np.ndarray], device="cuda", out_frames: int = 3000,
+                                 n_mels: int = N_MELS) -> Tuple[torch.Tensor, List[int]]:
     """Clips of different lengths in ONE launch set, each treated as if it were alone (an addition: whisper's log-mel of a padded
-    batch pads first and floors at the batch maximum, which log_mel_spectrogram reproduces).  -> (mel [B, 80, out_frames] float32 on
+    batch pads first and floors at the batch maximum, which log_mel_spectrogram reproduces).  -> (mel [B, n_mels, out_frames] float32 on
     `device`, n_mel list[int]): clip b's own log-mel -- reflect padding at its own end, len(audios[b]) // 160 frames, floor at its own
     maximum - 8 -- followed by zeros (pad_or_trim to the encoder's 3000 frames).  Clips of more than out_frames * 160 samples or fewer
-    than 201 raise ValueError."""
+    than 201 raise ValueError, and so does an n_mels other than 80 or 128."""
+    n_mels = _check_n_mels(n_mels, "log_mel_spectrogram_per_clip")
     _lib.require_gpu()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -109,6 +120,6 @@ def log_mel_spectrogram_per_clip(audios: Sequence[np.ndarray], device="cuda", ou
     for i, a in enumerate(audios):
         batch[i, : ns[i]] = np.asarray(a, dtype=np.float32)
     from . import ops
-    consts = _device_constants(dev.index if dev.index is not None else torch.cuda.current_device())
-    mel = ops.logmel_ragged(torch.from_numpy(batch).to(dev), ns, consts, int(out_frames))
+    consts = _device_constants(dev.index if dev.index is not None else torch.cuda.current_device(), n_mels)
+    mel = ops.logmel_ragged(torch.from_numpy(batch).to(dev), ns, consts, int(out_frames), n_mels=n_mels)
     return mel, n_mel

@@ -191,12 +191,16 @@ class AlignModel(torch.nn.Module):
         return out
 
     # ------------------------------------------------------------------ reference API
+    def _n_mels(self) -> int:
+        """The backbone's mel bin count: 80, or 128 for the large-v3 generation (whisper's ModelDimensions.n_mels)."""
+        return int(self.whisper_model.dims.n_mels)
+
     def _mel_of(self, audios: Sequence[np.ndarray]) -> torch.Tensor:
         max_audio_len = max(map(len, audios))
         batch = np.zeros((len(audios), max_audio_len), dtype=np.float32)   # zero-pad to the batch max (:78-82), no mutation
         for i, a in enumerate(audios):
             batch[i, : len(a)] = np.asarray(a, dtype=np.float32)
-        return log_mel_spectrogram(batch, device=self._device())           # (:84) on the device
+        return log_mel_spectrogram(batch, device=self._device(), n_mels=self._n_mels())     # (:84) on the device, with the model's bin count
 
     def _features(self, mel: torch.Tensor, get_orig_len: bool):
         """-> (feats rows [., d] in compute dtype, B, T, clip stride in rows, embed_pad provider)."""
@@ -309,7 +313,9 @@ class AlignModel(torch.nn.Module):
             raise ValueError(f"per_clip: clips of more than 30 s ({max(n_mel)} > {N_FRAMES} mel frames) are not batched per clip; "
                              "align them one at a time (the long-form path)")
         eng = self.engine()
-        mel, n_mel = log_mel_spectrogram_per_clip(audios, device=eng.device, out_frames=N_FRAMES)
+        if self._n_mels() != eng.enc.n_mels:                                # (what engine.encode refuses, before the log-mel is launched)
+            raise ValueError(f"per_clip: the model's dims.n_mels = {self._n_mels()} but its conv1.weight takes {eng.enc.n_mels} mel bins")
+        mel, n_mel = log_mel_spectrogram_per_clip(audios, device=eng.device, out_frames=N_FRAMES, n_mels=self._n_mels())
         T = [frame_plan(n, True)[0][2] for n in n_mel]
         feats = eng.encode(mel)
         return feats, len(T), max(1, max(T)), torch.tensor(T, dtype=torch.int32).to(eng.device), T

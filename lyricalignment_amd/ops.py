@@ -496,9 +496,9 @@ def _frame_counts(n_frames: torch.Tensor, batch: int, what: str) -> torch.Tensor
     return n_frames.contiguous()
 
 
-def logmel_ragged(audio: torch.Tensor, n_samples, consts: torch.Tensor, out_frames: int = 3000) -> torch.Tensor:
-    """la_logmel_ragged_f32_prepared: audio [B, Nmax] f32 (device; clip b = the first n_samples[b] samples of row b), n_samples = host
-    sequence of ints -> mel [B, 80, out_frames] f32: each clip's own log-mel (its own reflect padding and -8 floor) in frames
+def logmel_ragged(audio: torch.Tensor, n_samples, consts: torch.Tensor, out_frames: int = 3000, n_mels: int = 80) -> torch.Tensor:
+    """la_logmel_ragged_f32_prepared_n: audio [B, Nmax] f32 (device; clip b = the first n_samples[b] samples of row b), n_samples = host
+    sequence of ints -> mel [B, n_mels, out_frames] f32 (n_mels = 80 or 128, the count `consts` were built for): each clip's own log-mel (its own reflect padding and -8 floor) in frames
     0 .. n_samples[b] // 160 - 1, zeros after.  Clips of fewer than 201 samples are refused here (the reflect padding needs them)."""
     _dev(audio, "audio", torch.float32); _dev(consts, "consts", torch.uint8)
     if audio.dim() != 2 or not audio.is_contiguous():
@@ -514,12 +514,15 @@ def logmel_ragged(audio: torch.Tensor, n_samples, consts: torch.Tensor, out_fram
     if N // 160 > int(out_frames):
         raise ValueError("logmel_ragged: out_frames < Nmax // 160")
     nsd = torch.tensor(ns, dtype=torch.int32).to(audio.device)
-    mel = torch.empty((B, 80, int(out_frames)), dtype=torch.float32, device=audio.device)
+    n_mels = int(n_mels)
+    if n_mels not in (80, 128):
+        raise ValueError(f"logmel_ragged: n_mels = {n_mels}, the kernels are built for 80 or 128")
+    mel = torch.empty((B, n_mels, int(out_frames)), dtype=torch.float32, device=audio.device)
     need = ctypes.c_size_t(0)
-    check(lib().la_logmel_ragged_workspace_bytes(B, N, ctypes.byref(need)), "logmel_ragged_workspace_bytes")
+    check(lib().la_logmel_workspace_bytes_n(n_mels, B, N, ctypes.byref(need)), "logmel_workspace_bytes_n")
     ws = torch.empty((need.value,), dtype=torch.uint8, device=audio.device)
-    check(lib().la_logmel_ragged_f32_prepared(ptr(audio), ptr(nsd), B, N, ptr(consts), ptr(mel), mel.stride(0), mel.stride(1), int(out_frames),
-                                              ptr(ws), need.value, stream_ptr()), "logmel_ragged_f32_prepared")
+    check(lib().la_logmel_ragged_f32_prepared_n(n_mels, ptr(audio), ptr(nsd), B, N, ptr(consts), ptr(mel), mel.stride(0), mel.stride(1),
+                                                int(out_frames), ptr(ws), need.value, stream_ptr()), "logmel_ragged_f32_prepared_n")
     return mel
 
 

@@ -383,7 +383,7 @@ def transcribe(model, audio, *, task: str = "transcribe", language: Optional[str
                patience: Optional[float] = None, without_timestamps: bool = False, suppress_tokens="-1", suppress_blank: bool = True,
                max_initial_timestamp: Optional[float] = 1.0, tokenizer: Optional[TokenizerSpec] = None,
                rng: Optional[torch.Generator] = None, mel: Optional[torch.Tensor] = None) -> dict:
-    """whisper.transcribe for one recording: audio float32 [N] at 16 kHz (or a ready log-mel [80, frames]).
+    """whisper.transcribe for one recording: audio float32 [N] at 16 kHz (or a ready log-mel [n_mels, frames]).
     -> {"text", "tokens", "segments": [{seek, start, end, tokens, text, temperature, avg_logprob, compression_ratio, no_speech_prob}],
         "language"}.  `initial_prompt`: token ids, or text when the vocabulary is available (tokenizer.py)."""
     from .audio_frontend import log_mel_spectrogram
@@ -395,7 +395,7 @@ def transcribe(model, audio, *, task: str = "transcribe", language: Optional[str
             raise FileNotFoundError("initial_prompt as text needs whisper's vocabulary (lyricalignment_amd/tokenizer.py); pass token ids")
         initial_prompt = tok.codec.encode(" " + initial_prompt.strip())
     if mel is None:
-        mel = log_mel_spectrogram(np.asarray(audio, dtype=np.float32), device=str(eng.device))
+        mel = log_mel_spectrogram(np.asarray(audio, dtype=np.float32), device=str(eng.device), n_mels=int(model.dims.n_mels))
     mel = mel.to(eng.device)
     content_frames = int(mel.shape[-1])
     mel = torch.nn.functional.pad(mel, (0, N_FRAMES))              # whisper pads 30 s of silence behind the recording

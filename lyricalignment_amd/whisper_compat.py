@@ -27,6 +27,13 @@ N_SAMPLES = 480000
 _DIMS = {  # name -> (n_state, n_head, n_layer)
     "tiny": (384, 6, 4), "base": (512, 8, 6), "small": (768, 12, 12), "medium": (1024, 16, 24),
     "large": (1280, 20, 32), "large-v1": (1280, 20, 32), "large-v2": (1280, 20, 32),
+    "large-v3": (1280, 20, 32), "large-v3-turbo": (1280, 20, 32), "turbo": (1280, 20, 32),
+}
+# what the large-v3 generation changes besides: 128 mel bins, one more token (Cantonese), and in the turbo models a decoder of 4 layers
+# behind the same encoder.  ("large" stays the 80-bin model it has been here.)  No checkpoint of these has been loaded by this project.
+_DIMS_MORE = {
+    "large-v3": dict(n_mels=128, n_vocab=51866),
+    "large-v3-turbo": dict(n_mels=128, n_vocab=51866, n_text_layer=4), "turbo": dict(n_mels=128, n_vocab=51866, n_text_layer=4),
 }
 
 
@@ -136,7 +143,7 @@ class Whisper(nn.Module):
         return decoder_engine(self, prompt, audio_features, greedy=(int(max_new_tokens), int(eot), int(beam_size)))
 
     def decode(self, mel_or_features: torch.Tensor, options=None, tokenizer=None):
-        """whisper.decode on 30 s windows: mel [B, 80, 3000] (or encoder outputs [B, 1500, d]) -> list of DecodingResult
+        """whisper.decode on 30 s windows: mel [B, n_mels, 3000] (or encoder outputs [B, 1500, d]) -> list of DecodingResult
         (lyricalignment_amd.transcribe: logit filters, greedy / sampling / beam search; token ids, text only with a tokenizer)."""
         from .transcribe import decode
         x = mel_or_features
@@ -156,7 +163,9 @@ def dims_for(name: str) -> ModelDimensions:
     if name not in _DIMS:
         raise KeyError(f"unknown whisper model {name!r}")
     d, h, l = _DIMS[name]
-    return ModelDimensions(n_audio_state=d, n_audio_head=h, n_audio_layer=l, n_text_state=d, n_text_head=h, n_text_layer=l)
+    fields = dict(n_audio_state=d, n_audio_head=h, n_audio_layer=l, n_text_state=d, n_text_head=h, n_text_layer=l)
+    fields.update(_DIMS_MORE.get(name, {}))
+    return ModelDimensions(**fields)
 
 
 class HostIndependentRng:
