@@ -134,6 +134,9 @@ int la_timer_read_work(double *total_ms, int64_t *timed_launches, double *timed_
  *   "x2_small"        LA_X2_SMALL         0 = the x2_inference route only where every product fills the 256 x 256 kernel (9 clips on at d = 1024;
  *                                         default) | 1 = at every batch size: the products outside that kernel's domain run on the 128 x 128
  *                                         f16x2 kernel (la_gemm_f16x2_small) instead of the float32-MFMA kernel (needs x2_inference = 1)
+ *   "gemm_epi16"      LA_GEMM_EPI16       1 = interior output tiles of the 256 x 256 kernel with a 16-bit result and no residual (plain / LayerNorm-
+ *                                         consumer epilogues) run the epilogue arithmetic in the accumulator layout and cross the LDS transpose as
+ *                                         16-bit values (default) | 0 = every tile crosses it as float32 (twice the staging; identical bits: A/B partner)
  * A library built with -DLA_EXPERIMENTS (tools/build_variant.sh; la_has_experiments() == 1) additionally carries the measured-slower
  * kernel structures of rounds 2-4 and their per-launch developer switches; the shipped library has neither. */
 int la_set_option(const char *name, int64_t value);

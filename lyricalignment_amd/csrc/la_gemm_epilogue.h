@@ -1,6 +1,7 @@
 // la_gemm_epilogue.h -- epilogues of the 256 x 256 GEMM kernel (la_gemm_pp_kernel.h): one wave's 128 x 64 output tile from the MFMA
 // accumulator layout through the wave's LDS region to row-major quads -- LayerNorm fold / bias, GELU, residual (f32 rows or the
-// split stream), wide stores, the 16-bit copy, per-segment row statistics.
+// split stream), wide stores, the 16-bit copy, per-segment row statistics.  16-bit results without a residual take the arithmetic first
+// and cross the LDS as 16-bit quads (wave_epilogue16).
 #pragma once
 #include <type_traits>
 
@@ -83,6 +84,84 @@ __device__ __forceinline__ void epi_quad(f32x4 &v, const float (&b4)[4], const f
     }
 }
 
+// Interior wave tile with a 16-bit result and no residual (option gemm_epi16): the epilogue arithmetic runs IN the accumulator
+// layout, one 16-row block mi at a time, and the block crosses the LDS as 16-bit values -- 4 ds_write_b64 + 2 ds_read_b128 per block
+// where the float32 staging of wave_epilogue takes 4 ds_write_b128 + 4 ds_read_b128: half the bytes and half the LDS instructions.
+// Lane (r, q) holds columns 16 ni + 4 q + j of row 16 mi + r: its 16 bias values and 16 LN column sums are fixed for the tile and fetched
+// once (ds_bpermute from the one-column-per-lane values); one row's (mean, rstd) per block comes from stats_row (the kernel's LDS
+// table, at this wave's first row).  Same epi_quad, same operands, same rounding per element as wave_epilogue: identical bits.
+// Round 2's form of this idea held all 8 blocks' statistics and broadcast operands live and spilled 107-127 registers; here the
+// live set is 128 accumulators + 32 column operands + one row's statistics + one block's packed quads.
+// LDS layout of a block: 16 rows of 128 B (64 x 16 bit) = 2 KiB, four blocks rotating through the wave's region (8 KiB of its 8.5 KiB;
+// a wave's LDS operations complete in order, so a block's writes may follow the reads of the block that held the buffer before).
+// The 8-byte quad (ni, q) of row r -- chunk c = 2 ni + (q >> 1) of the row's eight 16-byte chunks, half q & 1 -- lies at
+//   r * 128 + 16 * (c ^ (r & 7)) + 8 * ((q & 1) ^ (r >> 3)).
+// Writes (ds_write_b64: groups of 16 consecutive lanes = one q, r = 0..15; 32 banks = 128 B): within an instruction c and q are fixed, so
+// the lanes' 8-byte slots mod 128 B are 2 (c ^ (r & 7)) + ((q & 1) ^ (r >> 3)): r & 7 runs through all 8 chunks for r < 8 and again for
+// r >= 8, where the half is the other one -- 16 different slots, every bank once: conflict-free.
+// Reads (ds_read_b128: 64 banks = 256 B = two rows; groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32): lane L takes
+// chunk L & 7 of row (L >> 3) [+ 8 in the second read].  A group holds four rows, two even and two odd (the parity picks the 128-byte
+// half of the bank row), and of two rows of equal parity one with chunks 0-3 and one with chunks 4-7; rows of equal parity in one group
+// differ by 2, so bit 2 of their swizzle r & 7 is the same and the two sets of four chunks stay apart: 16 slots of 16 B, conflict-free.
+// Rows 8-15 come back with their two quads exchanged (the half bit): the second read's registers are stored in the other order.
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+template <typename T16, int EQ>
+__device__ __forceinline__ void wave_epilogue16(T16 *cw0, int64_t ldc, f32x4 (&acc)[8][4], bool has_bias, bool do_gelu, int epi, float bias_l,
+                                                float csum_l, unsigned char *reg, const float2 *stats_row, int lane) {
+    // (opaque lane: hipcc must not start the 32 column fetches above the caller's main loop, where every register is spoken for)
+    asm volatile("" : "+v"(lane));
+    const int r = lane & 15, q = lane >> 4;
+    float b16[4][4], cs16[4][4];
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            b16[ni][j] = __int_as_float(__builtin_amdgcn_ds_bpermute((ni * 16 + q * 4 + j) * 4, __float_as_int(bias_l)));
+            cs16[ni][j] = EQ == 2 ? __int_as_float(__builtin_amdgcn_ds_bpermute((ni * 16 + q * 4 + j) * 4, __float_as_int(csum_l))) : 0.f;
+        }
+    unsigned char *wr = reg + r * 128 + (((q & 1) ^ (r >> 3)) << 3);
+    const int wx = (q >> 1) ^ (r & 7);
+    const int row = lane >> 3, ch = lane & 7;
+    const unsigned char *rd = reg + row * 128 + ((ch ^ row) << 4);
+    T16 *cw = cw0 + (int64_t)row * ldc + ch * 8;
+    // Step mi: request block mi - 1 back from LDS, run block mi's arithmetic under that round trip and write its quads, then store block
+    // mi - 1.  The empty asm closes a step: hipcc takes the steps one at a time (one row's statistics, one block's quads live).
+    // The activation (none / the sigmoid form / the erfc form, a per-launch choice) selects one of three straight-line copies of the
+    // steps: with the choice left inside epi_quad every quad ends in scalar branches and hipcc rebuilds the LDS addresses behind each.
+    auto steps = [&](auto gm) __attribute__((always_inline)) {
+        constexpr int GM = decltype(gm)::value;                          // 0 no GELU, 1 gelu_sig2 (experiment build: or gelu_sig), 2 gelu_pk
+        const int epi_q = GM == 2 ? 4096 : (epi & 8192);
+#pragma unroll
+        for (int mi = 0; mi <= 8; ++mi) {
+            u32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+            if (mi > 0) {
+                lo = *reinterpret_cast<const u32x4 *>(rd + ((mi - 1) & 3) * 2048);
+                hi = *reinterpret_cast<const u32x4 *>(rd + ((mi - 1) & 3) * 2048 + 1024);
+            }
+            if (mi < 8) {
+                unsigned char *buf = wr + (mi & 3) * 2048;
+                float2 st = make_float2(0.f, 0.f);
+                if constexpr (EQ == 2) st = stats_row[mi * 16 + r];
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) {
+                    f32x4 v = acc[mi][ni];
+                    epi_quad<false, EQ>(v, b16[ni], cs16[ni], st, has_bias, GM != 0, epi_q);
+                    *reinterpret_cast<u32x2 *>(buf + ((wx ^ (2 * ni)) << 4)) = __builtin_bit_cast(u32x2, la::Pack4<T16>::run(v[0], v[1], v[2], v[3]));
+                }
+            }
+            if (mi > 0) {
+                *reinterpret_cast<u32x4 *>(cw + (int64_t)(mi * 16 - 16) * ldc) = lo;
+                *reinterpret_cast<u32x4 *>(cw + (int64_t)(mi * 16 - 8) * ldc) = u32x4{hi.z, hi.w, hi.x, hi.y};
+            }
+            asm volatile("" ::: "memory");
+        }
+    };
+    if (!do_gelu) steps(std::integral_constant<int, 0>{});
+    else if (epi & 4096) steps(std::integral_constant<int, 2>{});
+    else steps(std::integral_constant<int, 1>{});
+}
+
 // The wave's 128x64 tile leaves the accumulator layout FIRST: per pass of 32 rows the 8 accumulator tuples go through the wave's
 // LDS region and come back row-major (lane (r, q) = columns 4r..4r+3 of row 4 it + q), and the whole epilogue arithmetic runs
 // there, where a lane's four columns are fixed for the tile (bias / column sums: 8 registers, fetched from the one-column-per-
@@ -117,6 +196,15 @@ __device__ __forceinline__ void wave_epilogue(const GemmParams &p, int z, f32x4 
     const bool do_gelu = p.epilogue & LA_EPI_GELU;
     const bool do_res = (p.epilogue & LA_EPI_RESIDUAL) && R;
     const int epi = p.epilogue;
+    // option gemm_epi16 (LA_EPI_STAGE16: set by the launch for 16-bit results without a residual): interior wave tiles whose rows take
+    // 16-byte stores go through the 16-bit staging; edge tiles and unaligned C stay on the forms below
+    if constexpr (!OUT_F32 && STG == 0 && (LNM == 0 || LNM == 4)) {
+        if ((epi & LA_EPI_STAGE16) && wrow0 + 128 <= p.M && wcol0 + 64 <= p.N && (p.ldc * (int64_t)sizeof(TC)) % 16 == 0 && (uintptr_t)C % 16 == 0) {
+            wave_epilogue16<T16, LNC ? 2 : 0>(C + (int64_t)wrow0 * p.ldc + wcol0, p.ldc, acc, has_bias, do_gelu, epi, bias_l, csum_l, reg,
+                                              LNC ? stats_tab + (wrow0 - tile_m0) : nullptr, lane);
+            return;
+        }
+    }
     // the lane's four columns 4r .. 4r+3 of the wave's 64: from the lanes that hold them (bias_l / csum_l = column `lane`)
     float b4[4], cs4[4];
 #pragma unroll

@@ -37,6 +37,7 @@ struct GemmParams {
 // internal epilogue bits (beside the public LA_EPI_* of lyricalign.h)
 constexpr int LA_EPI_SPLIT_INPLACE = 1 << 20;    // the residual is the split stream itself
 constexpr int LA_EPI_SPLIT_PASS32 = 1 << 21;     // (experiment build, LA_EPI_SPLIT_PASS=32) the 32-row passes without the one-pass-ahead requests
+constexpr int LA_EPI_STAGE16 = 1 << 22;         // option gemm_epi16: interior tiles of a 16-bit result without residual take wave_epilogue16
 constexpr int LA_EPI_Q4_PRIO = 1 << 23;          // (experiment build, LA_GEMM_Q4_PRIO=1) gemm_q4_kernel's prologue / epilogue at wave priority 3
 
 // The 256 x 256 kernel by operand type (dtype: LA_BF16 | LA_F16).  launch_pp16: plain / LayerNorm-producer (p.C2) / LayerNorm-consumer

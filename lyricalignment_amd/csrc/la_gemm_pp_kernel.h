@@ -168,6 +168,8 @@ int launch_pp(GemmParams p, int batch, hipStream_t stream) {
                       "in the experiment build only (tools/build_variant.sh, bfloat16)");
         return LA_EUNSUPPORTED;
     }
+    // option gemm_epi16: 16-bit results without a residual cross the epilogue's LDS transpose as 16-bit values (wave_epilogue16)
+    if (!OUT_F32 && la::opts().gemm_epi16 && !((p.epilogue & LA_EPI_RESIDUAL) && p.residual)) p.epilogue |= LA_EPI_STAGE16;
     if (lnm == 2) return duo ? launch_pp_loop<OUT_F32, true, T16, 2>(p, batch, stream) : launch_pp_loop<OUT_F32, false, T16, 2>(p, batch, stream);
     if constexpr (OUT_F32) {
         if (lnm == 1) return duo ? launch_pp_loop<OUT_F32, true, T16, 1>(p, batch, stream) : launch_pp_loop<OUT_F32, false, T16, 1>(p, batch, stream);

@@ -62,6 +62,7 @@ const OptionDesc kOptions[] = {
     {"ln_fusion", "LA_LN_FUSION", &Options::ln_fusion, false},       {"resid_split", "LA_RESID_SPLIT", &Options::resid_split, false},
     {"x2_inference", "LA_X2_INFERENCE", &Options::x2_inference, false}, {"x2_small", "LA_X2_SMALL", &Options::x2_small, false},
     {"gru_timeout_us", "LA_GRU_TIMEOUT_US", &Options::gru_timeout_us, false}, {"gru_fault_step", "LA_GRU_FAULT_STEP", &Options::gru_fault_step, false},
+    {"gemm_epi16", "LA_GEMM_EPI16", &Options::gemm_epi16, false},
 };
 }  // namespace
 

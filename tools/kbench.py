@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks on the config-2 shapes (developer tool; run on the GPU box).
     python tools/kbench.py gemm|attn|gru|fc|all [--iters N]
+    python tools/kbench.py epi16      option gemm_epi16 off / on on the QKV, MLP-up and plain 16-bit launches (shipped library)
 Interleaved rounds in one process, random operands (cdna guide rules 24/25).
 The A/B modes that flip developer switches per launch (gemm --variants 73, persist, q4, q4w, order, epi, attn_ko / attn variants) need
 the EXPERIMENT build of the library: bash tools/build_variant.sh lab -DLA_EXPERIMENTS; LA_LIB_PATH=$PWD/ab/lab/liblyricalign_hip.so."""
@@ -247,6 +248,38 @@ def bench_persist(iters, flag_name="LA_GEMM_PERSIST", label="persistent", on="1"
         fl = 2.0 * M * N * K
         p_, o_ = sorted(res[on])[1], sorted(res["0"])[1]
         print(f"{label} {name:30s} N={N} K={K}: {label} {p_*1e3:7.1f} us ({fl/p_/1e9:6.1f} TF/s) | one 8-wave workgroup per tile {o_*1e3:7.1f} us ({fl/o_/1e9:6.1f} TF/s) | {100*(o_/p_-1):+.1f} % | identical bits: {same}", flush=True)
+
+
+def bench_epi16(iters, rounds=5):
+    """Option gemm_epi16 (the interior-tile epilogue of 16-bit results crosses the LDS as 16-bit values) off and on, on the two
+    LayerNorm-consumer launches of an encoder block and the plain 16-bit form, interleaved rounds in one process, bit identity checked."""
+    M = 48000
+    prev = _lib.get_option("gemm_epi16")
+    for name, N, K, kind in (("qkv (LN consumer)", 3072, 1024, "ln"), ("mlp_up (LN consumer + GELU)", 4096, 1024, "ln_gelu"), ("plain 16-bit", 3072, 1024, "plain")):
+        a, w = rnd(M, K), rnd(N, K, scale=K ** -0.5)
+        bias, csum = torch.randn(N, device="cuda"), torch.randn(N, device="cuda") * 0.1
+        stats = torch.stack([torch.randn(M, device="cuda") * 0.01, torch.rand(M, device="cuda") + 0.5], dim=1).contiguous()
+        outs = {v: torch.empty(M, N, device="cuda", dtype=torch.bfloat16) for v in (0, 1)}
+
+        def run(v):
+            _lib.set_option("gemm_epi16", v)
+            if kind == "plain":
+                ops.gemm(a, w, outs[v], bias=bias)
+            else:
+                ops.gemm(a, w, outs[v], bias=bias, gelu=kind == "ln_gelu", ln_stats=stats, ln_csum=csum)
+
+        res = {0: [], 1: []}
+        for rd in range(rounds):
+            for v in (0, 1):
+                res[v].append(timeit(lambda: run(v), iters)[0])
+        same = bool(torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)))
+        fl = 2.0 * M * N * K
+        for v in (0, 1):
+            print(f"epi16 {name:28s} N={N} K={K} gemm_epi16={v}: rounds (us) {' '.join(f'{t * 1e3:7.1f}' for t in res[v])} | median {sorted(res[v])[rounds // 2] * 1e3:7.1f} us "
+                  f"({fl / sorted(res[v])[rounds // 2] / 1e9:6.1f} TF/s)", flush=True)
+        o_, n_ = sorted(res[0])[rounds // 2], sorted(res[1])[rounds // 2]
+        print(f"epi16 {name:28s} 16-bit staging vs float32 staging: {100 * (o_ / n_ - 1):+.2f} % | identical bits: {same}", flush=True)
+    _lib.set_option("gemm_epi16", prev)
 
 
 def bench_f32emu(iters):
@@ -607,6 +640,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if a.what == "epi":
         bench_epi_probe(a.iters)
+        sys.exit(0)
+    if a.what == "epi16":
+        bench_epi16(a.iters)
         sys.exit(0)
     if a.what == "attn_fwd":
         bench_attn_fwd(a.iters)
