@@ -284,6 +284,45 @@ int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride, int64_t e
                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Repeated lyric lines: the DP of la_viterbi_lattice_batch on the lattice with REPEATABLE label spans -- a chorus printed once and sung
+ * twice.  la_viterbi_lattice_batch's arguments through win_stride, then
+ *   repeat_from [batch][repeat_stride] (repeat_stride >= max_labels; entries 0 .. L_b - 1 of row b are read; may be NULL): repeat_from[a]
+ *       = e with a < e <= L_b declares labels a .. e-1 repeatable: having finished label e-1 the path may return to label a.  Any other
+ *       value (-1 by convention) = no repeat span starts at a; it is never used as an index.  One repeat span per start position; spans
+ *       may nest or overlap.
+ *   repeat_penalty (>= 0, not NaN): charged per taken repeat arc.  There is no bound on the number of repetitions but this.
+ *   path [batch][path_stride] (path_stride >= max_frames; may be NULL): the lattice state at every frame t < T_b; -1 for t >= T_b and
+ *       for a clip without a backtrace (LA_EEMPTY, LA_EINVAL, no path inside the windows).
+ * The only new target is the odd state 2a+1.  It gets two more predecessors, both from the previous frame: K = 2e, the silence after
+ * the span (always), and K-1 = 2e-1, label e-1, only if labels[a] != labels[e-1] (the equal-neighbour rule: a one-label span returns
+ * through the silence alone).  The DP is frame-synchronous, so an arc to the left makes no cycle.  Per cell: the existing rule, then
+ * the optional span's J and J-1, then dp[K] - repeat_penalty and dp[K-1] - repeat_penalty, each replacing the winner only if STRICTLY
+ * greater; the emission is added last and the window gate applies as in la_viterbi_windows_batch.  Start states and termination are
+ * unchanged; everything is float64 in this order, so results are reproducible to the bit.
+ * onset / offset are those of a label's FIRST visit in time (a visit = a maximal run of frames in one odd state; `path` holds them
+ * all).  A label inside a taken skip jump on one pass and visited on another has its visit's onset, not -1.  status is LA_OK iff
+ * every label is visited at least once or lies inside a skip jump the path took, else LA_EINFEASIBLE.
+ * With repeat_from NULL or all -1, onset, offset, final_score and status equal la_viterbi_lattice_batch's bit for bit.
+ * Up to 4095 labels (LA_EUNSUPPORTED above).  la_viterbi_repeats_workspace_bytes() = la_viterbi_lattice_workspace_bytes(); the
+ * backpointers are three 64-bit masks whatever is given.  Argument errors (la_viterbi_lattice_batch's, a repeat_stride below max_labels
+ * with a repeat_from, a path_stride below max_frames with a path, a negative or NaN repeat_penalty) are answered on the host before
+ * anything is enqueued; never synchronises, allocates or frees.  The posterior sweeps and the training loss do not know this lattice.
+ */
+int la_viterbi_repeats_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_viterbi_repeats_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                             const int32_t *labels, int32_t labels_stride,
+                             const int32_t *n_labels, const int32_t *n_frames,
+                             int32_t batch, int32_t max_frames, int32_t max_labels,
+                             int32_t *onset, int32_t *offset, int32_t out_stride,
+                             double *final_score, int32_t *status,
+                             const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                             const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                             const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty,
+                             int32_t *path, int32_t path_stride,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
  * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
  * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable

@@ -64,6 +64,9 @@ SYMBOLS = {
     "la_viterbi_lattice_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_viterbi_lattice_batch": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, c_double,
                                            _P, _P, _I32, _P, _SZ, _P]),
+    "la_viterbi_repeats_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
+    "la_viterbi_repeats_batch": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, c_double,
+                                           _P, _P, _I32, _P, _I32, c_double, _P, _I32, _P, _SZ, _P]),
     "la_alignment_posteriors_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_alignment_posteriors": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
                                           _P, _I64, _I64, _P, _SZ, _P]),

@@ -130,6 +130,28 @@ __device__ __forceinline__ SpanSource span_source(const int32_t *skip_row, const
     return s;
 }
 
+// The repeat span that starts at label a (repeatable spans, la_viterbi.hip): repeat_row[a] = e with a < e <= L declares labels a .. e-1
+// repeatable -- having finished label e-1 the path may return to label a.  What it gives state k: only the odd state 2a+1 is a target;
+// its sources are K = 2e (the silence after the span) and, where km1_ok, K-1 (label e-1: only when labels[a] != labels[e-1], the
+// equal-neighbour rule, so a one-label span returns through the silence alone).  K = -1: none -- a null repeat_row, an even state, a
+// state past the clip's last, or any entry outside a < e <= L (never used as an index).
+struct RepeatSource {
+    int K;
+    bool km1_ok;
+};
+__device__ __forceinline__ RepeatSource repeat_source(const int32_t *repeat_row, const int32_t *lab, int k, bool valid, int L) {
+    RepeatSource s{-1, false};
+    if (repeat_row && valid && (k & 1)) {
+        const int a = k >> 1;
+        const int e = repeat_row[a];
+        if (e > a && e <= L) {
+            s.K = 2 * e;
+            s.km1_ok = lab[a] != lab[e - 1];
+        }
+    }
+    return s;
+}
+
 // log(exp(a) + exp(b) [+ exp(c)]), -inf safe: float64 maximum, float32 correction.  The correction log(sum exp(x - max)) lies
 // in [0, ln 3], so its float32 rounding is <= ~1e-7 absolute per step while the path scores themselves stay float64.
 __device__ __forceinline__ double log_add3(double a, double b, double c) {

@@ -37,6 +37,18 @@
 // unchanged.
 //
 // More than 511 labels (la_viterbi_lattice_batch): the span and window faces of viterbi_strip_kernel, described there.
+//
+// Repeatable spans (the REP instantiations, la_viterbi_repeats_batch): a line sung more often than printed.  repeat_from[a] = e with
+// a < e <= L lets the path return to label a after label e-1: the odd state 2a+1 gets two more predecessors from the previous frame,
+// K = 2e (the silence after the span, always) and K-1 = 2e-1 (label e-1, only when labels[a] != labels[e-1]).  The DP is
+// frame-synchronous, so an arc to the left makes no cycle; it is the skip arcs' fetch with a source to the right of the target
+// (ds_bpermute in the one-wave form, the LDS row elsewhere; repeat_source in la_lattice.h is the rule, beside span_source).  Order per
+// cell: the existing rule, J, J-1, then K and K-1 (each charged repeat_penalty, each only if strictly greater), the emission last.
+// Backpointer codes 5 and 6 fit the three ballot words of the span faces.  REP exists only on top of SPANS + WIN with null pointers
+// meaning "absent"; the once-per-clip test reads "a span or a repeat arc", so a clip with neither runs the plain loop.  The path is no
+// longer monotone: the backtrace writes the state of every frame to `path`, onset / offset are those of a label's FIRST visit in time,
+// and a label inside a taken skip jump on one pass and visited on another keeps its visit (the kSkipped mark goes to on_s, only where
+// there is no visit yet, and a visit overwrites it); the backtrace thread recomputes K(kk) from repeat_from.
 #include <type_traits>
 
 #include "la_lattice.h"
@@ -47,7 +59,7 @@ using namespace la::lattice;
 
 constexpr double kNeg = -10000000.0;  // utils/alignment.py:144
 constexpr int PF = 8;                 // emission prefetch depth (frames)
-constexpr int kSkipped = -2;          // off_s marker of a label inside a taken jump (written out as -1)
+constexpr int kSkipped = -2;          // off_s marker of a label inside a taken jump (written out as -1); the repeat face marks on_s / onset
 
 struct VitParams : LatticeIn {
     int32_t *onset, *offset;
@@ -59,6 +71,12 @@ struct VitParams : LatticeIn {
     // run_viterbi_core face (DUMP instantiation only, batch 1): row 0 of dp is READ, rows >= 1 of dp / bt are written
     double *dp_dump;    // [T][S]
     long long *bt_dump; // [T][S]
+    // repeatable spans (REP instantiations only): repeat_from [batch][repeat_stride], entries 0 .. L_b - 1 of row b are read; null = none
+    const int32_t *repeat_from;
+    int32_t repeat_stride;
+    double repeat_penalty;
+    int32_t *path;      // [batch][path_stride]: the state at every frame (REP instantiations only); null = not wanted
+    int32_t path_stride;
 
     void set_outputs(int32_t *onset_, int32_t *offset_, int32_t out_stride_, double *final_score_, int32_t *status_) {
         onset = onset_, offset = offset_, out_stride = out_stride_, final_score = final_score_, status = status_;
@@ -67,7 +85,7 @@ struct VitParams : LatticeIn {
 
 // The recurrence cell, for both kernels: the winner among a state's predecessors and its backpointer code.
 struct Cell {
-    int code;      // 0 stay, 1 advance, 2 skip: the offset back to the predecessor; 3 jump from J, 4 jump from J-1
+    int code;      // 0 stay, 1 advance, 2 skip: the offset back to the predecessor; 3 jump from J, 4 jump from J-1; 5 repeat from K, 6 from K-1
     double best;
 };
 // p0, p1, p2: dp[j-1][k], [k-1], [k-2]; the reference's comparisons in the reference's order
@@ -80,19 +98,22 @@ __device__ __forceinline__ Cell choose_neighbour(double p0, double p1, double p2
     return {code, best};
 }
 // The two arcs of the span that ends at this state (J >= 0): each is charged pen and must beat the winner so far STRICTLY, J before J-1.
-// dp_jm1 is dereferenced only where that arc exists.
+// dp_jm1 is dereferenced only where that arc exists.  C0 = 5: the same rule for the two arcs of the repeat span that starts at this
+// state (sources K, K-1, codes 5 and 6), applied after the skip span's.
+template <int C0 = 3>
 __device__ __forceinline__ Cell jump_step(Cell c, const double *dp_j, const double *dp_jm1, bool jm1_ok, double pen) {
     const double vj = *dp_j - pen;
-    if (vj > c.best) c = {3, vj};
+    if (vj > c.best) c = {C0, vj};
     if (jm1_ok) {
         const double vm = *dp_jm1 - pen;
-        if (vm > c.best) c = {4, vm};
+        if (vm > c.best) c = {C0 + 1, vm};
     }
     return c;
 }
 
-template <int NW, bool DPP, bool SPANS, bool DUMP = false, bool WIN = false>
+template <int NW, bool DPP, bool SPANS, bool DUMP = false, bool WIN = false, bool REP = false>
 __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
+    static_assert(!REP || WIN, "repeatable spans are a face of the span + window forms (null pointers: absent)");
     static_assert(!DPP || NW == 1, "DPP neighbour exchange is single-wave only");
     static_assert(!DUMP || (!DPP && !SPANS), "the dp / bt dump is a face of the plain LDS-exchange form");
     static_assert(!WIN || (SPANS && !DUMP), "frame windows are a face of the optional-span forms");
@@ -120,6 +141,13 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         p.offset[(int64_t)b * p.out_stride + n] = -1;
         on_s[n] = -1;
         off_s[n] = -1;
+    }
+    [[maybe_unused]] int32_t *path_b = nullptr;   // every frame -1 until the backtrace has been there
+    if constexpr (REP) {
+        if (p.path) {
+            path_b = p.path + (int64_t)b * p.path_stride;
+            for (int t = k; t < p.max_frames; t += NT) path_b[t] = -1;
+        }
     }
     if (L <= 0) {  // reference: IndexError at cur_label[0] (:152)
         if (k == 0) { p.status[b] = LA_EEMPTY; p.final_score[b] = 0.0; }
@@ -149,12 +177,23 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         jm1_ok = src.jm1_ok;
         j_s[k] = J;
     }
+    // the repeat span that starts at this state's label (odd states only)
+    [[maybe_unused]] int K = -1;
+    [[maybe_unused]] bool km1_ok = false;
+    [[maybe_unused]] const int32_t *rep_b = nullptr;
+    if constexpr (REP) {
+        if (p.repeat_from) rep_b = p.repeat_from + (int64_t)b * p.repeat_stride;
+        const RepeatSource src = repeat_source(rep_b, lab, k, valid, L);
+        K = src.K;
+        km1_ok = src.km1_ok;
+    }
+    [[maybe_unused]] const double rpen = p.repeat_penalty;
     const double pen = p.penalty;
     const float *emb = p.em + (int64_t)b * p.em_bs + col;
     // this state's frame window; lanes without a state keep the open one (nothing is read past 2 L_b <= win_stride - 1)
     int wlo = 0, whi = 0x7fffffff;
     if constexpr (WIN) {
-        if (valid) {
+        if (valid && (!REP || p.win_lo)) {   // (repeats: a null window pair = every window open)
             wlo = p.win_lo[(int64_t)b * p.win_stride + k];
             whi = p.win_hi[(int64_t)b * p.win_stride + k];
         }
@@ -172,8 +211,10 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         if (k < 2) { rowbuf[k] = kNeg; rowbuf[NT + 2 + k] = kNeg; }  // slots for k-1, k-2 of states 0,1
     }
     // workgroup-uniform (one wave: a ballot): a clip without a span runs a frame loop without any of the jump code
-    const bool has_span = SPANS && (NW == 1 ? __ballot(J >= 0) != 0ull : __syncthreads_or(J >= 0) != 0);
+    // (repeats: neither a span nor a repeat arc; has_span then reads "has a jump of either kind")
+    const bool has_span = SPANS && (NW == 1 ? __ballot(J >= 0 || K >= 0) != 0ull : __syncthreads_or(J >= 0 || K >= 0) != 0);
     const int gather_addr = (J >= 0 ? J : lane) << 2;   // (single wave: J < S <= 64)
+    [[maybe_unused]] const int gather_addr_k = (K >= 0 ? K : lane) << 2;   // (K <= 2 L < S)
 
     float e_buf[PF];
 #pragma unroll
@@ -201,12 +242,17 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
                 const int j = j0 + i;
                 if (j >= T) break;
                 double p0 = cur, p1, p2, pj = kNeg, pjm1 = kNeg;
+                [[maybe_unused]] double pk = kNeg, pkm1 = kNeg;
                 if (DPP) {
                     p1 = wave_shr1(p0, 0.0);
                     p2 = wave_shr1(p1, 0.0);
                     if (HAS) {
                         pj = wave_gather(p0, gather_addr);
                         pjm1 = wave_gather(p1, gather_addr);   // lane J of the shifted row holds dp[J-1]
+                        if constexpr (REP) {                   // a source to the right of the target: the same fetch
+                            pk = wave_gather(p0, gather_addr_k);
+                            pkm1 = wave_gather(p1, gather_addr_k);
+                        }
                     }
                 } else {
                     double *rb = rowbuf + parity * (NT + 2);
@@ -218,10 +264,19 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
                         pj = rb[J + 2];
                         pjm1 = rb[J + 1];
                     }
+                    if constexpr (REP) {
+                        if (HAS && K >= 0) {
+                            pk = rb[K + 2];
+                            pkm1 = rb[K + 1];
+                        }
+                    }
                     parity ^= 1;
                 }
                 Cell c = choose_neighbour(p0, p1, p2, can_skip, k == 0);
                 if (HAS && J >= 0) c = jump_step(c, &pj, &pjm1, jm1_ok, pen);
+                if constexpr (REP) {
+                    if (HAS && K >= 0) c = jump_step<5>(c, &pk, &pkm1, km1_ok, rpen);
+                }
                 const int code = c.code;
                 cur = c.best + (double)e_cur[i];
                 if (DUMP && valid) {
@@ -261,12 +316,31 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
                 if (kk != knext) off_s[nn] = j + 1;  // last frame in this state + 1
                 on_s[nn] = j;                        // keeps decreasing to the first frame
             }
+            if constexpr (REP) {
+                if (path_b) path_b[j] = kk;
+            }
             knext = kk;
             if (j > 0) {
                 const unsigned long long *row = bt + ((int64_t)j * NW + (kk >> 6)) * MW;
                 const int sh = kk & 63;
                 int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
-                if constexpr (SPANS) {
+                if constexpr (REP) {
+                    // The path is no longer monotone: a label inside a taken skip jump on one pass may be visited on another, and then the
+                    // visit wins.  A taken jump marks on_s = kSkipped only where the label has no visit so far, and a visit (above, at an
+                    // earlier frame) overwrites the mark; the onset / offset left at the end are those of the FIRST visit in time.
+                    if (has_span) {                      // (uniform; with a jump of either kind the third mask covers every state)
+                        code |= (int)((row[2] >> sh) & 1ull) << 2;
+                        if (code >= 5) {
+                            const int Kk = repeat_source(rep_b, lab, kk, true, L).K;   // recomputed, as the strip kernel recomputes J
+                            code = kk - (Kk - (code - 5));                            // (negative: the predecessor lies to the right)
+                        } else if (code >= 3) {
+                            const int Jk = j_s[kk];
+                            for (int m = Jk >> 1; m < (kk >> 1); ++m)
+                                if (on_s[m] == -1) on_s[m] = kSkipped;
+                            code = kk - (Jk - (code - 3));
+                        }
+                    }
+                } else if constexpr (SPANS) {
                     if (has_span) {                      // (uniform: a span-free clip's backtrace is the plain DP's)
                         const int Jk = j_s[kk];          // the third mask exists only where spans do
                         if (Jk >= 0) code |= (int)((row[2] >> sh) & 1ull) << 2;
@@ -281,7 +355,8 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
         }
         int st = LA_OK;
         for (int nn = 0; nn < L; ++nn) {
-            if (SPANS && off_s[nn] == kSkipped) off_s[nn] = -1;
+            if (REP && on_s[nn] == kSkipped) on_s[nn] = -1;    // (never visited: off_s is still -1)
+            else if (!REP && SPANS && off_s[nn] == kSkipped) off_s[nn] = -1;
             else if (on_s[nn] < 0) st = LA_EINFEASIBLE;  // reference: ValueError from list.index (:183)
         }
         p.status[b] = st;   // (no path inside the windows: every on_s is -1, so LA_EINFEASIBLE)
@@ -306,9 +381,10 @@ __global__ __launch_bounds__(NW * 64) void viterbi_kernel(VitParams p) {
 // (the two rows take 131,104 B of LDS at R = 8: no room for a J array); the backtrace thread recomputes J(kk) from skip_from.
 // Masks are then [frame][r][wave][3], the third word written and read only where the clip has a span.  The window's gate is applied
 // to the emission as it leaves the prefetch registers, off the loop-carried chain, as in viterbi_kernel.
-template <int R, bool SPANS = false, bool WIN = false>
+template <int R, bool SPANS = false, bool WIN = false, bool REP = false>
 __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
     static_assert(!WIN || SPANS, "frame windows are a face of the optional-span forms");
+    static_assert(!REP || WIN, "repeatable spans are a face of the span + window forms (null pointers: absent)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // (R = 8 with spans: J, the window pairs and two generations of 4 x 8 prefetched emissions do not fit 128 VGPRs; the face waits on
     // the barrier, not on the loads, so its prefetch is two frames deep, and one frame deep with the 16 window registers)
@@ -323,6 +399,13 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
     const int S = 2 * L + 1;
     int32_t *on_g = p.onset + (int64_t)b * p.out_stride, *off_g = p.offset + (int64_t)b * p.out_stride;
     for (int n = tid; n < p.max_labels; n += NT) { on_g[n] = -1; off_g[n] = -1; }
+    [[maybe_unused]] int32_t *path_b = nullptr;   // every frame -1 until the backtrace has been there
+    if constexpr (REP) {
+        if (p.path) {
+            path_b = p.path + (int64_t)b * p.path_stride;
+            for (int t = tid; t < p.max_frames; t += NT) path_b[t] = -1;
+        }
+    }
     if (L <= 0) {
         if (tid == 0) { p.status[b] = LA_EEMPTY; p.final_score[b] = 0.0; }
         return;
@@ -351,6 +434,10 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
     [[maybe_unused]] bool jm1_ok[SPANS ? R : 1];
     [[maybe_unused]] int wlo[WIN ? R : 1], whi[WIN ? R : 1];
     [[maybe_unused]] bool has_span = false;
+    // the repeat span that starts at each owned ODD state's label (k0 is even: the odd states are r = 2 h + 1)
+    [[maybe_unused]] const int32_t *rep_b = nullptr;
+    [[maybe_unused]] int K[REP ? R / 2 : 1];
+    [[maybe_unused]] bool km1_ok[REP ? R / 2 : 1];
     if constexpr (SPANS) {
         if (!WIN || p.skip_from) skip_b = p.skip_from + (int64_t)b * p.skip_stride;   // (windows: a null skip_from = no span anywhere)
         bool any = false;
@@ -361,19 +448,30 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
             jm1_ok[r] = src.jm1_ok;
             any |= src.J >= 0;
         }
-        has_span = __syncthreads_or(any) != 0;   // workgroup-uniform: a clip without a span runs the plain loop
+        if constexpr (REP) {
+            if (p.repeat_from) rep_b = p.repeat_from + (int64_t)b * p.repeat_stride;
+#pragma unroll
+            for (int h = 0; h < R / 2; ++h) {
+                const RepeatSource src = repeat_source(rep_b, lab, k0 + 2 * h + 1, valid[2 * h + 1], L);
+                K[h] = src.K;
+                km1_ok[h] = src.km1_ok;
+                any |= src.K >= 0;
+            }
+        }
+        has_span = __syncthreads_or(any) != 0;   // workgroup-uniform: a clip without a span (repeats: without any jump) runs the plain loop
     }
     if constexpr (WIN) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             wlo[r] = 0, whi[r] = 0x7fffffff;
-            if (valid[r]) {
+            if (valid[r] && (!REP || p.win_lo)) {   // (repeats: a null window pair = every window open)
                 wlo[r] = p.win_lo[(int64_t)b * p.win_stride + k0 + r];
                 whi[r] = p.win_hi[(int64_t)b * p.win_stride + k0 + r];
             }
         }
     }
     [[maybe_unused]] const double pen = p.penalty;
+    [[maybe_unused]] const double rpen = p.repeat_penalty;
     const float *emb = p.em + (int64_t)b * p.em_bs;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -434,6 +532,9 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
                     Cell c = choose_neighbour(prev[r + 2], prev[r + 1], prev[r], can_skip[r], k0 + r == 0);
                     if constexpr (HAS) {
                         if (J[r] >= 0) c = jump_step(c, rb + J[r] + 2, rb + J[r] + 1, jm1_ok[r], pen);   // from the row, never from cur[]
+                        if constexpr (REP) {
+                            if ((r & 1) && K[r >> 1] >= 0) c = jump_step<5>(c, rb + K[r >> 1] + 2, rb + K[r >> 1] + 1, km1_ok[r >> 1], rpen);
+                        }
                     }
                     const int code = c.code;
                     cur[r] = c.best + (double)e_cur[i][r];
@@ -472,13 +573,31 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
                 if (kk != knext) { off_g[nn] = j + 1; ++entered; }
                 if (j == 0) on_g[nn] = 0;
             }
+            if constexpr (REP) {
+                if (path_b) path_b[j] = kk;
+            }
             int knew = kk;
             if (j > 0) {
                 const int t2 = kk / R, r = kk - t2 * R;
                 const unsigned long long *row = bt + (((int64_t)j * R + r) * 16 + (t2 >> 6)) * MW;
                 const int sh = t2 & 63;
                 int code = (int)((row[0] >> sh) & 1ull) | ((int)((row[1] >> sh) & 1ull) << 1);
-                if constexpr (SPANS) {
+                if constexpr (REP) {
+                    // No monotone path, so no entered + skipped count: a taken skip jump marks on_g = kSkipped only where the label has no
+                    // visit so far, a visit at an earlier frame overwrites the mark (the visit wins), and the status is taken from on_g below.
+                    if (has_span) {                          // (uniform; with a jump of either kind the third mask covers every state)
+                        code |= (int)((row[2] >> sh) & 1ull) << 2;
+                        if (code >= 5) {
+                            const int Kk = repeat_source(rep_b, lab, kk, true, L).K;   // K(kk), as the sweep computed it
+                            code = kk - (Kk - (code - 5));                            // (negative: the predecessor lies to the right)
+                        } else if (code >= 3) {
+                            const int ak = span_first(skip_b, kk >> 1);                // (code >= 3 only where the sweep saw a span: skip_b is not null)
+                            for (int m = ak; m < (kk >> 1); ++m)
+                                if (on_g[m] == -1) on_g[m] = kSkipped;
+                            code = kk - (2 * ak - (code - 3));
+                        }
+                    }
+                } else if constexpr (SPANS) {
                     if (has_span) {                          // (uniform: a span-free clip's backtrace is the plain DP's; skip_b is not null)
                         const int ak = span_first(skip_b, kk >> 1);      // J(kk) = 2 ak, as the sweep computed it
                         if (ak >= 0) {                               // the third mask is meaningful only for states with a span
@@ -498,7 +617,20 @@ __global__ __launch_bounds__(1024) void viterbi_strip_kernel(VitParams p) {
         }
         // the path is monotone in k, so every odd state is entered at most once and taken jumps do not overlap:
         // every label visited or inside a taken jump <=> entered + skipped == L
-        p.status[b] = entered + skipped == L ? LA_OK : LA_EINFEASIBLE;   // reference: ValueError from list.index (:183)
+        if constexpr (!REP) p.status[b] = entered + skipped == L ? LA_OK : LA_EINFEASIBLE;   // reference: ValueError from list.index (:183)
+    }
+    if constexpr (REP) {
+        // every label visited at least once, or inside a taken skip jump (its mark is written out as -1); by the whole workgroup
+        __threadfence_block();
+        __syncthreads();
+        bool missing = false;
+        for (int n = tid; n < L; n += NT) {
+            const int v = on_g[n];
+            if (v == kSkipped) on_g[n] = -1;
+            else missing |= v < 0;
+        }
+        const bool any_missing = __syncthreads_or(missing) != 0;
+        if (tid == 0) p.status[b] = any_missing ? LA_EINFEASIBLE : LA_OK;
     }
 }
 
@@ -552,34 +684,34 @@ int launch(const char *timer, int threads, const VitParams &p, const VitPlan &pl
 }
 
 // the lane-per-state forms; the single wave takes its neighbours by DPP unless the option is off or dp / bt are dumped
-template <bool SPANS, bool DUMP, bool WIN = false>
+template <bool SPANS, bool DUMP, bool WIN = false, bool REP = false>
 int launch_lanes(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
     switch (pl.nw) {
         case 1:
-            if (!DUMP && la::opts().viterbi_dpp) return launch<viterbi_kernel<1, true, SPANS, false, WIN>>(timer, 64, p, pl, batch, stream);
-            return launch<viterbi_kernel<1, false, SPANS, DUMP, WIN>>(timer, 64, p, pl, batch, stream);
-        case 2: return launch<viterbi_kernel<2, false, SPANS, DUMP, WIN>>(timer, 128, p, pl, batch, stream);
-        case 4: return launch<viterbi_kernel<4, false, SPANS, DUMP, WIN>>(timer, 256, p, pl, batch, stream);
-        case 8: return launch<viterbi_kernel<8, false, SPANS, DUMP, WIN>>(timer, 512, p, pl, batch, stream);
-        case 16: return launch<viterbi_kernel<16, false, SPANS, DUMP, WIN>>(timer, 1024, p, pl, batch, stream);
+            if (!DUMP && la::opts().viterbi_dpp) return launch<viterbi_kernel<1, true, SPANS, false, WIN, REP>>(timer, 64, p, pl, batch, stream);
+            return launch<viterbi_kernel<1, false, SPANS, DUMP, WIN, REP>>(timer, 64, p, pl, batch, stream);
+        case 2: return launch<viterbi_kernel<2, false, SPANS, DUMP, WIN, REP>>(timer, 128, p, pl, batch, stream);
+        case 4: return launch<viterbi_kernel<4, false, SPANS, DUMP, WIN, REP>>(timer, 256, p, pl, batch, stream);
+        case 8: return launch<viterbi_kernel<8, false, SPANS, DUMP, WIN, REP>>(timer, 512, p, pl, batch, stream);
+        case 16: return launch<viterbi_kernel<16, false, SPANS, DUMP, WIN, REP>>(timer, 1024, p, pl, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
 
 // the strip forms, R states per thread
-template <bool SPANS, bool WIN>
+template <bool SPANS, bool WIN, bool REP = false>
 int launch_strip(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
     switch (pl.strip) {
-        case 2: return launch<viterbi_strip_kernel<2, SPANS, WIN>>(timer, 1024, p, pl, batch, stream);
-        case 4: return launch<viterbi_strip_kernel<4, SPANS, WIN>>(timer, 1024, p, pl, batch, stream);
-        case 8: return launch<viterbi_strip_kernel<8, SPANS, WIN>>(timer, 1024, p, pl, batch, stream);
+        case 2: return launch<viterbi_strip_kernel<2, SPANS, WIN, REP>>(timer, 1024, p, pl, batch, stream);
+        case 4: return launch<viterbi_strip_kernel<4, SPANS, WIN, REP>>(timer, 1024, p, pl, batch, stream);
+        case 8: return launch<viterbi_strip_kernel<8, SPANS, WIN, REP>>(timer, 1024, p, pl, batch, stream);
     }
     return LA_EUNSUPPORTED;
 }
 
-template <bool SPANS, bool WIN>
+template <bool SPANS, bool WIN, bool REP = false>
 int launch_face(const char *timer, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
-    return pl.strip ? launch_strip<SPANS, WIN>(timer, p, pl, batch, stream) : launch_lanes<SPANS, false, WIN>(timer, p, pl, batch, stream);
+    return pl.strip ? launch_strip<SPANS, WIN, REP>(timer, p, pl, batch, stream) : launch_lanes<SPANS, false, WIN, REP>(timer, p, pl, batch, stream);
 }
 
 // What the four batch entries (and their workspace queries) differ in.  la_viterbi_lattice_batch takes its face from the pointers that
@@ -592,9 +724,10 @@ struct Entry {
     bool limit_first;                      // the label limit is reported before the stride check (la_viterbi_batch: after it)
     const char *over_batch, *over_query;   // the label-limit message of the batch call and of the workspace query
 };
-enum EntryId { kPlain, kSpans, kWindows, kLattice };   // the first three are (int)Face of the entry's fixed face; kLattice: decided per call
+// the first three are (int)Face of the entry's fixed face; kLattice, kRepeats: decided per call
+enum EntryId { kPlain, kSpans, kWindows, kLattice, kRepeats };
 static_assert(kPlain == (int)Face::Plain && kSpans == (int)Face::Spans && kWindows == (int)Face::Windows, "kEntries rows follow Face");
-const Entry kEntries[4] = {
+const Entry kEntries[5] = {
     {face_names(Sweep::Dp, Face::Plain), 2, 4095, false, "viterbi: max_labels %d exceeds 4095",
      "viterbi: max_labels %d exceeds 4095 (8192 lattice states per workgroup)"},
     {face_names(Sweep::Dp, Face::Spans), 3, 511, true, "viterbi_spans: max_labels %d exceeds 511 (one lane per lattice state)",
@@ -603,7 +736,10 @@ const Entry kEntries[4] = {
      "viterbi_windows: max_labels %d exceeds 511 (one lane per lattice state)"},
     {{"viterbi_lattice_batch", "viterbi_lattice", "viterbi_lattice"}, 3, 4095, true,
      "viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)",
-     "viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)"}};
+     "viterbi_lattice: max_labels %d exceeds 4095 (8192 lattice states per workgroup)"},
+    {{"viterbi_repeats_batch", "viterbi_repeats", "viterbi_repeats"}, 3, 4095, true,
+     "viterbi_repeats: max_labels %d exceeds 4095 (8192 lattice states per workgroup)",
+     "viterbi_repeats: max_labels %d exceeds 4095 (8192 lattice states per workgroup)"}};
 
 int query_workspace(EntryId id, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     const Entry &e = kEntries[id];
@@ -635,8 +771,8 @@ int run_batch(EntryId id, VitParams p, int32_t batch, void *workspace, size_t wo
     const Entry &e = kEntries[id];
     const char *who = e.names.entry;
     if (batch == 0) return LA_OK;
-    Face face = id == kLattice ? Face::Plain : (Face)id;
-    if (id == kLattice) {
+    Face face = id >= kLattice ? Face::Plain : (Face)id;
+    if (id == kLattice || id == kRepeats) {
         LA_CHECK_ARG((p.win_lo == nullptr) == (p.win_hi == nullptr), "%s: win_lo and win_hi go together (both null: no windows)", who);
         face = p.win_lo ? Face::Windows : p.skip_from ? Face::Spans : Face::Plain;
     }
@@ -644,12 +780,17 @@ int run_batch(EntryId id, VitParams p, int32_t batch, void *workspace, size_t wo
     LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
     // (la_viterbi_batch has no penalty: 0.  The lattice entry checks the one it was given whatever the face)
     LA_CHECK_ARG(p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
+    if (id == kRepeats) LA_CHECK_ARG(p.repeat_penalty >= 0.0, "%s: repeat_penalty must be >= 0 (and not NaN)", who);
     VitPlan pl;
     const bool planned = plan_viterbi(batch, p.max_frames, p.max_labels, e.mask_words, e.label_limit, &pl);
     LA_CHECK_ARG(p.strides_ok(face, p.out_stride, false) || (e.limit_first && !planned), "%s: strides smaller than max_labels", who);
     if (!planned) {
         la::set_error(e.over_batch, p.max_labels);
         return LA_EUNSUPPORTED;
+    }
+    if (id == kRepeats) {
+        LA_CHECK_ARG(!p.repeat_from || p.repeat_stride >= p.max_labels, "%s: repeat_stride smaller than max_labels", who);
+        LA_CHECK_ARG(!p.path || p.path_stride >= p.max_frames, "%s: path_stride smaller than max_frames", who);
     }
     LA_CHECK_ARG(pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes), "%s: workspace too small (%zu < %zu)", who,
                  workspace_bytes, pl.ws_bytes);
@@ -662,6 +803,8 @@ int run_batch(EntryId id, VitParams p, int32_t batch, void *workspace, size_t wo
     }
     p.bt_global = reinterpret_cast<unsigned long long *>(workspace);
     p.bt_in_lds = pl.bt_in_lds ? 1 : 0;
+    // the repeat face sits on top of the span + window one whatever is given: null pointers are "absent" inside the kernel
+    if (id == kRepeats) return launch_face<true, true, true>(timer, p, pl, batch, stream);
     switch (face) {
         case Face::Plain: return launch_face<false, false>(timer, p, pl, batch, stream);
         case Face::Spans: return launch_face<true, false>(timer, p, pl, batch, stream);
@@ -735,6 +878,26 @@ extern "C" int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride
                      batch_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset,
                                   offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride),
                      batch, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int la_viterbi_repeats_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace(kRepeats, batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_viterbi_repeats_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                        const int32_t *labels, int32_t labels_stride, const int32_t *n_labels,
+                                        const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
+                                        int32_t *onset, int32_t *offset, int32_t out_stride, double *final_score,
+                                        int32_t *status, const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                        const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                        const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty,
+                                        int32_t *path, int32_t path_stride,
+                                        void *workspace, size_t workspace_bytes, void *stream_) {
+    VitParams p = batch_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset,
+                               offset, out_stride, final_score, status, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride);
+    p.repeat_from = repeat_from, p.repeat_stride = repeat_stride, p.repeat_penalty = repeat_penalty;
+    p.path = path, p.path_stride = path_stride;
+    return run_batch(kRepeats, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // run_viterbi_core(dp, bt, lp, ls, label) of the reference (utils/alignment.py:73-119) for ONE utterance: same

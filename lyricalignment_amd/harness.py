@@ -203,6 +203,24 @@ def _sheet_lines_out(res, lines: Sequence[str], per_line=()):
     return (out, *extra)
 
 
+def _line_occurrences(segments, lines: Sequence[str]) -> List[list]:
+    """One clip's visits (char_index, onset_s, offset_s) in time order -> per line the list of its occurrences, each [[onset, offset, char],
+    ...]: a new occurrence of a line begins where a visit does not continue the line's last one (its character index does not go up)."""
+    start_of, line_of = [], []
+    for i, line in enumerate(lines):
+        start_of.append(len(line_of))
+        line_of += [i] * len(line)
+    out: List[list] = [[] for _ in lines]
+    last = None                                  # (line, character index) of the previous visit
+    for n, on, off in segments:
+        i = line_of[n]
+        if last is None or last[0] != i or n <= last[1]:
+            out[i].append([])
+        out[i][-1].append([on, off, lines[i][n - start_of[i]]])
+        last = (i, n)
+    return out
+
+
 def _timed_lines(who: str, lrc) -> List[tuple]:
     pairs = parse_lrc(lrc) if isinstance(lrc, str) else [(float(s), str(line)) for s, line in lrc]
     if not pairs:
@@ -218,7 +236,8 @@ def _sheet_confidence(res, scores, lines: Sequence[str]):
 
 
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
-                       use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False):
+                       use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
+                       repeat_penalty: float = 0.0):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
@@ -226,9 +245,23 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     with_confidence: -> (lines_out, sung), sung[i] = the probability under the model that line i was sung (a Python float: present_prob
     of the line's first character, AlignModel.align(return_span_confidence=True)); 1 for a mandatory line, and 1 - span_skip_prob of an
     optional line's span.
-    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song)."""
+    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song).
+    repeatable (one flag per line; None: the result as above): lines with repeatable[i] may be sung again right after they were sung (a
+    chorus marked "x2"; AlignModel.align(repeat_spans=...), repeat_penalty >= 0 per return).  Each line's entry is then the LIST of its
+    occurrences in time order, each [[onset, offset, char], ...] -- empty if the alignment left the line out.  Not with with_confidence
+    (ValueError)."""
     lines = list(lines)
     ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
+    if repeatable is not None:
+        from .utils.alignment import repeats_from_lines
+        if with_confidence:
+            raise ValueError("align_record_lines: repeatable does not go with with_confidence (no posteriors on the lattice with repeatable spans)")
+        repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
+        with torch.no_grad():
+            _, segments = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                      repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty,
+                                      return_segments=True)
+        return _line_occurrences(segments[0], lines)
     with torch.no_grad():
         if with_confidence:
             res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,

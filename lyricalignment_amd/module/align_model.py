@@ -337,7 +337,8 @@ class AlignModel(torch.nn.Module):
               use_ctc: bool = True, hop_size_second: float = 0.02, get_orig_len: bool = True, return_frames: bool = False,
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
               skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
-              return_anchored_confidence: bool = False, return_sheet_confidence: bool = False):
+              return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
+              repeat_penalty: float = 0.0, return_segments: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -381,8 +382,16 @@ class AlignModel(torch.nn.Module):
         to 4095 labels, with or without optional_spans, onset_anchors / char_windows, per_clip and the long form
         (ops.alignment_posteriors_lattice on the lattice the DP ran on); window_log_prob is 0.0 without windows.  Up to 511 labels the numbers
         are return_anchored_confidence's exactly.  The sweep keeps every alpha row: T * 1024 R * 8 bytes per clip beyond 511 labels (R = 2 /
-        4 / 8 for up to 1023 / 2047 / 4095 labels).  Not together with any of the three older confidence keywords (ValueError)."""
-        from ..utils.alignment import LatticeResult, _formatted, _labels_to_device, _skip_from_of_spans, _windows_of, run_lattice
+        4 / 8 for up to 1023 / 2047 / 4095 labels).  Not together with any of the three older confidence keywords (ValueError).
+        repeat_spans (addition): repeat_spans[b] = list of (a, e) pairs -- having sung label e-1 of clip b the path may return to label a
+        (a chorus printed once and sung twice; ops.viterbi_repeats_batch, repeat_penalty >= 0 per return).  The result keeps its shape: the
+        FIRST visit per character, None for a character never visited.  With optional_spans, char_windows / onset_anchors, per_clip and
+        the long form, up to 4095 labels; with return_frames the DP's four tensors and path [B, T] (the lattice state per frame).  Not
+        with any confidence keyword (ValueError).  None or all-empty: the call as it was.
+        return_segments (addition): -> (seconds, segments), segments[b] = the time-ordered list of (char_index, onset_s, offset_s) of EVERY
+        visit, with or without repeat_spans."""
+        from ..utils.alignment import (LatticeResult, _formatted, _labels_to_device, _repeat_rows, _segments_from_path, _skip_from_of_spans,
+                                       _windows_of, run_lattice)
         if return_anchored_confidence and (return_confidence or return_span_confidence):
             raise ValueError("align: return_anchored_confidence does not go with return_confidence / return_span_confidence (it returns "
                              "their numbers on the windowed lattice)")
@@ -412,8 +421,9 @@ class AlignModel(torch.nn.Module):
                              "keyword: return_span_confidence=True gives them)")
         confidence = ("sheet" if return_sheet_confidence else "anchored" if return_anchored_confidence else "span" if return_span_confidence
                       else "plain" if return_confidence else None)
+        repeat_from = _repeat_rows("align", repeat_spans, return_segments, lab_lists, confidence is not None)
         # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
-        need_em = confidence is not None or skip_from is not None or windows is not None
+        need_em = confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
         head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
                                        want_emissions=need_em, **kw)
         if need_em:
@@ -421,12 +431,13 @@ class AlignModel(torch.nn.Module):
             # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same bits;
             # the sheet confidence keeps the fused head's, which run_lattice uses only where there is neither a span nor a window)
             r = run_lattice(head[4], lab_dev, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
-                            dp=None if return_anchored_confidence else head[:4])
+                            dp=None if return_anchored_confidence else head[:4], repeat_from=repeat_from, repeat_penalty=repeat_penalty)
         else:
             r = LatticeResult(*head)
-        if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors
-            return tuple(t for t in r if t is not None)
-        return _formatted(r, lab_lists, hop_size_second, optional_spans)
+        if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path)
+            return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,))
+        seconds = _formatted(r, lab_lists, hop_size_second, optional_spans)
+        return (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
 
 
 def encoder_only_engine(whisper_model, mel: torch.Tensor) -> torch.Tensor:

@@ -179,6 +179,43 @@ def viterbi_lattice_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
                     None if win_lo is None else (win_lo, win_hi))
 
 
+def viterbi_repeats_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                          skip_from: Optional[torch.Tensor] = None, skip_penalty: float = 0.0, win_lo: Optional[torch.Tensor] = None,
+                          win_hi: Optional[torch.Tensor] = None, repeat_from: Optional[torch.Tensor] = None, repeat_penalty: float = 0.0
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """la_viterbi_repeats_batch: viterbi_lattice_batch on the lattice with REPEATABLE label spans, for up to 4095 labels.  repeat_from
+    [B, >= Lmax] i32 (device): repeat_from[b, a] = e (a < e <= L_b) lets the path of clip b return to label a after label e-1, any number
+    of times, each return charged repeat_penalty; anything else (-1) = no repeat span starts at a.  None or all -1: onset, offset, score
+    and status are viterbi_lattice_batch's bit for bit.
+    -> onset, offset (a label's FIRST visit in time), final_score, status, path [B,T] i32 (the lattice state at every frame t < T_b;
+    -1 for t >= T_b and for a clip whose status is LA_EEMPTY or LA_EINVAL or that has no path inside its windows)."""
+    who = "viterbi_repeats_batch"
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError(f"{who}: win_lo and win_hi go together")
+    windows = None if win_lo is None else (win_lo, win_hi)
+    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, "lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty, windows)
+    if repeat_from is not None:
+        _dev(repeat_from, "repeat_from", torch.int32)
+        if repeat_from.dim() != 2 or repeat_from.shape[0] != B or repeat_from.shape[1] < Lmax or repeat_from.stride(1) != 1:
+            raise ValueError(f"{who}: repeat_from [B, >= Lmax] with unit inner stride expected")
+    repeat_penalty = float(repeat_penalty)
+    if not repeat_penalty >= 0.0:
+        raise ValueError(f"{who}: repeat_penalty must be >= 0")
+    dev = em.device
+    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
+    score = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    ws, need = _lattice_workspace("viterbi_repeats_workspace_bytes", B, T, Lmax, dev)
+    skip_stride = skip_from.stride(0) if skip_from is not None else 0
+    check(lib().la_viterbi_repeats_batch(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), *_face_args("lattice", skip_from, skip_stride, skip_penalty, windows),
+        ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty, ptr(path), T,
+        ptr(ws), need, stream_ptr()), who)
+    return onset, offset, score, status, path
+
+
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
                          onset: torch.Tensor, offset: torch.Tensor, boundary_window: int = 2, want_gamma: bool = False):
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,

@@ -81,6 +81,66 @@ def _skip_from_of_spans(optional_spans, label_lists: List[List[int]]):
     return rows if any_span else None
 
 
+def repeats_from_lines(line_lengths: Sequence[int], repeatable: Sequence[bool]) -> List[int]:
+    """One clip's repeat_from array (include/lyricalign.h la_viterbi_repeats_batch) for lyrics given as consecutive lines of
+    line_lengths[i] characters: L entries, repeat_from[start of line i] = end of line i for every line with repeatable[i] (the line may
+    be sung again right after it was sung), -1 elsewhere."""
+    lengths = [int(v) for v in line_lengths]
+    if len(lengths) != len(repeatable):
+        raise ValueError("repeats_from_lines: one repeatable flag per line expected")
+    if any(v <= 0 for v in lengths):
+        raise ValueError("repeats_from_lines: every line must hold at least one character")
+    repeat_from = [-1] * sum(lengths)
+    a = 0
+    for n_chars, rpt in zip(lengths, repeatable):
+        if rpt:
+            repeat_from[a] = a + n_chars
+        a += n_chars
+    return repeat_from
+
+
+def _repeat_from_of_spans(repeat_spans, label_lists: List[List[int]]):
+    """repeat_spans[b] = list of (a, e) pairs: having sung label e-1 of utterance b the path may return to label a -> host int32 tensor
+    [B, Lmax] of repeat_from rows (-1 = none), or None when no utterance has a span.  ValueError for a < 0, a >= e, e > L_b or two spans
+    with one start."""
+    if repeat_spans is None:
+        return None
+    if len(repeat_spans) != len(label_lists):
+        raise ValueError(f"repeat_spans: {len(label_lists)} span lists expected, one per utterance")
+    Lmax = max(1, max((len(l) for l in label_lists), default=1))
+    rows = torch.full((len(label_lists), Lmax), -1, dtype=torch.int32)
+    any_span = False
+    for b, spans in enumerate(repeat_spans):
+        L = len(label_lists[b])
+        for a, e in (spans or ()):
+            a, e = int(a), int(e)
+            if a < 0 or a >= e or e > L:
+                raise ValueError(f"repeat_spans[{b}]: span ({a}, {e}) needs 0 <= a < e <= {L}")
+            if int(rows[b, a]) >= 0:
+                raise ValueError(f"repeat_spans[{b}]: two spans start at {a} (one span per start position)")
+            rows[b, a] = e
+            any_span = True
+    return rows if any_span else None
+
+
+def _segments_from_path(path, frame_counts: Sequence[int], hop_size_second: float):
+    """path [B, T] (ops.viterbi_repeats_batch) -> per utterance the time-ordered list of (char_index, onset_s, offset_s) of every visit: the
+    maximal runs of frames in one odd lattice state (a repeated line has one visit per time it was sung)."""
+    rows = path.cpu().numpy()
+    out = []
+    for b, T in enumerate(frame_counts):
+        row, visits, t = rows[b, : int(T)], [], 0
+        while t < len(row):
+            u = t
+            while u + 1 < len(row) and row[u + 1] == row[t]:
+                u += 1
+            if row[t] >= 0 and row[t] % 2 == 1:
+                visits.append((int(row[t]) // 2, float(t) * hop_size_second, float(u + 1) * hop_size_second))
+            t = u + 1
+        out.append(visits)
+    return out
+
+
 def _frame_bound(seconds: float, hop: float, n_frames: int, up: bool) -> int:
     """ceil (up) or floor of seconds / hop with a 1e-9 guard against the division's rounding, clamped to -1 .. n_frames + 1."""
     x = min(max(float(seconds) / hop, -1.0), float(n_frames) + 1.0)
@@ -213,12 +273,24 @@ class LatticeResult(NamedTuple):
     present_prob: Optional[torch.Tensor] = None
     span_skip_prob: Optional[torch.Tensor] = None
     log_z_free: Optional[torch.Tensor] = None
+    path = None             # (no tuple field: the eleven above are what the lattices without repeatable spans return; see below)
+
+
+class RepeatLatticeResult(LatticeResult):
+    """LatticeResult of the lattice with repeatable spans: the same eleven tuple fields (no posteriors exist there, so seven are None) and,
+    behind them, `path` [B, T] int32 -- the lattice state per frame, ops.viterbi_repeats_batch's fifth output."""
+
+    def __new__(cls, onset, offset, score, status, path):
+        r = super().__new__(cls, onset, offset, score, status)
+        r.path = path
+        return r
 
 
 POSTERIOR_MAX_LABELS = 511      # one lane per lattice state in the sum-product sweeps and in the span / window entries of the DP
 
 
-def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0.0, confidence=None, boundary_window=2, dp=None) -> LatticeResult:
+def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0.0, confidence=None, boundary_window=2, dp=None,
+                repeat_from=None, repeat_penalty=0.0) -> LatticeResult:
     """The one place where the face of an alignment is decided (csrc/la_lattice.h Face, through the ops wrappers): the DP and, if asked
     for, the posteriors on the lattice that skip_from (host rows of _skip_from_of_spans, or None) and windows (host (win_lo, win_hi)
     of _windows_of, or None) describe.  em / lab / n_lab / nf are device tensors.
@@ -230,9 +302,20 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     ops.alignment_posteriors_lattice on the lattice given, log_z_free from a second call without windows where windows were given, else
     from log_z itself; the result is filled exactly as for "anchored".
     More than 511 labels (up to 4095): the DP with spans or windows is ops.viterbi_lattice_batch; the three older kinds of confidence
-    stop at 511 and raise NotImplementedError before anything is launched ("sheet" is the kind for whole songs)."""
+    stop at 511 and raise NotImplementedError before anything is launched ("sheet" is the kind for whole songs).
+    repeat_from (host rows of _repeat_from_of_spans, or None) / repeat_penalty: the lattice with repeatable spans, at any size up to
+    4095 labels, with or without skip_from and windows -- ops.viterbi_repeats_batch; the result's `path` holds the state per frame.  No
+    kind of confidence exists on that lattice: ValueError before anything is launched."""
     if confidence not in (None, "plain", "span", "anchored", "sheet"):
         raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
+    if repeat_from is not None:
+        if confidence is not None:
+            raise ValueError("run_lattice: no posteriors on the lattice with repeatable spans (repeat_from goes with confidence=None)")
+        dev = em.device
+        win = (None, None) if windows is None else (windows[0].to(dev), windows[1].to(dev))
+        out = ops.viterbi_repeats_batch(em, lab, n_lab, nf, None if skip_from is None else skip_from.to(dev), skip_penalty, *win,
+                                        repeat_from.to(dev), repeat_penalty)
+        return RepeatLatticeResult(*out)
     wide = lab.shape[1] > POSTERIOR_MAX_LABELS
     if wide and confidence not in (None, "sheet"):
         raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posterior sweeps "
@@ -295,8 +378,21 @@ def _device_of(prediction) -> torch.device:
     return torch.device(f"cuda:{torch.cuda.current_device()}")
 
 
+def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, scored: bool):
+    """The repeat_from rows a public function hands to run_lattice: _repeat_from_of_spans' where a span is given; all -1 where only the
+    segments are asked for (the same result, with its path); None otherwise.  ValueError with any kind of confidence."""
+    rows = _repeat_from_of_spans(repeat_spans, label_lists)
+    if (rows is not None or return_segments) and scored:
+        raise ValueError(f"{who}: repeat_spans / return_segments do not go with a confidence (no posteriors on the lattice with "
+                         "repeatable spans)")
+    if rows is None and return_segments:
+        rows = torch.full((len(label_lists), max(1, max((len(l) for l in label_lists), default=1))), -1, dtype=torch.int32)
+    return rows
+
+
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
-             char_windows=None, onset_anchors=None, anchored=False, sheet=False):
+             char_windows=None, onset_anchors=None, anchored=False, sheet=False, repeat_spans=None, repeat_penalty=0.0,
+             return_segments=False):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -317,14 +413,17 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
                          "(perform_viterbi(_ctc)_anchored_scored give them)")
     confidence = "sheet" if sheet else "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
+    repeat_from = _repeat_rows("perform_viterbi", repeat_spans, return_segments, lists, confidence is not None)
     em = ops.emissions_from_logits(pred, lab, n_lab, variant)
     nf = torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
-    r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window)
-    return _formatted(r, lists, hop_size_second, optional_spans)
+    r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, repeat_from=repeat_from,
+                    repeat_penalty=repeat_penalty)
+    seconds = _formatted(r, lists, hop_size_second, optional_spans)
+    return (seconds, _segments_from_path(r.path, counts, hop_size_second)) if return_segments else seconds
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                    char_windows=None, onset_anchors=None):
+                    char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
     aligned over its first n_frames[b] rows, as if it had been handed over alone.
     optional_spans (addition): optional_spans[b] = list of (a, n) pairs, labels a .. n-1 of utterance b may be left out by the path
@@ -334,39 +433,51 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     the DP runs on the lattice with per-state frame windows (la_viterbi_windows_batch), with or without optional_spans.  None or
     all-empty: the call as it was.  An utterance without a path inside its windows raises like one too short for its labels.
     Up to 4095 labels with any of these keywords (beyond 511 the DP is la_viterbi_lattice_batch); the _scored functions at most 511,
-    except perform_viterbi(_ctc)_sheet_scored, which take whole songs (up to 4095)."""
+    except perform_viterbi(_ctc)_sheet_scored, which take whole songs (up to 4095).
+    repeat_spans (addition): repeat_spans[b] = list of (a, e) pairs -- having sung label e-1 of utterance b the path may return to label
+    a (a chorus printed once and sung twice; la_viterbi_repeats_batch, repeat_penalty >= 0 per return, the only control of how often).
+    The result keeps its shape: the FIRST visit per character, None for a character never visited.  ValueError for a < 0, a >= e, e > L
+    or two spans with one start.  With optional_spans, char_windows / onset_anchors and n_frames, up to 4095 labels; the _scored
+    functions and anchored_alignment_loss raise ValueError with it.  None or all-empty: the call as it was.
+    return_segments (addition): -> (predicted_onset_offset, segments), segments[b] = the time-ordered list of (char_index, onset_s,
+    offset_s) of EVERY visit, with or without repeat_spans."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
-                    skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
+                    skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
+                    repeat_penalty=repeat_penalty, return_segments=return_segments)
 
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                        char_windows=None, onset_anchors=None):
+                        char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
-                    skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
+                    skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
+                    repeat_penalty=repeat_penalty, return_segments=return_segments)
 
 
 def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                           char_windows=None, onset_anchors=None):
+                           char_windows=None, onset_anchors=None, repeat_spans=None):
     """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
     scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
     sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi.
     optional_spans / skip_penalty as perform_viterbi: skipped characters are None (their three scores 0), and each dict additionally holds
     "sung_prob": [L] (probability that the character is on the path at all) and "span_skip_prob": one value per span, in the order given
     (probability that the span was left out) -- la_alignment_posteriors_spans.  Without a span the dicts are as before, without these keys.
-    char_windows / onset_anchors: ValueError unless None or all-empty (perform_viterbi_anchored_scored is the function for them)."""
+    char_windows / onset_anchors: ValueError unless None or all-empty (perform_viterbi_anchored_scored is the function for them).
+    repeat_spans: ValueError unless None or all-empty, here and in every other _scored function (no posteriors on that lattice)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
-                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    repeat_spans=repeat_spans)
 
 
 def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                               skip_penalty=0.0, char_windows=None, onset_anchors=None):
+                               skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
-                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors)
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    repeat_spans=repeat_spans)
 
 
 def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                    skip_penalty=0.0, char_windows=None, onset_anchors=None):
+                                    skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
     """perform_viterbi with char_windows / onset_anchors plus the confidence GIVEN them (addition): -> (predicted_onset_offset, scores).
     The DP and the forward-backward sweep run on the lattice with per-state frame windows (la_viterbi_windows_batch,
     la_alignment_posteriors_windows), with or without optional_spans.  scores[b] holds perform_viterbi_scored's keys with optional_spans
@@ -377,19 +488,21 @@ def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, bo
     window_log_prob 0.0.  An utterance without a path inside its windows raises as in perform_viterbi."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    anchored=True)
+                    anchored=True,
+                    repeat_spans=repeat_spans)
 
 
 def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                        skip_penalty=0.0, char_windows=None, onset_anchors=None):
+                                        skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
     """perform_viterbi_ctc plus the confidence given the windows: see perform_viterbi_anchored_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    anchored=True)
+                    anchored=True,
+                    repeat_spans=repeat_spans)
 
 
 def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                 skip_penalty=0.0, char_windows=None, onset_anchors=None):
+                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
     """Whole-song timing with its confidences (addition): perform_viterbi_anchored_scored's (predicted_onset_offset, scores) for up to 4095
     labels, with or without optional_spans and char_windows / onset_anchors (la_viterbi_lattice_batch's routing for the DP,
     la_alignment_posteriors_lattice for the posteriors).  window_log_prob is 0.0 without windows.  Up to 511 labels the numbers are
@@ -397,15 +510,17 @@ def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, bound
     511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    sheet=True)
+                    sheet=True,
+                    repeat_spans=repeat_spans)
 
 
 def perform_viterbi_ctc_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                     skip_penalty=0.0, char_windows=None, onset_anchors=None):
+                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
     """perform_viterbi_ctc plus the whole-song confidences: see perform_viterbi_sheet_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    sheet=True)
+                    sheet=True,
+                    repeat_spans=repeat_spans)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
@@ -450,7 +565,7 @@ def anchored_loss_inputs(labels, frame_counts: Sequence[int], onset_anchors=None
 
 
 def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_windows=None, optional_spans=None, skip_penalty=0.0,
-                            hop_size_second=0.02, n_frames=None, on_infeasible="raise"):
+                            hop_size_second=0.02, n_frames=None, on_infeasible="raise", repeat_spans=None):
     """Training from line times (addition; the reference's losses need a label for every frame): -log of the total weight of the alignments
     that char_windows / onset_anchors (per utterance, in windows_from_anchors' form, seconds in the utterance's own frames) and
     optional_spans (as perform_viterbi) allow, per frame and averaged over the batch -- include/lyricalign.h la_anchored_alignment_loss.
@@ -461,7 +576,10 @@ def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_window
     -> a device scalar with a grad_fn: `loss.backward(); optimizer.step()` works with it.
     on_infeasible: "raise" reads the per-clip status once (ONE host synchronisation per call) and raises ValueError naming the first clip
     without a path inside its windows (or without labels); "skip" does not read it: such a clip adds nothing to the loss (still divided by
-    B) and gets a zero gradient."""
+    B) and gets a zero gradient.
+    repeat_spans: ValueError unless None or all-empty (the loss does not know the lattice with repeatable spans)."""
+    if repeat_spans is not None and any(len(v or ()) for v in repeat_spans):
+        raise ValueError("anchored_alignment_loss: repeat_spans are not supported (no sum-product sweep on the lattice with repeatable spans)")
     if on_infeasible not in ("raise", "skip"):
         raise ValueError('anchored_alignment_loss: on_infeasible must be "raise" or "skip"')
     if not torch.is_tensor(align_logit) or align_logit.dim() != 3 or not align_logit.is_cuda or align_logit.dtype != torch.float32:
