@@ -138,7 +138,9 @@ int la_timer_read_work(double *total_ms, int64_t *timed_launches, double *timed_
  *                                         consumer epilogues) run the epilogue arithmetic in the accumulator layout and cross the LDS transpose as
  *                                         16-bit values (default) | 0 = every tile crosses it as float32 (twice the staging; identical bits: A/B partner)
  * A library built with -DLA_EXPERIMENTS (tools/build_variant.sh; la_has_experiments() == 1) additionally carries the measured-slower
- * kernel structures of rounds 2-4 and their per-launch developer switches; the shipped library has neither. */
+ * GEMM kernel structures of rounds 2-4 and their per-launch developer switches; the shipped library has neither.  The attention
+ * kernels have one form per (element type, workgroup size, LA_Q_LOG2) in every build; their timing knock-outs are compile-time masks
+ * (-DLA_ATTN_KO=<mask>, -DLA_X2F_KO=<mask>: one library per mask, tools/ab_attn_knockouts.sh), never a switch read at a launch. */
 int la_set_option(const char *name, int64_t value);
 int la_get_option(const char *name, int64_t *value);
 int la_has_experiments(void);

@@ -18,21 +18,16 @@
 // row sums carry the same factor and it cancels in O = sum P v / sum P.
 #include <type_traits>
 
+#include "la_attn_tile.h"
 #include "la_x2.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
+using namespace la::attn;
 
 #ifndef LA_X2F_KO
-#define LA_X2F_KO 0                     // timing-only builds (tools/ab_x2f_knockouts.sh; results are garbage): bit mask of parts of the forward
+#define LA_X2F_KO 0                     // timing-only builds (tools/ab_attn_knockouts.sh; results are garbage): bit mask of parts of the forward
 #endif                                  // tile loop left out -- 1 exponentials, 2 V^T fragment reads, 4 K fragment reads, 8 staging, 16 MFMAs, 32 barrier
-constexpr int KT = 64;                  // keys per tile
-constexpr int IMG = KT * 128;           // one plane of one K or V tile: [64 keys][128 B]
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
 struct FwdParams {
@@ -103,51 +98,13 @@ __global__ __launch_bounds__(1024) void heads_split_kernel(const float *x, int64
     }
 }
 
-// Block -> (query tile, head, clip): as la_attention.hip block_coord -- the query tiles of one (clip, head) share one XCD's L2
-struct BlockCoord { int qt, head, clip; };
-__device__ __forceinline__ BlockCoord block_coord(int nq, int n_head, int batch) {
-    const int L = blockIdx.x, pairs = n_head * batch;
-    int pair, qt;
-    if ((pairs & 7) == 0) {
-        const int x = L & 7, idx = L >> 3;
-        pair = x + 8 * (idx / nq);
-        qt = idx % nq;
-    } else {
-        pair = L / nq;
-        qt = L % nq;
-    }
-    return BlockCoord{qt, pair % n_head, pair / n_head};
-}
-// accumulator register -> row (key / dv index) inside a 32x32 tile for lane half h
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-// K images: 16-B slot s of row r at slot s ^ ((r >> 1) & 7) (ds_read_b128 rows); V images: s ^ (((r >> 1) & 1) << 2) (ds_read_b64_tr_b16)
-__device__ __forceinline__ int kswz(int r) { return (r >> 1) & 7; }
-__device__ __forceinline__ int vswz(int r) { return ((r >> 1) & 1) << 2; }
 __device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-// staging: a piece = rows 8i .. 8i+7 of one image (16 B per lane); wave w brings pieces w * PER .. of the hi and lo image of a K or V tile
-template <int PER> struct KvOff { unsigned k[PER], v[PER]; };
-template <int PER>
-__device__ __forceinline__ KvOff<PER> kv_offsets(int64_t C, int key0, int T, int wave, int lane) {
-    KvOff<PER> o;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int r = (wave * PER + i) * 8 + (lane >> 3), ps = lane & 7;
-        const int rr = key0 + r < T ? r : T - 1 - key0;          // rows past the end: the last key (masked in the scores)
-        o.k[i] = (unsigned)(rr * C * 4) + ((ps ^ kswz(r)) << 4);
-        o.v[i] = (unsigned)(rr * C * 4) + ((ps ^ vswz(r)) << 4);
-    }
-    return o;
-}
+// one operand tile: the hi and the lo image of token rows key0 .. key0 + 63
 template <int PER>
 __device__ __forceinline__ void stage_tile(const unsigned short *base, int64_t C, int key0, const unsigned (&off)[PER], unsigned buf, int wave) {
     const unsigned short *src = base + (int64_t)key0 * 2 * C;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const unsigned piece = (wave * PER + i) * 1024;
-        la::glds16_so(off[i], src, buf + piece);
-        la::glds16_so(off[i], src + C, buf + IMG + piece);
-    }
+    stage_pair<PER>(src, off, buf, src, C, off, buf + IMG, wave);
 }
 
 // (a, b) -> packed halves hi = (f16 a, f16 b) and lo = (f16 (a - hi.x), f16 (b - hi.y)): one v_cvt_pk_f16_f32 and two mixed-precision
@@ -211,24 +168,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x2_fwd_kernel(FwdParams 
     const int nkv_all = nkv;
     if (p.causal) nkv = min(nkv, (min(p.q_len, (qt + 1) * QT) - 1) / KT + 1);   // tiles above the block's diagonal are all masked
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(la::lds_addr_u32(lds));
-    const KvOff<PER> off_full = kv_offsets<PER>(C, 0, KT, wave, lane);
-    const KvOff<PER> off_last = kv_offsets<PER>(C, (nkv_all - 1) * KT, T, wave, lane);
+    const KvOff<PER> off_full = kv_offsets<PER, 4>(C, 0, KT, wave, lane);
+    const KvOff<PER> off_last = kv_offsets<PER, 4>(C, (nkv_all - 1) * KT, T, wave, lane);
     auto stage = [&](int t, unsigned buf) __attribute__((always_inline)) {
         stage_tile<PER>(kbase, C, t * KT, t == nkv_all - 1 ? off_last.k : off_full.k, buf, wave);
         stage_tile<PER>(vbase, C, t * KT, t == nkv_all - 1 ? off_last.v : off_full.v, buf + 2 * IMG, wave);
     };
     stage(0, lds0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // the Q fragments are "used" here so that their wait sits before the loop (la_attention.hip: otherwise every tile waits for its
-    // successor's staging loads)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 t0 = __builtin_bit_cast(u32x4, qh[c]), t1 = __builtin_bit_cast(u32x4, ql[c]);
-        asm volatile("" : "+v"(t0), "+v"(t1));
-        qh[c] = __builtin_bit_cast(uint4, t0);
-        ql[c] = __builtin_bit_cast(uint4, t1);
-    }
+    for (int c = 0; c < 4; ++c) pin_frags(qh[c], ql[c]);
     __syncthreads();
 
     const int g = lane >> 4, q4 = (lane & 15) >> 2, pp = lane & 3;
@@ -253,10 +202,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x2_fwd_kernel(FwdParams 
             for (int c = 0; c < 4; ++c)
 #pragma unroll
                 for (int sub = 0; sub < 2; ++sub) {
-                    const int row = sub * 32 + i32;
-                    const int off = row * 128 + (((2 * c + h) ^ kswz(row)) << 4);
                     if constexpr (LA_X2F_KO & 4) { kfh[sub][c] = qh[(c + sub) & 3]; kfl[sub][c] = ql[(c + sub) & 3]; }
                     else {
+                        const int row = sub * 32 + i32;
+                        const int off = row * 128 + (((2 * c + h) ^ kswz(row)) << 4);
                         kfh[sub][c] = *reinterpret_cast<const uint4 *>(kl + off);
                         kfl[sub][c] = *reinterpret_cast<const uint4 *>(kl + IMG + off);
                     }
@@ -336,7 +285,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x2_fwd_kernel(FwdParams 
                 const f16x8 phv = __builtin_bit_cast(f16x8, ph), plv = __builtin_bit_cast(f16x8, pl);
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    // lane (dv = 32b + 16(g&1) + (lane&15), half g>>1): 4 keys key0 .. key0+3 per read
+                    // lane (dv = 32b + 16(g&1) + (lane&15), half g>>1): 4 keys key0 .. key0+3 per read (tr_frag with the hi and lo image
+                    // sharing one integer offset: the form this kernel's address arithmetic was compiled from)
                     const int key0 = sub * 32 + 16 * ks + 4 * (g >> 1);
                     const int slot = b * 4 + 2 * (g & 1) + (pp >> 1);
                     const int r0 = key0 + q4, r1 = key0 + 8 + q4;
@@ -378,13 +328,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_x2_fwd_kernel(FwdParams 
     const float inv = p.sv[bh] / l;
     if (p.lse && q_valid && h == 0) p.lse[((int64_t)clip * p.n_head + head) * p.q_len + qrow] = fmaf(m_run - 13.0f, kLn2, __logf(l));
     if (q_valid) {
-        float *orow = p.out + ((int64_t)clip * p.q_len + qrow) * p.ld_out + head * 64;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                *reinterpret_cast<float4 *>(orow + 32 * b + 8 * r4 + 4 * h) =
-                    make_float4(o[b][4 * r4 + 0] * inv, o[b][4 * r4 + 1] * inv, o[b][4 * r4 + 2] * inv, o[b][4 * r4 + 3] * inv);
+        store_row_scaled(p.out + ((int64_t)clip * p.q_len + qrow) * p.ld_out + head * 64, o, inv, h);
     }
 }
 
@@ -413,22 +357,6 @@ struct BwdParams {
     int q_len, kv_len, n_head, causal, batch;
 };
 
-// fragment readers.  Row fragment (A operand, M = token row of the image, K = 16 columns of the head dimension: c): ds_read_b128
-__device__ __forceinline__ f16x8 row_frag(const unsigned char *img, int row, int c, int h) {
-    return __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(img + row * 128 + (((2 * c + h) ^ kswz(row)) << 4)));
-}
-// Transposed fragment (A operand, M = 32 columns of the head dimension: b, K = 16 token rows tok0 ..): lane (col = 32b + 16(g&1) + (lane&15),
-// half g>>1) gets token rows tok0 + 4(g>>1) + {0..3} and + 8
-struct TrLane { int g, q4, pp; };
-__device__ __forceinline__ f16x8 tr_frag(const unsigned char *img, int tok0, int b, const TrLane &L) {
-    const int key0 = tok0 + 4 * (L.g >> 1);
-    const int slot = b * 4 + 2 * (L.g & 1) + (L.pp >> 1);
-    const int r0 = key0 + L.q4, r1 = key0 + 8 + L.q4;
-    typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
-    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(img + r0 * 128 + ((slot ^ vswz(r0)) << 4) + (L.pp & 1) * 8));
-    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(img + r1 * 128 + ((slot ^ vswz(r1)) << 4) + (L.pp & 1) * 8));
-    return __builtin_bit_cast(f16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 // acc += A B with both operands as (hi, lo): small terms first
 __device__ __forceinline__ f32x16 mma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x16 acc) {
     acc = mfma(al, bh, acc);
@@ -469,7 +397,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_kv_kernel(Bwd
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i32 = lane & 31, h = lane >> 5;
-    const TrLane L{lane >> 4, (lane & 15) >> 2, lane & 3};
+    const int g = lane >> 4, q4 = (lane & 15) >> 2, pp = lane & 3;
     const unsigned short *qbase = p.qp + (int64_t)clip * Tq * 2 * C + head * 64;
     const unsigned short *dobase = p.dop + (int64_t)clip * Tq * 2 * C + head * 64;
     const int bh = clip * p.n_head + head;
@@ -507,8 +435,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_kv_kernel(Bwd
     const int nq = (Tq + KT - 1) / KT;
     const int t0 = p.causal ? (kt * KB) / KT : 0;            // causal: query tiles wholly before the block's first key see none of its keys
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(la::lds_addr_u32(lds));
-    const KvOff<PER> off_full = kv_offsets<PER>(C, 0, KT, wave, lane);
-    const KvOff<PER> off_last = kv_offsets<PER>(C, (nq - 1) * KT, Tq, wave, lane);
+    const KvOff<PER> off_full = kv_offsets<PER, 4>(C, 0, KT, wave, lane);
+    const KvOff<PER> off_last = kv_offsets<PER, 4>(C, (nq - 1) * KT, Tq, wave, lane);
     auto stage = [&](int t, unsigned buf) __attribute__((always_inline)) {
         const KvOff<PER> &o = t == nq - 1 ? off_last : off_full;
         stage_tile<PER>(qbase, C, t * KT, o.k, buf, wave);
@@ -532,12 +460,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_kv_kernel(Bwd
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {          // (fragment loads waited for here, not inside the loop: see the forward kernel)
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 a0 = __builtin_bit_cast(u32x4, kh[c]), a1 = __builtin_bit_cast(u32x4, kl[c]), a2 = __builtin_bit_cast(u32x4, vh[c]), a3 = __builtin_bit_cast(u32x4, vl[c]);
-        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
-        kh[c] = __builtin_bit_cast(uint4, a0); kl[c] = __builtin_bit_cast(uint4, a1); vh[c] = __builtin_bit_cast(uint4, a2); vl[c] = __builtin_bit_cast(uint4, a3);
-    }
+    for (int c = 0; c < 4; ++c) pin_frags(kh[c], kl[c], vh[c], vl[c]);
     __syncthreads();
 
     auto tile = [&](int t, auto curc, auto maskc) __attribute__((always_inline)) {
@@ -558,10 +481,10 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_kv_kernel(Bwd
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const f16x8 ah = row_frag(qr, row, c, h), al = row_frag(qr + IMG, row, c, h);
+                const f16x8 ah = row_frag<f16x8>(qr, row, c, h), al = row_frag<f16x8>(qr + IMG, row, c, h);
                 s = mma3(ah, al, __builtin_bit_cast(f16x8, kh[c]), __builtin_bit_cast(f16x8, kl[c]), s);
                 if constexpr (DK) {
-                    const f16x8 gh = row_frag(dor, row, c, h), gl = row_frag(dor + IMG, row, c, h);
+                    const f16x8 gh = row_frag<f16x8>(dor, row, c, h), gl = row_frag<f16x8>(dor + IMG, row, c, h);
                     dp = mma3(gh, gl, __builtin_bit_cast(f16x8, vh[c]), __builtin_bit_cast(f16x8, vl[c]), dp);
                 }
             }
@@ -592,8 +515,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_kv_kernel(Bwd
                 if constexpr (DK) split8(dp, ks, sh, sl);
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    if constexpr (DV) dv[b] = mma3(tr_frag(dotr, sub * 32 + 16 * ks, b, L), tr_frag(dotr + IMG, sub * 32 + 16 * ks, b, L), ph, pl, dv[b]);
-                    if constexpr (DK) dk[b] = mma3(tr_frag(qtr, sub * 32 + 16 * ks, b, L), tr_frag(qtr + IMG, sub * 32 + 16 * ks, b, L), sh, sl, dk[b]);
+                    if constexpr (DV) dv[b] = mma3(tr_frag<f16x8>(dotr, sub * 32 + 16 * ks, b, g, q4, pp), tr_frag<f16x8>(dotr + IMG, sub * 32 + 16 * ks, b, g, q4, pp), ph, pl, dv[b]);
+                    if constexpr (DK) dk[b] = mma3(tr_frag<f16x8>(qtr, sub * 32 + 16 * ks, b, g, q4, pp), tr_frag<f16x8>(qtr + IMG, sub * 32 + 16 * ks, b, g, q4, pp), sh, sl, dk[b]);
                 }
             }
         }
@@ -614,19 +537,9 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_kv_kernel(Bwd
     // ---- epilogue: dV = dV^T s_dO^-1 2^-13,  dK = dK^T s_q^-1 s_dS^-1 (s_dS = 2^-20 s_dO s_v in terms of the scales) ----
     if (k_valid) {
         const float cv = isdo * 0x1p-13f, ck = isq * 0x1p20f * isdo * isv;
-        float *dvrow = p.dv + ((int64_t)clip * Tk + krow) * p.ld_dkv + head * 64;
-        float *dkrow = p.dk + ((int64_t)clip * Tk + krow) * p.ld_dkv + head * 64;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                if constexpr (DV)
-                    *reinterpret_cast<float4 *>(dvrow + 32 * b + 8 * r4 + 4 * h) =
-                        make_float4(dv[b][4 * r4 + 0] * cv, dv[b][4 * r4 + 1] * cv, dv[b][4 * r4 + 2] * cv, dv[b][4 * r4 + 3] * cv);
-                if constexpr (DK)
-                    *reinterpret_cast<float4 *>(dkrow + 32 * b + 8 * r4 + 4 * h) =
-                        make_float4(dk[b][4 * r4 + 0] * ck, dk[b][4 * r4 + 1] * ck, dk[b][4 * r4 + 2] * ck, dk[b][4 * r4 + 3] * ck);
-            }
+        const int64_t row = ((int64_t)clip * Tk + krow) * p.ld_dkv + head * 64;
+        if constexpr (DV) store_row_scaled(p.dv + row, dv, cv, h);
+        if constexpr (DK) store_row_scaled(p.dk + row, dk, ck, h);
     }
 }
 
@@ -640,7 +553,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_q_kernel(BwdP
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i32 = lane & 31, h = lane >> 5;
-    const TrLane L{lane >> 4, (lane & 15) >> 2, lane & 3};
+    const int g = lane >> 4, q4 = (lane & 15) >> 2, pp = lane & 3;
     const unsigned short *kbase = p.kp + (int64_t)clip * T * 2 * C + head * 64;
     const unsigned short *vbase = p.vp + (int64_t)clip * T * 2 * C + head * 64;
     const int bh = clip * p.n_head + head;
@@ -674,8 +587,8 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_q_kernel(BwdP
     const int nkv_all = nkv;
     if (p.causal) nkv = min(nkv, (min(Tq, (qt + 1) * QT) - 1) / KT + 1);   // tiles above the block's diagonal are all masked
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(la::lds_addr_u32(lds));
-    const KvOff<PER> off_full = kv_offsets<PER>(C, 0, KT, wave, lane);
-    const KvOff<PER> off_last = kv_offsets<PER>(C, (nkv_all - 1) * KT, T, wave, lane);
+    const KvOff<PER> off_full = kv_offsets<PER, 4>(C, 0, KT, wave, lane);
+    const KvOff<PER> off_last = kv_offsets<PER, 4>(C, (nkv_all - 1) * KT, T, wave, lane);
     auto stage = [&](int t, unsigned buf) __attribute__((always_inline)) {
         const KvOff<PER> &o = t == nkv_all - 1 ? off_last : off_full;
         stage_tile<PER>(kbase, C, t * KT, o.k, buf, wave);
@@ -685,12 +598,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_q_kernel(BwdP
     stage(0, lds0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 a0 = __builtin_bit_cast(u32x4, qh[c]), a1 = __builtin_bit_cast(u32x4, ql[c]), a2 = __builtin_bit_cast(u32x4, gh[c]), a3 = __builtin_bit_cast(u32x4, gl[c]);
-        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
-        qh[c] = __builtin_bit_cast(uint4, a0); ql[c] = __builtin_bit_cast(uint4, a1); gh[c] = __builtin_bit_cast(uint4, a2); gl[c] = __builtin_bit_cast(uint4, a3);
-    }
+    for (int c = 0; c < 4; ++c) pin_frags(qh[c], ql[c], gh[c], gl[c]);
     __syncthreads();
 
     auto tile = [&](int t, auto curc, auto maskc) __attribute__((always_inline)) {
@@ -706,9 +614,9 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_q_kernel(BwdP
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const f16x8 ah = row_frag(kr, row, c, h), al = row_frag(kr + IMG, row, c, h);
+                const f16x8 ah = row_frag<f16x8>(kr, row, c, h), al = row_frag<f16x8>(kr + IMG, row, c, h);
                 s = mma3(ah, al, __builtin_bit_cast(f16x8, qh[c]), __builtin_bit_cast(f16x8, ql[c]), s);
-                const f16x8 bh_ = row_frag(vr, row, c, h), bl_ = row_frag(vr + IMG, row, c, h);
+                const f16x8 bh_ = row_frag<f16x8>(vr, row, c, h), bl_ = row_frag<f16x8>(vr + IMG, row, c, h);
                 dp = mma3(bh_, bl_, __builtin_bit_cast(f16x8, gh[c]), __builtin_bit_cast(f16x8, gl[c]), dp);
             }
             const int kmax = p.causal ? min(T - 1, qrow) : T - 1;
@@ -727,7 +635,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_q_kernel(BwdP
                 split8(dp, ks, sh, sl);
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
-                    dq[b] = mma3(tr_frag(ktr, sub * 32 + 16 * ks, b, L), tr_frag(ktr + IMG, sub * 32 + 16 * ks, b, L), sh, sl, dq[b]);
+                    dq[b] = mma3(tr_frag<f16x8>(ktr, sub * 32 + 16 * ks, b, g, q4, pp), tr_frag<f16x8>(ktr + IMG, sub * 32 + 16 * ks, b, g, q4, pp), sh, sl, dq[b]);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -744,13 +652,7 @@ __global__ __launch_bounds__(64 * BWD_NW, 2) void attention_x2_bwd_q_kernel(BwdP
 
     if (q_valid) {
         const float cq = isk * 0x1p20f * isdo * isv;
-        float *dqrow = p.dq + ((int64_t)clip * Tq + qrow) * p.ld_dq + head * 64;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                *reinterpret_cast<float4 *>(dqrow + 32 * b + 8 * r4 + 4 * h) =
-                    make_float4(dq[b][4 * r4 + 0] * cq, dq[b][4 * r4 + 1] * cq, dq[b][4 * r4 + 2] * cq, dq[b][4 * r4 + 3] * cq);
+        store_row_scaled(p.dq + ((int64_t)clip * Tq + qrow) * p.ld_dq + head * 64, dq, cq, h);
     }
 }
 
@@ -783,15 +685,11 @@ struct FwdWorkspace {
     size_t bytes;
 };
 FwdWorkspace fwd_workspace(void *base, int B, int Tq, int Tk, int H) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t C = 64 * (size_t)H;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += up(n); return o; };
-    const size_t oq = take((size_t)B * Tq * 2 * C * 2), ok = take((size_t)B * Tk * 2 * C * 2), ov = take((size_t)B * Tk * 2 * C * 2);
-    const size_t osq = take((size_t)B * H * 4), osk = take((size_t)B * H * 4), osv = take((size_t)B * H * 4);
-    char *b = reinterpret_cast<char *>(base);
-    return FwdWorkspace{reinterpret_cast<unsigned short *>(b + oq), reinterpret_cast<unsigned short *>(b + ok), reinterpret_cast<unsigned short *>(b + ov),
-                        reinterpret_cast<float *>(b + osq), reinterpret_cast<float *>(b + osk), reinterpret_cast<float *>(b + osv), off};
+    const size_t C = 64 * (size_t)H, nq = (size_t)B * Tq * 2 * C, nk = (size_t)B * Tk * 2 * C, ns = (size_t)B * H;
+    Carver c{reinterpret_cast<char *>(base)};
+    FwdWorkspace w{c.take<unsigned short>(nq), c.take<unsigned short>(nk), c.take<unsigned short>(nk), c.take<float>(ns), c.take<float>(ns), c.take<float>(ns), 0};
+    w.bytes = c.off;
+    return w;
 }
 
 }  // namespace
@@ -809,11 +707,9 @@ extern "C" int la_attention_lse_f16x2(const float *q, int64_t ld_q, const float 
                                       size_t workspace_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (batch == 0 || q_len == 0) return LA_OK;
-    LA_CHECK_ARG(q && k && v && out && batch > 0 && q_len > 0 && kv_len > 0 && n_head > 0, "attention_lse_f16x2: bad arguments");
-    LA_CHECK_ARG(!causal || q_len == kv_len, "attention_lse_f16x2: causal masking is defined for self-attention (q_len == kv_len)");
-    LA_CHECK_ARG(ld_q >= n_head * 64 && ld_kv >= n_head * 64 && ld_out >= n_head * 64, "attention_lse_f16x2: leading dimensions too small");
-    LA_CHECK_ARG(ld_q % 4 == 0 && ld_kv % 4 == 0 && ld_out % 4 == 0 && (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0 &&
-                     (uintptr_t)out % 16 == 0, "attention_lse_f16x2: rows must be 16-byte aligned");
+    if (const int rc = check_forward_args("attention_lse_f16x2", LA_F32, q && k && v && out, q, k, v, out, ld_q, n_head * 64, ld_kv, ld_out, batch, q_len, kv_len,
+                                          n_head, causal && q_len != kv_len ? "causal masking is defined for self-attention (q_len == kv_len)" : nullptr))
+        return rc;
     const FwdWorkspace ws = fwd_workspace(workspace, batch, q_len, kv_len, n_head);
     LA_CHECK_ARG(workspace && (uintptr_t)workspace % 256 == 0 && workspace_bytes >= ws.bytes, "attention_lse_f16x2: workspace missing, misaligned or too small");
     la::TimerScope ts("attention_f16x2", stream);
@@ -834,18 +730,12 @@ struct BwdWorkspace {
     size_t bytes;
 };
 BwdWorkspace bwd_workspace(void *base, int B, int Tq, int Tk, int H) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t C = 64 * (size_t)H;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += up(n); return o; };
-    const size_t oq = take((size_t)B * Tq * 2 * C * 2), ok = take((size_t)B * Tk * 2 * C * 2), ov = take((size_t)B * Tk * 2 * C * 2),
-                 og = take((size_t)B * Tq * 2 * C * 2);
-    const size_t osq = take((size_t)B * H * 4), osk = take((size_t)B * H * 4), osv = take((size_t)B * H * 4), osg = take((size_t)B * H * 4);
-    const size_t ol = take((size_t)B * H * Tq * 4), od = take((size_t)B * H * Tq * 4);
-    char *b = reinterpret_cast<char *>(base);
-    auto us = [&](size_t o) { return reinterpret_cast<unsigned short *>(b + o); };
-    auto fl = [&](size_t o) { return reinterpret_cast<float *>(b + o); };
-    return BwdWorkspace{us(oq), us(ok), us(ov), us(og), fl(osq), fl(osk), fl(osv), fl(osg), fl(ol), fl(od), off};
+    const size_t C = 64 * (size_t)H, nq = (size_t)B * Tq * 2 * C, nk = (size_t)B * Tk * 2 * C, ns = (size_t)B * H;
+    Carver c{reinterpret_cast<char *>(base)};
+    BwdWorkspace w{c.take<unsigned short>(nq), c.take<unsigned short>(nk), c.take<unsigned short>(nk), c.take<unsigned short>(nq), c.take<float>(ns),
+                   c.take<float>(ns), c.take<float>(ns), c.take<float>(ns), c.take<float>(ns * Tq), c.take<float>(ns * Tq), 0};
+    w.bytes = c.off;
+    return w;
 }
 }  // namespace
 

@@ -354,8 +354,8 @@ def test_attention_backward_f16x2_is_deterministic_and_matches_the_float32_sweep
     (la_attention_bwd_f32) relative to each gradient's largest magnitude, for self-attention with a ragged last tile, heads of different
     magnitude, a causal mask, and a cross shape (q_len != kv_len)."""
     from lyricalignment_amd import encoder_train as et, ops
-    for (B, Tq, Tk, H, causal) in ((2, 1500, 1500, 2, False), (1, 333, 333, 3, True), (2, 200, 1500, 1, False)):
-        d = 64 * H
+    for (B, Tq, Tk, H, causal) in ((2, 1500, 1500, 2, False), (1, 333, 333, 3, True), (2, 200, 1500, 1, False), (1, 257, 257, 8, False)):
+        d = 64 * H                  # (8 heads: the XCD-aware block order of both sweeps)
         g = torch.Generator().manual_seed(Tq + Tk)
         q = (torch.randn(B * Tq, d, generator=g) * 0.35).cuda()
         kv = torch.randn(B * Tk, 2 * d, generator=g)

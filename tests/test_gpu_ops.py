@@ -147,10 +147,11 @@ def test_mel_to_rows_and_cast():
     assert torch.equal(ops.cast_bf16(x.cuda()).cpu(), x.bfloat16())
 
 
-@pytest.mark.parametrize("B,T,H", [(1, 5, 1), (2, 64, 2), (1, 200, 3), (2, 1500, 2), (1, 129, 1)])
+@pytest.mark.parametrize("B,T,H", [(1, 5, 1), (2, 64, 2), (1, 200, 3), (2, 1500, 2), (1, 129, 1), (1, 65, 8), (1, 257, 8)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_attention(B, T, H, dtype):
-    """softmax(q k^T) v per head, q pre-scaled; fp64 reference on the host over the FULL tensor."""
+    """softmax(q k^T) v per head, q pre-scaled; fp64 reference on the host over the FULL tensor.  Heads x clips a multiple of 8 takes the
+    XCD-aware block order (block_coord), every other shape the natural one; T = 65: a last tile of one key; T <= 64: a single tile."""
     from lyricalignment_amd import ops
     d = H * 64
     qkv = _rand(B * T, 3 * d, seed=20 + T, scale=1.0)
@@ -186,7 +187,7 @@ def test_attention_online_rescale_spike(nw, attn_nw):
         np.testing.assert_allclose(out.double().numpy(), ref.numpy(), rtol=0, atol=tol)
 
 
-@pytest.mark.parametrize("B,T,H", [(1, 5, 1), (2, 64, 2), (1, 200, 3), (2, 1500, 2), (1, 129, 1)])
+@pytest.mark.parametrize("B,T,H", [(1, 5, 1), (2, 64, 2), (1, 200, 3), (2, 1500, 2), (1, 129, 1), (1, 65, 8), (1, 257, 8)])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_attention_q_log2(B, T, H, dtype):
     """LA_Q_LOG2: q carries log2(e) / 8, the scores arrive in the exp2 domain (bf16: the kernel that starts its running maximum at
@@ -249,8 +250,8 @@ def test_attention_256_query_workgroups_give_the_same_bits(dtype, q_log2, attn_n
     against the 4-wave / 128-query form (option attn_nw = 4): every query's sweep over the keys is the same arithmetic in the same
     order, so the outputs are identical -- T = 1500 (the encoder; a partial last query block in both forms) and 1100, peaked scores."""
     from lyricalignment_amd import ops
-    for B, T, H in ((2, 1500, 3), (1, 1100, 2)):
-        d = H * 64
+    for B, T, H in ((2, 1500, 3), (1, 1100, 2), (1, 257, 8)):     # (257 x 8 heads: the 8-wave form under the XCD-aware block order, whose
+        d = H * 64                                                # 4-wave partner test_attention / test_attention_q_log2 hold against float64)
         qkv = _rand(B * T, 3 * d, seed=40 + T, scale=1.0)
         qkv[:, :d] *= 0.125 * 3.0 * (1.4426950408889634 if q_log2 else 1.0)
         x = qkv.to(dtype).cuda()

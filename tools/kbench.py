@@ -3,7 +3,7 @@
     python tools/kbench.py gemm|attn|gru|fc|all [--iters N]
     python tools/kbench.py epi16      option gemm_epi16 off / on on the QKV, MLP-up and plain 16-bit launches (shipped library)
 Interleaved rounds in one process, random operands (cdna guide rules 24/25).
-The A/B modes that flip developer switches per launch (gemm --variants 73, persist, q4, q4w, order, epi, attn_ko / attn variants) need
+The A/B modes that flip developer switches per launch (gemm --variants 73, persist, q4, q4w, order, epi) need
 the EXPERIMENT build of the library: bash tools/build_variant.sh lab -DLA_EXPERIMENTS; LA_LIB_PATH=$PWD/ab/lab/liblyricalign_hip.so."""
 import argparse, os, sys, time
 import numpy as np
@@ -505,6 +505,7 @@ def bench_attn_fwd(iters):
 
 
 def bench_attn(iters):
+    """The 16-bit attention at 32 clips x 16 heads x 1500: 128-query (4 waves) and 256-query (8 waves) workgroups, option attn_nw."""
     B, T, H = 32, 1500, 16
     qkv = rnd(B * T, 3 * H * 64)
     qkv[:, : H * 64] *= float(os.environ.get("KB_QSCALE", "0.125"))   # q pre-scaled by 1/8: scores ~ N(0, 1) like a real layer
@@ -512,60 +513,30 @@ def bench_attn(iters):
     fl = 4.0 * T * T * H * 64 * B
     ref = None
     for rd in range(3):
-        for nw, msum, thr in (("4", False, "0"), ("4", False, "8"), ("4", False, "opt"), ("8", False, "opt"), ("8", False, "8"), ("4", True, "8")):
-            os.environ["LA_ATTN_NW"] = nw
-            _lib.set_option("attn_nw", int(nw))
-            if thr.startswith("opt"):              # the default: optimistic softmax, no per-tile maximum
-                os.environ.pop("LA_ATTN_OPT", None)
-            else:
-                os.environ["LA_ATTN_OPT"] = "0"
-            os.environ["LA_ATTN_THR"] = thr
-            if msum:
-                os.environ["LA_ATTN_MSUM"] = "1"
-            else:
-                os.environ.pop("LA_ATTN_MSUM", None)
+        for nw in (4, 8):
+            _lib.set_option("attn_nw", nw)
             med, mn = timeit(lambda: ops.attention(qkv, B, T, H, out=out), iters)
             if ref is None:
                 ref = out.clone()
             dmax = float((out.float() - ref.float()).abs().max())
-            print(f"attention B={B} T={T} H={H} waves/workgroup {nw} msum {int(msum)} defer-thr {thr}: median {med*1e3:.1f} us  min {mn*1e3:.1f} us  {fl/med/1e9:.1f} TF/s  "
+            print(f"attention B={B} T={T} H={H} waves/workgroup {nw}: median {med*1e3:.1f} us  min {mn*1e3:.1f} us  {fl/med/1e9:.1f} TF/s  "
                   f"max abs diff to the first run: {dmax:.3e}", flush=True)
-    os.environ.pop("LA_ATTN_NW", None); os.environ.pop("LA_ATTN_MSUM", None); os.environ.pop("LA_ATTN_THR", None); os.environ.pop("LA_ATTN_OPT", None)
+    _lib.set_option("attn_nw", 0)
 
 
 def bench_attn_knockout(iters):
-    """Diagnostic build only (LA_EXTRA_CXXFLAGS=-DLA_ATTN_KNOCKOUT python -m lyricalignment_amd.build): the tile loop with parts
-    left out -- 1 exponentials, 2 V^T fragment reads, 4 K fragment reads, 8 staging, 16 MFMAs (bit mask); results are garbage."""
+    """The 16-bit attention with whichever knock-out mask the loaded library was built with (-DLA_ATTN_KO=<mask>, one library per mask:
+    tools/ab_attn_knockouts.sh runs the series and labels the lines) -- 1 exponentials, 2 V^T fragment reads, 4 K fragment reads,
+    8 staging, 16 MFMAs, 32 the tile barrier left out (bit mask); results are garbage."""
     B, T, H = 32, 1500, 16
     qkv = rnd(B * T, 3 * H * 64)
     qkv[:, : H * 64] *= 0.125
     out = torch.empty(B * T, H * 64, device="cuda", dtype=torch.bfloat16)
-    names = {0: "full", 1: "no exp", 2: "no V reads", 4: "no K reads", 6: "no K/V reads", 8: "no staging", 14: "no LDS traffic at all",
-             16: "no MFMA", 17: "no MFMA, no exp", 7: "no exp, no K/V reads", 15: "no exp, no LDS traffic", 30: "no MFMA, no LDS traffic",
-             100: "optimistic softmax, full", 101: "optimistic, no exp", 106: "optimistic, no K/V reads", 108: "optimistic, no staging",
-             132: "optimistic, no tile barrier", 140: "optimistic, no tile barrier, no staging", 114: "optimistic, no LDS traffic", 116: "optimistic, no MFMA", 130: "optimistic, no MFMA, no LDS traffic",
-             201: "optimistic, S phase at raised priority", 202: "optimistic, S and PV raised", 203: "optimistic, softmax raised"}
-    for rd in range(2):
-        for ko, nm in names.items():
-            os.environ["LA_ATTN_KO"] = str(ko)
-            med, mn = timeit(lambda: ops.attention(qkv, B, T, H, out=out), iters)
-            print(f"attention knockout {ko:2d} ({nm}): median {med*1e3:.1f} us  min {mn*1e3:.1f} us", flush=True)
-    os.environ.pop("LA_ATTN_KO", None)
-
-
-def bench_attn_occupancy(iters):
-    """Diagnostic build (-DLA_ATTN_KNOCKOUT): the shipped attention kernel at 4 / 3 / 2 / 1 workgroups (= waves per SIMD) per CU,
-    forced by unused dynamic LDS."""
-    B, T, H = 32, 1500, 16
-    qkv = rnd(B * T, 3 * H * 64)
-    qkv[:, : H * 64] *= 0.125
-    out = torch.empty(B * T, H * 64, device="cuda", dtype=torch.bfloat16)
-    os.environ["LA_ATTN_KO"] = "100"
-    for pad, occ in ((0, 4), (20480, 3), (49152, 2), (102400, 1)):
-        os.environ["LA_ATTN_LDSPAD"] = str(pad)
+    for nw in (4, 8):
+        _lib.set_option("attn_nw", nw)
         med, mn = timeit(lambda: ops.attention(qkv, B, T, H, out=out), iters)
-        print(f"attention at {occ} waves per SIMD: median {med*1e3:.1f} us  min {mn*1e3:.1f} us", flush=True)
-    os.environ.pop("LA_ATTN_KO", None); os.environ.pop("LA_ATTN_LDSPAD", None)
+        print(f"attention (knock-out build) waves/workgroup {nw}: median {med*1e3:.1f} us  min {mn*1e3:.1f} us", flush=True)
+    _lib.set_option("attn_nw", 0)
 
 
 def bench_gru(iters):
@@ -668,7 +639,6 @@ if __name__ == "__main__":
     if a.what in ("gemm", "all"): bench_gemm(a.iters)
     if a.what in ("attn", "all"): bench_attn(a.iters)
     if a.what == "attn_ko": bench_attn_knockout(a.iters)
-    if a.what == "attn_occ": bench_attn_occupancy(a.iters)
     if a.what in ("gru", "all"): bench_gru(a.iters)
     if a.what == "gru_delay": bench_gru_delay(a.iters)
     if a.what in ("fc", "all"): bench_fc(a.iters)
