@@ -923,6 +923,15 @@ int la_gemm_f16x2(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A,
 int la_gemm_f16x2_small(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
                         float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream);
 int la_gemm_f16x2_small_slots(int32_t M, int32_t N, int32_t K);
+/* Which kernel takes a product: pure host queries (no device call) for callers that route products themselves, so that they ask the
+ * library's rule instead of restating it.
+ *   la_gemm_f16x2_domain:  1 where (M, N, K, slots) lies in la_gemm_f16x2's domain (the test that entry makes), else 0.
+ *   la_gemm_f16x2_slots:   the split-K slots that bring an M x N product with few 256 x 256 tiles up to that domain (1 = none needed).
+ *   la_gemm_fills_chip:    1 where a 16-bit la_gemm of M x N x batch runs on the 256 x 256 kernel (option gemm_tile = 0): N > 128 and
+ *                          enough 256 x 256 tiles x batch to fill the chip. */
+int la_gemm_f16x2_domain(int32_t M, int32_t N, int32_t K, int32_t slots);
+int la_gemm_f16x2_slots(int32_t M, int32_t N);
+int la_gemm_fills_chip(int32_t M, int32_t N, int32_t batch);
 /* la_layernorm (eps 1e-5, statistics in float32 over the row) whose result leaves as the f16x2 planes of the next Linear's operand instead of
  * as float32 rows: planes [rows][2][kp] + inv_scale [rows] as la_split_f16x2 would make them from LN(x) gamma + beta (float32 inference on the
  * f16x2 products: module/align_model.py:72-123 is float32 throughout).  d % 4 == 0, d <= 4096. */

@@ -46,6 +46,9 @@ SYMBOLS = {
     "la_gemm_f16x2": (c_int32, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I32, _P]),
     "la_gemm_f16x2_small": (c_int32, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I32, _P]),
     "la_gemm_f16x2_small_slots": (c_int32, [_I32, _I32, _I32]),
+    "la_gemm_f16x2_domain": (c_int32, [_I32, _I32, _I32, _I32]),
+    "la_gemm_f16x2_slots": (c_int32, [_I32, _I32]),
+    "la_gemm_fills_chip": (c_int32, [_I32, _I32, _I32]),
     "la_layernorm_f16x2": (c_int32, [_P, _I64, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "la_fc_emissions_x2_workspace_bytes": (c_int32, [_I32, _I32, _I32, _I32, _I32, POINTER(_SZ)]),
     "la_fc_emissions_x2": (c_int32, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I64, _I64, _P, _SZ, _P]),

@@ -83,8 +83,9 @@ __global__ __launch_bounds__(1024) void heads_split_kernel(const float *x, int64
     unsigned short *dst = planes + (int64_t)clip * T * 2 * C + head * 64 + c4 * 4;
     auto put = [&](int r, const float4 &w) {
         const unsigned a = la::x2::pack_hi_lo(w.x * s), b = la::x2::pack_hi_lo(w.y * s), c = la::x2::pack_hi_lo(w.z * s), d = la::x2::pack_hi_lo(w.w * s);
-        *reinterpret_cast<uint2 *>(dst + (int64_t)r * 2 * C) = make_uint2((a & 0xffffu) | (b << 16), (c & 0xffffu) | (d << 16));
-        *reinterpret_cast<uint2 *>(dst + (int64_t)r * 2 * C + C) = make_uint2((a >> 16) | (b & 0xffff0000u), (c >> 16) | (d & 0xffff0000u));
+        using la::x2::plane_word;
+        *reinterpret_cast<uint2 *>(dst + (int64_t)r * 2 * C) = make_uint2(plane_word<0>(a, b), plane_word<0>(c, d));
+        *reinterpret_cast<uint2 *>(dst + (int64_t)r * 2 * C + C) = make_uint2(plane_word<1>(a, b), plane_word<1>(c, d));
     };
     if (cached) {
 #pragma unroll

@@ -23,32 +23,53 @@
 #include "la_gemm_core.h"
 #include "la_gemm_epilogue.h"
 #include "la_gemm_params.h"
+#include "la_x2.h"
 
 using namespace la::gemm;
 
 namespace {
 
-// power of two s with max |x| s in [2^13, 2^14); max == 0 (or not finite) -> 1.  Returns s, *inv = 1 / s (both exact).
-__device__ __forceinline__ float x2_scale(float mx, float *inv) {
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) { *inv = 1.f; return 1.f; }
-    int e;
-    (void)frexpf(mx, &e);                    // mx = m 2^e, m in [0.5, 1)
-    int sh = 14 - e;
-    sh = sh > 126 ? 126 : (sh < -126 ? -126 : sh);
-    *inv = ldexpf(1.f, -sh);
-    return ldexpf(1.f, sh);
-}
-
-__device__ __forceinline__ void x2_split(float xs, unsigned short &hi, unsigned short &lo) {
-    const _Float16 h = (_Float16)xs;
-    const _Float16 l = (_Float16)(xs - (float)h);
-    hi = __builtin_bit_cast(unsigned short, h);
-    lo = __builtin_bit_cast(unsigned short, l);
-}
+using la::x2::scale_for;
+using la::x2::split;
 
 // optional activation applied to the float32 values before they are split (act: 0 none, 1 exact-erf GELU): the MLP's hidden operand
 // gelu(u) is never materialised in float32 -- the forward and the weight-gradient products split it straight from u
 __device__ __forceinline__ float x2_act(float v, int act) { return act == 1 ? la::gelu_erf(v) : v; }
+__device__ __forceinline__ float4 act4(const float4 &v, int act) { return make_float4(x2_act(v.x, act), x2_act(v.y, act), x2_act(v.z, act), x2_act(v.w, act)); }
+
+// ---- pieces the two row kernels (one wave per row) share ----
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float max_abs4(const float4 &v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+// four consecutive values, scaled, into element quad i of the row's two planes
+__device__ __forceinline__ void store_quad(const float4 &v, float s, unsigned short *hi, unsigned short *lo, int i) {
+    ushort4 h, l;
+    split(v.x * s, h.x, l.x); split(v.y * s, h.y, l.y); split(v.z * s, h.z, l.z); split(v.w * s, h.w, l.w);
+    reinterpret_cast<ushort4 *>(hi)[i] = h;
+    reinterpret_cast<ushort4 *>(lo)[i] = l;
+}
+// the row as a wave holds it in registers (lane's quads lane + 64 j, the first n4 of them real)
+template <int NV>
+__device__ __forceinline__ void store_cached(const float4 (&v)[NV], float s, unsigned short *hi, unsigned short *lo, int lane, int n4) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int i = lane + 64 * j;
+        if (i < n4) store_quad(v[j], s, hi, lo, i);
+    }
+}
+// the end of a row: zeros from element `from` to the plane length, and the row's inverse scale
+__device__ __forceinline__ void finish_row(unsigned short *hi, unsigned short *lo, int from, int64_t kp, float *inv_scale, int row, float inv, int lane) {
+    for (int i = from + lane; i < kp; i += 64) { hi[i] = 0; lo[i] = 0; }
+    if (lane == 0) inv_scale[row] = inv;
+}
 
 // one wave per row, four rows per workgroup: pass 1 = the row's largest magnitude, pass 2 = split + store.  Rows of up to 4096 columns
 // (every operand of the encoder) stay in registers between the passes -- 16 float4 per lane, all loads in flight at once: one read of x
@@ -78,50 +99,26 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float *x, int64_t
         }
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            if (act) v[j] = make_float4(x2_act(v[j].x, act), x2_act(v[j].y, act), x2_act(v[j].z, act), x2_act(v[j].w, act));
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v[j].x), fabsf(v[j].y)), fmaxf(fabsf(v[j].z), fabsf(v[j].w))));
+            if (act) v[j] = act4(v[j], act);
+            mx = fmaxf(mx, max_abs4(v[j]));
         }
     } else {
-        for (int i = lane; i < c4; i += 64) {
-            const float4 w = reinterpret_cast<const float4 *>(xr)[i];
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(x2_act(w.x, act)), fabsf(x2_act(w.y, act))), fmaxf(fabsf(x2_act(w.z, act)), fabsf(x2_act(w.w, act)))));
-        }
+        for (int i = lane; i < c4; i += 64) mx = fmaxf(mx, max_abs4(act4(reinterpret_cast<const float4 *>(xr)[i], act)));
     }
     for (int i = c4 * 4 + lane; i < cols; i += 64) mx = fmaxf(mx, fabsf(x2_act(xr[i], act)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     float inv;
-    const float s = x2_scale(mx, &inv);
+    const float s = scale_for(mx, &inv);
     // one atomic per row into 64 words that lie 128 B apart (all 64 in one or two cache lines made the rows' 24000 atomics queue on one
     // L2 channel: +34 us per operand, more than the pass they were to save)
     if (tmax && lane == 0) atomicMax(tmax + (row & 63) * 32, __float_as_uint(mx != mx ? __uint_as_float(0x7f800000u) : mx));
     if (cached) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int i = lane + 64 * j;
-            if (i < c4) {
-                ushort4 h, l;
-                x2_split(v[j].x * s, h.x, l.x); x2_split(v[j].y * s, h.y, l.y); x2_split(v[j].z * s, h.z, l.z); x2_split(v[j].w * s, h.w, l.w);
-                reinterpret_cast<ushort4 *>(hi)[i] = h;
-                reinterpret_cast<ushort4 *>(lo)[i] = l;
-            }
-        }
+        store_cached(v, s, hi, lo, lane, c4);
     } else {
-        for (int i = lane; i < c4; i += 64) {
-            const float4 w = reinterpret_cast<const float4 *>(xr)[i];
-            ushort4 h, l;
-            x2_split(x2_act(w.x, act) * s, h.x, l.x); x2_split(x2_act(w.y, act) * s, h.y, l.y); x2_split(x2_act(w.z, act) * s, h.z, l.z);
-            x2_split(x2_act(w.w, act) * s, h.w, l.w);
-            reinterpret_cast<ushort4 *>(hi)[i] = h;
-            reinterpret_cast<ushort4 *>(lo)[i] = l;
-        }
+        for (int i = lane; i < c4; i += 64) store_quad(act4(reinterpret_cast<const float4 *>(xr)[i], act), s, hi, lo, i);
     }
-    for (int i = c4 * 4 + lane; i < kp; i += 64) {
-        unsigned short h = 0, l = 0;
-        if (i < cols) x2_split(x2_act(xr[i], act) * s, h, l);
-        hi[i] = h; lo[i] = l;
-    }
-    if (lane == 0) inv_scale[row] = inv;
+    for (int i = c4 * 4 + lane; i < cols; i += 64) split(x2_act(xr[i], act) * s, hi[i], lo[i]);      // (columns past the last whole quad)
+    finish_row(hi, lo, cols, kp, inv_scale, row, inv, lane);
 }
 
 // LayerNorm and the operand split in ONE pass over the rows (float32 inference on the f16x2 products, la_model.cpp): y = LN(x) gamma + beta is
@@ -146,9 +143,7 @@ __global__ __launch_bounds__(256) void ln_split_rows_kernel(const float *x, int6
             sum += (v[j].x + v[j].y) + (v[j].z + v[j].w);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum / (float)d;
+    const float mean = wave_sum(sum) / (float)d;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -158,9 +153,7 @@ __global__ __launch_bounds__(256) void ln_split_rows_kernel(const float *x, int6
             sq += (a * a + b * b) + (c2 * c2 + d2 * d2);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    const float rstd = 1.0f / sqrtf(sq / (float)d + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)d + 1e-5f);
     float mx = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -169,26 +162,14 @@ __global__ __launch_bounds__(256) void ln_split_rows_kernel(const float *x, int6
             const float4 g = *reinterpret_cast<const float4 *>(gamma + c), bt = *reinterpret_cast<const float4 *>(beta + c);
             v[j] = make_float4((v[j].x - mean) * rstd * g.x + bt.x, (v[j].y - mean) * rstd * g.y + bt.y, (v[j].z - mean) * rstd * g.z + bt.z,
                                (v[j].w - mean) * rstd * g.w + bt.w);
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v[j].x), fabsf(v[j].y)), fmaxf(fabsf(v[j].z), fabsf(v[j].w))));
+            mx = fmaxf(mx, max_abs4(v[j]));
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     float inv;
-    const float s = x2_scale(mx, &inv);
+    const float s = scale_for(wave_max(mx), &inv);
     unsigned short *hi = planes + (int64_t)row * 2 * kp, *lo = hi + kp;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int i = lane + 64 * j;
-        if (i * 4 < d) {
-            ushort4 h, l;
-            x2_split(v[j].x * s, h.x, l.x); x2_split(v[j].y * s, h.y, l.y); x2_split(v[j].z * s, h.z, l.z); x2_split(v[j].w * s, h.w, l.w);
-            reinterpret_cast<ushort4 *>(hi)[i] = h;
-            reinterpret_cast<ushort4 *>(lo)[i] = l;
-        }
-    }
-    for (int i = d + lane; i < kp; i += 64) { hi[i] = 0; lo[i] = 0; }
-    if (lane == 0) inv_scale[row] = inv;
+    store_cached(v, s, hi, lo, lane, d / 4);
+    finish_row(hi, lo, d, kp, inv_scale, row, inv, lane);
 }
 
 // column maxima of |x| as ordered unsigned bit patterns (|x| >= 0: the float order is the integer order)
@@ -204,7 +185,7 @@ __global__ __launch_bounds__(256) void colmax_kernel(const float *x, int64_t ldx
     __syncthreads();
     if (ry == 0 && col < cols) {
         mx = fmaxf(fmaxf(red[0][cx], red[1][cx]), fmaxf(red[2][cx], red[3][cx]));
-        if (mx != mx) mx = __uint_as_float(0x7f800000u);            // a NaN column: scale 1 (x2_scale), the NaNs pass through the split
+        if (mx != mx) mx = __uint_as_float(0x7f800000u);            // a NaN column: scale 1 (scale_for), the NaNs pass through the split
         atomicMax(colmax + col, __float_as_uint(mx));
     }
 }
@@ -315,12 +296,12 @@ __global__ __launch_bounds__(256) void split_transposed_kernel(const float *x, i
     }
     if (k >= cols) return;
     float inv;
-    const float s = x2_scale(__uint_as_float(TMAX ? tm : colmax[k]), &inv);
+    const float s = scale_for(__uint_as_float(TMAX ? tm : colmax[k]), &inv);
     unsigned short *hi = planes + (int64_t)k * 2 * mp + m0 + mq * 16, *lo = hi + mp;
     if (m0 + mq * 16 < mp) {                                      // (mp is a multiple of 16: whole 16-element pieces)
         unsigned short h[16], l[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) x2_split(tv[i] * s, h[i], l[i]);
+        for (int i = 0; i < 16; ++i) split(tv[i] * s, h[i], l[i]);
         uint4 *ph = reinterpret_cast<uint4 *>(hi), *pl = reinterpret_cast<uint4 *>(lo);
         ph[0] = *reinterpret_cast<uint4 *>(&h[0]); ph[1] = *reinterpret_cast<uint4 *>(&h[8]);
         pl[0] = *reinterpret_cast<uint4 *>(&l[0]); pl[1] = *reinterpret_cast<uint4 *>(&l[8]);
@@ -455,46 +436,6 @@ extern "C" int la_split_f16x2_t_act(const float *x, int64_t ldx, int32_t rows, i
 
 extern "C" int la_split_f16x2_t(const float *x, int64_t ldx, int32_t rows, int32_t cols, void *planes_t, int64_t mp, float *inv_scale_t, void *stream_) {
     return la_split_f16x2_t_act(x, ldx, rows, cols, planes_t, mp, inv_scale_t, 0, stream_);
-}
-
-extern "C" int la_gemm_f16x2(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
-                             float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream_) {
-    if (M == 0 || N == 0) return LA_OK;
-    LA_CHECK_ARG(A && sa && W && sw && C, "gemm_f16x2: null pointer");
-    LA_CHECK_ARG(M > 0 && N > 0 && K > 0 && slots >= 1, "gemm_f16x2: bad sizes");
-    LA_CHECK_ARG((epilogue & ~(LA_EPI_BIAS | LA_EPI_GELU | LA_EPI_RESIDUAL | LA_EPI_RES_GELU_GRAD)) == 0,
-                 "gemm_f16x2: epilogue takes BIAS, GELU, RESIDUAL, RES_GELU_GRAD only");
-    LA_CHECK_ARG(!(epilogue & LA_EPI_RES_GELU_GRAD) || (epilogue & LA_EPI_RESIDUAL), "gemm_f16x2: RES_GELU_GRAD reads the residual operand (set RESIDUAL too)");
-    LA_CHECK_ARG(!(epilogue & LA_EPI_BIAS) || bias, "gemm_f16x2: bias epilogue without pointer");
-    LA_CHECK_ARG(!(epilogue & LA_EPI_RESIDUAL) || residual, "gemm_f16x2: residual epilogue without pointer");
-    LA_CHECK_ARG((uintptr_t)A % 16 == 0 && (uintptr_t)W % 16 == 0, "gemm_f16x2: planes must be 16-byte aligned");
-    const int Kc = K / slots;
-    if (K % slots != 0 || Kc % 128 != 0 || Kc < 256 || N <= 128 || (int64_t)la::cdiv(M, 256) * la::cdiv(N, 256) * slots < 192) {
-        la::set_error("gemm_f16x2: M=%d N=%d K=%d slots=%d outside the 256x256 kernel's domain (K / slots a multiple of 128 and >= 256, N > 128, "
-                      ">= 192 tiles x slots)", M, N, K, slots);
-        return LA_EUNSUPPORTED;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    float *out = C;
-    int64_t out_ld = ldc, out_stride = 0;
-    int epi = epilogue | LA_EPI_OUT_F32;
-    if (slots > 1) {
-        out = static_cast<float *>(la::stream_scratch(stream, la::SCRATCH_SPLITK, (size_t)slots * M * N * sizeof(float)));
-        if (!out) { la::set_error("gemm_f16x2: split-K scratch allocation failed"); return LA_EHIP; }
-        out_ld = N; out_stride = (int64_t)M * N;
-        epi = LA_EPI_OUT_F32;                          // bias / activation / residual after the slots are summed
-    }
-    GemmParams p{M, N, Kc, A, (int64_t)2 * K, (int64_t)Kc, W, (int64_t)2 * K, (int64_t)Kc, out, out_ld, out_stride,
-                 slots > 1 ? nullptr : bias, 0, slots > 1 ? nullptr : residual, ldr, 0, epi, 0, la::cdiv(N, BN), pick_group(3 * Kc, 2, la::cdiv(N, BN))};
-    p.plane_a = K; p.plane_w = K;
-    p.ln_stats = sa; p.ln_csum = sw;
-    const int rc = launch_x2_f16(p, slots, stream);
-    if (rc != LA_OK || slots == 1) return rc;
-    const int64_t total = (int64_t)M * N;
-    hipLaunchKernelGGL(x2_reduce_kernel, dim3((unsigned)la::cdiv(total, (int64_t)256)), dim3(256), 0, stream, out, slots, M, N, C, ldc, bias,
-                       residual, ldr, epilogue);
-    LA_LAUNCH_CHECK();
-    return LA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -669,56 +610,102 @@ extern "C" int la_gemm_f16x2_small_slots(int32_t M, int32_t N, int32_t K) {
     return S;
 }
 
-extern "C" int la_gemm_f16x2_small(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
-                                   float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream_) {
-    if (M == 0 || N == 0) return LA_OK;
-    LA_CHECK_ARG(A && sa && W && sw && C, "gemm_f16x2_small: null pointer");
-    LA_CHECK_ARG(M > 0 && N > 0 && K > 0 && slots >= 0, "gemm_f16x2_small: bad sizes");
+// ---------------------------------------------------------------------------------------------------------------------
+// The two product entries: the same argument checks (x2_checks), then each entry's own domain test, then the same run (x2_run: split-K output,
+// parameter block, the entry's launcher, slot sum).  `name` is the entry's, for the message texts.
+namespace {
+
+int x2_checks(const char *name, int min_slots, int M, int N, int K, int slots, const void *A, const float *sa, const void *W, const float *sw,
+              const float *C, const float *bias, const float *residual, int epilogue) {
+    LA_CHECK_ARG(A && sa && W && sw && C, "%s: null pointer", name);
+    LA_CHECK_ARG(M > 0 && N > 0 && K > 0 && slots >= min_slots, "%s: bad sizes", name);
     LA_CHECK_ARG((epilogue & ~(LA_EPI_BIAS | LA_EPI_GELU | LA_EPI_RESIDUAL | LA_EPI_RES_GELU_GRAD)) == 0,
-                 "gemm_f16x2_small: epilogue takes BIAS, GELU, RESIDUAL, RES_GELU_GRAD only");
-    LA_CHECK_ARG(!(epilogue & LA_EPI_RES_GELU_GRAD) || (epilogue & LA_EPI_RESIDUAL), "gemm_f16x2_small: RES_GELU_GRAD reads the residual operand (set RESIDUAL too)");
-    LA_CHECK_ARG(!(epilogue & LA_EPI_BIAS) || bias, "gemm_f16x2_small: bias epilogue without pointer");
-    LA_CHECK_ARG(!(epilogue & LA_EPI_RESIDUAL) || residual, "gemm_f16x2_small: residual epilogue without pointer");
-    LA_CHECK_ARG((uintptr_t)A % 16 == 0 && (uintptr_t)W % 16 == 0, "gemm_f16x2_small: planes must be 16-byte aligned");
-    LA_CHECK_ARG(ldc >= N && (!(epilogue & LA_EPI_RESIDUAL) || ldr >= N), "gemm_f16x2_small: row pitches must cover N");
-    if (slots == 0) slots = la_gemm_f16x2_small_slots(M, N, K);
-    if (K % slots != 0 || (K / slots) % 32 != 0 || slots > 64) {
-        la::set_error("gemm_f16x2_small: M=%d N=%d K=%d slots=%d outside the 128x128 kernel's domain (K / slots a multiple of 32, at most 64 slots)",
-                      M, N, K, slots);
-        return LA_EUNSUPPORTED;
-    }
+                 "%s: epilogue takes BIAS, GELU, RESIDUAL, RES_GELU_GRAD only", name);
+    LA_CHECK_ARG(!(epilogue & LA_EPI_RES_GELU_GRAD) || (epilogue & LA_EPI_RESIDUAL), "%s: RES_GELU_GRAD reads the residual operand (set RESIDUAL too)", name);
+    LA_CHECK_ARG(!(epilogue & LA_EPI_BIAS) || bias, "%s: bias epilogue without pointer", name);
+    LA_CHECK_ARG(!(epilogue & LA_EPI_RESIDUAL) || residual, "%s: residual epilogue without pointer", name);
+    LA_CHECK_ARG((uintptr_t)A % 16 == 0 && (uintptr_t)W % 16 == 0, "%s: planes must be 16-byte aligned", name);
+    return LA_OK;
+}
+
+typedef int (*X2Launch)(GemmParams &p, int64_t K, int slots, hipStream_t stream);
+
+int x2_run(const char *name, X2Launch launch, int M, int N, int K, int slots, const void *A, const float *sa, const void *W, const float *sw, float *C,
+           int64_t ldc, const float *bias, const float *residual, int64_t ldr, int epilogue, hipStream_t stream) {
     const int Kc = K / slots;
-    hipStream_t stream = (hipStream_t)stream_;
     float *out = C;
     int64_t out_ld = ldc, out_stride = 0;
-    int epi = epilogue;
-    if (slots > 1) {
+    if (slots > 1) {                                    // partial sums per slot; bias / activation / residual after the slots are summed
         out = static_cast<float *>(la::stream_scratch(stream, la::SCRATCH_SPLITK, (size_t)slots * M * N * sizeof(float)));
-        if (!out) { la::set_error("gemm_f16x2_small: split-K scratch allocation failed"); return LA_EHIP; }
+        if (!out) { la::set_error("%s: split-K scratch allocation failed", name); return LA_EHIP; }
         out_ld = N; out_stride = (int64_t)M * N;
-        epi = 0;                                       // bias / activation / residual after the slots are summed
     }
-    const int tiles_n = la::cdiv(N, BN);
     GemmParams p{M, N, Kc, A, (int64_t)2 * K, (int64_t)Kc, W, (int64_t)2 * K, (int64_t)Kc, out, out_ld, out_stride,
-                 slots > 1 ? nullptr : bias, 0, slots > 1 ? nullptr : residual, ldr, 0, epi, la::cdiv(M, SmallX2::TM), tiles_n,
-                 pick_group(2 * Kc, 2, tiles_n)};
+                 slots > 1 ? nullptr : bias, 0, slots > 1 ? nullptr : residual, ldr, 0, slots > 1 ? 0 : epilogue, 0, la::cdiv(N, BN), 0};
     p.plane_a = K; p.plane_w = K;
     p.ln_stats = sa; p.ln_csum = sw;
-    {
-        static la::DeviceOnce attr_once;
-        if (attr_once.pending()) {
-            LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16x2_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SmallX2::LDS));
-            attr_once.mark();
-        }
-        // its own timer family (exact-name matching: "gemm_f16x2" counts the 256 x 256 kernel only), at the algorithmic flops as there
-        la::TimerScope ts("gemm_f16x2_small", stream, 2.0 * M * N * (double)K);
-        hipLaunchKernelGGL(gemm_f16x2_small_kernel, dim3(p.tiles_m * p.tiles_n, slots), dim3(SmallX2::THREADS), SmallX2::LDS, stream, p);
-        LA_LAUNCH_CHECK();
-    }
-    if (slots == 1) return LA_OK;
+    const int rc = launch(p, K, slots, stream);
+    if (rc != LA_OK || slots == 1) return rc;
     const int64_t total = (int64_t)M * N;
     hipLaunchKernelGGL(x2_reduce_kernel, dim3((unsigned)la::cdiv(total, (int64_t)256)), dim3(256), 0, stream, out, slots, M, N, C, ldc, bias,
                        residual, ldr, epilogue);
     LA_LAUNCH_CHECK();
     return LA_OK;
+}
+
+int big_launch(GemmParams &p, int64_t, int slots, hipStream_t stream) {
+    p.epilogue |= LA_EPI_OUT_F32;
+    p.group = pick_group(3 * p.K, 2, p.tiles_n);
+    return launch_x2_f16(p, slots, stream);             // (timer family "gemm_f16x2")
+}
+
+int small_launch(GemmParams &p, int64_t K, int slots, hipStream_t stream) {
+    p.tiles_m = la::cdiv(p.M, SmallX2::TM);
+    p.group = pick_group(2 * p.K, 2, p.tiles_n);
+    static la::DeviceOnce attr_once;
+    if (attr_once.pending()) {
+        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_f16x2_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SmallX2::LDS));
+        attr_once.mark();
+    }
+    // its own timer family (exact-name matching: "gemm_f16x2" counts the 256 x 256 kernel only), at the algorithmic flops as there
+    la::TimerScope ts("gemm_f16x2_small", stream, 2.0 * p.M * p.N * (double)K);
+    hipLaunchKernelGGL(gemm_f16x2_small_kernel, dim3(p.tiles_m * p.tiles_n, slots), dim3(SmallX2::THREADS), SmallX2::LDS, stream, p);
+    LA_LAUNCH_CHECK();
+    return LA_OK;
+}
+
+}  // namespace
+
+extern "C" int la_gemm_f16x2(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
+                             float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream) {
+    if (M == 0 || N == 0) return LA_OK;
+    if (const int rc = x2_checks("gemm_f16x2", 1, M, N, K, slots, A, sa, W, sw, C, bias, residual, epilogue)) return rc;
+    if (!x2_domain(M, N, K, slots)) {
+        la::set_error("gemm_f16x2: M=%d N=%d K=%d slots=%d outside the 256x256 kernel's domain (K / slots a multiple of 128 and >= 256, N > 128, "
+                      ">= %d tiles x slots)", M, N, K, slots, FILL_TILES);
+        return LA_EUNSUPPORTED;
+    }
+    return x2_run("gemm_f16x2", big_launch, M, N, K, slots, A, sa, W, sw, C, ldc, bias, residual, ldr, epilogue, (hipStream_t)stream);
+}
+
+extern "C" int la_gemm_f16x2_small(int32_t M, int32_t N, int32_t K, int32_t slots, const void *A, const float *sa, const void *W, const float *sw,
+                                   float *C, int64_t ldc, const float *bias, const float *residual, int64_t ldr, int32_t epilogue, void *stream) {
+    if (M == 0 || N == 0) return LA_OK;
+    if (const int rc = x2_checks("gemm_f16x2_small", 0, M, N, K, slots, A, sa, W, sw, C, bias, residual, epilogue)) return rc;
+    LA_CHECK_ARG(ldc >= N && (!(epilogue & LA_EPI_RESIDUAL) || ldr >= N), "gemm_f16x2_small: row pitches must cover N");
+    if (slots == 0) slots = la_gemm_f16x2_small_slots(M, N, K);
+    if (!x2_small_k_ok(K, slots) || slots > 64) {
+        la::set_error("gemm_f16x2_small: M=%d N=%d K=%d slots=%d outside the 128x128 kernel's domain (K / slots a multiple of 32, at most 64 slots)",
+                      M, N, K, slots);
+        return LA_EUNSUPPORTED;
+    }
+    return x2_run("gemm_f16x2_small", small_launch, M, N, K, slots, A, sa, W, sw, C, ldc, bias, residual, ldr, epilogue, (hipStream_t)stream);
+}
+
+// The pure host queries of the routing rule (DESIGN.md "Product routing"), for callers that pick a kernel themselves:
+// is (M, N, K, slots) in la_gemm_f16x2's domain (1 / 0), and the split-K slots that bring (M, N) up to it (1 = none needed).
+extern "C" int la_gemm_f16x2_domain(int32_t M, int32_t N, int32_t K, int32_t slots) { return M > 0 && N > 0 && K > 0 && x2_domain(M, N, K, slots); }
+extern "C" int la_gemm_f16x2_slots(int32_t M, int32_t N) {
+    if (M <= 0 || N <= 0) return 1;
+    return std::max(1, la::cdiv(FILL_TILES, tiles256(M, N)));
 }

@@ -199,6 +199,10 @@ bool use_big_tile(int M, int N, int batch) {
 
 }  // namespace
 
+// The 16-bit rule of la_gemm (before its gemm_tile option): do M x N x batch fill the chip with 256 x 256 tiles?  N > 128: a 256-column tile on
+// the gathered-label logits (N = Lmax + 1) would compute mostly padding.
+extern "C" int la_gemm_fills_chip(int32_t M, int32_t N, int32_t batch) { return N > 128 && fills_chip(M, N, batch); }
+
 // ldw: row pitch of W in elements (0 = dense [N][K])
 // Split-K tail: C[m][n] = epilogue(sum_s P[s][m][n]) in a fixed order (deterministic), same epilogue order as the GEMM kernels
 // (bias, activation, residual).
@@ -278,10 +282,9 @@ static int gemm_run_ldw(int dtype, int M, int N, int K, int batch, const void *A
     typedef Cfg<2, 2> Small;
     typedef Cfg<4, 3> Big;
     if (dtype == LA_BF16 || dtype == LA_F16) {
-        // 256x256 ping-pong kernel once it can fill the chip (>= 192 tiles); LA_GEMM_TILE=512 forces it, 128/256 forbid it
-        // (a 256-column tile on N <= 128 -- the gathered-label logits, N = Lmax + 1 -- would compute mostly padding)
+        // 256x256 ping-pong kernel once it can fill the chip (la_gemm_fills_chip); LA_GEMM_TILE=512 forces it, 128/256 forbid it
         const int forced = la::opts().gemm_tile;
-        const bool pp = forced == 512 || (forced == 0 && N > 128 && (int64_t)la::cdiv(M, 256) * la::cdiv(N, 256) * batch >= 192);
+        const bool pp = forced == 512 || (forced == 0 && la_gemm_fills_chip(M, N, batch));
         const bool half = dtype == LA_F16;
         if (ln) {
             if (!pp || (epilogue & LA_EPI_MISH)) {
@@ -379,7 +382,7 @@ extern "C" int la_gemm_split(int32_t dtype, int32_t M, int32_t N, int32_t K, int
     }
     LA_CHECK_ARG(A && W && hi && lo, "gemm_split: null pointer");
     LA_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0, "gemm_split: bad sizes");
-    if (N <= 128 || (int64_t)la::cdiv(M, 256) * la::cdiv(N, 256) * batch < 192 || K % 64 != 0) {
+    if (!la_gemm_fills_chip(M, N, batch) || K % 64 != 0) {
         la::set_error("gemm_split: shape M=%d N=%d K=%d batch=%d does not run on the 256x256 kernel the split epilogue is built into", M, N, K, batch);
         return LA_EUNSUPPORTED;
     }

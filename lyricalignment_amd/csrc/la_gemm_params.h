@@ -34,6 +34,17 @@ struct GemmParams {
                                        // (mean, sum of squared deviations) of each 64-column segment (la_ln_stats_finalize)
 };
 
+// Which kernel takes a product (DESIGN.md "Product routing"): the arithmetic every routing condition of the library is composed from.
+// A site states its own conjunction of these (la_fc_emissions has no N term, la_gemm_split its own K term, ...); none restates a number.
+constexpr int FILL_TILES = 192;        // 256 x 256 tiles (x batch slots) from which the 256 x 256 kernels fill the chip's 256 CUs
+inline int64_t tiles256(int64_t M, int64_t N, int64_t slots = 1) { return (int64_t)la::cdiv(M, 256) * la::cdiv(N, 256) * slots; }
+inline bool fills_chip(int64_t M, int64_t N, int64_t slots = 1) { return tiles256(M, N, slots) >= FILL_TILES; }
+// K of the f16x2 products, per split-K slot: the 256 x 256 kernel walks whole 128-element chunks, at least two; the 128 x 128 one 32-element sub-stages
+inline bool x2_k_ok(int K, int slots = 1) { return slots > 0 && K % slots == 0 && (K / slots) % 128 == 0 && K / slots >= 256; }
+inline bool x2_small_k_ok(int K, int slots = 1) { return slots > 0 && K % slots == 0 && (K / slots) % 32 == 0; }
+// la_gemm_f16x2's domain
+inline bool x2_domain(int64_t M, int N, int K, int slots = 1) { return x2_k_ok(K, slots) && N > 128 && fills_chip(M, N, slots); }
+
 // internal epilogue bits (beside the public LA_EPI_* of lyricalign.h)
 constexpr int LA_EPI_SPLIT_INPLACE = 1 << 20;    // the residual is the split stream itself
 constexpr int LA_EPI_SPLIT_PASS32 = 1 << 21;     // (experiment build, LA_EPI_SPLIT_PASS=32) the 32-row passes without the one-pass-ahead requests

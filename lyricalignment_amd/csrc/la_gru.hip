@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "la_common.h"
+#include "la_x2.h"
 
 using la::bf16_t;
 
@@ -151,11 +152,9 @@ __device__ __forceinline__ void mma_step(const uint4 &a, const uint4 &w, f32x4 &
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(w.w), acc, 0, 0, 0);
 }
 
-__device__ __forceinline__ unsigned x2_pack_hi_lo(float x) {          // x (already scaled) -> f16 hi | f16 lo << 16
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
-}
+// the split arithmetic of the f16x2 forms: la_x2.h.  Their scales take the shift limit 100 (a weight row's inverse scale is multiplied by h's
+// 2^-14 and must stay normal)
+constexpr int X2_SHIFT_LIMIT = 100;
 // ---------------------------------------------------------------------------------------------------------------
 // Counter hand-off form: h travels through `out` itself (the next layer / the FC read it anyway).
 // MAXKS: compile-time bound on H / KSTEP (register-resident W for bf16: H <= 512)
@@ -722,25 +721,17 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruFwdParams p) {
         }
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sc = 1.f, inv = 1.f;
-        if (mx > 0.f && mx < 3.0e38f) {
-            int e;
-            (void)frexpf(mx, &e);
-            int sh = 14 - e;
-            sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
-            sc = ldexpf(1.f, sh);
-            inv = ldexpf(1.f, -sh);
-        }
+        float inv;
+        const float sc = la::x2::scale_for<X2_SHIFT_LIMIT>(mx, &inv);
         wscale[g] = inv * 6.103515625e-05f;                     // x 2^-14
 #pragma unroll
         for (int ks = 0; ks < MAXKS; ++ks)
             if (ks < nks) {
                 const float4 a = *reinterpret_cast<const float4 *>(wr + ks * 32), b = *reinterpret_cast<const float4 *>(wr + ks * 32 + 4);
-                const unsigned p0 = x2_pack_hi_lo(a.x * sc), p1 = x2_pack_hi_lo(a.y * sc), p2 = x2_pack_hi_lo(a.z * sc), p3 = x2_pack_hi_lo(a.w * sc);
-                const unsigned p4 = x2_pack_hi_lo(b.x * sc), p5 = x2_pack_hi_lo(b.y * sc), p6 = x2_pack_hi_lo(b.z * sc), p7 = x2_pack_hi_lo(b.w * sc);
-                whi[g][ks] = make_uint4((p0 & 0xffffu) | (p1 << 16), (p2 & 0xffffu) | (p3 << 16), (p4 & 0xffffu) | (p5 << 16), (p6 & 0xffffu) | (p7 << 16));
-                wlo[g][ks] = make_uint4((p0 >> 16) | (p1 & 0xffff0000u), (p2 >> 16) | (p3 & 0xffff0000u), (p4 >> 16) | (p5 & 0xffff0000u),
-                                        (p6 >> 16) | (p7 & 0xffff0000u));
+                const unsigned pk[8] = {la::x2::pack_hi_lo(a.x * sc), la::x2::pack_hi_lo(a.y * sc), la::x2::pack_hi_lo(a.z * sc), la::x2::pack_hi_lo(a.w * sc),
+                                        la::x2::pack_hi_lo(b.x * sc), la::x2::pack_hi_lo(b.y * sc), la::x2::pack_hi_lo(b.z * sc), la::x2::pack_hi_lo(b.w * sc)};
+                whi[g][ks] = la::x2::plane_frag<0>(pk);
+                wlo[g][ks] = la::x2::plane_frag<1>(pk);
             }
     }
     int *ok_s = reinterpret_cast<int *>(lds);
@@ -799,8 +790,8 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruFwdParams p) {
                     if ((pending & (1u << k)) && v[k][1] == want && v[k][3] == want) {
                         const int idx = tid + k * 256;
                         const int row = idx / cpr, c = idx - row * cpr;
-                        *reinterpret_cast<unsigned *>(shi + row * pitch + c * 4) = (v[k][0] & 0xffffu) | (v[k][2] << 16);
-                        *reinterpret_cast<unsigned *>(slo + row * pitch + c * 4) = (v[k][0] >> 16) | (v[k][2] & 0xffff0000u);
+                        *reinterpret_cast<unsigned *>(shi + row * pitch + c * 4) = la::x2::plane_word<0>(v[k][0], v[k][2]);
+                        *reinterpret_cast<unsigned *>(slo + row * pitch + c * 4) = la::x2::plane_word<1>(v[k][0], v[k][2]);
                         pending &= ~(1u << k);
                     }
                 if (pending && (++spins & 63u) == 0) {
@@ -846,7 +837,7 @@ __global__ __launch_bounds__(256, 1) void gru_train_x2_kernel(GruFwdParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{x2_pack_hi_lo(hnew[i] * 16384.0f), (unsigned)(step + 1)}, xr,
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2{la::x2::pack_hi_lo(hnew[i] * 16384.0f), (unsigned)(step + 1)}, xr,
                                                       wbase + ((4 * q + i) * H + jcol) * 8, 0, 16 /* sc1 */);
             }
         }
@@ -1083,25 +1074,14 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_x2_kernel(GruBwdParams p) {
                 for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(wj(ks * 32 + q * 8 + e)));
             mx = fmaxf(mx, __shfl_xor(mx, 16));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
-            float sc = 1.f, inv = 1.f;
-            if (mx > 0.f && mx < 3.0e38f) {
-                int e2;
-                (void)frexpf(mx, &e2);
-                int sh = 14 - e2;
-                sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
-                sc = ldexpf(1.f, sh);
-                inv = ldexpf(1.f, -sh);
-            }
-            wscale[tau] = inv;
+            const float sc = la::x2::scale_for<X2_SHIFT_LIMIT>(mx, &wscale[tau]);
 #pragma unroll
             for (int ks = 0; ks < 6; ++ks) {
                 unsigned pk[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) pk[e] = x2_pack_hi_lo(wj(ks * 32 + q * 8 + e) * sc);
-                whi[tau][ks] = make_uint4((pk[0] & 0xffffu) | (pk[1] << 16), (pk[2] & 0xffffu) | (pk[3] << 16), (pk[4] & 0xffffu) | (pk[5] << 16),
-                                          (pk[6] & 0xffffu) | (pk[7] << 16));
-                wlo[tau][ks] = make_uint4((pk[0] >> 16) | (pk[1] & 0xffff0000u), (pk[2] >> 16) | (pk[3] & 0xffff0000u),
-                                          (pk[4] >> 16) | (pk[5] & 0xffff0000u), (pk[6] >> 16) | (pk[7] & 0xffff0000u));
+                for (int e = 0; e < 8; ++e) pk[e] = la::x2::pack_hi_lo(wj(ks * 32 + q * 8 + e) * sc);
+                whi[tau][ks] = la::x2::plane_frag<0>(pk);
+                wlo[tau][ks] = la::x2::plane_frag<1>(pk);
             }
         }
     }
@@ -1205,22 +1185,11 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_x2_kernel(GruBwdParams p) {
         for (int i = 0; i < 4; ++i) {
             const int c = 4 * q + i;
             const float m = fmaxf(fmaxf(cmax[c], cmax[16 + c]), fmaxf(cmax[32 + c], cmax[48 + c]));
-            float sc = 1.f, inv = 1.f;
-            if (m > 0.f && m < 3.0e38f) {
-                int e2;
-                (void)frexpf(m, &e2);
-                int sh = 14 - e2;
-                sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
-                sc = ldexpf(1.f, sh);
-                inv = ldexpf(1.f, -sh);
-            }
-            inv_c[i] = inv;
+            const float sc = la::x2::scale_for<X2_SHIFT_LIMIT>(m, &inv_c[i]);
 #pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                const unsigned pk = x2_pack_hi_lo(x[i][g] * sc);
-                *reinterpret_cast<unsigned short *>(a_hi + c * APITCH + (g * 64 + ul) * 2) = (unsigned short)(pk & 0xffffu);
-                *reinterpret_cast<unsigned short *>(a_lo + c * APITCH + (g * 64 + ul) * 2) = (unsigned short)(pk >> 16);
-            }
+            for (int g = 0; g < 3; ++g)
+                la::x2::split(x[i][g] * sc, *reinterpret_cast<unsigned short *>(a_hi + c * APITCH + (g * 64 + ul) * 2),
+                              *reinterpret_cast<unsigned short *>(a_lo + c * APITCH + (g * 64 + ul) * 2));
         }
         __syncthreads();
         // ---- partial dh for all H units from the local 192 columns: three f16 products per k-step and tile ----

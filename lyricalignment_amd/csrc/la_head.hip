@@ -11,6 +11,7 @@
 //                    the reference's emission formulas to raw                     (this file)
 // Algorithmic traffic: reads act + W_fc once, writes 8 B per row per 64 columns; 2*M*V*K flops.
 #include "la_gemm_core.h"
+#include "la_gemm_params.h"
 #include "la_gemm_pp.h"
 
 using la::bf16_t;
@@ -282,10 +283,8 @@ HeadPlan plan_head(int batch, int frames, int in_dim, int vocab, int max_labels,
     return pl;
 }
 
-// Is the float32 normaliser product in the f16x2 kernel's domain?
-bool fc_x2_ok(int rows, int in_dim, int vocab) {
-    return in_dim % 128 == 0 && in_dim >= 256 && (int64_t)la::cdiv(rows, PP::TM) * la::cdiv(vocab, PP::TN) >= 192;
-}
+// Is the float32 normaliser product in the f16x2 kernel's domain?  (No N term: the vocabulary is wide; DESIGN.md "Product routing".)
+bool fc_x2_ok(int rows, int in_dim, int vocab) { return x2_k_ok(in_dim) && fills_chip(rows, vocab); }
 
 }  // namespace
 
@@ -348,8 +347,7 @@ static int fc_emissions_impl(int32_t dtype, const void *act, int64_t ld_act, con
         typedef Cfg<4, 3> Big;
         static bool attr_bf16 = false, attr_bf16_big = false, attr_f32 = false, attr_pp = false;
         const int force_tile = la::opts().gemm_tile;
-        const bool pp_ok = dtype != LA_F32 && !force_tile && in_dim % 64 == 0 && in_dim >= 128 && (ld_act * 2) % 16 == 0 &&
-                           (int64_t)la::cdiv(rows, PP::TM) * la::cdiv(vocab, PP::TN) >= 192;
+        const bool pp_ok = dtype != LA_F32 && !force_tile && in_dim % 64 == 0 && in_dim >= 128 && (ld_act * 2) % 16 == 0 && fills_chip(rows, vocab);
         if (!pp_ok && !x2) lp.nparts = 2 * pl.tiles_n;      // the 128-column kernels write two strips per tile
         if (x2) {
             static la::DeviceOnce attr_x2;

@@ -6,6 +6,7 @@
 // Host code only: it enqueues the op-level kernels of this library (la_gemm, la_attention, la_gru_layer, ...) on the
 // caller's stream in the order engine.AlignEngine.encode / head_hidden / emissions do, out of a caller-provided workspace.
 #include "la_common.h"
+#include "la_gemm_params.h"
 
 namespace {
 
@@ -35,28 +36,29 @@ struct EncBufs {
     size_t total;
 };
 
-// la_gemm_f16x2's domain at slots = 1 (the 256 x 256 kernel): K a multiple of 128 and >= 256, N > 128, >= 192 tiles
-bool x2_big_ok(int64_t M, int N, int K) { return K % 128 == 0 && K >= 256 && N > 128 && la::cdiv(M, 256) * la::cdiv(N, 256) >= 192; }
+using la::gemm::fills_chip;
+
+// la_gemm_f16x2's domain at slots = 1 (the weight planes are packed at their own K).  The routing rules: DESIGN.md "Product routing".
+bool x2_big_ok(int64_t M, int N, int K) { return la::gemm::x2_domain(M, N, K); }
 
 // Does the float32 encoder run its blocks on the f16 matrix pipe (la_gemm_f16x2 + la_layernorm_f16x2 + la_attention_lse_f16x2)?  The blocks
-// carry the weight planes, the option is on, and every Linear of a block lies in the 256 x 256 kernel's domain: >= 192 tiles for the narrowest
-// (N = d), K = d a multiple of 128 and >= 256.  With option x2_small at every batch size: the products outside that domain run on the
-// 128 x 128 f16x2 kernel (x2_gemm), which takes any d that is a multiple of 32.
+// carry the weight planes, the option is on, and every Linear of a block lies in the 256 x 256 kernel's domain: the narrowest one (N = d) fills
+// the chip, K = d suits the kernel.  With option x2_small at every batch size: the products outside that domain run on the 128 x 128 f16x2
+// kernel (x2_gemm), which takes any d that is a multiple of 32.
 bool encoder_x2(const la_encoder_weights *w, int batch) {
     if ((w->dtype & 0xff) != LA_F32 || w->n_layer < 1 || !la::opts().x2_inference) return false;
     const int d = w->d;
     const bool small = la::opts().x2_small != 0;
-    if (small ? (d % 32 != 0 || d > 1024 * 4) : (d % 128 != 0 || d < 256 || d > 1024 * 4)) return false;
+    if (d > 1024 * 4 || !(small ? la::gemm::x2_small_k_ok(d) : la::gemm::x2_k_ok(d))) return false;
     for (int l = 0; l < w->n_layer; ++l) {
         const la_encoder_block &k = w->blocks[l];
         if (!(k.wqkv_x2 && k.wqkv_x2s && k.wo_x2 && k.wo_x2s && k.w1_x2 && k.w1_x2s && k.w2_x2 && k.w2_x2s)) return false;
     }
-    return small || la::cdiv((int64_t)batch * N_CTX, 256) * la::cdiv(d, 256) >= 192;
+    return small || fills_chip((int64_t)batch * N_CTX, d);
 }
 
 // One f16x2 product of the float32 routes: the 256 x 256 kernel wherever the shape lies in its domain, else (option x2_small) the 128 x 128
-// kernel with its own split-K rule (slots = 0; split-K partial sums in the library's stream scratch, as float32 la_gemm's).  engine.py
-// _x2_gemm makes the same choice.
+// kernel with its own split-K rule (slots = 0; split-K partial sums in the library's stream scratch, as float32 la_gemm's).
 int x2_gemm(int M, int N, int K, const void *A, const float *sa, const void *W, const float *sw, float *C, int64_t ldc, const float *bias,
             const float *residual, int64_t ldr, int epilogue, hipStream_t stream) {
     if (x2_big_ok(M, N, K)) return la_gemm_f16x2(M, N, K, 1, A, sa, W, sw, C, ldc, bias, residual, ldr, epilogue, stream);
@@ -94,8 +96,8 @@ bool encoder_fused_ln(const la_encoder_weights *w, int batch) {
     if ((w->dtype & 0xff) == LA_F32 || w->n_layer < 1 || !w->blocks[0].wqkv_ln || w->d <= 128) return false;
     if (!la::opts().ln_fusion) return false;
     const int64_t M = (int64_t)batch * N_CTX;
-    // every GEMM of a block (and the batched conv2) must run on the 256x256 kernel the fold is built into: >= 192 tiles
-    return la::cdiv(M, 256) * la::cdiv(w->d, 256) >= 192 && (int64_t)la::cdiv(N_CTX, 256) * la::cdiv(w->d, 256) * batch >= 192;
+    // every GEMM of a block (and the batched conv2) must run on the 256x256 kernel the fold is built into
+    return fills_chip(M, w->d) && fills_chip(N_CTX, w->d, batch);
 }
 
 #define LA_TRY(expr)                   \
@@ -239,7 +241,7 @@ bool head_x2(const la_head_weights *w) {
     return w->dtype == LA_F32 && la::opts().x2_inference && w->w_ih_x2[0] && w->w_ih_x2s[0] && w->w_ih_x2[1] && w->w_ih_x2s[1] && w->w_fc_x2 && w->w_fc_x2s;
 }
 // one input projection [rows][K] x [6H][K]^T in la_gemm_f16x2's domain -- or, with option x2_small, in la_gemm_f16x2_small's (x2_gemm picks)?
-bool proj_x2_ok(int64_t rows, int K, int H) { return x2_big_ok(rows, 6 * H, K) || (la::opts().x2_small && K % 32 == 0); }
+bool proj_x2_ok(int64_t rows, int K, int H) { return x2_big_ok(rows, 6 * H, K) || (la::opts().x2_small && la::gemm::x2_small_k_ok(K)); }
 
 int carve_head(void *ws, const la_head_weights *w, int batch, int frames, int max_labels, HeadBufs *b) {
     Carve c(ws);

@@ -86,7 +86,12 @@ def x2_inference_on() -> bool:
 
 def _x2_domain(M: int, N: int, K: int) -> bool:
     """la_gemm_f16x2's domain without split-K slots (the weight planes are packed at their own K)."""
-    return K % 128 == 0 and K >= 256 and N > 128 and -(-M // 256) * -(-N // 256) >= 192
+    return bool(_lib.lib().la_gemm_f16x2_domain(M, N, K, 1))
+
+
+def _fills_chip(M: int, N: int, batch: int = 1) -> bool:
+    """Does a 16-bit M x N x batch product run on the 256 x 256 kernel (la_gemm_fills_chip)?"""
+    return bool(_lib.lib().la_gemm_fills_chip(M, N, batch))
 
 
 def x2_small_on() -> bool:
@@ -95,9 +100,20 @@ def x2_small_on() -> bool:
     return _lib.get_option("x2_small") != 0
 
 
+def _x2_small_ok(K: int) -> bool:
+    """Option x2_small is on and the 128 x 128 f16x2 kernel walks this K (whole 32-element sub-stages)."""
+    return x2_small_on() and K % 32 == 0
+
+
+def _x2_route(M: int, N: int, K: int) -> bool:
+    """Does a float32 product with packed weight planes take an f16x2 kernel?  In la_gemm_f16x2's domain, or on the 128 x 128 kernel (the
+    encoder asks this of its narrowest Linear, M x d x d)."""
+    return _x2_domain(M, N, K) or _x2_small_ok(K)
+
+
 def _x2_gemm(a, w, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One f16x2 product of the float32 routes, on the kernel la_model.cpp x2_gemm picks: the 256 x 256 one in its domain, else the 128 x 128 one
-    with its own split-K rule (option x2_small)."""
+    """One f16x2 product of the float32 routes: the 256 x 256 kernel in its domain, else the 128 x 128 one with its own split-K rule (option
+    x2_small).  The rule is the library's (DESIGN.md "Product routing")."""
     from . import f32x2
     if _x2_domain(a.rows, w.rows, a.kp):
         return f32x2.gemm(a, w, out=out, bias=bias, residual=residual)
@@ -376,10 +392,10 @@ class AlignEngine:
         # LayerNorm folded into the GEMMs around it: the GEMMs that write the f32 residual stream x also store it rounded to
         # bf16 (h = raw x), a small kernel takes the row statistics of h, and the QKV / MLP-up GEMMs apply
         # rstd (acc - mean c) + b' in their epilogue on gamma-folded weights.  Only where every GEMM of a block runs on the
-        # 256x256 kernel (>= 192 tiles, i.e. >= 9 clips at d = 1024) and in the 16-bit modes (float16: the raw stream must stay
-        # below 65504, as it must for whisper's own fp16 inference); otherwise the separate LayerNorm pass.
-        fused = (LN_FUSION and dt in (torch.bfloat16, torch.float16) and e.blocks and e.blocks[0].wqkv_ln is not None and d > 128
-                 and -(-M // 256) * -(-d // 256) >= 192 and -(-N_CTX // 256) * -(-d // 256) * B >= 192)
+        # 256x256 kernel (i.e. >= 9 clips at d = 1024) and in the 16-bit modes (float16: the raw stream must stay below 65504, as it
+        # must for whisper's own fp16 inference); otherwise the separate LayerNorm pass.
+        fused = (LN_FUSION and dt in (torch.bfloat16, torch.float16) and e.blocks and e.blocks[0].wqkv_ln is not None
+                 and _fills_chip(M, d) and _fills_chip(N_CTX, d, B))
         split = fused and RESID_SPLIT
         if split:
             lo = x.view(torch.uint8).view(-1)[: M * d].view(M, d)         # the stream's lo bytes live in the first quarter of x
@@ -423,7 +439,7 @@ class AlignEngine:
                     ops.gemm(u, blk.w2, x, bias=blk.b2, residual=x, out_f32=True, out16=h, ln_part=part)     # x += mlp; h = bf16(x)
                 row_stats()
         elif (dt == torch.float32 and e.blocks and all(b_.x2 is not None for b_ in e.blocks) and x2_inference_on() and d <= 4096
-              and (-(-M // 256) * -(-d // 256) >= 192 or (x2_small_on() and d % 32 == 0))):
+              and _x2_route(M, d, d)):
             # float32 on the f16 matrix pipe at float32 accuracy: la_encoder_forward's x2 route, spelled out over the op-level calls
             from . import f32x2
             pl = lambda t: f32x2.Planes(t[0], t[1], t[0].shape[0], t[0].shape[2], t[0].shape[2])
@@ -672,11 +688,11 @@ class AlignEngine:
         for layer in range(n_layers):
             gi = self._get("gi", (Bbuf, T, 2, 3 * H), torch.float32)[:B]
             K = hw.w_ih[layer].shape[1]
-            small = hw.w_ih_x2 is not None and K % 32 == 0 and x2_inference_on() and x2_small_on()
-            if (hw.w_ih_x2 is not None and stride_a == T * lda and lda == K and _x2_domain(B * T, 6 * H, K) and x2_inference_on()):
+            x2 = hw.w_ih_x2 is not None and x2_inference_on()
+            if x2 and stride_a == T * lda and lda == K and _x2_domain(B * T, 6 * H, K):
                 _x2_linear(x[: B * T] if x.dim() == 2 else x.view(-1, K)[: B * T], hw.w_ih_x2[layer], hw.b_ih[layer], out=gi.view(B * T, 6 * H))
-            elif small and x.dim() == 2 and x.stride(1) == 1:
-                # (option x2_small: la_align_head_forward's proj_x2_ok -- the clips' rows split clip by clip where they are not adjacent)
+            elif x2 and _x2_small_ok(K) and x.dim() == 2 and x.stride(1) == 1:
+                # (option x2_small: the clips' rows split clip by clip where they are not adjacent)
                 from . import f32x2
                 if stride_a == T * lda:
                     a = f32x2.split(x[: B * T, :K], K)

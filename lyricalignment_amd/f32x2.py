@@ -5,7 +5,8 @@ operands at 1/16 of its 16-bit MFMA rate.  A float32 matrix whose rows are scale
 IEEE-half planes (hi + lo = 22 bits), and one pass of the 256 x 256 f16 kernel (three products per 32-wide k chunk) accumulates
 a_lo w_hi + a_hi w_lo + a_hi w_hi in float32 -- 3/16 of the float32 pipe's cost, error against a float64 product smaller than
 the float32 kernel's own (profiles/r5_kbench_f32emu.txt).  This module is the host side: which products take that path (the
-large ones: >= 192 tiles of 256 x 256, counting split-K slots), their operand splits, and the three product shapes of a Linear
+large ones: the library's routing rule, DESIGN.md "Product routing", with this module's policy on split-K slots on top), their
+operand splits, and the three product shapes of a Linear
 
     linear(x, w, bias, residual)   y  = x w^T (+ bias) (+ residual)          forward
     gemm_nn(dy, w)                 dx = dy w                                  input gradient
@@ -32,7 +33,6 @@ from ._lib import check, lib, ptr, stream_ptr
 
 ENABLED = os.environ.get("LA_F32X2", "1") != "0"
 FUSE_ACT = os.environ.get("LA_F32X2_ACT", "1") != "0"     # 0: gelu(x) through its own float32 buffer before the split (A/B partner)
-MIN_TILES = 192          # the 256 x 256 kernel's domain (la_gemm_f16x2)
 
 
 def _rup(x: int, m: int) -> int:
@@ -84,11 +84,10 @@ def split(x: torch.Tensor, kp: Optional[int] = None, act: Optional[str] = None, 
     kp = _rup(k, 128) if kp is None else kp
     planes = torch.empty((rows, 2, kp), dtype=torch.float16, device=x.device)
     inv = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    if omax is not None and REUSE_MAX:
-        check(lib().la_split_f16x2_max(ptr(x), x.stride(0), rows, k, ptr(planes), kp, ptr(inv), ACT[act], ptr(omax.words), stream_ptr()), "split_f16x2")
+    words = omax.words if (omax is not None and REUSE_MAX) else None
+    check(lib().la_split_f16x2_max(ptr(x), x.stride(0), rows, k, ptr(planes), kp, ptr(inv), ACT[act], ptr(words), stream_ptr()), "split_f16x2")
+    if words is not None:
         omax.act, omax.valid = act, True
-    else:
-        check(lib().la_split_f16x2_act(ptr(x), x.stride(0), rows, k, ptr(planes), kp, ptr(inv), ACT[act], stream_ptr()), "split_f16x2")
     return Planes(planes, inv, rows, k, kp)
 
 
@@ -141,17 +140,17 @@ class WeightPlanes:
 
 def slots_for(M: int, N: int) -> int:
     """Split-K slots that bring a product with few 256 x 256 tiles up to the kernel's domain (1 = none needed)."""
-    tiles = -(-M // 256) * -(-N // 256)
-    return max(1, -(-MIN_TILES // tiles))
+    return int(lib().la_gemm_f16x2_slots(M, N))
 
 
 def eligible(M: int, N: int, K: int) -> bool:
-    """Does C [M, N] = A [M, K] W [N, K]^T take the f16x2 path?  Large products only: N > 128, at least 256 of K per split-K slot and
-    no more than 16 slots (beyond that the partial sums cost more than the float32 kernel)."""
-    if not ENABLED or N <= 128 or K < 256:
+    """Does C [M, N] = A [M, K] W [N, K]^T take the f16x2 path?  Where the padded product lies in la_gemm_f16x2's domain, with this module's
+    policy on top: at least 256 of K per split-K slot before padding and no more than 16 slots (beyond that the partial sums cost more
+    than the float32 kernel)."""
+    if not ENABLED:
         return False
     s = slots_for(M, N)
-    return s <= 16 and K // s >= 256
+    return bool(s <= 16 and K // s >= 256 and lib().la_gemm_f16x2_domain(M, N, padded_k(M, N, K), s))
 
 
 def padded_k(M: int, N: int, K: int) -> int:
@@ -160,31 +159,39 @@ def padded_k(M: int, N: int, K: int) -> int:
     return s * _rup(-(-K // s), 128)
 
 
-def gemm(a: Planes, w: Planes, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-         residual: Optional[torch.Tensor] = None, gelu: bool = False, gelu_grad_of: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out [a.rows, w.rows] f32 = epi(A W^T) from split operands of the same plane length.  gelu_grad_of = u [a.rows, w.rows]: the
-    product is multiplied by gelu'(u) in the epilogue (LA_EPI_RES_GELU_GRAD; u takes the residual operand's place)."""
+def _product(name: str, slots: int, a: Planes, w: Planes, out, bias, residual, gelu: bool, gelu_grad_of) -> torch.Tensor:
+    """The body of gemm / gemm_small: result buffer, epilogue flags and the call of la_<name>."""
+    entry = name.replace("_f16x2", "")
     if a.kp != w.kp:
-        raise ValueError(f"f32x2.gemm: operands were split to different plane lengths ({a.kp}, {w.kp})")
+        raise ValueError(f"f32x2.{entry}: operands were split to different plane lengths ({a.kp}, {w.kp})")
     M, N = a.rows, w.rows
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.planes.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (M, N):
+        raise ValueError(f"f32x2.{entry}: out must be a float32 [{M}, {N}] row view")
     epi = 0
     if bias is not None:
         epi |= _lib.EPI_BIAS
     if gelu_grad_of is not None:
         if residual is not None:
-            raise ValueError("f32x2.gemm: gelu_grad_of takes the residual operand's place")
+            raise ValueError(f"f32x2.{entry}: gelu_grad_of takes the residual operand's place")
         residual = gelu_grad_of
         epi |= _lib.EPI_RES_GELU_GRAD
     if residual is not None:
         epi |= _lib.EPI_RESIDUAL
     if gelu:
         epi |= _lib.EPI_GELU
-    check(lib().la_gemm_f16x2(M, N, a.kp, slots_for(M, N), ptr(a.planes), ptr(a.inv_scale), ptr(w.planes), ptr(w.inv_scale), ptr(out),
-                              out.stride(0), ptr(bias), ptr(residual), residual.stride(0) if residual is not None else 0, epi,
-                              stream_ptr()), "gemm_f16x2")
+    check(getattr(lib(), "la_" + name)(M, N, a.kp, slots, ptr(a.planes), ptr(a.inv_scale), ptr(w.planes), ptr(w.inv_scale), ptr(out),
+                                       out.stride(0), ptr(bias), ptr(residual), residual.stride(0) if residual is not None else 0, epi,
+                                       stream_ptr()), name)
     return out
+
+
+def gemm(a: Planes, w: Planes, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+         residual: Optional[torch.Tensor] = None, gelu: bool = False, gelu_grad_of: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [a.rows, w.rows] f32 = epi(A W^T) from split operands of the same plane length.  gelu_grad_of = u [a.rows, w.rows]: the
+    product is multiplied by gelu'(u) in the epilogue (LA_EPI_RES_GELU_GRAD; u takes the residual operand's place)."""
+    return _product("gemm_f16x2", slots_for(a.rows, w.rows), a, w, out, bias, residual, gelu, gelu_grad_of)
 
 
 def slots_small(M: int, N: int, K: int) -> int:
@@ -199,29 +206,7 @@ def gemm_small(a: Planes, w: Planes, out: Optional[torch.Tensor] = None, bias: O
     """gemm on the 128 x 128 f16x2 kernel (la_gemm_f16x2_small): the same arguments and result, for the products outside the 256 x 256
     kernel's domain (any M, N; plane length / slots a multiple of 32).  slots None = slots_small(M, N, K); where both kernels take a
     shape with slots = 1 the bits equal gemm's."""
-    if a.kp != w.kp:
-        raise ValueError(f"f32x2.gemm_small: operands were split to different plane lengths ({a.kp}, {w.kp})")
-    M, N = a.rows, w.rows
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.planes.device)
-    elif out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (M, N):
-        raise ValueError(f"f32x2.gemm_small: out must be a float32 [{M}, {N}] row view")
-    epi = 0
-    if bias is not None:
-        epi |= _lib.EPI_BIAS
-    if gelu_grad_of is not None:
-        if residual is not None:
-            raise ValueError("f32x2.gemm_small: gelu_grad_of takes the residual operand's place")
-        residual = gelu_grad_of
-        epi |= _lib.EPI_RES_GELU_GRAD
-    if residual is not None:
-        epi |= _lib.EPI_RESIDUAL
-    if gelu:
-        epi |= _lib.EPI_GELU
-    check(lib().la_gemm_f16x2_small(M, N, a.kp, 0 if slots is None else int(slots), ptr(a.planes), ptr(a.inv_scale), ptr(w.planes),
-                                    ptr(w.inv_scale), ptr(out), out.stride(0), ptr(bias), ptr(residual),
-                                    residual.stride(0) if residual is not None else 0, epi, stream_ptr()), "gemm_f16x2_small")
-    return out
+    return _product("gemm_f16x2_small", 0 if slots is None else int(slots), a, w, out, bias, residual, gelu, gelu_grad_of)
 
 
 def _plain2d(t: torch.Tensor) -> bool:

@@ -15,7 +15,6 @@ from __future__ import annotations
 import argparse
 import ctypes
 import os
-import statistics
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,17 +36,11 @@ def main():
     sys.path.insert(0, os.path.join(HERE, ".."))
     import torch
     from lyricalignment_amd import _lib
-    from lyricalignment_amd._lib import SYMBOLS, lib, ptr, stream_ptr
+    from lyricalignment_amd._lib import lib, ptr, stream_ptr
+    from ab_pair import load_sibling, measure_leg, verdict
     _lib.require_gpu()
     dev = torch.device("cuda:0")
     DT = {"f32": (torch.float32, _lib.LA_F32), "bf16": (torch.bfloat16, _lib.LA_BF16), "f16": (torch.float16, _lib.LA_F16)}
-
-    def load(path):
-        other = ctypes.CDLL(os.path.abspath(path))
-        for name in ENTRIES:
-            fn = getattr(other, name)
-            fn.restype, fn.argtypes = SYMBOLS[name]
-        return other
 
     def make_call(L_, kind, dt, qlog2, B, T, x):
         """-> (call, outputs by name) for library L_ on the inputs x"""
@@ -80,15 +73,6 @@ def main():
             assert run() == 0, L_.la_last_error()
         return call, outs
 
-    def time_once(fn):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        return s.elapsed_time(e)
-
     def ab(other, who):
         """-> {leg: (bit-equal, this median, other median)}"""
         res = {}
@@ -103,38 +87,18 @@ def main():
                 fwd()
                 x.update(o=fo["out"], lse=fo["lse"], do=torch.randn(B * T, d, device=dev, generator=g) * 1e-3)
             legs = [make_call(L_, kind, dt, qlog2, B, T, x) for L_ in (lib(), other)]
-            for fn, _ in legs:
-                for _ in range(3):
-                    fn()
-            torch.cuda.synchronize()
-            equal = all(legs[0][1][k].cpu().view(torch.uint8).numpy().tobytes() == legs[1][1][k].cpu().view(torch.uint8).numpy().tobytes() for k in legs[0][1])
-            ts = [[], []]
-            for r in range(args.runs):
-                for i in ((0, 1) if r % 2 == 0 else (1, 0)):
-                    ts[i].append(time_once(legs[i][0]))
-            m, pm = statistics.median(ts[0]), statistics.median(ts[1])
-            res[name] = (equal, m, pm)
-            print(f"{name:28s} {1e3 * m:9.1f} us ({1e3 * min(ts[0]):.1f} .. {1e3 * max(ts[0]):.1f})   against {who} {1e3 * pm:9.1f} us "
-                  f"({1e3 * min(ts[1]):.1f} .. {1e3 * max(ts[1]):.1f}): {100 * (m / pm - 1):+.2f} % of its median; outputs {'bit-equal' if equal else 'DIFFER'}", flush=True)
+            res[name] = measure_leg(name, legs, args.runs, who)
             del legs, x
             torch.cuda.empty_cache()
         return res
 
     print(f"# attention kernels on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up of 3, the two libraries "
           f"alternated call by call (first place alternating), device events around one call", flush=True)
-    got = ab(load(args.parent_lib), "the parent's")
-    broken = [f"{n}: outputs differ from the parent's" for n, (eq, _, _) in got.items() if not eq]
+    got, ctl = ab(load_sibling(args.parent_lib, ENTRIES), "the parent's"), None
     if args.control:
         print("# the same against a copy of this build's own library", flush=True)
-        ctl = ab(load(args.control), "the copy's")
-        for n, (_, m, pm) in got.items():
-            margin = abs(ctl[n][1] / ctl[n][2] - 1)
-            ok = m / pm - 1 <= margin
-            print(f"{n:28s} excess over the parent {100 * (m / pm - 1):+.2f} %, control margin {100 * margin:.2f} %: {'passes' if ok else 'ABOVE THE MARGIN'}")
-            if not ok:
-                broken.append(f"{n}: {100 * (m / pm - 1):+.2f} % over the parent, control margin {100 * margin:.2f} %")
-    print(f"verdict: {'every leg bit-equal' + (' and inside the control margin' if args.control else '') if not broken else 'RULE BROKEN: ' + '; '.join(broken)}")
-    return 1 if broken else 0
+        ctl = ab(load_sibling(args.control, ENTRIES), "the copy's")
+    return verdict(got, ctl)
 
 
 if __name__ == "__main__":

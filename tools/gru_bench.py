@@ -63,18 +63,16 @@ def main():
     sys.path.insert(0, os.path.join(HERE, ".."))
     import torch
     from lyricalignment_amd import _lib
-    from lyricalignment_amd._lib import SYMBOLS, lib, ptr, stream_ptr
+    from lyricalignment_amd._lib import lib, ptr, stream_ptr
+    from ab_pair import alternate, load_sibling, same_bytes
     _lib.require_gpu()
     torch.cuda.set_device(0)
     dev = torch.device("cuda:0")
     libs = [("", lib())]
     if args.parent_lib:
-        parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
-        for name in ("la_gru_workspace_bytes", "la_gru_layer", "la_gru_layer_ragged", "la_gru_layer_train_fwd", "la_gru_layer_bwd",
-                     "la_set_option", "la_get_option", "la_last_error"):
-            fn = getattr(parent, name)
-            fn.restype, fn.argtypes = SYMBOLS[name]
-        libs.append(("parent commit: ", parent))
+        libs.append(("parent commit: ", load_sibling(args.parent_lib, ("la_gru_workspace_bytes", "la_gru_layer", "la_gru_layer_ragged",
+                                                                        "la_gru_layer_train_fwd", "la_gru_layer_bwd", "la_set_option",
+                                                                        "la_get_option", "la_last_error"))))
     DT = {"f32": (torch.float32, _lib.LA_F32), "bf16": (torch.bfloat16, _lib.LA_BF16), "f16": (torch.float16, _lib.LA_F16)}
 
     def pin(L_, opts):
@@ -128,15 +126,6 @@ def main():
         outs["timeout_flag"] = flag
         return call, outs
 
-    def time_once(fn):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        return s.elapsed_time(e)
-
     say(f"# GRU recurrence kernels on {torch.cuda.get_device_name(0)}, T = {T}, H = {H}: median (min .. max) of {args.runs} calls after a warm-up "
         f"of 3, the two libraries alternated call by call (first place alternating), device events around one call, ms")
     broken = []
@@ -177,15 +166,12 @@ def main():
                 a, b_ = legs[0][2][k], legs[1][2][k]
                 if valid is not None and a.dim() == 3:
                     a, b_ = torch.where(valid, a, torch.zeros_like(a)), torch.where(valid, b_, torch.zeros_like(b_))
-                if a.cpu().view(torch.uint8).numpy().tobytes() != b_.cpu().view(torch.uint8).numpy().tobytes():
+                if not same_bytes(a, b_):
                     differ.append(k)
             equal = not differ
             if differ:
                 broken.append(f"{name}: {', '.join(differ)} differ from the parent commit's")
-        ts = [[] for _ in legs]
-        for r in range(args.runs):                 # who goes first alternates too: the call after the other library's is not the same call
-            for i in (range(len(legs)) if r % 2 == 0 else reversed(range(len(legs)))):
-                ts[i].append(time_once(legs[i][1]))
+        ts = alternate([fn for _, fn, _ in legs], args.runs)
         m, lo, hi = statistics.median(ts[0]), min(ts[0]), max(ts[0])
         line = f"{name:34s} {m:8.3f} ({lo:.3f} .. {hi:.3f})   {1e3 * m / T:6.3f} us per step"
         if len(legs) == 2:
