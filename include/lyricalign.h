@@ -308,7 +308,8 @@ int la_viterbi_lattice_batch(const float *em, int64_t em_batch_stride, int64_t e
  * Up to 4095 labels (LA_EUNSUPPORTED above).  la_viterbi_repeats_workspace_bytes() = la_viterbi_lattice_workspace_bytes(); the
  * backpointers are three 64-bit masks whatever is given.  Argument errors (la_viterbi_lattice_batch's, a repeat_stride below max_labels
  * with a repeat_from, a path_stride below max_frames with a path, a negative or NaN repeat_penalty) are answered on the host before
- * anything is enqueued; never synchronises, allocates or frees.  The posterior sweeps and the training loss do not know this lattice.
+ * anything is enqueued; never synchronises, allocates or frees.  The sum-product sweep of this lattice is la_alignment_posteriors_repeats
+ * (up to 511 labels); the four older posterior entries and the training loss do not know this lattice.
  */
 int la_viterbi_repeats_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
 
@@ -478,6 +479,57 @@ int la_alignment_posteriors_lattice(const float *em, int64_t em_batch_stride, in
                                     const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
                                     float *occupancy, float *onset_prob, float *offset_prob, float *present_prob,
                                     float *span_skip_prob,
+                                    double *log_z, int32_t *status,
+                                    float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Confidence for repeated lyric lines: the sum-product sweep on the lattice of la_viterbi_repeats_batch.  The arguments are
+ * la_alignment_posteriors_lattice's through win_stride (skip_from and the pair win_lo / win_hi each optional), then
+ *   repeat_from, repeat_stride, repeat_penalty: as la_viterbi_repeats_batch (repeat_from may be NULL: no repeat span);
+ *   path [batch][path_stride] (path_stride >= max_frames; may be NULL): la_viterbi_repeats_batch's `path` for the same lattice;
+ * then the outputs, with `visits` where present_prob stood, and two more:
+ *   repeat_count [batch][out_stride], path_prob [batch][path_stride] (may be NULL; needs path).
+ * onset / offset are la_viterbi_repeats_batch's outputs for the same lattice: a label's FIRST visit.
+ * A path may visit a label more than once on this lattice, so some sums that are probabilities on the other lattices are EXPECTED
+ * COUNTS here and can exceed 1 (values above 2 occur with soft emissions).  No output is clamped.
+ *   gamma_t(k), log_z, occupancy: unchanged in meaning (rows of gamma sum to 1; occupancy is about the first visit's segment).
+ *   entry_t(n): the probability that A visit of label n begins at frame t; exit_t(n): that a visit ends there.  The repeat arcs
+ *       K -> 2a+1 and K-1 -> 2a+1 count as entries of label a and as exits of their source.
+ *   visits[n] = sum_t entry_t(n): the expected number of visits of label n.  Equal to present_prob where no repeat span exists.
+ *   onset_prob / offset_prob[n]: the expected number of visits that begin / end within boundary_window frames of the reported
+ *       boundary; probabilities whenever two visits of the label cannot begin within 2 boundary_window + 1 frames of each other.
+ *   repeat_count[a]: the expected number of times the path takes a repeat arc of the span that starts at a (0 where none starts):
+ *       sum over t >= 1 and the sources K and (where allowed) K-1 of exp(alpha_{t-1}(src) - repeat_penalty + beta_t(2a+1) - log_z).
+ *   span_skip_prob[n]: its formula unchanged; an expected count where a repeat span covers the optional span (a skip per pass).
+ *   path_prob[b][t] = gamma_t(path[b][t]), 0 for t >= T_b, for a path value that names no state and for failed clips: the
+ *       occupancy of every visit, not only the first, is the mean of path_prob over the visit's frames.
+ * For every label n:  visits[n] + sum over optional spans (a', e') with a' <= n < e' of span_skip_prob[e']
+ *                     = 1 + sum over repeat spans (a, e) with a <= n < e of repeat_count[a].
+ * Backward a source folds the arcs that leave it in one fixed order (skip targets ascending, then repeat targets ascending), no
+ * atomics: a clip's numbers do not depend on its batch mates and two calls agree to the bit.  With repeat_from NULL or all -1,
+ * occupancy, onset_prob, offset_prob, span_skip_prob, log_z, status and gamma_out equal la_alignment_posteriors_lattice's bit for
+ * bit, visits equals its present_prob and repeat_count is 0.
+ * Up to 511 labels (LA_EUNSUPPORTED above); the workspace is la_alignment_posteriors_windows' size.  Statuses and the zeroing of
+ * failed rows as in la_alignment_posteriors_windows (repeat_count and path_prob rows are zeroed too).  Argument errors (the
+ * lattice entry's, a repeat_stride below max_labels with a repeat_from, a path_stride below max_frames with a path or path_prob,
+ * path_prob without path, a negative or NaN repeat_penalty) are answered on the host under this entry's name before anything is
+ * enqueued; never synchronises, allocates or frees.
+ */
+int la_alignment_posteriors_repeats_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors_repeats(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                    const int32_t *labels, int32_t labels_stride,
+                                    const int32_t *n_labels, const int32_t *n_frames,
+                                    int32_t batch, int32_t max_frames, int32_t max_labels,
+                                    const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                                    int32_t boundary_window,
+                                    const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                    const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                    const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty,
+                                    const int32_t *path, int32_t path_stride,
+                                    float *occupancy, float *onset_prob, float *offset_prob, float *visits,
+                                    float *span_skip_prob, float *repeat_count, float *path_prob,
                                     double *log_z, int32_t *status,
                                     float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
                                     void *workspace, size_t workspace_bytes, void *stream);

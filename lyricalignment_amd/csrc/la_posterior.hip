@@ -33,7 +33,20 @@
 // present and span-skip terms all carry a beta_t or alpha_t factor of the gated cell and need nothing more.  log_z is the windowed
 // one: every output is a posterior GIVEN the windows; log_z = -inf (no path inside them) is the LA_EINFEASIBLE exit.
 //
-// LAYOUT 1, up to 511 labels: posterior_kernel<NW, DPP, SPANS, WIN>, one workgroup per clip, one lane per state, the sums lane-local
+//   Repeatable spans (REP, only on top of SPANS + WIN, null pointers = absent; lane-per-state form only): the lattice of
+// la_viterbi_repeats_batch.  The odd state 2a+1 with repeat_from[a] = e has two more predecessors, K = 2e and (where allowed) K-1
+// (la_lattice.h repeat_source), each weighing exp(-repeat_penalty): the arcs point LEFT, but the sweep is frame-synchronous, so (frame,
+// state) stays a DAG.  Forward they are the jump arcs' fetch with the source to the right.  Backward K and K-1 are sources and join the
+// per-source arc lists: state k is K of the repeat spans that END at position (k+1)/2 when even, K-1 of them when odd; a list word is
+// target | kRepeatArc and so carries its own penalty; FOLD ORDER per source: skip targets ascending, then repeat targets ascending.  A
+// path may now visit a label more than once, so entry / exit terms and what is summed from them are EXPECTED COUNTS (include/lyricalign.h
+// la_alignment_posteriors_repeats): the repeat-in term joins the entry term (present_prob's slot holds `visits`) and, through js, the exit
+// term of its source; repeat_count[a] -- the mass of the repeat arcs into 2a+1 -- accumulates in a register of lane 2a+1, the label's row
+// lane.  path_prob[t] = gamma_t(path[t]) is stored by the lane the DP's path names, the path value prefetched with the emissions.  The
+// once-per-clip test reads "a span or a repeat arc"; without a repeat arc every shared output has the SPANS + WIN face's bits
+// (log_add_jump(x, -inf) is x).
+//
+// LAYOUT 1, up to 511 labels: posterior_kernel<NW, DPP, SPANS, WIN[, REP]>, one workgroup per clip, one lane per state, the sums lane-local
 // registers, alpha rows [batch][max_frames][64 NW].  S <= 64: ONE wave64, neighbours by DPP wave shifts, alpha(J) by ds_bpermute, no
 // LDS and no barrier in the loops.  64 < S <= 1024: up to 16 waves, the previous row through a double-buffered float64 row in LDS,
 // one barrier per frame.  Emissions and stored alpha rows are prefetched a block of steps ahead of the dependency chain.  The arc
@@ -77,6 +90,17 @@ struct PostParams : LatticeIn {
     double *acc_ws;    // strip form: [batch][512 R][5]: occupancy, onset and offset sums of label n, span-skip sums of states 2n and 2n+1
     int32_t *csr_ws;   // strip form: [batch][2048 R]: jump arcs by source thread, (r << 16) | target
 };
+// what the REP instantiations take besides (every other kernel takes PostParams itself; present_prob is where `visits` goes)
+struct RepParams : PostParams {
+    const int32_t *repeat_from;  // [batch][repeat_stride], entries 0 .. L_b - 1 of row b are read; null = none
+    int32_t repeat_stride;
+    double repeat_penalty;
+    const int32_t *path;  // [batch][path_stride]: the DP's state per frame; null = not given
+    int32_t path_stride;
+    float *repeat_count;  // [batch][out_stride]
+    float *path_prob;     // [batch][path_stride]; null = not wanted
+};
+constexpr int kRepeatArc = 1 << 16;  // arc-list word of a repeat arc: its target | this bit (it is charged repeat_penalty)
 
 // ---- the cell: every expression of the two sweeps that is more than an exchange of neighbours ------------------------------------
 // alpha_t(k) before its emission: alpha_{t-1} of k, k-1 and (where the labels differ) k-2
@@ -110,8 +134,9 @@ struct Cell {
     double at, be, log_z, am1, am2, jin, out, js;
     float g;
     bool can_skip;
+    double rin;  // REP: the repeat arcs into k
 };
-template <bool HAS>
+template <bool HAS, bool REP = false>
 __device__ __forceinline__ void add_cell(const Cell &c, bool label, bool acc, bool jump_end, int t, int T, int on, int off, int w,
                                          double &s_occ, double &s_on, double &s_off, double &s_pres, double &s_skip) {
     auto entry = [&] {  // first frame of the label (at t = 0 every path through the cell enters here)
@@ -119,6 +144,9 @@ __device__ __forceinline__ void add_cell(const Cell &c, bool label, bool acc, bo
         if (t > 0) {
             double in = log_add2(c.am1, c.can_skip ? c.am2 : -INFINITY);
             if (HAS) in = log_add_jump(in, c.jin);
+            if constexpr (REP) {
+                if (HAS) in = log_add_jump(in, c.rin);  // a return is an entry of its target (and, through js, an exit of its source)
+            }
             en = __expf((float)(in + c.be - c.log_z));
         }
         return en;
@@ -144,10 +172,11 @@ __device__ __forceinline__ void add_cell(const Cell &c, bool label, bool acc, bo
     }
 }
 
-template <int NW, bool DPP, bool SPANS, bool WIN = false>
-__global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
+template <int NW, bool DPP, bool SPANS, bool WIN = false, bool REP = false>
+__global__ __launch_bounds__(NW * 64) void posterior_kernel(std::conditional_t<REP, RepParams, PostParams> p) {
     static_assert(!DPP || NW == 1, "DPP neighbour exchange is single-wave only");
     static_assert(!WIN || SPANS, "frame windows are a face of the optional-span forms");
+    static_assert(!REP || WIN, "repeatable spans are a face of the span + window forms (null pointers: absent)");
     constexpr int NT = NW * 64;
     // steps per prefetch block: 8; 4 in the multi-wave form, which also prefetches two neighbour alpha columns (1024 threads leave 128
     // VGPRs).  A clip with spans in the multi-wave form prefetches alpha(J) and alpha(J-1) as well, and its steps are several times
@@ -160,8 +189,10 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     // span < 2 NT) | the span mass of every state, for adding lanes 2n and 2n+1
     __shared__ int32_t skip_s[SPANS ? NT / 2 + 1 : 1];
     __shared__ int32_t deg_s[SPANS ? NT : 1];
-    __shared__ int32_t tgt_s[SPANS ? 2 * NT : 1];
+    // (repeats: at most 2 more arcs per repeat span, one span per start label: < 3 NT in all; and the span end of every start label)
+    __shared__ int32_t tgt_s[SPANS ? (REP ? 3 : 2) * NT : 1];
     __shared__ double pair_s[SPANS ? NT : 1];
+    __shared__ int32_t rep_s[REP ? NT / 2 : 1];
 
     const int b = blockIdx.x;
     const int k = threadIdx.x;
@@ -185,11 +216,21 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
         if (gam && k < Sg)
             for (int t = t_from; t < p.max_frames; ++t) gam[(int64_t)t * p.gamma_rs + k] = 0.f;
     };
+    [[maybe_unused]] auto zero_path_prob_from = [&](int t_from) {
+        if constexpr (REP) {
+            if (p.path_prob)
+                for (int t = t_from + k; t < p.max_frames; t += NT) p.path_prob[(int64_t)b * p.path_stride + t] = 0.f;
+        }
+    };
     auto fail = [&](int st, double lz) {
         if (row_lane) { occ_g[n] = 0.f; onp_g[n] = 0.f; offp_g[n] = 0.f; }
         if constexpr (SPANS) {
             if (row_lane) pres_g[n] = 0.f;
             if (skip_lane) skp_g[n] = 0.f;
+        }
+        if constexpr (REP) {
+            if (row_lane) p.repeat_count[(int64_t)b * p.out_stride + n] = 0.f;
+            zero_path_prob_from(0);
         }
         zero_gamma_from(0);
         if (k == 0) { p.status[b] = st; p.log_z[b] = lz; }
@@ -224,11 +265,30 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
         J = src.J;
         jm1_ok = src.jm1_ok;
     }
+    // the repeat span that starts at this state's label (odd states only); and, for the arc lists, what repeat_source gives every start
+    // label a (lane a asks for state 2a+1): K, with kRepeatArc set where K-1 is a source as well, or -1
+    [[maybe_unused]] int K = -1;
+    [[maybe_unused]] bool km1_ok = false;
+    if constexpr (REP) {
+        const int32_t *rep_b = p.repeat_from ? p.repeat_from + (int64_t)b * p.repeat_stride : nullptr;
+        if (k < L) {  // (L <= NT / 2)
+            const RepeatSource of_label = repeat_source(rep_b, lab, 2 * k + 1, true, L);
+            rep_s[k] = of_label.K >= 0 ? (of_label.K | (of_label.km1_ok ? kRepeatArc : 0)) : -1;
+        }
+        const RepeatSource src = repeat_source(rep_b, lab, k, valid, L);
+        K = src.K;
+        km1_ok = src.km1_ok;
+    }
     // workgroup-uniform, taken once: a clip without a span runs the loops of the plain kernel
+    // (repeats: neither a span nor a repeat arc; has_span then reads "has a jump of either kind")
     bool has_span = false;
-    if constexpr (SPANS) has_span = __syncthreads_or(J >= 0) != 0;
+    if constexpr (REP) has_span = __syncthreads_or(J >= 0 || K >= 0) != 0;
+    else if constexpr (SPANS) has_span = __syncthreads_or(J >= 0) != 0;
     const double pen = p.penalty;
     const int gather_addr = ((J >= 0 ? J : k) & 63) << 2;  // (single wave: J < S <= 64)
+    [[maybe_unused]] double rpen = 0.0;
+    if constexpr (REP) rpen = p.repeat_penalty;
+    [[maybe_unused]] const int gather_addr_k = ((K >= 0 ? K : k) & 63) << 2;
     // jump arcs by SOURCE: state k is J of the spans that start at position (k+1)/2 when even, J-1 of them when odd
     int deg = 0, first = 0, maxdeg = 0;  // out-degree, offset of this lane's list in tgt_s
     if constexpr (SPANS) {
@@ -239,6 +299,17 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
             if (valid)
                 for (int m = want + 1; m <= L; ++m)
                     if (skip_s[m] == want) deg += two(m) ? 2 : 1;
+            // repeat arcs: state k is K of the repeat spans that END at position (k+1)/2 when even, K-1 of them when odd (where
+            // repeat_source allows that arc); the target is the start label's state 2a+1, to the LEFT of k
+            [[maybe_unused]] auto returns_to = [&](int a) {
+                const int w = rep_s[a];
+                return w >= 0 && (odd ? (w & kRepeatArc) != 0 && (w & (kRepeatArc - 1)) == k + 1 : w == k || w == (k | kRepeatArc));
+            };
+            if constexpr (REP) {
+                if (valid)
+                    for (int a = 0; a < want; ++a)
+                        if (returns_to(a)) ++deg;
+            }
             deg_s[k] = deg;
             __syncthreads();
             for (int i = 0; i < S; ++i) {  // uniform loop, broadcast reads
@@ -252,6 +323,10 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                     tgt_s[i++] = 2 * m;
                     if (two(m)) tgt_s[i++] = 2 * m + 1;
                 }
+                if constexpr (REP) {  // after the skip targets, ascending as well
+                    for (int a = 0; a < want; ++a)
+                        if (returns_to(a)) tgt_s[i++] = (2 * a + 1) | kRepeatArc;
+                }
             }
             maxdeg = deg;
             for (int o = 32; o; o >>= 1) maxdeg = max(maxdeg, __shfl_xor(maxdeg, o));
@@ -263,7 +338,7 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     // this state's frame window; lanes without a state keep the open one (nothing is read past 2 L_b <= win_stride - 1)
     int wlo = 0, whi = 0x7fffffff;
     if constexpr (WIN) {
-        if (valid) {
+        if (valid && (!REP || p.win_lo)) {  // (repeats: a null window pair = every window open)
             wlo = p.win_lo[(int64_t)b * p.win_stride + k];
             whi = p.win_hi[(int64_t)b * p.win_stride + k];
         }
@@ -292,12 +367,17 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                 const int t = t0 + u;
                 if (t < T) {  // workgroup-uniform
                     double a1, a2, aj = NEG, ajm = NEG;
+                    [[maybe_unused]] double ak = NEG, akm = NEG;
                     if (DPP) {
                         a1 = wave_shr1(a, NEG);
                         a2 = wave_shr1(a1, NEG);
                         if (HAS) {
                             aj = wave_gather(a, gather_addr);
                             ajm = wave_gather(a1, gather_addr);  // lane J of the shifted row holds alpha(J-1)
+                            if constexpr (REP) {                   // a source to the right of the target: the same fetch
+                                ak = wave_gather(a, gather_addr_k);
+                                akm = wave_gather(a1, gather_addr_k);
+                            }
                         }
                     } else {
                         double *rb = rowbuf[DPP ? 0 : parity];
@@ -309,10 +389,19 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                             aj = rb[J + 2];
                             ajm = rb[J + 1];
                         }
+                        if constexpr (REP) {
+                            if (HAS && K >= 0) {
+                                ak = rb[K + 2];
+                                akm = rb[K + 1];
+                            }
+                        }
                         parity ^= 1;
                     }
                     double sum = forward_step(a, a1, a2, can_skip);
                     if (HAS && J >= 0) sum = log_add_jump(sum, jump_in(aj, ajm, jm1_ok, pen));
+                    if constexpr (REP) {  // after the J terms
+                        if (HAS && K >= 0) sum = log_add_jump(sum, jump_in(ak, akm, km1_ok, rpen));
+                    }
                     a = valid ? sum + (double)ec[u] : NEG;
                     aw[(int64_t)t * NT] = a;
                 }
@@ -334,16 +423,35 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
     const bool acc_lane = odd && valid && on >= 0 && off > on;
     const int w = p.window;
     double s_occ = 0.0, s_on = 0.0, s_off = 0.0, s_pres = 0.0, s_skip = 0.0;
+    [[maybe_unused]] double s_rep = 0.0;  // lane 2a+1: the mass of the repeat arcs into it
+    [[maybe_unused]] const int32_t *path_b = nullptr;
+    [[maybe_unused]] float *pp_g = nullptr;
+    if constexpr (REP) {
+        if (p.path_prob) {  // (the host: only with a path)
+            path_b = p.path + (int64_t)b * p.path_stride;
+            pp_g = p.path_prob + (int64_t)b * p.path_stride;
+        }
+    }
     double be = NEG;
     auto backward = [&](auto has_c) {
         constexpr bool HAS = decltype(has_c)::value;
         constexpr int U = HAS ? UJ : UP;
-        constexpr bool JPF = HAS && !DPP;  // multi-wave form with spans: alpha_{t-1}(J), alpha_{t-1}(J-1) from the workspace as well
+        // multi-wave form with spans: alpha_{t-1}(J), alpha_{t-1}(J-1) from the workspace as well (not in the 16-wave repeat form: below)
+        constexpr bool JPF = HAS && !DPP && !(REP && NW == 16);
         float ev[U];
         double av[U + 1];                 // alpha_t(k) for t = t0 .. t0 - U (the last one is alpha_{t-1} of the block's last step)
         double av1[DPP ? 1 : U], av2[DPP ? 1 : U];  // multi-wave form: alpha_{t-1}(k-1), alpha_{t-1}(k-2) straight from the workspace
         double avj[JPF ? U : 1], avjm[JPF ? U : 1];
+        // and alpha_{t-1}(K), alpha_{t-1}(K-1) -- except at 16 waves, where the registers do not hold them a block ahead (they feed the
+        // sums alone, not beta: the load at the step's start is off the loop-carried chain)
+        constexpr bool KPF = JPF && REP && NW != 16;
+        [[maybe_unused]] double avk[KPF ? U : 1], avkm[KPF ? U : 1];
+        [[maybe_unused]] int pv[REP ? U : 1];  // the reported path's state at the block's frames (workgroup-uniform)
         auto fetch = [&](int t0) {  // steps t0, t0 - 1, ..., t0 - U + 1
+            if constexpr (REP) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) pv[u] = path_b ? path_b[max(t0 - u, 0)] : -1;
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) ev[u] = emb[(int64_t)max(t0 - u, 0) * p.em_rs];
 #pragma unroll
@@ -358,6 +466,10 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                         avj[u] = J >= 0 ? aw[r - k + J] : NEG;
                         avjm[u] = (J >= 0 && jm1_ok) ? aw[r - k + J - 1] : NEG;
                     }
+                    if constexpr (KPF) {
+                        avk[u] = K >= 0 ? aw[r - k + K] : NEG;
+                        avkm[u] = (K >= 0 && km1_ok) ? aw[r - k + K - 1] : NEG;
+                    }
                 }
             }
         };
@@ -365,6 +477,16 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
         for (int t0 = T - 1; t0 >= 0; t0 -= U) {
             float ec[U];
             double ac[U + 1], ac1[DPP ? 1 : U], ac2[DPP ? 1 : U], acj[JPF ? U : 1], acjm[JPF ? U : 1];
+            [[maybe_unused]] double ack[KPF ? U : 1], ackm[KPF ? U : 1];
+            [[maybe_unused]] int pc[REP ? U : 1];
+            if constexpr (REP) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) pc[u] = pv[u];
+            }
+            if constexpr (KPF) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) { ack[u] = avk[u]; ackm[u] = avkm[u]; }
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) ec[u] = ev[u];
 #pragma unroll
@@ -387,7 +509,7 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                     const double eg = WIN ? (double)gated(ec[u], t) : e;
                     Cell c;
                     c.at = ac[u], c.log_z = log_z, c.can_skip = can_skip;
-                    c.out = NEG, c.js = NEG, c.jin = NEG;
+                    c.out = NEG, c.js = NEG, c.jin = NEG, c.rin = NEG;
                     if (t == T - 1) {
                         be = (k == S - 1 || k == S - 2) ? eg : NEG;
                     } else {
@@ -403,13 +525,20 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                             b2 = rb[k + 4];
                             parity ^= 1;
                         }
-                        if (HAS) {  // fixed order: this lane's targets, ascending
+                        if (HAS) {  // fixed order: this lane's targets, ascending (repeats: skip targets, then repeat targets)
                             const double *rb = rowbuf[DPP ? 0 : parity ^ 1];
                             for (int i = 0; i < maxdeg; ++i) {
                                 const bool act = i < deg;
-                                const int d = act ? tgt_s[first + i] : k;
-                                const double bv = DPP ? wave_gather(be, (d & 63) << 2) : rb[d + 2];
-                                if (act) c.js = log_add_jump(c.js, bv - pen);
+                                if constexpr (REP) {  // every arc carries its own penalty
+                                    const int ent = act ? tgt_s[first + i] : k;
+                                    const int d = ent & (kRepeatArc - 1);
+                                    const double bv = DPP ? wave_gather(be, (d & 63) << 2) : rb[d + 2];
+                                    if (act) c.js = log_add_jump(c.js, bv - ((ent & kRepeatArc) ? rpen : pen));
+                                } else {
+                                    const int d = act ? tgt_s[first + i] : k;
+                                    const double bv = DPP ? wave_gather(be, (d & 63) << 2) : rb[d + 2];
+                                    if (act) c.js = log_add_jump(c.js, bv - pen);
+                                }
                             }
                         }
                         const BetaStep st = backward_step<HAS>(be, b1, b2, can_skip_from, c.js, eg, valid);
@@ -427,16 +556,41 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
                         if (DPP) {
                             aj = wave_gather(ac[u + 1], gather_addr);
                             ajm = wave_gather(c.am1, gather_addr);
-                        } else {
+                        } else if (JPF) {
                             aj = acj[JPF ? u : 0];
                             ajm = acjm[JPF ? u : 0];
+                        } else {  // the 16-wave repeat form: read at the step's start (they feed the sums alone, not beta)
+                            const double *prow = aw + (int64_t)max(t - 1, 0) * NT - k;
+                            aj = J >= 0 ? prow[J] : NEG;
+                            ajm = (J >= 0 && jm1_ok) ? prow[J - 1] : NEG;
                         }
                         if (J >= 0 && t > 0) c.jin = jump_in(aj, ajm, jm1_ok, pen);
+                        if constexpr (REP) {
+                            double ak, akm;
+                            if (DPP) {
+                                ak = wave_gather(ac[u + 1], gather_addr_k);
+                                akm = wave_gather(c.am1, gather_addr_k);
+                            } else if (KPF) {
+                                ak = ack[KPF ? u : 0];
+                                akm = ackm[KPF ? u : 0];
+                            } else {
+                                const double *prow = aw + (int64_t)max(t - 1, 0) * NT - k;
+                                ak = K >= 0 ? prow[K] : NEG;
+                                akm = (K >= 0 && km1_ok) ? prow[K - 1] : NEG;
+                            }
+                            if (K >= 0 && t > 0) c.rin = jump_in(ak, akm, km1_ok, rpen);
+                        }
                     }
                     c.be = be;
                     c.g = cell_gamma(c.at, be, e, log_z);
                     if (gam && k < Sg) gam[(int64_t)t * p.gamma_rs + k] = c.g;
-                    add_cell<HAS>(c, odd && valid, acc_lane, J >= 0, t, T, on, off, w, s_occ, s_on, s_off, s_pres, s_skip);
+                    if constexpr (REP) {
+                        // gamma at the reported path: stored by the lane whose state the path names (a value that names none: 0, by lane 0)
+                        const bool named = pc[u] >= 0 && pc[u] < S;
+                        if (pp_g && k == (named ? pc[u] : 0)) pp_g[t] = named ? c.g : 0.f;
+                        if (HAS && K >= 0 && t > 0) s_rep += (double)__expf((float)(c.rin + be - log_z));
+                    }
+                    add_cell<HAS, REP>(c, odd && valid, acc_lane, J >= 0, t, T, on, off, w, s_occ, s_on, s_off, s_pres, s_skip);
                 }
             }
         }
@@ -458,6 +612,10 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(PostParams p) {
         occ_g[n] = acc_lane ? (float)(s_occ / (double)(off - on)) : 0.f;
         onp_g[n] = acc_lane ? (float)s_on : 0.f;
         offp_g[n] = acc_lane ? (float)s_off : 0.f;
+    }
+    if constexpr (REP) {
+        if (row_lane) p.repeat_count[(int64_t)b * p.out_stride + n] = (has_span && valid) ? (float)s_rep : 0.f;
+        zero_path_prob_from(T);
     }
     zero_gamma_from(T);
     if (k == 0) { p.status[b] = LA_OK; p.log_z[b] = log_z; }
@@ -942,8 +1100,8 @@ bool plan_posterior(int batch, int max_frames, int max_labels, int label_limit, 
     return true;
 }
 
-template <auto kern>
-int launch(const char *timer, int threads, const PostParams &p, const PostPlan &pl, int batch, hipStream_t stream) {
+template <auto kern, class Params = PostParams>
+int launch(const char *timer, int threads, const Params &p, const PostPlan &pl, int batch, hipStream_t stream) {
     static la::DeviceOnce attr_once;  // once per instantiation, to the planner's budget (pl.lds_bytes never exceeds it)
     if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
         LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
@@ -974,7 +1132,24 @@ int launch_face(const char *timer, const PostParams &p, const PostPlan &pl, int 
     return LA_EUNSUPPORTED;
 }
 
-// What the four entries (and their workspace queries) differ in.  la_alignment_posteriors_lattice takes its face from the pointers that
+// the repeat face sits on top of the span + window one whatever is given: null pointers are "absent" inside the kernel.  Lane per state only
+int launch_repeats(const char *timer, const RepParams &p, const PostPlan &pl, int batch, hipStream_t stream) {
+    // static LDS of the widest form: two rows, fin, skip_s, deg_s, tgt_s (3 NT words with the repeat arcs), pair_s, rep_s
+    static_assert((2 * (1024 + 4) + 2 + 1024) * sizeof(double) + (1024 / 2 + 1 + 1024 + 3 * 1024 + 1024 / 2) * sizeof(int32_t) <= 64 * 1024 &&
+                      64 * 1024 <= kLdsBudget, "the arc lists with the repeat arcs fit the workgroup's LDS");
+    switch (pl.R ? 0 : pl.nw) {
+        case 1:
+            if (la::opts().viterbi_dpp) return launch<posterior_kernel<1, true, true, true, true>, RepParams>(timer, 64, p, pl, batch, stream);
+            return launch<posterior_kernel<1, false, true, true, true>, RepParams>(timer, 64, p, pl, batch, stream);
+        case 2: return launch<posterior_kernel<2, false, true, true, true>, RepParams>(timer, 128, p, pl, batch, stream);
+        case 4: return launch<posterior_kernel<4, false, true, true, true>, RepParams>(timer, 256, p, pl, batch, stream);
+        case 8: return launch<posterior_kernel<8, false, true, true, true>, RepParams>(timer, 512, p, pl, batch, stream);
+        case 16: return launch<posterior_kernel<16, false, true, true, true>, RepParams>(timer, 1024, p, pl, batch, stream);
+    }
+    return LA_EUNSUPPORTED;
+}
+
+// What the five entries (and their workspace queries) differ in.  la_alignment_posteriors_lattice takes its face from the pointers that
 // are present, always writes the span outputs (so skip_stride is their row pitch whatever the face) and reports its label limit before
 // the strides; up to 511 labels its call then IS the matching entry's sweep, under that entry's timer.
 struct Entry {
@@ -985,15 +1160,16 @@ struct Entry {
     bool limit_first;     // the label limit is reported before the stride checks (the other entries: after them)
     const char *over_entry, *over_query;   // the label-limit message of the entry and of its workspace query
 };
-enum EntryId { kPlain, kSpans, kWindows, kLattice };   // the first three are (int)Face of the entry's fixed face; kLattice: decided per call
+enum EntryId { kPlain, kSpans, kWindows, kLattice, kRepeats };   // the first three are (int)Face of the entry's fixed face; kLattice, kRepeats: decided per call
 static_assert(kPlain == (int)Face::Plain && kSpans == (int)Face::Spans && kWindows == (int)Face::Windows, "kEntries rows follow Face");
 constexpr char kOverLanes[] = "%s: max_labels %d exceeds 511", kOverStrip[] = "%s: max_labels %d exceeds 4095 (8192 lattice states per workgroup)";
 constexpr char kOverLanesQuery[] = "%s: max_labels %d exceeds 511 (one lane per lattice state, 1024 states per workgroup)";
-const Entry kEntries[4] = {
+const Entry kEntries[5] = {
     {face_names(Sweep::Posteriors, Face::Plain), 511, 8, false, false, kOverLanes, kOverLanesQuery},
     {face_names(Sweep::Posteriors, Face::Spans), 511, 8, true, false, kOverLanes, kOverLanesQuery},
     {face_names(Sweep::Posteriors, Face::Windows), 511, 8, true, false, kOverLanes, kOverLanesQuery},
-    {{"alignment_posteriors_lattice", "alignment_posteriors_lattice", "posterior_lattice"}, 4095, 16, true, true, kOverStrip, kOverStrip}};
+    {{"alignment_posteriors_lattice", "alignment_posteriors_lattice", "posterior_lattice"}, 4095, 16, true, true, kOverStrip, kOverStrip},
+    {{"alignment_posteriors_repeats", "alignment_posteriors_repeats", "posterior_repeats"}, 511, 8, true, true, kOverLanes, kOverLanesQuery}};
 
 int query_workspace(EntryId id, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     const Entry &e = kEntries[id];
@@ -1007,14 +1183,15 @@ int query_workspace(EntryId id, int32_t batch, int32_t max_frames, int32_t max_l
     return LA_OK;
 }
 
-// the four la_alignment_posteriors* entry points: p holds the caller's arguments, null / zero standing in for what the entry does not
-// have (Windows: skip_from may be null, skip_stride stays the row pitch of span_skip_prob); the workspace fields are set here
-int run_posteriors(EntryId id, PostParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+// the five la_alignment_posteriors* entry points: p holds the caller's arguments, null / zero standing in for what the entry does not
+// have (Windows: skip_from may be null, skip_stride stays the row pitch of span_skip_prob); the workspace fields are set here.  The
+// RepParams part is read for kRepeats only
+int run_posteriors(EntryId id, RepParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
     const Entry &e = kEntries[id];
     const char *who = e.names.entry;
     if (batch == 0) return LA_OK;
-    Face face = id == kLattice ? Face::Plain : (Face)id;
-    if (id == kLattice) {
+    Face face = (id == kLattice || id == kRepeats) ? Face::Plain : (Face)id;
+    if (id == kLattice || id == kRepeats) {
         LA_CHECK_ARG((p.win_lo == nullptr) == (p.win_hi == nullptr), "%s: win_lo and win_hi go together (both null: no windows)", who);
         face = p.win_lo ? Face::Windows : p.skip_from ? Face::Spans : Face::Plain;
     }
@@ -1025,6 +1202,11 @@ int run_posteriors(EntryId id, PostParams p, int32_t batch, void *workspace, siz
     LA_CHECK_ARG(p.window >= 0, "%s: negative boundary_window", who);
     // (la_alignment_posteriors has no penalty: 0.  The lattice entry checks the one it was given whatever the face)
     LA_CHECK_ARG(p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
+    if (id == kRepeats) {
+        LA_CHECK_ARG(p.repeat_count, "%s: null output pointer", who);
+        LA_CHECK_ARG(p.repeat_penalty >= 0.0, "%s: repeat_penalty must be >= 0 (and not NaN)", who);
+        LA_CHECK_ARG(!p.path_prob || p.path, "%s: path_prob needs the path it is asked about", who);
+    }
     PostPlan pl;
     const bool planned = plan_posterior(batch, p.max_frames, p.max_labels, e.label_limit, &pl);
     if (planned || !e.limit_first) {
@@ -1032,6 +1214,10 @@ int run_posteriors(EntryId id, PostParams p, int32_t batch, void *workspace, siz
                      "%s: strides smaller than max_labels", who);
         LA_CHECK_ARG(!p.gamma || (p.gamma_rs >= 2 * (int64_t)p.max_labels + 1 && (batch == 1 || p.gamma_bs >= (int64_t)p.max_frames * p.gamma_rs)),
                      "%s: gamma strides smaller than [max_frames][2 max_labels + 1]", who);
+        if (id == kRepeats) {
+            LA_CHECK_ARG(!p.repeat_from || p.repeat_stride >= p.max_labels, "%s: repeat_stride smaller than max_labels", who);
+            LA_CHECK_ARG(!(p.path || p.path_prob) || p.path_stride >= p.max_frames, "%s: path_stride smaller than max_frames", who);
+        }
     }
     if (!planned) {
         la::set_error(e.over_entry, who, p.max_labels);
@@ -1046,6 +1232,7 @@ int run_posteriors(EntryId id, PostParams p, int32_t batch, void *workspace, siz
         p.acc_ws = reinterpret_cast<double *>(ws + pl.alpha_bytes);
         p.csr_ws = reinterpret_cast<int32_t *>(ws + pl.alpha_bytes + pl.acc_bytes);
     }
+    if (id == kRepeats) return launch_repeats(e.names.timer, p, pl, batch, stream);
     const char *timer = pl.R ? e.names.timer : kEntries[(int)face].names.timer;
     int st = LA_EUNSUPPORTED;
     switch (face) {
@@ -1059,6 +1246,12 @@ int run_posteriors(EntryId id, PostParams p, int32_t batch, void *workspace, siz
         LA_LAUNCH_CHECK();
     }
     return st;
+}
+
+int run_posteriors(EntryId id, const PostParams &pp, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    RepParams p{};
+    static_cast<PostParams &>(p) = pp;
+    return run_posteriors(id, p, batch, workspace, workspace_bytes, stream);
 }
 
 // the caller's arguments of an entry point by name; null / zero stands in for what the entry does not have
@@ -1096,6 +1289,31 @@ extern "C" int la_alignment_posteriors_windows_workspace_bytes(int32_t batch, in
 
 extern "C" int la_alignment_posteriors_lattice_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     return query_workspace(kLattice, batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_alignment_posteriors_repeats_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace(kRepeats, batch, max_frames, max_labels, bytes);
+}
+
+extern "C" int la_alignment_posteriors_repeats(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
+                                               int32_t labels_stride, const int32_t *n_labels, const int32_t *n_frames, int32_t batch,
+                                               int32_t max_frames, int32_t max_labels, const int32_t *onset, const int32_t *offset,
+                                               int32_t out_stride, int32_t boundary_window, const int32_t *skip_from, int32_t skip_stride,
+                                               double skip_penalty, const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                               const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty,
+                                               const int32_t *path, int32_t path_stride, float *occupancy, float *onset_prob,
+                                               float *offset_prob, float *visits, float *span_skip_prob, float *repeat_count,
+                                               float *path_prob, double *log_z, int32_t *status, float *gamma_out,
+                                               int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
+                                               size_t workspace_bytes, void *stream_) {
+    RepParams p{};
+    static_cast<PostParams &>(p) =
+        shared_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset, offset,
+                      out_stride, boundary_window, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride, occupancy, onset_prob,
+                      offset_prob, visits, span_skip_prob, log_z, status, gamma_out, gamma_batch_stride, gamma_row_stride);
+    p.repeat_from = repeat_from, p.repeat_stride = repeat_stride, p.repeat_penalty = repeat_penalty;
+    p.path = path, p.path_stride = path_stride, p.repeat_count = repeat_count, p.path_prob = path_prob;
+    return run_posteriors(kRepeats, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int la_alignment_posteriors(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,

@@ -206,17 +206,27 @@ def _sheet_lines_out(res, lines: Sequence[str], per_line=()):
 def _line_occurrences(segments, lines: Sequence[str]) -> List[list]:
     """One clip's visits (char_index, onset_s, offset_s) in time order -> per line the list of its occurrences, each [[onset, offset, char],
     ...]: a new occurrence of a line begins where a visit does not continue the line's last one (its character index does not go up)."""
+    out: List[list] = [[] for _ in lines]
+    for (n, on, off), (i, k, j) in zip(segments, _occurrence_of_visits(segments, lines)):
+        if k == len(out[i]):
+            out[i].append([])
+        out[i][k].append([on, off, lines[i][j]])
+    return out
+
+
+def _occurrence_of_visits(segments, lines: Sequence[str]) -> List[tuple]:
+    """Per visit of _line_occurrences' input: (its line, which occurrence of that line it belongs to, its character's index in the line)."""
     start_of, line_of = [], []
     for i, line in enumerate(lines):
         start_of.append(len(line_of))
         line_of += [i] * len(line)
-    out: List[list] = [[] for _ in lines]
-    last = None                                  # (line, character index) of the previous visit
-    for n, on, off in segments:
+    count = [0] * len(lines)
+    out, last = [], None                         # last: (line, character index) of the previous visit
+    for n, _, _ in segments:
         i = line_of[n]
         if last is None or last[0] != i or n <= last[1]:
-            out[i].append([])
-        out[i][-1].append([on, off, lines[i][n - start_of[i]]])
+            count[i] += 1
+        out.append((i, count[i] - 1, n - start_of[i]))
         last = (i, n)
     return out
 
@@ -237,7 +247,7 @@ def _sheet_confidence(res, scores, lines: Sequence[str]):
 
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
-                       repeat_penalty: float = 0.0):
+                       repeat_penalty: float = 0.0, with_visit_confidence: bool = False):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
@@ -249,14 +259,37 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     repeatable (one flag per line; None: the result as above): lines with repeatable[i] may be sung again right after they were sung (a
     chorus marked "x2"; AlignModel.align(repeat_spans=...), repeat_penalty >= 0 per return).  Each line's entry is then the LIST of its
     occurrences in time order, each [[onset, offset, char], ...] -- empty if the alignment left the line out.  Not with with_confidence
-    (ValueError)."""
+    (ValueError).
+    with_visit_confidence (with repeatable; at most 511 characters): -> (occurrences, conf), conf[i] = {"visits": the expected number of
+    times line i was sung (AlignModel.align(return_repeat_confidence=True)'s `visits` of its first character: an expected count, it can
+    exceed 1), "repeat_count": the expected number of returns of a repeatable line (None for the others), "occurrence_occupancy": one
+    number per listed occurrence, the mean visit_occupancy of its characters}."""
     lines = list(lines)
     ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
+    if with_visit_confidence and repeatable is None:
+        raise ValueError("align_record_lines: with_visit_confidence goes with repeatable (with_confidence is the keyword without it)")
     if repeatable is not None:
         from .utils.alignment import repeats_from_lines
         if with_confidence:
             raise ValueError("align_record_lines: repeatable does not go with with_confidence (no posteriors on the lattice with repeatable spans)")
         repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
+        if with_visit_confidence:
+            repeat_spans = [(a, e) for a, e in enumerate(repeat_from) if e >= 0]
+            with torch.no_grad():
+                _, segments, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                                  repeat_spans=[repeat_spans], repeat_penalty=repeat_penalty, return_segments=True,
+                                                  return_repeat_confidence=True)
+            occurrences = _line_occurrences(segments[0], lines)
+            per = [[[] for _ in occ] for occ in occurrences]
+            for v, (i, k, _) in zip(scores[0]["visit_occupancy"], _occurrence_of_visits(segments[0], lines)):
+                per[i][k].append(v)
+            conf, pos = [], 0
+            for i, line in enumerate(lines):
+                conf.append({"visits": float(scores[0]["visits"][pos]),
+                             "repeat_count": scores[0]["repeat_count"].get((pos, pos + len(ids[i]))) if repeatable[i] else None,
+                             "occurrence_occupancy": [float(np.mean(v)) for v in per[i]]})
+                pos += len(ids[i])
+            return occurrences, conf
         with torch.no_grad():
             _, segments = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                       repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty,

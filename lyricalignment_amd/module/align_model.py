@@ -338,7 +338,7 @@ class AlignModel(torch.nn.Module):
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
               skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
-              repeat_penalty: float = 0.0, return_segments: bool = False):
+              repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -387,17 +387,35 @@ class AlignModel(torch.nn.Module):
         (a chorus printed once and sung twice; ops.viterbi_repeats_batch, repeat_penalty >= 0 per return).  The result keeps its shape: the
         FIRST visit per character, None for a character never visited.  With optional_spans, char_windows / onset_anchors, per_clip and
         the long form, up to 4095 labels; with return_frames the DP's four tensors and path [B, T] (the lattice state per frame).  Not
-        with any confidence keyword (ValueError).  None or all-empty: the call as it was.
+        with any of the four older confidence keywords (ValueError; return_repeat_confidence is the keyword).  None or all-empty: the call
+        as it was.
         return_segments (addition): -> (seconds, segments), segments[b] = the time-ordered list of (char_index, onset_s, offset_s) of EVERY
-        visit, with or without repeat_spans."""
-        from ..utils.alignment import (LatticeResult, _formatted, _labels_to_device, _repeat_rows, _segments_from_path, _skip_from_of_spans,
-                                       _windows_of, run_lattice)
+        visit, with or without repeat_spans.
+        return_repeat_confidence (addition): the confidence of the lattice with repeat_spans (ops.alignment_posteriors_repeats on the DP's
+        onset / offset / path), with or without optional_spans, onset_anchors / char_windows, per_clip, the long form and return_segments:
+        -> (seconds, scores), or (seconds, segments, scores) with return_segments.  A path may visit a character more than once, so some
+        numbers are EXPECTED COUNTS that can exceed 1 (nothing is clamped).  scores[b] holds "occupancy", "onset_prob", "offset_prob" [L]
+        (about the reported, first visit), "path_log_posterior", "visits" [L] (the expected number of times the character is sung),
+        "repeat_count" {(a, e): the expected number of returns} per span of repeat_spans[b], "span_skip_prob" (one value per span of
+        optional_spans[b]), "visit_occupancy" (one number per entry of segments[b]: the mean posterior of the reported state over that
+        visit's frames) and, where windows are given, "window_log_prob" (from a second sweep without them).  With no repeat span anywhere
+        the numbers it shares with return_sheet_confidence are that keyword's exactly.  Up to 511 labels (NotImplementedError before
+        anything is launched).  With return_frames the DP's four tensors, (occupancy, onset_prob, offset_prob, log_z, visits,
+        span_skip_prob [, log_z_free with windows]) and path.  Not together with another confidence keyword (ValueError)."""
+        from ..utils.alignment import (POSTERIOR_MAX_LABELS, LatticeResult, _formatted, _formatted_repeat, _label_lists, _labels_to_device,
+                                       _repeat_from_of_spans, _repeat_rows, _segments_from_path, _skip_from_of_spans, _windows_of, run_lattice)
         if return_anchored_confidence and (return_confidence or return_span_confidence):
             raise ValueError("align: return_anchored_confidence does not go with return_confidence / return_span_confidence (it returns "
                              "their numbers on the windowed lattice)")
         if return_sheet_confidence and (return_confidence or return_span_confidence or return_anchored_confidence):
             raise ValueError("align: return_sheet_confidence does not go with return_confidence / return_span_confidence / "
                              "return_anchored_confidence (it returns their numbers at any size up to 4095 labels)")
+        if return_repeat_confidence:
+            if return_confidence or return_span_confidence or return_anchored_confidence or return_sheet_confidence:
+                raise ValueError("align: return_repeat_confidence does not go with another confidence keyword")
+            widest = max((len(l) for l in _label_lists(labels, len(labels))), default=0)
+            if widest > POSTERIOR_MAX_LABELS:
+                raise NotImplementedError(f"align: {widest} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -421,7 +439,10 @@ class AlignModel(torch.nn.Module):
                              "keyword: return_span_confidence=True gives them)")
         confidence = ("sheet" if return_sheet_confidence else "anchored" if return_anchored_confidence else "span" if return_span_confidence
                       else "plain" if return_confidence else None)
-        repeat_from = _repeat_rows("align", repeat_spans, return_segments, lab_lists, confidence is not None)
+        if return_repeat_confidence:
+            confidence, repeat_from = "repeat", _repeat_from_of_spans(repeat_spans, lab_lists)
+        else:
+            repeat_from = _repeat_rows("align", repeat_spans, return_segments, lab_lists, confidence is not None)
         # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
         need_em = confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
         head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
@@ -436,6 +457,9 @@ class AlignModel(torch.nn.Module):
             r = LatticeResult(*head)
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path)
             return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,))
+        if return_repeat_confidence:
+            seconds, segments, scores = _formatted_repeat(r, lab_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
+            return (seconds, segments, scores) if return_segments else (seconds, scores)
         seconds = _formatted(r, lab_lists, hop_size_second, optional_spans)
         return (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
 

@@ -264,6 +264,59 @@ def alignment_posteriors_lattice(em: torch.Tensor, labels: torch.Tensor, n_label
                        skip_from, skip_penalty, None if win_lo is None else (win_lo, win_hi))
 
 
+def alignment_posteriors_repeats(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                                 onset: torch.Tensor, offset: torch.Tensor, skip_from: Optional[torch.Tensor] = None,
+                                 skip_penalty: float = 0.0, win_lo: Optional[torch.Tensor] = None, win_hi: Optional[torch.Tensor] = None,
+                                 repeat_from: Optional[torch.Tensor] = None, repeat_penalty: float = 0.0,
+                                 path: Optional[torch.Tensor] = None, boundary_window: int = 2, want_gamma: bool = False):
+    """la_alignment_posteriors_repeats: forward-backward on the lattice of viterbi_repeats_batch, for up to 511 labels
+    (NotImplementedError above, before a launch); onset / offset / path = its outputs for the same lattice.  A path may visit a label
+    more than once, so visits, onset_prob, offset_prob, repeat_count and (under a repeat span) span_skip_prob are EXPECTED COUNTS that
+    can exceed 1; nothing is clamped (include/lyricalign.h).  repeat_from None or all -1: the numbers of alignment_posteriors_lattice
+    bit for bit, visits = its present_prob, repeat_count 0.
+    -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, visits [B,Lmax] f32, span_skip_prob [B,Lmax+1] f32,
+    repeat_count [B,Lmax] f32, path_prob [B,T] f32 (gamma at the given path; None without a path) [, gamma [B,T,2*Lmax+1] f32]."""
+    who = "alignment_posteriors_repeats"
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError(f"{who}: win_lo and win_hi go together")
+    windows = None if win_lo is None else (win_lo, win_hi)
+    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, "lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty,
+                                                                    windows, (onset, offset), boundary_window)
+    if repeat_from is not None:
+        _dev(repeat_from, "repeat_from", torch.int32)
+        if repeat_from.dim() != 2 or repeat_from.shape[0] != B or repeat_from.shape[1] < Lmax or repeat_from.stride(1) != 1:
+            raise ValueError(f"{who}: repeat_from [B, >= Lmax] with unit inner stride expected")
+    if path is not None:
+        _dev(path, "path", torch.int32)
+        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < T or path.stride(1) != 1:
+            raise ValueError(f"{who}: path [B, >= T] with unit inner stride expected")
+    repeat_penalty = float(repeat_penalty)
+    if not repeat_penalty >= 0.0:
+        raise ValueError(f"{who}: repeat_penalty must be >= 0")
+    if Lmax > 511:
+        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds 511 (the repeat lattice's posteriors are one lane per state)")
+    onset = onset.contiguous(); offset = offset.contiguous()
+    dev = em.device
+    occupancy, onset_prob, offset_prob, visits, repeat_count = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(5))
+    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
+    skip_stride = skip_from.stride(0) if skip_from is not None else Lmax + 1   # the row pitch of skip_from AND of span_skip_prob
+    span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
+    path_prob = torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None
+    ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
+    check(lib().la_alignment_posteriors_repeats(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, int(boundary_window), *_face_args("lattice", skip_from, skip_stride, skip_penalty, windows),
+        ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty,
+        ptr(path), path.stride(0) if path is not None else 0,
+        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(visits), ptr(span_skip_prob), ptr(repeat_count), ptr(path_prob),
+        ptr(log_z), ptr(status), ptr(gamma), gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
+        ptr(ws), need, stream_ptr()), who)
+    res = (occupancy, onset_prob, offset_prob, log_z, status, visits, span_skip_prob, repeat_count, path_prob)
+    return res + (gamma,) if want_gamma else res
+
+
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:
     """logits [B,T,V] f32 device -> compact emissions [B,T,Lmax+1] f32."""
     _dev(logits, "logits", torch.float32); _dev(labels, "labels", torch.int32); _dev(n_labels, "n_labels", torch.int32)

@@ -123,22 +123,26 @@ def _repeat_from_of_spans(repeat_spans, label_lists: List[List[int]]):
     return rows if any_span else None
 
 
+def _visits_of_row(row):
+    """One clip's lattice state per frame -> the time-ordered list of (char_index, first frame, last frame + 1) of every visit: the maximal
+    runs of frames in one odd lattice state."""
+    visits, t = [], 0
+    while t < len(row):
+        u = t
+        while u + 1 < len(row) and row[u + 1] == row[t]:
+            u += 1
+        if row[t] >= 0 and row[t] % 2 == 1:
+            visits.append((int(row[t]) // 2, t, u + 1))
+        t = u + 1
+    return visits
+
+
 def _segments_from_path(path, frame_counts: Sequence[int], hop_size_second: float):
     """path [B, T] (ops.viterbi_repeats_batch) -> per utterance the time-ordered list of (char_index, onset_s, offset_s) of every visit: the
     maximal runs of frames in one odd lattice state (a repeated line has one visit per time it was sung)."""
     rows = path.cpu().numpy()
-    out = []
-    for b, T in enumerate(frame_counts):
-        row, visits, t = rows[b, : int(T)], [], 0
-        while t < len(row):
-            u = t
-            while u + 1 < len(row) and row[u + 1] == row[t]:
-                u += 1
-            if row[t] >= 0 and row[t] % 2 == 1:
-                visits.append((int(row[t]) // 2, float(t) * hop_size_second, float(u + 1) * hop_size_second))
-            t = u + 1
-        out.append(visits)
-    return out
+    return [[(n, float(t) * hop_size_second, float(u) * hop_size_second) for n, t, u in _visits_of_row(rows[b, : int(T)])]
+            for b, T in enumerate(frame_counts)]
 
 
 def _frame_bound(seconds: float, hop: float, n_frames: int, up: bool) -> int:
@@ -277,12 +281,18 @@ class LatticeResult(NamedTuple):
 
 
 class RepeatLatticeResult(LatticeResult):
-    """LatticeResult of the lattice with repeatable spans: the same eleven tuple fields (no posteriors exist there, so seven are None) and,
-    behind them, `path` [B, T] int32 -- the lattice state per frame, ops.viterbi_repeats_batch's fifth output."""
+    """LatticeResult of the lattice with repeatable spans: the same eleven tuple fields (seven are None unless confidence="repeat" was
+    asked for; present_prob then holds `visits`, an expected count) and, behind them as attributes, `path` [B, T] int32 -- the lattice
+    state per frame, ops.viterbi_repeats_batch's fifth output -- and with confidence="repeat" `visits` [B, Lmax] (= present_prob),
+    `repeat_count` [B, Lmax] and `path_prob` [B, T] (ops.alignment_posteriors_repeats)."""
+    visits = None
+    repeat_count = None
+    path_prob = None
 
-    def __new__(cls, onset, offset, score, status, path):
-        r = super().__new__(cls, onset, offset, score, status)
+    def __new__(cls, onset, offset, score, status, path, posteriors=(), repeat_count=None, path_prob=None):
+        r = super().__new__(cls, onset, offset, score, status, *posteriors)
         r.path = path
+        r.visits, r.repeat_count, r.path_prob = r.present_prob, repeat_count, path_prob
         return r
 
 
@@ -304,18 +314,35 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     More than 511 labels (up to 4095): the DP with spans or windows is ops.viterbi_lattice_batch; the three older kinds of confidence
     stop at 511 and raise NotImplementedError before anything is launched ("sheet" is the kind for whole songs).
     repeat_from (host rows of _repeat_from_of_spans, or None) / repeat_penalty: the lattice with repeatable spans, at any size up to
-    4095 labels, with or without skip_from and windows -- ops.viterbi_repeats_batch; the result's `path` holds the state per frame.  No
-    kind of confidence exists on that lattice: ValueError before anything is launched."""
-    if confidence not in (None, "plain", "span", "anchored", "sheet"):
+    4095 labels, with or without skip_from and windows -- ops.viterbi_repeats_batch; the result's `path` holds the state per frame.  The
+    four older kinds of confidence do not exist on that lattice: ValueError before anything is launched.
+    "repeat": the posteriors of that lattice (ops.alignment_posteriors_repeats on the DP's onset / offset / path; repeat_from None = no
+    repeat span), up to 511 labels (NotImplementedError before anything is launched).  The eleven fields are filled as for "sheet" with
+    `visits` (an expected count) in present_prob's place -- log_z_free from a second sweep without windows where windows were given,
+    None otherwise -- and repeat_count / path_prob are attributes of the result."""
+    if confidence not in (None, "plain", "span", "anchored", "sheet", "repeat"):
         raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
-    if repeat_from is not None:
-        if confidence is not None:
-            raise ValueError("run_lattice: no posteriors on the lattice with repeatable spans (repeat_from goes with confidence=None)")
+    if repeat_from is not None or confidence == "repeat":
+        if confidence not in (None, "repeat"):
+            raise ValueError("run_lattice: on the lattice with repeatable spans the posteriors are confidence=\"repeat\" "
+                             "(repeat_from does not go with the four older kinds)")
+        if confidence == "repeat" and lab.shape[1] > POSTERIOR_MAX_LABELS:
+            raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posteriors "
+                                      "on the lattice with repeatable spans")
         dev = em.device
         win = (None, None) if windows is None else (windows[0].to(dev), windows[1].to(dev))
-        out = ops.viterbi_repeats_batch(em, lab, n_lab, nf, None if skip_from is None else skip_from.to(dev), skip_penalty, *win,
-                                        repeat_from.to(dev), repeat_penalty)
-        return RepeatLatticeResult(*out)
+        skip_dev = None if skip_from is None else skip_from.to(dev)
+        rep_dev = None if repeat_from is None else repeat_from.to(dev)
+        out = ops.viterbi_repeats_batch(em, lab, n_lab, nf, skip_dev, skip_penalty, *win, rep_dev, repeat_penalty)
+        if confidence is None:
+            return RepeatLatticeResult(*out)
+        post = ops.alignment_posteriors_repeats(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, *win, rep_dev, repeat_penalty,
+                                                out[4], boundary_window=boundary_window)
+        log_z_free = None
+        if windows is not None:
+            log_z_free = ops.alignment_posteriors_repeats(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, None, None, rep_dev,
+                                                          repeat_penalty, boundary_window=boundary_window)[3]
+        return RepeatLatticeResult(*out, posteriors=(*post[:4], *post[5:7], log_z_free), repeat_count=post[7], path_prob=post[8])
     wide = lab.shape[1] > POSTERIOR_MAX_LABELS
     if wide and confidence not in (None, "sheet"):
         raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posterior sweeps "
@@ -371,6 +398,28 @@ def _formatted(r: LatticeResult, label_lists, hop_size_second, optional_spans):
                                             r.span_skip_prob, spans, r.log_z_free)
 
 
+def _formatted_repeat(r: RepeatLatticeResult, label_lists, frame_counts, hop_size_second, optional_spans, repeat_spans):
+    """What the public functions return for a run_lattice(confidence="repeat") result -> seconds, segments, scores.  scores[b] holds
+    "occupancy", "onset_prob", "offset_prob" [L] (about the reported, FIRST visit), "path_log_posterior", "visits" [L] (the expected number
+    of visits: it can exceed 1), "repeat_count" {(a, e): expected number of returns} for the spans of repeat_spans[b], "span_skip_prob"
+    (one value per span of optional_spans[b]; an expected count under a repeat span), "visit_occupancy" (one number per entry of
+    segments[b]: the mean posterior of the reported state over that visit's frames) and, where windows were given, "window_log_prob"."""
+    seconds = _seconds_from_frames(r.onset, r.offset, r.status, label_lists, hop_size_second, skipped_as_none=True)
+    spans = optional_spans if optional_spans is not None else [[] for _ in label_lists]
+    scores = _scores_from_posteriors(r.occupancy, r.onset_prob, r.offset_prob, r.log_z, r.score, label_lists, r.visits, r.span_skip_prob,
+                                     spans, r.log_z_free)
+    rows, pp, rc = r.path.cpu().numpy(), r.path_prob.cpu().numpy(), r.repeat_count.cpu().numpy()
+    segments = []
+    for b, T in enumerate(frame_counts):
+        visits = _visits_of_row(rows[b, : int(T)])
+        segments.append([(n, float(t) * hop_size_second, float(u) * hop_size_second) for n, t, u in visits])
+        d = scores[b]
+        d["visits"] = d.pop("sung_prob")
+        d["repeat_count"] = {(int(a), int(e)): float(rc[b, int(a)]) for a, e in ((repeat_spans[b] or ()) if repeat_spans is not None else ())}
+        d["visit_occupancy"] = [float(pp[b, t:u].astype(np.float64).mean()) for _, t, u in visits]
+    return seconds, segments, scores
+
+
 def _device_of(prediction) -> torch.device:
     _lib.require_gpu()
     if torch.is_tensor(prediction) and prediction.is_cuda:
@@ -392,7 +441,7 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, anchored=False, sheet=False, repeat_spans=None, repeat_penalty=0.0,
-             return_segments=False):
+             return_segments=False, repeat_scored=False):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -409,15 +458,24 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     # (additions) optional spans and per-state frame windows; None / all-empty keywords take the reference's lattice unchanged
     skip_from = _skip_from_of_spans(optional_spans, lists)
     windows = _windows_of(char_windows, onset_anchors, lists, counts, hop_size_second)
-    if windows is not None and boundary_window is not None and not (anchored or sheet):
+    if windows is not None and boundary_window is not None and not (anchored or sheet or repeat_scored):
         raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
                          "(perform_viterbi(_ctc)_anchored_scored give them)")
     confidence = "sheet" if sheet else "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
-    repeat_from = _repeat_rows("perform_viterbi", repeat_spans, return_segments, lists, confidence is not None)
+    if repeat_scored:
+        confidence, repeat_from = "repeat", _repeat_from_of_spans(repeat_spans, lists)
+        if lab.shape[1] > POSTERIOR_MAX_LABELS:
+            raise NotImplementedError(f"perform_viterbi_repeat_scored: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of "
+                                      "the posteriors on the lattice with repeatable spans")
+    else:
+        repeat_from = _repeat_rows("perform_viterbi", repeat_spans, return_segments, lists, confidence is not None)
     em = ops.emissions_from_logits(pred, lab, n_lab, variant)
     nf = torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
     r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, repeat_from=repeat_from,
                     repeat_penalty=repeat_penalty)
+    if repeat_scored:
+        seconds, segments, scores = _formatted_repeat(r, lists, counts, hop_size_second, optional_spans, repeat_spans)
+        return (seconds, segments, scores) if return_segments else (seconds, scores)
     seconds = _formatted(r, lists, hop_size_second, optional_spans)
     return (seconds, _segments_from_path(r.path, counts, hop_size_second)) if return_segments else seconds
 
@@ -437,8 +495,9 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     repeat_spans (addition): repeat_spans[b] = list of (a, e) pairs -- having sung label e-1 of utterance b the path may return to label
     a (a chorus printed once and sung twice; la_viterbi_repeats_batch, repeat_penalty >= 0 per return, the only control of how often).
     The result keeps its shape: the FIRST visit per character, None for a character never visited.  ValueError for a < 0, a >= e, e > L
-    or two spans with one start.  With optional_spans, char_windows / onset_anchors and n_frames, up to 4095 labels; the _scored
-    functions and anchored_alignment_loss raise ValueError with it.  None or all-empty: the call as it was.
+    or two spans with one start.  With optional_spans, char_windows / onset_anchors and n_frames, up to 4095 labels; the older _scored
+    functions and anchored_alignment_loss raise ValueError with it (perform_viterbi(_ctc)_repeat_scored: its confidence, up to 511
+    labels).  None or all-empty: the call as it was.
     return_segments (addition): -> (predicted_onset_offset, segments), segments[b] = the time-ordered list of (char_index, onset_s,
     offset_s) of EVERY visit, with or without repeat_spans."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
@@ -462,7 +521,8 @@ def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_wi
     "sung_prob": [L] (probability that the character is on the path at all) and "span_skip_prob": one value per span, in the order given
     (probability that the span was left out) -- la_alignment_posteriors_spans.  Without a span the dicts are as before, without these keys.
     char_windows / onset_anchors: ValueError unless None or all-empty (perform_viterbi_anchored_scored is the function for them).
-    repeat_spans: ValueError unless None or all-empty, here and in every other _scored function (no posteriors on that lattice)."""
+    repeat_spans: ValueError unless None or all-empty, here and in the anchored / sheet _scored functions
+    (perform_viterbi(_ctc)_repeat_scored give the posteriors of that lattice)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     repeat_spans=repeat_spans)
@@ -521,6 +581,39 @@ def perform_viterbi_ctc_sheet_scored(prediction, labels, hop_size_second=0.02, b
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     sheet=True,
                     repeat_spans=repeat_spans)
+
+
+def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                  skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
+                                  return_segments=False):
+    """perform_viterbi with repeat_spans plus the confidence of that lattice (addition): -> (predicted_onset_offset, scores), or
+    (predicted_onset_offset, segments, scores) with return_segments.  The DP is la_viterbi_repeats_batch, the sweep
+    la_alignment_posteriors_repeats, with or without optional_spans, char_windows / onset_anchors and n_frames; up to 511 labels
+    (NotImplementedError before anything is launched).  A path may visit a character more than once on this lattice, so some numbers are
+    EXPECTED COUNTS, can exceed 1 and are not clamped.  scores[b] holds
+      "occupancy", "onset_prob", "offset_prob" [L]: about the reported (first) visit; onset_prob / offset_prob count the visits that begin /
+          end within boundary_window frames of the reported boundary (probabilities unless two visits can begin that close together);
+      "path_log_posterior": final_score - log_z <= 0;
+      "visits" [L]: the expected number of times the character is sung (sung_prob where no repeat span exists);
+      "repeat_count": {(a, e): the expected number of returns of that span} for the spans of repeat_spans[b];
+      "span_skip_prob": one value per span of optional_spans[b] (an expected count where a repeat span covers the optional span);
+      "visit_occupancy": one number per entry of segments[b], the mean posterior of the reported state over that visit's frames -- the
+          occupancy of every visit, not only the first;
+      "window_log_prob" (only where char_windows / onset_anchors are given): log_z(windowed) - log_z(same lattice, no windows) <= 0, from
+          a second sweep without them.
+    With no repeat span anywhere the numbers it shares with perform_viterbi_sheet_scored are that function's exactly."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True)
+
+
+def perform_viterbi_ctc_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                      skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
+                                      return_segments=False):
+    """perform_viterbi_ctc plus the confidence of the lattice with repeatable spans: see perform_viterbi_repeat_scored."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
