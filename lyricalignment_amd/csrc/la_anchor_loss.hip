@@ -19,8 +19,8 @@
 //   prep        one workgroup per clip: the frame counts as an array, skip_from compacted to [B][Lmax+1], the -1 onset / offset rows the
 //               sweep wants, and per label position the chain "next position with the same class" + "first position of its class"
 //   emissions   one 256-thread workgroup per (b, t) row, the row held in registers between the maximum and the sum (ONE read): the
-//               reduction order of emissions_from_logits_kernel (la_elementwise.hip), so the same bits; keeps lse_{1..V-1} (as the row's maximum
-//               and the log of the sum, apart) and x[t][V]
+//               reduction order and the emission formulas of emissions_from_logits_kernel (la_elementwise.hip) -- both call la_row.h's one
+//               definition -- so the same bits; keeps lse_{1..V-1} (as the row's maximum and the log of the sum, apart) and x[t][V]
 //   sweep       la_alignment_posteriors_windows (la_posterior.hip, through the C ABI) with gamma written to the workspace; log_z and status
 //   gradient    one 1024-thread workgroup per (b, t) row: g_sil / g_voiced by a fixed-order reduction of the gamma row, then every lane
 //               streams its 16-byte pieces of the row from the load to the store through registers (a 21129-wide row is 21 floats per
@@ -29,21 +29,11 @@
 //               time, and nothing of a clip's rows depends on its batch mates
 //   finish      one thread: nll per clip and the scalar loss, clips summed in ascending order
 #include "la_lattice.h"
+#include "la_row.h"
 
 namespace {
 
 using la::lattice::waves_for_labels;
-
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------------
 struct Layout {
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(256) void anchor_emissions_kernel(const float *logi
     const int row = blockIdx.x;
     const int b = row / frames, t = row % frames;
     const float *x = logits + (int64_t)b * bs + (int64_t)t * rs;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
 
     float v[CAP > 0 ? CAP : 1];
     float m = -INFINITY;
@@ -135,10 +125,7 @@ __global__ __launch_bounds__(256) void anchor_emissions_kernel(const float *logi
     } else {
         for (int c = 1 + tid; c < V; c += 256) m = fmaxf(m, x[c]);
     }
-    m = wave_max_f(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    m = la::block4_max(m, red);
     float s = 0.f;
     if (CAP > 0) {
 #pragma unroll
@@ -146,29 +133,23 @@ __global__ __launch_bounds__(256) void anchor_emissions_kernel(const float *logi
     } else {
         for (int c = 1 + tid; c < V; c += 256) s += expf(x[c] - m);
     }
-    s = wave_sum_f(s);
-    if (lane == 0) red[4 + wave] = s;
-    __syncthreads();
-    s = (red[4] + red[5]) + (red[6] + red[7]);
-    const float logsum = logf(s);
+    const float logsum = logf(la::block4_sum(s, red + 4));
 
     const int L = min(n_labels[b], max_labels);
     float *e = em + (int64_t)b * em_bs + (int64_t)t * em_rs;
     const int32_t *lab = labels + (int64_t)b * labels_stride;
     const float xl = x[V];
-    const float sil = 1.0f / (1.0f + expf(-xl));
-    const float log_sil = logf(sil);
-    const float log_voiced = logf(1.0f - sil);
+    const la::SilenceTerms sil = la::silence_terms(xl);
     if (tid == 0) {
-        e[0] = fmaxf(log_sil, -1000.0f);
+        e[0] = la::silence_emission(sil.log_sil);
         max_out[row] = m;
         logsum_out[row] = logsum;
         xs_out[row] = xl;
     }
     for (int n = tid; n < L; n += 256) {
         const int c = lab[n];
-        float val = -1000.0f;
-        if (c >= 1 && c < V) val = fmaxf(((x[c] - m) - logsum) + log_voiced, -1000.0f);
+        float val = la::kEmissionFloor;
+        if (c >= 1 && c < V) val = la::voiced_emission(x[c], m, logsum, sil.log_voiced);
         e[1 + n] = val;
     }
 }
@@ -231,8 +212,8 @@ __global__ __launch_bounds__(kGradThreads) void anchor_grad_kernel(GradParams p)
             gs = g;
         }
     }
-    gs = wave_sum_f(gs);
-    gv = wave_sum_f(gv);
+    gs = la::wave_sum(gs);
+    gv = la::wave_sum(gv);
     if (lane == 0) { red[0][wave] = gs; red[1][wave] = gv; }
     __syncthreads();
     float g_sil = 0.f, g_voiced = 0.f;

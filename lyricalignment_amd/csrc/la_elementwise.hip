@@ -1,22 +1,13 @@
 // la_elementwise.hip -- HBM-bound row kernels: emission prep from materialised
 // logits, LayerNorm, casts, mel -> channels-last rows.  One wave64 (or one
 // 256-thread workgroup) per row, 16-byte accesses wherever the row pitch allows.
-#include "la_common.h"
+// The reduction order of a row and the emission formulas live in la_row.h.
+#include "la_row.h"
 
 using la::bf16_t;
+using la::wave_sum;
 
 namespace {
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---------------------------------------------------------------------------
 // emission prep from [B][T][V] f32 logits  (utils/alignment.py:123-134, :14-20)
@@ -32,43 +23,33 @@ __global__ __launch_bounds__(256) void emissions_from_logits_kernel(
     const float *x = logits + (int64_t)b * bs + (int64_t)t * rs;
     const int c0 = variant == LA_VARIANT_CTC ? 1 : 0;
     const int c1 = variant == LA_VARIANT_CTC ? vocab - 1 : vocab;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
 
     float m = -INFINITY;
     for (int c = c0 + tid; c < c1; c += 256) m = fmaxf(m, x[c]);
-    m = wave_max(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    m = la::block4_max(m, red);
     float s = 0.f;
     for (int c = c0 + tid; c < c1; c += 256) s += expf(x[c] - m);
-    s = wave_sum(s);
-    if (lane == 0) red[4 + wave] = s;
-    __syncthreads();
-    s = (red[4] + red[5]) + (red[6] + red[7]);
-    const float logsum = logf(s);
+    const float logsum = logf(la::block4_sum(s, red + 4));
 
     const int L = min(n_labels[b], max_labels);
     float *e = em + (int64_t)b * em_bs + (int64_t)t * em_rs;
     const int32_t *lab = labels + (int64_t)b * labels_stride;
     if (variant == LA_VARIANT_CTC) {
-        const float xl = x[vocab - 1];
-        const float sil = 1.0f / (1.0f + expf(-xl));       // F.sigmoid (:125)
-        const float log_sil = logf(sil);                    // (:128)
-        const float log_voiced = logf(1.0f - sil);          // naive form, may be -inf (:126,:129)
-        if (tid == 0) e[0] = fmaxf(log_sil, -1000.0f);      // (:134)
+        const la::SilenceTerms sil = la::silence_terms(x[vocab - 1]);
+        if (tid == 0) e[0] = la::silence_emission(sil.log_sil);
         for (int n = tid; n < L; n += 256) {
             const int c = lab[n];
-            float v = -1000.0f;
-            if (c >= 1 && c < vocab - 1) v = fmaxf(((x[c] - m) - logsum) + log_voiced, -1000.0f);  // (:131-132)
+            float v = la::kEmissionFloor;
+            if (c >= 1 && c < vocab - 1) v = la::voiced_emission(x[c], m, logsum, sil.log_voiced);
             e[1 + n] = v;
         }
     } else {
-        if (tid == 0) e[0] = fmaxf((x[0] - m) - logsum, -1000.0f);  // (:16,:20)
+        if (tid == 0) e[0] = la::plain_emission(x[0], m, logsum);
         for (int n = tid; n < L; n += 256) {
             const int c = lab[n];
-            float v = -1000.0f;
-            if (c >= 1 && c < vocab) v = fmaxf((x[c] - m) - logsum, -1000.0f);  // (:18)
+            float v = la::kEmissionFloor;
+            if (c >= 1 && c < vocab) v = la::plain_emission(x[c], m, logsum);
             e[1 + n] = v;
         }
     }
@@ -498,11 +479,8 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float *x, int64_t 
     const float m = vals[(int64_t)blockIdx.x * k];
     float s = 0.f;
     for (int c = threadIdx.x; c < cols; c += 256) s += expf(r[c] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) lse[blockIdx.x] = m + logf((red[0] + red[1]) + (red[2] + red[3]));
+    s = la::block4_sum(s, red);
+    if (threadIdx.x == 0) lse[blockIdx.x] = m + logf(s);
 }
 }  // namespace
 

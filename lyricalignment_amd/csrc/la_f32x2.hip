@@ -23,6 +23,7 @@
 #include "la_gemm_core.h"
 #include "la_gemm_epilogue.h"
 #include "la_gemm_params.h"
+#include "la_row.h"
 #include "la_x2.h"
 
 using namespace la::gemm;
@@ -37,17 +38,9 @@ using la::x2::split;
 __device__ __forceinline__ float x2_act(float v, int act) { return act == 1 ? la::gelu_erf(v) : v; }
 __device__ __forceinline__ float4 act4(const float4 &v, int act) { return make_float4(x2_act(v.x, act), x2_act(v.y, act), x2_act(v.z, act), x2_act(v.w, act)); }
 
-// ---- pieces the two row kernels (one wave per row) share ----
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+// ---- pieces the two row kernels (one wave per row) share (the wave butterflies: la_row.h) ----
+using la::wave_max;
+using la::wave_sum;
 __device__ __forceinline__ float max_abs4(const float4 &v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 // four consecutive values, scaled, into element quad i of the row's two planes
 __device__ __forceinline__ void store_quad(const float4 &v, float s, unsigned short *hi, unsigned short *lo, int i) {

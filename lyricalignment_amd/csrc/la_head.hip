@@ -8,11 +8,14 @@
 //  3. lse GEMM:      the full [B*T] x V product, but the epilogue only reduces each 64-column
 //                    accumulator strip to (max, sum exp(x - max)) per row        (this file)
 //  4. merge:         per row, combine the 2*ceil(V/128) partials into the log-normaliser and apply
-//                    the reference's emission formulas to raw                     (this file)
+//                    the reference's emission formulas to raw                     (this file; the formulas and the wave
+//                    butterflies are la_row.h's, shared with la_emissions_from_logits and the anchored loss)
+// The three lse kernels are a main loop plus strip_lse; route_lse picks the form and its geometry, launch_lse launches it.
 // Algorithmic traffic: reads act + W_fc once, writes 8 B per row per 64 columns; 2*M*V*K flops.
 #include "la_gemm_core.h"
 #include "la_gemm_params.h"
 #include "la_gemm_pp.h"
+#include "la_row.h"
 
 using la::bf16_t;
 using namespace la::gemm;
@@ -35,34 +38,27 @@ struct LseParams {
     const float *sa = nullptr, *sw = nullptr;
 };
 
-template <typename T, typename C>
-__global__ __launch_bounds__(C::THREADS, 2) void fc_lse_kernel(LseParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
-    const TileCoord tc = tile_coord(tile, p.tiles_m, p.tiles_n, p.group);
-    const int tn = tc.tn;
-    const int m0 = tc.tm * C::TM, n0 = tn * BN;
-    f32x4 acc[4][4];
-    mainloop<T, C>(reinterpret_cast<const T *>(p.A), p.lda, p.M, reinterpret_cast<const T *>(p.W), p.K, p.N, p.K, m0, n0, lds, acc);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+// The strip reduction every normaliser kernel ends in: MB blocks of 16 rows x one 64-column strip of MFMA accumulators (lane = row r
+// of a block, columns ni * 16 + q * 4 + j) -> one (max, sum exp(x - max)) partial per row.  value(mi, ni, j) is the masked logit of
+// an accumulator element (-inf outside [lo, hi]); row0 the wave's first row, strip its index among the row's partials.
+template <int MB, typename Value>
+__device__ __forceinline__ void strip_lse(const LseParams &p, int row0, int strip, Value value) {
+    const int lane = threadIdx.x & 63;
     const int r = lane & 15, q = lane >> 4;
+    float2 *out = p.partials + strip;   // once: re-formed in every row block it is a 64-bit vector add each (profiles/head_rows_refactor.txt)
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
+    for (int mi = 0; mi < MB; ++mi) {
         float v[16];
         float mx = -INFINITY;
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + ni * 16 + q * 4 + j;
-                const bool ok = n >= p.lo && n <= p.hi;
-                const float x = ok ? acc[mi][ni][j] + p.bias[n < p.N ? n : p.N - 1] : -INFINITY;
+                const float x = value(mi, ni, j);
                 v[ni * 4 + j] = x;
                 mx = fmaxf(mx, x);
             }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 16));   // (across the four quads of a row: part of a wave, not la::wave_max)
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float sum = 0.f;
         if (mx > -INFINITY) {
@@ -73,9 +69,43 @@ __global__ __launch_bounds__(C::THREADS, 2) void fc_lse_kernel(LseParams p) {
         }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
-        const int m = m0 + wm * 64 + mi * 16 + r;
-        if (q == 0 && m < p.M) p.partials[(int64_t)m * p.nparts + tn * 2 + wn] = make_float2(mx, sum);
+        const int m = row0 + mi * 16 + r;
+        if (q == 0 && m < p.M) out[(int64_t)m * p.nparts] = make_float2(mx, sum);
     }
+}
+
+// bias and column mask of a lane's 16 columns of the strip that starts at column n_strip
+struct StripCols {
+    float b[4][4];
+    bool ok[4][4];
+};
+__device__ __forceinline__ StripCols strip_cols(const LseParams &p, int n_strip) {
+    const int q = (threadIdx.x & 63) >> 4;
+    StripCols c;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = n_strip + ni * 16 + q * 4 + j;
+            c.ok[ni][j] = n >= p.lo && n <= p.hi;
+            c.b[ni][j] = p.bias[n < p.N ? n : p.N - 1];
+        }
+    return c;
+}
+
+template <typename T, typename C>
+__global__ __launch_bounds__(C::THREADS, 2) void fc_lse_kernel(LseParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+    const TileCoord tc = tile_coord(tile, p.tiles_m, p.tiles_n, p.group);
+    const int m0 = tc.tm * C::TM, n0 = tc.tn * BN;
+    f32x4 acc[4][4];
+    mainloop<T, C>(reinterpret_cast<const T *>(p.A), p.lda, p.M, reinterpret_cast<const T *>(p.W), p.K, p.N, p.K, m0, n0, lds, acc);
+
+    const int wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const StripCols c = strip_cols(p, n0 + wn * 64);
+    strip_lse<4>(p, m0 + wm * 64, tc.tn * 2 + wn, [&](int mi, int ni, int j) { return c.ok[ni][j] ? acc[mi][ni][j] + c.b[ni][j] : -INFINITY; });
 }
 
 // The same reduction on the 256x256 ping-pong main loop (bf16, large row counts): a wave owns 128 rows x one 64-column strip.
@@ -86,8 +116,7 @@ __global__ __launch_bounds__(PP::THREADS, 2) void fc_lse_pp_kernel(LseParams p) 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const TileCoord tc = tile_coord(tile, p.tiles_m, p.tiles_n, p.group);
-    const int tn = tc.tn;
-    const int m0 = tc.tm * PP::TM, n0 = tn * PP::TN;
+    const int m0 = tc.tm * PP::TM, n0 = tc.tn * PP::TN;
     f32x4 acc[8][4];
 #ifdef LA_TILE_STAMPS
     unsigned long long stamp_unused = 0;
@@ -97,43 +126,10 @@ __global__ __launch_bounds__(PP::THREADS, 2) void fc_lse_pp_kernel(LseParams p) 
 #endif
     else mainloop_pp<T16>(reinterpret_cast<const T16 *>(p.A), p.lda, p.M, reinterpret_cast<const T16 *>(p.W), p.K, p.N, p.K, m0, n0, lds, acc);
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6;
     const int wr = wave >> 2, wc = wave & 3;
-    const int r = lane & 15, q = lane >> 4;
-    float b4[4][4];
-    bool ok4[4][4];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wc * 64 + ni * 16 + q * 4 + j;
-            ok4[ni][j] = n >= p.lo && n <= p.hi;
-            b4[ni][j] = p.bias[n < p.N ? n : p.N - 1];
-        }
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-        float v[16];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float x = ok4[ni][j] ? acc[mi][ni][j] + b4[ni][j] : -INFINITY;
-                v[ni * 4 + j] = x;
-                mx = fmaxf(mx, x);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-        if (mx > -INFINITY) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f((v[i] - mx) * kLog2e);  // (as in fc_lse_kernel)
-        }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        const int m = m0 + wr * 128 + mi * 16 + r;
-        if (q == 0 && m < p.M) p.partials[(int64_t)m * p.nparts + tn * 4 + wc] = make_float2(mx, sum);
-    }
+    const StripCols c = strip_cols(p, n0 + wc * 64);
+    strip_lse<8>(p, m0 + wr * 128, tc.tn * 4 + wc, [&](int mi, int ni, int j) { return c.ok[ni][j] ? acc[mi][ni][j] + c.b[ni][j] : -INFINITY; });
 }
 
 // The same reduction for FLOAT32 rows on the f16 matrix pipe at float32 accuracy (la_f32x2.hip): act and W_fc as half planes [.][2][K] with
@@ -143,54 +139,24 @@ __global__ __launch_bounds__(PP::THREADS, 2) void fc_lse_x2_kernel(LseParams p) 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const TileCoord tc = tile_coord(tile, p.tiles_m, p.tiles_n, p.group);
-    const int tn = tc.tn;
-    const int m0 = tc.tm * PP::TM, n0 = tn * PP::TN;
+    const int m0 = tc.tm * PP::TM, n0 = tc.tn * PP::TN;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = wave >> 2, wc = wave & 3;
-    const int r = lane & 15, q = lane >> 4;
     f32x4 acc[8][4];
     mainloop_duo_seg_asm<la::f16_t>(reinterpret_cast<const la::f16_t *>(p.A), 2 * (int64_t)p.K, p.M, reinterpret_cast<const la::f16_t *>(p.W),
                                     2 * (int64_t)p.K, p.N, p.K, p.K, p.K, m0, n0, lds, acc);
     // (per-column / per-row operands are loaded AFTER the main loop: 56 more live registers across it spill the hand-placed loop's fragments)
-    float b4[4][4], sw4[4][4];
-    bool ok4[4][4];
+    const StripCols c = strip_cols(p, n0 + wc * 64);
+    float sw4[4][4];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wc * 64 + ni * 16 + q * 4 + j;
-            const int nc = n < p.N ? n : p.N - 1;
-            ok4[ni][j] = n >= p.lo && n <= p.hi;
-            b4[ni][j] = p.bias[nc];
-            sw4[ni][j] = p.sw[nc];
-        }
+        for (int j = 0; j < 4; ++j) sw4[ni][j] = p.sw[min(n0 + wc * 64 + ni * 16 + (lane >> 4) * 4 + j, p.N - 1)];
     float sa8[8];
 #pragma unroll
-    for (int mi = 0; mi < 8; ++mi) sa8[mi] = p.sa[min(m0 + wr * 128 + mi * 16 + r, p.M - 1)];
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-        float v[16];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float x = ok4[ni][j] ? acc[mi][ni][j] * (sa8[mi] * sw4[ni][j]) + b4[ni][j] : -INFINITY;
-                v[ni * 4 + j] = x;
-                mx = fmaxf(mx, x);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-        if (mx > -INFINITY) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f((v[i] - mx) * kLog2e);  // (as in fc_lse_kernel)
-        }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        const int m = m0 + wr * 128 + mi * 16 + r;
-        if (q == 0 && m < p.M) p.partials[(int64_t)m * p.nparts + tn * 4 + wc] = make_float2(mx, sum);
-    }
+    for (int mi = 0; mi < 8; ++mi) sa8[mi] = p.sa[min(m0 + wr * 128 + mi * 16 + (lane & 15), p.M - 1)];
+    strip_lse<8>(p, m0 + wr * 128, tc.tn * 4 + wc,
+                 [&](int mi, int ni, int j) { return c.ok[ni][j] ? acc[mi][ni][j] * (sa8[mi] * sw4[ni][j]) + c.b[ni][j] : -INFINITY; });
 }
 
 // Wg[b][s][:] = W_fc[col(b, s)][:], bg[b][s] = b_fc[col(b, s)];  col = silence column for s = 0, labels[b][s-1] otherwise
@@ -226,16 +192,13 @@ __global__ __launch_bounds__(256) void merge_emissions_kernel(const float2 *part
     const float2 *pr = partials + (int64_t)row * nparts;
     float mx = -INFINITY;
     for (int i = lane; i < nparts; i += 64) mx = fmaxf(mx, pr[i].x);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = la::wave_max(mx);
     float sum = 0.f;
     for (int i = lane; i < nparts; i += 64) {
         const float2 v = pr[i];
         if (v.y > 0.f) sum += v.y * __builtin_amdgcn_exp2f((v.x - mx) * kLog2e);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float logsum = logf(sum);
+    const float logsum = logf(la::wave_sum(sum));
 
     const int b = row / frames, t = row % frames;
     const int L = min(n_labels[b], max_labels);
@@ -244,32 +207,30 @@ __global__ __launch_bounds__(256) void merge_emissions_kernel(const float2 *part
     const int32_t *lab = labels + (int64_t)b * labels_stride;
     const int hi = variant == LA_VARIANT_CTC ? vocab - 2 : vocab - 1;
     if (variant == LA_VARIANT_CTC) {
-        const float sil = 1.0f / (1.0f + expf(-x[0]));
-        const float log_sil = logf(sil), log_voiced = logf(1.0f - sil);  // naive forms on purpose (:125-129)
-        if (lane == 0) e[0] = fmaxf(log_sil, -1000.0f);
+        const la::SilenceTerms sil = la::silence_terms(x[0]);
+        if (lane == 0) e[0] = la::silence_emission(sil.log_sil);
         for (int n = lane; n < L; n += 64) {
             const int c = lab[n];
-            e[1 + n] = (c >= 1 && c <= hi) ? fmaxf(((x[1 + n] - mx) - logsum) + log_voiced, -1000.0f) : -1000.0f;
+            e[1 + n] = (c >= 1 && c <= hi) ? la::voiced_emission(x[1 + n], mx, logsum, sil.log_voiced) : la::kEmissionFloor;
         }
     } else {
-        if (lane == 0) e[0] = fmaxf((x[0] - mx) - logsum, -1000.0f);
+        if (lane == 0) e[0] = la::plain_emission(x[0], mx, logsum);
         for (int n = lane; n < L; n += 64) {
             const int c = lab[n];
-            e[1 + n] = (c >= 1 && c <= hi) ? fmaxf((x[1 + n] - mx) - logsum, -1000.0f) : -1000.0f;
+            e[1 + n] = (c >= 1 && c <= hi) ? la::plain_emission(x[1 + n], mx, logsum) : la::kEmissionFloor;
         }
     }
 }
 
 struct HeadPlan {
     size_t off_wg, off_bg, off_raw, off_part, off_planes = 0, off_inv = 0, total;
-    int tiles_n, nparts;
+    int nparts;
 };
 
 HeadPlan plan_head(int batch, int frames, int in_dim, int vocab, int max_labels, int es, bool x2 = false) {
     HeadPlan pl;
     const int64_t rows = (int64_t)batch * frames, S = max_labels + 1;
-    pl.tiles_n = la::cdiv(vocab, BN);
-    pl.nparts = 4 * la::cdiv(vocab, PP::TN);     // 64-column strips, rounded up to whole 256-column tiles (>= 2 * tiles_n)
+    pl.nparts = 4 * la::cdiv(vocab, PP::TN);     // 64-column strips, rounded up to whole 256-column tiles (>= 2 per 128-column tile)
     size_t o = 0;
     pl.off_wg = o;   o += la::round_up((int64_t)batch * S * in_dim * es, 256);
     pl.off_bg = o;   o += la::round_up((int64_t)batch * S * 4, 256);
@@ -285,6 +246,48 @@ HeadPlan plan_head(int batch, int frames, int in_dim, int vocab, int max_labels,
 
 // Is the float32 normaliser product in the f16x2 kernel's domain?  (No N term: the vocabulary is wide; DESIGN.md "Product routing".)
 bool fc_x2_ok(int rows, int in_dim, int vocab) { return x2_k_ok(in_dim) && fills_chip(rows, vocab); }
+
+// ---- the normaliser product's form and launch geometry, decided in ONE place (DESIGN.md "Product routing") ----
+typedef Cfg<2, 2> Small;   // 128 rows x 128 columns
+typedef Cfg<4, 3> Big;     // 256 rows x 128 columns
+enum LseForm { LSE_X2, LSE_PP_DUO, LSE_PP, LSE_ROWS256, LSE_ROWS128 };
+struct LseRoute {
+    LseForm form;
+    int tiles_m, tiles_n, group, nparts;
+};
+
+// x2: the caller gave the planes of W_fc and fc_x2_ok holds.  plan_nparts: the strips per row the workspace was planned for.
+LseRoute route_lse(int dtype, int rows, int in_dim, int vocab, int64_t ld_act, bool x2, int plan_nparts) {
+    const int es = dtype == LA_F32 ? 4 : 2, tiles128 = la::cdiv(vocab, BN);
+    const int force_tile = la::opts().gemm_tile;
+    const bool pp_ok = dtype != LA_F32 && !force_tile && in_dim % 64 == 0 && in_dim >= 128 && (ld_act * 2) % 16 == 0 && fills_chip(rows, vocab);
+    if (x2 || pp_ok) {
+        // 256 x 256 tiles, four strips each.  The strips of the last (partial) 256-column tile that no 128-column tile would have produced
+        // must still hold neutral partials: every strip is written by these kernels, masked columns give (-inf, 0)
+        const bool duo = in_dim % 128 == 0 && in_dim >= 256 && la::opts().gemm_loop != 99;    // (99: the ping-pong loop everywhere)
+        const int group = x2 ? pick_group(3 * in_dim, 2, tiles128) : pick_group(in_dim, es, tiles128);
+        return {x2 ? LSE_X2 : duo ? LSE_PP_DUO : LSE_PP, la::cdiv(rows, PP::TM), la::cdiv(vocab, PP::TN), std::max(1, group / 2), plan_nparts};
+    }
+    // the 128-column kernels write two strips per tile
+    const bool big = dtype == LA_BF16 && rows >= 4096 && force_tile == 256;
+    return {big ? LSE_ROWS256 : LSE_ROWS128, la::cdiv(rows, big ? Big::TM : Small::TM), tiles128, pick_group(in_dim, es, tiles128), 2 * tiles128};
+}
+
+// One normaliser launch: the kernel's dynamic-LDS ceiling raised once per DEVICE (la_common.h DeviceOnce), the family timer, the launch
+template <void (*KERN)(LseParams), typename CF>
+int launch_lse(const LseParams &lp, const char *family, hipStream_t stream) {
+    static la::DeviceOnce attr_once;
+    if (attr_once.pending()) {
+        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS));
+        attr_once.mark();
+    }
+    {
+        la::TimerScope ts(family, stream);
+        hipLaunchKernelGGL(KERN, dim3(lp.tiles_m * lp.tiles_n), dim3(CF::THREADS), CF::LDS, stream, lp);
+    }
+    LA_LAUNCH_CHECK();
+    return LA_OK;
+}
 
 }  // namespace
 
@@ -339,85 +342,35 @@ static int fc_emissions_impl(int32_t dtype, const void *act, int64_t ld_act, con
                           S, (int64_t)frames * S, bg, S, nullptr, 0, 0, LA_EPI_BIAS | LA_EPI_OUT_F32, stream);
     if (rc != LA_OK) return rc;
     // 3. row normaliser partials over the full vocabulary
-    LseParams lp{rows, vocab, in_dim, act, ld_act, w_fc, b_fc, partials, pl.nparts,
+    const LseRoute rt = route_lse(dtype, rows, in_dim, vocab, ld_act, x2, pl.nparts);
+    LseParams lp{rows, vocab, in_dim, act, ld_act, w_fc, b_fc, partials, rt.nparts,
                  variant == LA_VARIANT_CTC ? 1 : 0, variant == LA_VARIANT_CTC ? vocab - 2 : vocab - 1,
-                 0, pl.tiles_n, pick_group(in_dim, es, pl.tiles_n)};
-    {
-        typedef Cfg<2, 2> Small;
-        typedef Cfg<4, 3> Big;
-        static bool attr_bf16 = false, attr_bf16_big = false, attr_f32 = false, attr_pp = false;
-        const int force_tile = la::opts().gemm_tile;
-        const bool pp_ok = dtype != LA_F32 && !force_tile && in_dim % 64 == 0 && in_dim >= 128 && (ld_act * 2) % 16 == 0 && fills_chip(rows, vocab);
-        if (!pp_ok && !x2) lp.nparts = 2 * pl.tiles_n;      // the 128-column kernels write two strips per tile
-        if (x2) {
-            static la::DeviceOnce attr_x2;
-            if (attr_x2.pending()) {
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_x2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS));
-                attr_x2.mark();
-            }
-            void *planes = ws + pl.off_planes;
-            float *inv = reinterpret_cast<float *>(ws + pl.off_inv);
-            rc = la_split_f16x2(static_cast<const float *>(act), ld_act, rows, in_dim, planes, in_dim, inv, stream_);
-            if (rc != LA_OK) return rc;
-            lp.A = planes; lp.W = w_x2; lp.sa = inv; lp.sw = w_x2s;
-            lp.tiles_m = la::cdiv(rows, PP::TM);
-            lp.tiles_n = la::cdiv(vocab, PP::TN);
-            lp.group = std::max(1, pick_group(3 * in_dim, 2, la::cdiv(vocab, BN)) / 2);
-            la::TimerScope ts("fc_lse_f32", stream);
-            hipLaunchKernelGGL(fc_lse_x2_kernel, dim3(lp.tiles_m * lp.tiles_n), dim3(PP::THREADS), PP::LDS, stream, lp);
-        } else if (pp_ok) {
-            // the strips of the last (partial) 256-column tile that no 128-column tile would have produced must still hold
-            // neutral partials: every strip is written by this kernel, masked columns give (-inf, 0)
-            if (!attr_pp) {
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_pp_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS));
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_pp_kernel<la::f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS));
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_pp_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS));
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_pp_kernel<la::f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS));
-                attr_pp = true;
-            }
-            lp.tiles_m = la::cdiv(rows, PP::TM);
-            lp.tiles_n = la::cdiv(vocab, PP::TN);
-            lp.group = std::max(1, pick_group(in_dim, es, la::cdiv(vocab, BN)) / 2);
-            la::TimerScope ts("fc_lse_bf16", stream);
-            const bool duo = in_dim % 128 == 0 && in_dim >= 256 && la::opts().gemm_loop != 99;    // (99: the ping-pong loop everywhere)
-            if (duo) {
-                if (dtype == LA_F16) hipLaunchKernelGGL((fc_lse_pp_kernel<la::f16_t, true>), dim3(lp.tiles_m * lp.tiles_n), dim3(PP::THREADS), PP::LDS, stream, lp);
-                else hipLaunchKernelGGL((fc_lse_pp_kernel<bf16_t, true>), dim3(lp.tiles_m * lp.tiles_n), dim3(PP::THREADS), PP::LDS, stream, lp);
-            } else if (dtype == LA_F16) hipLaunchKernelGGL(fc_lse_pp_kernel<la::f16_t>, dim3(lp.tiles_m * lp.tiles_n), dim3(PP::THREADS), PP::LDS, stream, lp);
-            else hipLaunchKernelGGL(fc_lse_pp_kernel<bf16_t>, dim3(lp.tiles_m * lp.tiles_n), dim3(PP::THREADS), PP::LDS, stream, lp);
-        } else if (dtype == LA_BF16 && rows >= 4096 && force_tile == 256) {
-            if (!attr_bf16_big) {
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_kernel<bf16_t, Big>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Big::LDS));
-                attr_bf16_big = true;
-            }
-            lp.tiles_m = la::cdiv(rows, Big::TM);
-            la::TimerScope ts("fc_lse_bf16", stream);
-            hipLaunchKernelGGL((fc_lse_kernel<bf16_t, Big>), dim3(lp.tiles_m * lp.tiles_n), dim3(Big::THREADS), Big::LDS, stream, lp);
-        } else if (dtype == LA_BF16 || dtype == LA_F16) {
-            if (!attr_bf16) {
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_kernel<bf16_t, Small>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Small::LDS));
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_kernel<la::f16_t, Small>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Small::LDS));
-                attr_bf16 = true;
-            }
-            lp.tiles_m = la::cdiv(rows, Small::TM);
-            la::TimerScope ts("fc_lse_bf16", stream);
-            if (dtype == LA_F16) hipLaunchKernelGGL((fc_lse_kernel<la::f16_t, Small>), dim3(lp.tiles_m * lp.tiles_n), dim3(Small::THREADS), Small::LDS, stream, lp);
-            else hipLaunchKernelGGL((fc_lse_kernel<bf16_t, Small>), dim3(lp.tiles_m * lp.tiles_n), dim3(Small::THREADS), Small::LDS, stream, lp);
-        } else {
-            if (!attr_f32) {
-                LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fc_lse_kernel<float, Small>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Small::LDS));
-                attr_f32 = true;
-            }
-            lp.tiles_m = la::cdiv(rows, Small::TM);
-            la::TimerScope ts("fc_lse_f32", stream);
-            hipLaunchKernelGGL((fc_lse_kernel<float, Small>), dim3(lp.tiles_m * lp.tiles_n), dim3(Small::THREADS), Small::LDS, stream, lp);
-        }
-        LA_LAUNCH_CHECK();
+                 rt.tiles_m, rt.tiles_n, rt.group};
+    if (rt.form == LSE_X2) {
+        void *planes = ws + pl.off_planes;
+        float *inv = reinterpret_cast<float *>(ws + pl.off_inv);
+        rc = la_split_f16x2(static_cast<const float *>(act), ld_act, rows, in_dim, planes, in_dim, inv, stream_);
+        if (rc != LA_OK) return rc;
+        lp.A = planes; lp.W = w_x2; lp.sa = inv; lp.sw = w_x2s;
     }
+    const bool half = dtype == LA_F16;
+    const char *fam16 = "fc_lse_bf16", *fam32 = "fc_lse_f32";   // timer families
+    switch (rt.form) {
+    case LSE_X2: rc = launch_lse<fc_lse_x2_kernel, PP>(lp, fam32, stream); break;
+    case LSE_PP_DUO:
+        rc = half ? launch_lse<fc_lse_pp_kernel<la::f16_t, true>, PP>(lp, fam16, stream) : launch_lse<fc_lse_pp_kernel<bf16_t, true>, PP>(lp, fam16, stream);
+        break;
+    case LSE_PP:
+        rc = half ? launch_lse<fc_lse_pp_kernel<la::f16_t>, PP>(lp, fam16, stream) : launch_lse<fc_lse_pp_kernel<bf16_t>, PP>(lp, fam16, stream);
+        break;
+    case LSE_ROWS256: rc = launch_lse<fc_lse_kernel<bf16_t, Big>, Big>(lp, fam16, stream); break;
+    case LSE_ROWS128:
+        rc = dtype == LA_F32 ? launch_lse<fc_lse_kernel<float, Small>, Small>(lp, fam32, stream)
+             : half          ? launch_lse<fc_lse_kernel<la::f16_t, Small>, Small>(lp, fam16, stream)
+                             : launch_lse<fc_lse_kernel<bf16_t, Small>, Small>(lp, fam16, stream);
+        break;
+    }
+    if (rc != LA_OK) return rc;
     // 4. merge
     hipLaunchKernelGGL(merge_emissions_kernel, dim3(la::cdiv(rows, 4)), dim3(256), 0, stream, partials, lp.nparts, raw,
                        frames, rows, variant, vocab, labels, labels_stride, n_labels, max_labels, em, em_batch_stride,

@@ -30,7 +30,7 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "la_common.h"
+#include "la_row.h"
 
 namespace {
 
@@ -187,11 +187,8 @@ __global__ __launch_bounds__(256, 2) void logmel_tile_kernel(const float *__rest
             if (live) mx = fmaxf(mx, v);
             outt[(m * 16 + 4 * lq + r) * OUTP + 16 * wave + lr] = v;
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    if (tid == 0) blockmax[(int64_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    mx = la::block4_max(mx, red);
+    if (tid == 0) blockmax[(int64_t)b * gridDim.x + blockIdx.x] = mx;
     const int f = tid & 63;
     if (j0 + f < frames) {
         float *dst = mel + (int64_t)b * mbs + j0 + f;
@@ -206,11 +203,7 @@ __global__ __launch_bounds__(256) void logmel_finish_kernel(float *mel, int64_t 
     __shared__ float red[4];
     float m = -INFINITY;
     for (int i = threadIdx.x; i < nblockmax; i += 256) m = fmaxf(m, blockmax[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    const float floor_v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) - 8.0f;
+    const float floor_v = la::block4_max(m, red) - 8.0f;
     for (int r = 0; r < 4; ++r) {
         float *row = mel + (int64_t)blockIdx.y * mbs + (int64_t)(blockIdx.x * 4 + r) * mrs;
         for (int j = threadIdx.x; j < frames; j += 256) row[j] = (fmaxf(row[j], floor_v) + 4.0f) / 4.0f;
@@ -225,11 +218,7 @@ __global__ __launch_bounds__(256) void logmel_finish_ragged_kernel(float *mel, i
     const int b = blockIdx.y;
     float m = -INFINITY;
     for (int i = threadIdx.x; i < tiles; i += 256) m = fmaxf(m, blockmax[(int64_t)b * tiles + i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    const float floor_v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) - 8.0f;
+    const float floor_v = la::block4_max(m, red) - 8.0f;
     const int frames = min(min(max(n_samples[b], 0), row_len) / HOP, out_frames);
     for (int r = 0; r < 4; ++r) {
         float *row = mel + (int64_t)b * mbs + (int64_t)(blockIdx.x * 4 + r) * mrs;

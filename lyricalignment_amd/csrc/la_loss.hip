@@ -15,22 +15,14 @@
 //                    as the Viterbi kernel with max replaced by log-sum-exp)
 //   dense_grad       one workgroup per row: dlogits = scale * ( w_ctc_b * softmax_[0,V) + valid/n_valid * softmax_[1,V)
 //                    - one-hot terms ), column V gets the BCE gradient
+// The reduction order of row_stats is la_row.h's (block4_max / block4_sum).
 #include "la_lattice.h"
+#include "la_row.h"
 
 namespace {
 
 using namespace la::lattice;
 
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // A row's normaliser: its maximum and the log of sum_c exp(x[c] - m), kept APART.  Every use takes (x - m) - log_s like torch's
 // log_softmax (and la_cross_entropy_f32, la_anchor_loss.hip): m + log_s rounded to one float costs an ulp OF m, which for logits with a
 // large common offset (1e4: 5e-4 per frame) is larger than the losses' own resolution and adds up over the frames of the lattice.
@@ -50,22 +42,16 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float *logits, int
     __shared__ float red[12];
     const int row = blockIdx.x;
     const float *x = logits + (int64_t)row * ldl;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     float m = -INFINITY;
     for (int c = 1 + tid; c < V; c += 256) m = fmaxf(m, x[c]);
-    m = wave_max_f(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    const float m1 = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));  // max over [1,V)
+    const float m1 = la::block4_max(m, red);                                 // max over [1,V)
     const float x0 = x[0];
     const float m0 = fmaxf(m1, x0);                                          // max over [0,V)
     float s = 0.f;
     for (int c = 1 + tid; c < V; c += 256) s += expf(x[c] - m1);
-    s = wave_sum_f(s);
-    if (lane == 0) red[4 + wave] = s;
-    __syncthreads();
+    const float s1 = la::block4_sum(s, red + 4);
     if (tid == 0) {
-        const float s1 = (red[4] + red[5]) + (red[6] + red[7]);
         const float ls1 = logf(s1);
         norm_ce[row] = RowNorm{m1, ls1};
         norm_all[row] = RowNorm{m0, logf(s1 * expf(m1 - m0) + expf(x0 - m0))};
@@ -400,11 +386,6 @@ extern "C" int la_multitask_loss(const float *logits, int64_t batch_stride, int6
     hipLaunchKernelGGL(row_stats_kernel, dim3(rows), dim3(256), 0, stream, logits, row_stride, rows, vocab,
                        use_ce ? frame_labels : nullptr, norm_all, norm_ce, acc);
     LA_LAUNCH_CHECK();
-    if (dlogits) {
-        // dense part first (it needs nll only to zero the CTC weight of infeasible utterances -> run the lattice's alpha
-        // pass first when CTC is on); order: lattice(alpha, nll) is inside ctc_lattice_kernel, so: zero nll, lattice
-        // WITHOUT gradient, dense, lattice scatter.  Two lattice launches keep every kernel simple; the lattice is tiny.
-    }
     const int S = 2 * max_labels + 1;
     auto launch_lattice = [&](float *dl) {
         if (!use_ctc) return;
@@ -423,7 +404,9 @@ extern "C" int la_multitask_loss(const float *logits, int64_t batch_stride, int6
 #undef LA_CTC_CASE
     };
     if (use_ctc) {
-        launch_lattice(nullptr);   // alpha sweep: nll per utterance + loss accumulators
+        // alpha sweep WITHOUT gradient: nll per utterance + loss accumulators.  Before the dense part, which needs nll to zero the CTC
+        // weight of infeasible utterances
+        launch_lattice(nullptr);
         LA_LAUNCH_CHECK();
     } else {
         LA_HIP(hipMemsetAsync(nll, 0, (size_t)batch * 4, stream));
@@ -433,7 +416,9 @@ extern "C" int la_multitask_loss(const float *logits, int64_t batch_stride, int6
                            norm_ce, frame_labels, n_labels, nll, acc, use_ce, use_ctc, scale, batch, dlogits, d_row_stride);
         LA_LAUNCH_CHECK();
         if (use_ctc) {
-            launch_lattice(dlogits);   // beta sweep on the stored alpha rows, occupancies subtracted from the dense softmax part
+            // beta sweep on the stored alpha rows, occupancies subtracted from the dense softmax part.  A second lattice launch keeps
+            // every kernel simple; the lattice is tiny
+            launch_lattice(dlogits);
             LA_LAUNCH_CHECK();
         }
     }

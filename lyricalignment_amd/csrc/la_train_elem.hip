@@ -1,7 +1,8 @@
 // la_train_elem.hip -- HBM-bound helpers of the fine-tune backward pass (float32, like the reference's training):
 // 2-D transpose with zero padding (turns dX = dY W and dW = dY^T X into the K-contiguous "NT" GEMMs la_gemm runs),
 // column sums (bias gradients), Mish backward, masked scaling (inter-layer GRU dropout, module/align_model.py:23-28).
-#include "la_common.h"
+// The float wave butterflies and the four-wave maximum are la_row.h's.
+#include "la_row.h"
 
 namespace {
 
@@ -87,17 +88,6 @@ __global__ void add_kernel(const float *a, const float *b, float *y, int64_t n) 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = a[i] + b[i];
 }
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // LayerNorm backward, one wave per row (row statistics recomputed):  xhat = (x - mean) rstd,  g = dy * gamma,
 // dx = rstd (g - mean(g) - xhat mean(g xhat));  also writes dy * xhat (its column sum is dgamma; colsum(dy) is dbeta)
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *x, const float *dy, const float *gamma, int M, int d,
@@ -108,16 +98,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *x, cons
     const float *xr = x + (int64_t)row * d, *gr = dy + (int64_t)row * d;
     float s = 0.f;
     for (int c = lane; c < d; c += 64) s += xr[c];
-    const float mean = wsum(s) / (float)d;
+    const float mean = la::wave_sum(s) / (float)d;
     float sq = 0.f;
     for (int c = lane; c < d; c += 64) { const float t = xr[c] - mean; sq += t * t; }
-    const float rstd = 1.0f / sqrtf(wsum(sq) / (float)d + 1e-5f);
+    const float rstd = 1.0f / sqrtf(la::wave_sum(sq) / (float)d + 1e-5f);
     float sg = 0.f, sgx = 0.f;
     for (int c = lane; c < d; c += 64) {
         const float xh = (xr[c] - mean) * rstd, g = gr[c] * gamma[c];
         sg += g; sgx += g * xh;
     }
-    const float mg = wsum(sg) / (float)d, mgx = wsum(sgx) / (float)d;
+    const float mg = la::wave_sum(sg) / (float)d, mgx = la::wave_sum(sgx) / (float)d;
     for (int c = lane; c < d; c += 64) {
         const float xh = (xr[c] - mean) * rstd, g = gr[c] * gamma[c];
         dx[(int64_t)row * d + c] = rstd * (g - mg - xh * mgx);
@@ -154,14 +144,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_sums_kernel(const float *x,
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) s += (xv[j].x + xv[j].y) + (xv[j].z + xv[j].w);
-        const float mean = wsum(s) / (float)d;
+        const float mean = la::wave_sum(s) / (float)d;
         float sq = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             xv[j].x -= mean; xv[j].y -= mean; xv[j].z -= mean; xv[j].w -= mean;
             sq += (xv[j].x * xv[j].x + xv[j].y * xv[j].y) + (xv[j].z * xv[j].z + xv[j].w * xv[j].w);
         }
-        const float rstd = 1.0f / sqrtf(wsum(sq) / (float)d + 1e-5f);
+        const float rstd = 1.0f / sqrtf(la::wave_sum(sq) / (float)d + 1e-5f);
         float sg = 0.f, sgx = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_sums_kernel(const float *x,
             sg += (g.x + g.y) + (g.z + g.w);
             sgx += (g.x * xv[j].x + g.y * xv[j].y) + (g.z * xv[j].z + g.w * xv[j].w);
         }
-        const float mg = wsum(sg) / (float)d, mgx = wsum(sgx) / (float)d;
+        const float mg = la::wave_sum(sg) / (float)d, mgx = la::wave_sum(sgx) / (float)d;
         float4 *dr = reinterpret_cast<float4 *>(dx + (int64_t)row * d);
         const float4 *rr = resid ? reinterpret_cast<const float4 *>(resid + (int64_t)row * d) : nullptr;
 #pragma unroll
@@ -225,10 +215,10 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float *s, int64_t ld,
     if (causal_q_len > 0) cols = min(cols_all, max(1, (int)(row % causal_q_len) + 1 + (cols_all - causal_q_len)));
     float m = -INFINITY;
     for (int c = lane; c < cols; c += 64) m = fmaxf(m, r[c]);
-    m = wmax(m);
+    m = la::wave_max(m);
     float sum = 0.f;
     for (int c = lane; c < cols; c += 64) { const float e = expf(r[c] - m); r[c] = e; sum += e; }
-    const float inv = 1.0f / wsum(sum);
+    const float inv = 1.0f / la::wave_sum(sum);
     for (int c = lane; c < cols; c += 64) r[c] *= inv;
     for (int c = cols + lane; c < ld; c += 64) r[c] = 0.f;
 }
@@ -298,19 +288,16 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float *logits, int64_
     const float *l = logits + (int64_t)r * ld;
     float m = -INFINITY;
     for (int c = threadIdx.x; c < V; c += 256) m = fmaxf(m, l[c]);
-    m = wmax(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
+    m = la::block4_max(m, red);
+    __syncthreads();   // the sums below reuse the four slots
     float s = 0.f;
     for (int c = threadIdx.x; c < V; c += 256) s += expf(l[c] - m);
-    s = wsum(s);
+    s = la::wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
         row_max[r] = m;
-        row_logsum[r] = logf(red[0] + red[1] + red[2] + red[3]);
+        row_logsum[r] = logf(red[0] + red[1] + red[2] + red[3]);   // left to right, NOT la::block4_sum's pairs: another rounding, kept for the bits
     }
 }
 __global__ __launch_bounds__(64) void ce_reduce_kernel(const float *logits, int64_t ld, const float *row_max, const float *row_logsum,

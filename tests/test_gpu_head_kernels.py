@@ -383,7 +383,7 @@ def _run_sweep(name, dt, B, T, K, V, x2=False, strips=None):
 
 
 # ---- the 128-column kernels at small shapes -----------------------------------------------------------------------------------------
-# Fewer than 192 tiles of 256 x 256 (pp_ok and fc_x2_ok false) and gemm_tile unset: the last two branches of fc_emissions_impl,
+# Fewer than 192 tiles of 256 x 256 (pp_ok and fc_x2_ok false) and gemm_tile unset: the 128-row form of route_lse,
 # fc_lse_kernel<float, Small> for float32 and fc_lse_kernel<T16, Small> for bf16 / f16.
 
 @pytest.mark.parametrize("B,T,K,V", [(5, 1, 32, 3), (5, 1, 32, 65), (3, 43, 32, 129), (3, 43, 96, 65), (3, 43, 96, 300), (5, 1, 96, 129)])
@@ -444,6 +444,25 @@ def test_16bit_256x256_kernel(dt, K):
         for key, em in pp.items():            # the header: the loop of the other K, identical bits
             assert torch.equal(_bits(em), _bits(out[key])), key
     _run_form(f"fc_lse_kernel<{dt},Small>@512rows", dt, 2, 256, K, V, family="fc_lse_bf16", strips=254, only=("gauss",), rows_from=(B, T))
+
+
+@pytest.mark.parametrize("K", [128, 256])
+def test_bf16_256x256_kernel_on_a_second_device(K):
+    """The forms that need their dynamic-LDS ceiling raised (128 KiB), on a device other than 0: the ceiling is a per-device attribute of
+    the kernel, so a process that has launched on device 0 must still raise it on device 1.  K = 128 the ping-pong loop, K = 256 the
+    hand-placed loop; the Gaussian case under the usual layout, guard and error checks (the float64 references are the device-0 tests'),
+    and the same bits as the same call on device 0."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs a second device")
+    B, T, V = BIG
+    form = f"fc_lse_pp_kernel<bf16{',true' if K == 256 else ''}>"
+    first = _run_form(form, "bf16", B, T, K, V, family="fc_lse_bf16", strips=256, only=("gauss",))
+    with torch.cuda.device(1):
+        second = _run_form(form + "@device1", "bf16", B, T, K, V, family="fc_lse_bf16", strips=256, only=("gauss",))
+        torch.cuda.synchronize()
+    assert first.keys() == second.keys() and len(first) == 2
+    for key, em in second.items():
+        assert torch.equal(_bits(em), _bits(first[key])), key
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
