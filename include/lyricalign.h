@@ -534,6 +534,39 @@ int la_alignment_posteriors_repeats(const float *em, int64_t em_batch_stride, in
                                     float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
                                     void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Whole-song confidence for repeated lyric lines: la_alignment_posteriors_repeats for up to 4095 labels.  The arguments are that
+ * entry's, unchanged and in the same order, and so is the meaning of every output (expected counts included).
+ * Up to 511 labels the call IS la_alignment_posteriors_repeats' sweep: the same kernel, the same workspace size, the same bits.
+ * 512 .. 4095 labels: R = 2 / 4 / 8 lattice states per thread (up to 1023 / 2047 / 4095 labels), the same cell, so a clip gives the
+ * same bits as in the lane-per-state form.  The workspace then holds, with NS = 1024 R,
+ *     batch * max_frames * NS * 8   bytes of alpha rows,
+ *   + batch * (NS / 2) * 6 * 8      bytes of sums (6 slots per label: occupancy, onset, offset, two span-skip halves, repeat_count),
+ *   + batch * 3 NS * 4              bytes of arc lists (at most 4 arcs per optional span, at most 2 per repeat span)
+ * -- la_alignment_posteriors_song_workspace_bytes -- and must be 16-byte aligned (at every label count).
+ * More than 4095 labels: LA_EUNSUPPORTED, reported before the stride checks.  The other argument errors are
+ * la_alignment_posteriors_repeats', answered on the host under this entry's name before anything is enqueued; never synchronises,
+ * allocates or frees.  With repeat_from NULL or all -1 the outputs shared with la_alignment_posteriors_lattice are that entry's bit
+ * for bit at every label count, visits equals its present_prob and repeat_count is 0.
+ */
+int la_alignment_posteriors_song_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors_song(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                 const int32_t *labels, int32_t labels_stride,
+                                 const int32_t *n_labels, const int32_t *n_frames,
+                                 int32_t batch, int32_t max_frames, int32_t max_labels,
+                                 const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                                 int32_t boundary_window,
+                                 const int32_t *skip_from, int32_t skip_stride, double skip_penalty,
+                                 const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                 const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty,
+                                 const int32_t *path, int32_t path_stride,
+                                 float *occupancy, float *onset_prob, float *offset_prob, float *visits,
+                                 float *span_skip_prob, float *repeat_count, float *path_prob,
+                                 double *log_z, int32_t *status,
+                                 float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* emission prep from materialised logits                                     */
 /*   (replaces utils/alignment.py:123-134 [CTC] and :14-20 [plain])           */

@@ -86,6 +86,10 @@ SYMBOLS = {
     "la_alignment_posteriors_repeats": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, c_double,
                                                   _P, _P, _I32, _P, _I32, c_double, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                   _I64, _I64, _P, _SZ, _P]),
+    "la_alignment_posteriors_song_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
+    "la_alignment_posteriors_song": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, c_double,
+                                               _P, _P, _I32, _P, _I32, c_double, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               _I64, _I64, _P, _SZ, _P]),
     "la_emissions_from_logits": (c_int32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I64, _I64, _P]),
     "la_logmel_workspace_bytes": (c_int32, [_I32, _I32, POINTER(_SZ)]),
     "la_logmel_f32": (c_int32, [_P, _I32, _I32, _P, _P, _P, _I64, _I64, _P, _SZ, _P]),

@@ -33,7 +33,7 @@
 // present and span-skip terms all carry a beta_t or alpha_t factor of the gated cell and need nothing more.  log_z is the windowed
 // one: every output is a posterior GIVEN the windows; log_z = -inf (no path inside them) is the LA_EINFEASIBLE exit.
 //
-//   Repeatable spans (REP, only on top of SPANS + WIN, null pointers = absent; lane-per-state form only): the lattice of
+//   Repeatable spans (REP, only on top of SPANS + WIN, null pointers = absent; both layouts): the lattice of
 // la_viterbi_repeats_batch.  The odd state 2a+1 with repeat_from[a] = e has two more predecessors, K = 2e and (where allowed) K-1
 // (la_lattice.h repeat_source), each weighing exp(-repeat_penalty): the arcs point LEFT, but the sweep is frame-synchronous, so (frame,
 // state) stays a DAG.  Forward they are the jump arcs' fetch with the source to the right.  Backward K and K-1 are sources and join the
@@ -44,7 +44,7 @@
 // term of its source; repeat_count[a] -- the mass of the repeat arcs into 2a+1 -- accumulates in a register of lane 2a+1, the label's row
 // lane.  path_prob[t] = gamma_t(path[t]) is stored by the lane the DP's path names, the path value prefetched with the emissions.  The
 // once-per-clip test reads "a span or a repeat arc"; without a repeat arc every shared output has the SPANS + WIN face's bits
-// (log_add_jump(x, -inf) is x).
+// (log_add_jump(x, -inf) is x).  Order per forward cell: the three-term step, J and J-1, K and K-1, the emission last.
 //
 // LAYOUT 1, up to 511 labels: posterior_kernel<NW, DPP, SPANS, WIN[, REP]>, one workgroup per clip, one lane per state, the sums lane-local
 // registers, alpha rows [batch][max_frames][64 NW].  S <= 64: ONE wave64, neighbours by DPP wave shifts, alpha(J) by ds_bpermute, no
@@ -52,7 +52,7 @@
 // one barrier per frame.  Emissions and stored alpha rows are prefetched a block of steps ahead of the dependency chain.  The arc
 // lists live in LDS (out-degree, offset by a uniform prefix loop, targets); the trip count is the wave's maximum out-degree.
 //
-// LAYOUT 2, 512 .. 4095 labels: posterior_strip_kernel<R, SPANS, WIN> on viterbi_strip_kernel's thread layout (la_viterbi.hip): one
+// LAYOUT 2, 512 .. 4095 labels: posterior_strip_kernel<R, SPANS, WIN[, REP]> on viterbi_strip_kernel's thread layout (la_viterbi.hip): one
 // workgroup of 1024 threads per clip, thread tid owns the R CONSECUTIVE states k = tid*R + r (R = 2 / 4 / 8), alpha rows
 // [batch][max_frames][1024 R] written as 16-byte pieces.  Neighbours inside a thread are registers; the two rightmost (backward:
 // leftmost) states of a thread reach the next thread through a double-buffered float64 row in LDS, one barrier per frame.  Where the
@@ -67,6 +67,14 @@
 //     the workspace behind a divergent branch; present_prob, which every label of a clip with a span adds to at every frame, stays
 //     in registers;
 //   * states 2n and 2n+1 belong to the same thread (R is even), so span_skip_prob's final add needs no exchange.
+//   REP in this layout (la_alignment_posteriors_song): K and km1_ok per owned odd state in registers; forward the K pair comes from the
+//   exchanged row like the J pair (a clip with a jump writes all R states there); repeat_from is staged beside skip_from in the
+//   not-yet-used row buffer and the repeat arcs join the thread's list behind the skip words of the same state -- ordered by r, then skip
+//   targets ascending, then repeat targets ascending: folded front to back that is the documented order per state.  A repeat word is
+//   (r << 16) | target | kStripRepeatArc (bit 15: bit 16 belongs to r here, targets are below 8192); at most 2 more arcs per repeat span,
+//   one span per start label, so this face's arc area is 3 NS words.  Backward alpha_{t-1}(K), (K-1) come from the workspace rows as
+//   (J), (J-1) do; repeat_count[a] accumulates in a sixth workspace slot of the owning thread (AW = 6 for this face only); path_prob[t] is
+//   stored by the thread that owns the state the path names, the path value fetched with the emissions.
 #include <type_traits>
 
 #include "la_lattice.h"
@@ -101,6 +109,8 @@ struct RepParams : PostParams {
     float *path_prob;     // [batch][path_stride]; null = not wanted
 };
 constexpr int kRepeatArc = 1 << 16;  // arc-list word of a repeat arc: its target | this bit (it is charged repeat_penalty)
+// the strip form's word is (r << 16) | target, so bit 16 is r's: there a repeat arc sets bit 15, free because a target is below 8192
+constexpr int kStripRepeatArc = 1 << 15, kStripTarget = kStripRepeatArc - 1;
 
 // ---- the cell: every expression of the two sweeps that is more than an exchange of neighbours ------------------------------------
 // alpha_t(k) before its emission: alpha_{t-1} of k, k-1 and (where the labels differ) k-2
@@ -621,16 +631,18 @@ __global__ __launch_bounds__(NW * 64) void posterior_kernel(std::conditional_t<R
     if (k == 0) { p.status[b] = LA_OK; p.log_z[b] = log_z; }
 }
 
-template <int R, bool SPANS, bool WIN>
-__global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
+template <int R, bool SPANS, bool WIN, bool REP = false>
+__global__ __launch_bounds__(1024) void posterior_strip_kernel(std::conditional_t<REP, RepParams, PostParams> p) {
     static_assert(!WIN || SPANS, "frame windows are a face of the optional-span forms");
+    static_assert(!REP || WIN, "repeatable spans are a face of the span + window forms (null pointers: absent)");
     static_assert(R == 2 || R == 4 || R == 8, "states per thread");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = 1024, NS = NT * R, NL = R / 2, ROW = NS + 4;
     // frames per prefetch block (emissions, and backward the alpha rows): the span-free loops / the loops of a clip with a span
     constexpr int UP = R == 2 ? 4 : R == 4 ? 2 : 1, UJ = 1;
     constexpr int CR = 4;  // arc words kept in registers
-    constexpr int AW = 5;  // sums per label kept in the workspace
+    constexpr int AW = REP ? 6 : 5;  // sums per label kept in the workspace (repeats: and the mass of the repeat arcs into the label)
+    constexpr int CW = REP ? 3 : 2;  // arc words per state in the workspace (repeats: at most 2 more arcs per span, one span per start label)
     // own state k at [k + 2]; [0], [1] and [NS + 2], [NS + 3] stay -inf: the neighbours of the first / last states
     double *rowbuf = reinterpret_cast<double *>(smem);  // [2][ROW]
     double *fin = rowbuf + 2 * ROW;                     // [2]
@@ -656,13 +668,23 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
                 for (int r = 0; r < R; ++r)
                     if (k0 + r < Sg) gam[(int64_t)t * p.gamma_rs + k0 + r] = 0.f;
     };
+    [[maybe_unused]] auto zero_path_prob_from = [&](int t_from) {
+        if constexpr (REP) {
+            if (p.path_prob)
+                for (int t = t_from + tid; t < p.max_frames; t += NT) p.path_prob[(int64_t)b * p.path_stride + t] = 0.f;
+        }
+    };
     auto fail = [&](int st, double lz) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int n = n0 + i;
             if (n < p.max_labels) { occ_g[n] = 0.f; onp_g[n] = 0.f; offp_g[n] = 0.f; pres_g[n] = 0.f; }
             if (n <= p.max_labels) skp_g[n] = 0.f;
+            if constexpr (REP) {
+                if (n < p.max_labels) p.repeat_count[(int64_t)b * p.out_stride + n] = 0.f;
+            }
         }
+        if constexpr (REP) zero_path_prob_from(0);
         zero_gamma_from(0);
         if (tid == 0) { p.status[b] = st; p.log_z[b] = lz; }
     };
@@ -691,6 +713,10 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
     [[maybe_unused]] int J[SPANS ? R : 1];
     [[maybe_unused]] bool jm1_ok[SPANS ? R : 1];
     [[maybe_unused]] int wlo[WIN ? R : 1], whi[WIN ? R : 1];
+    // the repeat span that starts at each owned ODD state's label (k0 is even: the odd states are r = 2 i + 1)
+    [[maybe_unused]] const int32_t *rep_b = nullptr;
+    [[maybe_unused]] int K[REP ? NL : 1];
+    [[maybe_unused]] bool km1_ok[REP ? NL : 1];
     bool has_span = false;
     if constexpr (SPANS) {
         if (!WIN || p.skip_from) skip_b = p.skip_from + (int64_t)b * p.skip_stride;  // (windows: a null skip_from = no span anywhere)
@@ -702,13 +728,24 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
             jm1_ok[r] = src.jm1_ok;
             any |= src.J >= 0;
         }
-        has_span = __syncthreads_or(any) != 0;  // workgroup-uniform, taken once: a clip without a span runs the plain loops
+        if constexpr (REP) {
+            if (p.repeat_from) rep_b = p.repeat_from + (int64_t)b * p.repeat_stride;
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                const RepeatSource src = repeat_source(rep_b, lab, k0 + 2 * i + 1, k0 + 2 * i + 1 < S, L);
+                K[i] = src.K;
+                km1_ok[i] = src.km1_ok;
+                any |= src.K >= 0;
+            }
+        }
+        // workgroup-uniform, taken once: a clip without a span (repeats: without a jump of either kind) runs the plain loops
+        has_span = __syncthreads_or(any) != 0;
     }
     if constexpr (WIN) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             wlo[r] = 0, whi[r] = 0x7fffffff;
-            if (k0 + r < S) {
+            if (k0 + r < S && (!REP || p.win_lo)) {  // (repeats: a null window pair = every window open)
                 wlo[r] = p.win_lo[(int64_t)b * p.win_stride + k0 + r];
                 whi[r] = p.win_hi[(int64_t)b * p.win_stride + k0 + r];
             }
@@ -719,9 +756,11 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
         else return e;
     };
     const double pen = p.penalty;
+    [[maybe_unused]] double rpen = 0.0;
+    if constexpr (REP) rpen = p.repeat_penalty;
 
     // jump arcs by SOURCE: state k is J of the spans that start at position (k+1)/2 when even, J-1 of them when odd.  This thread's
-    // list: tdeg words from csr[0], ordered by r, then ascending target
+    // list: tdeg words from csr[0], ordered by r, then ascending target (repeats: per r the skip targets, then the repeat targets)
     int tdeg = 0, maxdeg = 0;
     [[maybe_unused]] int ent_reg[CR] = {0, 0, 0, 0};
     [[maybe_unused]] const int32_t *csr = nullptr;
@@ -729,7 +768,18 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
         if (has_span) {
             int32_t *skip_s = reinterpret_cast<int32_t *>(rowbuf);      // [L + 1] <= 4 NS bytes
             int32_t *tot_s = reinterpret_cast<int32_t *>(rowbuf + ROW);  // [NT]
-            for (int m = tid; m <= L; m += NT) skip_s[m] = span_first(skip_b, m);
+            // repeats: beside it, what repeat_source gives every start label a: K, with kStripRepeatArc set where K-1 is a source as
+            // well, or -1 ([L] <= NS / 2 - 1 words behind the NS / 2 of skip_s: 4 NS bytes in all)
+            [[maybe_unused]] int32_t *rep_s = skip_s + NS / 2;
+            if constexpr (REP) {
+                for (int m = tid; m <= L; m += NT) skip_s[m] = skip_b ? span_first(skip_b, m) : -1;
+                for (int a = tid; a < L; a += NT) {
+                    const RepeatSource of_label = repeat_source(rep_b, lab, 2 * a + 1, true, L);
+                    rep_s[a] = of_label.K >= 0 ? (of_label.K | (of_label.km1_ok ? kStripRepeatArc : 0)) : -1;
+                }
+            } else {
+                for (int m = tid; m <= L; m += NT) skip_s[m] = span_first(skip_b, m);
+            }
             __syncthreads();
             // one pass over the end positions: a span (a, m) leaves from this thread's states 2a (always both targets) and 2a - 1
             // (the odd target only under the equal-neighbour rule), where they are its own: n0 <= a <= n0 + NL
@@ -747,10 +797,27 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
                     }
                 }
             };
+            // repeat arcs: state k is K of the repeat spans that END at position (k+1)/2 when even, K-1 of them when odd (where
+            // repeat_source allows that arc); the target is the start label's state 2a+1, to the LEFT of k.  One pass over the start labels
+            [[maybe_unused]] auto returns = [&](auto emit) {
+                const int a_end = min(L, n0 + NL);
+                for (int a = 0; a < a_end; ++a) {
+                    const int w = rep_s[a];
+                    if (w < 0) continue;
+                    const int e = (w & kStripTarget) >> 1;
+                    if (e < n0 || e > n0 + NL) continue;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        if (((k0 + r + 1) >> 1) != e) continue;
+                        if (!(r & 1) || (w & kStripRepeatArc)) emit(r, (2 * a + 1) | kStripRepeatArc);
+                    }
+                }
+            };
             int cnt[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) cnt[r] = 0;
             arcs([&](int r, int) { ++cnt[r]; });
+            if constexpr (REP) returns([&](int r, int) { ++cnt[r]; });
 #pragma unroll
             for (int r = 0; r < R; ++r) tdeg += cnt[r];
             tot_s[tid] = tdeg;
@@ -760,12 +827,14 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
                 const int v = tot_s[i];
                 if (i < tid) first += v;
             }
-            int32_t *mine = p.csr_ws + (int64_t)b * (2 * NS) + first;  // at most 4 arcs per span: < 2 NS in all
+            int32_t *mine = p.csr_ws + (int64_t)b * (CW * NS) + first;  // at most 4 arcs per span: < 2 NS in all (repeats: < 3 NS)
             int pos[R];                                                 // where the list of state r goes on: by r, then ascending target
             pos[0] = 0;
 #pragma unroll
             for (int r = 1; r < R; ++r) pos[r] = pos[r - 1] + cnt[r - 1];
             arcs([&](int r, int d) { mine[pos[r]++] = (r << 16) | d; });
+            // behind the skip targets of the same state: pos[r] has gone past them (cnt[r] counted both kinds)
+            if constexpr (REP) returns([&](int r, int d) { mine[pos[r]++] = (r << 16) | d; });
 #pragma unroll
             for (int q = 0; q < CR; ++q) ent_reg[q] = q < tdeg ? mine[q] : 0;   // (written by this thread)
             csr = mine;
@@ -845,6 +914,10 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
                         double sum = forward_step(prev[r + 2], prev[r + 1], prev[r], can_skip[r]);
                         if constexpr (HAS) {
                             if (J[r] >= 0) sum = log_add_jump(sum, jump_in(rb[J[r] + 2], rb[J[r] + 1], jm1_ok[r], pen));  // from the row, never from a[]
+                            if constexpr (REP) {  // after the J terms; the source lies to the right, in the same row
+                                if ((r & 1) && K[r >> 1] >= 0)
+                                    sum = log_add_jump(sum, jump_in(rb[K[r >> 1] + 2], rb[K[r >> 1] + 1], km1_ok[r >> 1], rpen));
+                            }
                         }
                         a[r] = k0 + r < S ? sum + (double)ec[u][r] : NEG;
                     }
@@ -875,6 +948,14 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
         acc_lane[i] = on[i] >= 0 && off[i] > on[i];
     }
     const int w = p.window;
+    [[maybe_unused]] const int32_t *path_b = nullptr;
+    [[maybe_unused]] float *pp_g = nullptr;
+    if constexpr (REP) {
+        if (p.path_prob) {  // (the host: only with a path)
+            path_b = p.path + (int64_t)b * p.path_stride;
+            pp_g = p.path_prob + (int64_t)b * p.path_stride;
+        }
+    }
     auto backward = [&](auto has_c) {
         constexpr bool HAS = decltype(has_c)::value;
         constexpr int U = HAS ? UJ : UP;
@@ -890,6 +971,7 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
         // alpha rows: `top` is alpha_t0 of the next block (carried, not fetched twice); nx[u] is row t0 - 1 - u, nl[u] the two values left of it
         double top[R], nx[U][R], nl[U][2];
         float ev[U][NL + 1];
+        [[maybe_unused]] int pv[REP ? U : 1];  // the reported path's state at the block's frames (workgroup-uniform)
         auto load_row = [&](double *dst, int t) {
             const double2 *src = reinterpret_cast<const double2 *>(aw + (int64_t)t * NS + k0);
 #pragma unroll
@@ -900,6 +982,10 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
             }
         };
         auto fetch = [&](int t0) {  // steps t0, t0 - 1, ..., t0 - U + 1
+            if constexpr (REP) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) pv[u] = path_b ? path_b[max(t0 - u, 0)] : -1;
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const float *row = emb + (int64_t)max(t0 - u, 0) * p.em_rs;
@@ -919,6 +1005,11 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
             float ec[U][NL + 1];
             double ar[U + 1][R], al[U][2];
             if constexpr (!PF) fetch(t0);
+            [[maybe_unused]] int pc[REP ? U : 1];
+            if constexpr (REP) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) pc[u] = pv[u];
+            }
 #pragma unroll
             for (int r = 0; r < R; ++r) ar[0][r] = top[r];
 #pragma unroll
@@ -961,12 +1052,14 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
                             for (int r = 0; r < R; ++r) js[r] = NEG;
                             auto fold = [&](int i, int ent) {
                                 const bool act = i < tdeg;
-                                const int d = act ? (ent & 0xffff) : k0, er = ent >> 16;
+                                const int d = act ? (ent & (REP ? kStripTarget : 0xffff)) : k0, er = ent >> 16;
                                 const double bv = rb[d + 2];
                                 double cur = js[0];
 #pragma unroll
                                 for (int r = 1; r < R; ++r) cur = er == r ? js[r] : cur;
-                                const double res = log_add_jump(cur, bv - pen);
+                                double apen = pen;  // repeats: every arc carries its own penalty
+                                if constexpr (REP) apen = (ent & kStripRepeatArc) ? rpen : pen;
+                                const double res = log_add_jump(cur, bv - apen);
 #pragma unroll
                                 for (int r = 0; r < R; ++r) js[r] = (act && er == r) ? res : js[r];
                             };
@@ -1007,13 +1100,32 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
                         }
                         const float g = cell_gamma(at, be[r], e, log_z);
                         if (gam && k < Sg) gam[(int64_t)t * p.gamma_rs + k] = g;
+                        [[maybe_unused]] double rin = NEG;  // repeats: log weight of the repeat arcs into state k at frame t
+                        if constexpr (REP) {
+                            // gamma at the reported path: stored by the thread that owns the state the path names (a value that names none: 0,
+                            // by state 0's)
+                            const bool named = pc[u] >= 0 && pc[u] < S;
+                            if (pp_g && k == (named ? pc[u] : 0)) pp_g[t] = named ? g : 0.f;
+                            if constexpr (HAS) {
+                                if (odd && K[i] >= 0 && t > 0) {
+                                    const double *prow = aw + (int64_t)(t - 1) * NS;
+                                    rin = jump_in(prow[K[i]], km1_ok[i] ? prow[K[i] - 1] : NEG, km1_ok[i], rpen);
+                                    acc[AW * i + 5] += (double)__expf((float)(rin + be[r] - log_z));
+                                }
+                            }
+                        }
                         if constexpr (HAS) {
                             // add_cell<true>'s text, kept here: through the helper the 8-states-per-thread span faces (which spill
                             // 140 / 182 VGPRs) came out 3 % slower on the anchors + optional lines leg (profiles/posterior_refactor.txt)
                             if (J[r] >= 0 && t > 0) acc[AW * i + 3 + (r & 1)] += (double)__expf((float)(jin + be[r] - log_z));
                             if (odd && valid) {
                                 float en = g;
-                                if (t > 0) en = __expf((float)(log_add_jump(log_add2(am1, can_skip[r] ? am2 : NEG), jin) + be[r] - log_z));
+                                if constexpr (REP) {  // a return is an entry of its target (and, through js, an exit of its source)
+                                    if (t > 0)
+                                        en = __expf((float)(log_add_jump(log_add_jump(log_add2(am1, can_skip[r] ? am2 : NEG), jin), rin) + be[r] - log_z));
+                                } else {
+                                    if (t > 0) en = __expf((float)(log_add_jump(log_add2(am1, can_skip[r] ? am2 : NEG), jin) + be[r] - log_z));
+                                }
                                 s_pres[i] += (double)en;
                                 if (acc_lane[i]) {
                                     if (t >= on[i] && t < off[i]) acc[AW * i] += (double)g;
@@ -1039,9 +1151,15 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
             if constexpr (HAS) {
                 if (n < p.max_labels) pres_g[n] = valid ? (float)s_pres[i] : 0.f;
                 if (n <= p.max_labels) skp_g[n] = J[2 * i] >= 0 ? (float)(acc[AW * i + 3] + acc[AW * i + 4]) : 0.f;  // states 2n and 2n+1
+                if constexpr (REP) {
+                    if (n < p.max_labels) p.repeat_count[(int64_t)b * p.out_stride + n] = valid ? (float)acc[AW * i + 5] : 0.f;
+                }
             } else {  // no jump: every path visits every label
                 if (n < p.max_labels) pres_g[n] = valid ? 1.f : 0.f;
                 if (n <= p.max_labels) skp_g[n] = 0.f;
+                if constexpr (REP) {
+                    if (n < p.max_labels) p.repeat_count[(int64_t)b * p.out_stride + n] = 0.f;
+                }
             }
         }
     };
@@ -1056,6 +1174,7 @@ __global__ __launch_bounds__(1024) void posterior_strip_kernel(PostParams p) {
             offp_g[n] = acc_lane[i] ? (float)acc[AW * i + 2] : 0.f;
         }
     }
+    if constexpr (REP) zero_path_prob_from(T);
     zero_gamma_from(T);
     if (tid == 0) { p.status[b] = LA_OK; p.log_z[b] = log_z; }
 }
@@ -1074,14 +1193,15 @@ __global__ void no_span_outputs_kernel(const int32_t *status, const int32_t *n_l
 
 // ---- host ----
 // up to 511 labels: nw waves, one lane per state, the workspace is the alpha rows.  512 .. 4095: R states per thread, the workspace is
-// the alpha rows | the sparse sums | the arc lists, the two rows in dynamic LDS
+// the alpha rows | the sparse sums | the arc lists, the two rows in dynamic LDS.  rep (the song entry): the strip form's REP face, with
+// 6 sums per label instead of 5 and 3 arc words per state instead of 2 (at most 4 arcs per optional span, at most 2 per repeat span)
 struct PostPlan {
     int nw, R;
     size_t lds_bytes, alpha_bytes, acc_bytes, csr_bytes;
     size_t ws_bytes() const { return alpha_bytes + acc_bytes + csr_bytes; }
 };
 
-bool plan_posterior(int batch, int max_frames, int max_labels, int label_limit, PostPlan *pl) {
+bool plan_posterior(int batch, int max_frames, int max_labels, int label_limit, PostPlan *pl, bool rep = false) {
     if (max_labels > label_limit) return false;
     *pl = PostPlan{};
     pl->nw = waves_for_labels(max_labels);
@@ -1094,8 +1214,8 @@ bool plan_posterior(int batch, int max_frames, int max_labels, int label_limit, 
     pl->alpha_bytes = (size_t)batch * (size_t)max_frames * NS * sizeof(double);
     if (pl->R) {
         pl->lds_bytes = (2 * (NS + 4) + 2) * sizeof(double);
-        pl->acc_bytes = (size_t)batch * (NS / 2) * 5 * sizeof(double);
-        pl->csr_bytes = (size_t)batch * 2 * NS * sizeof(int32_t);
+        pl->acc_bytes = (size_t)batch * (NS / 2) * (rep ? 6 : 5) * sizeof(double);
+        pl->csr_bytes = (size_t)batch * (rep ? 3 : 2) * NS * sizeof(int32_t);
     }
     return true;
 }
@@ -1132,12 +1252,17 @@ int launch_face(const char *timer, const PostParams &p, const PostPlan &pl, int 
     return LA_EUNSUPPORTED;
 }
 
-// the repeat face sits on top of the span + window one whatever is given: null pointers are "absent" inside the kernel.  Lane per state only
+// the repeat face sits on top of the span + window one whatever is given: null pointers are "absent" inside the kernel
 int launch_repeats(const char *timer, const RepParams &p, const PostPlan &pl, int batch, hipStream_t stream) {
     // static LDS of the widest form: two rows, fin, skip_s, deg_s, tgt_s (3 NT words with the repeat arcs), pair_s, rep_s
     static_assert((2 * (1024 + 4) + 2 + 1024) * sizeof(double) + (1024 / 2 + 1 + 1024 + 3 * 1024 + 1024 / 2) * sizeof(int32_t) <= 64 * 1024 &&
                       64 * 1024 <= kLdsBudget, "the arc lists with the repeat arcs fit the workgroup's LDS");
-    switch (pl.R ? 0 : pl.nw) {
+    switch (pl.R) {
+        case 2: return launch<posterior_strip_kernel<2, true, true, true>, RepParams>(timer, 1024, p, pl, batch, stream);
+        case 4: return launch<posterior_strip_kernel<4, true, true, true>, RepParams>(timer, 1024, p, pl, batch, stream);
+        case 8: return launch<posterior_strip_kernel<8, true, true, true>, RepParams>(timer, 1024, p, pl, batch, stream);
+    }
+    switch (pl.nw) {
         case 1:
             if (la::opts().viterbi_dpp) return launch<posterior_kernel<1, true, true, true, true>, RepParams>(timer, 64, p, pl, batch, stream);
             return launch<posterior_kernel<1, false, true, true, true>, RepParams>(timer, 64, p, pl, batch, stream);
@@ -1149,7 +1274,7 @@ int launch_repeats(const char *timer, const RepParams &p, const PostPlan &pl, in
     return LA_EUNSUPPORTED;
 }
 
-// What the five entries (and their workspace queries) differ in.  la_alignment_posteriors_lattice takes its face from the pointers that
+// What the six entries (and their workspace queries) differ in.  la_alignment_posteriors_lattice takes its face from the pointers that
 // are present, always writes the span outputs (so skip_stride is their row pitch whatever the face) and reports its label limit before
 // the strides; up to 511 labels its call then IS the matching entry's sweep, under that entry's timer.
 struct Entry {
@@ -1158,24 +1283,28 @@ struct Entry {
     size_t ws_align;      // the strip kernel moves alpha rows as 16-byte pieces
     bool span_outputs;    // present_prob and span_skip_prob are required
     bool limit_first;     // the label limit is reported before the stride checks (the other entries: after them)
+    bool repeats;         // takes the RepParams part (the REP faces)
     const char *over_entry, *over_query;   // the label-limit message of the entry and of its workspace query
 };
-enum EntryId { kPlain, kSpans, kWindows, kLattice, kRepeats };   // the first three are (int)Face of the entry's fixed face; kLattice, kRepeats: decided per call
+enum EntryId { kPlain, kSpans, kWindows, kLattice, kRepeats, kSong };   // the first three are (int)Face of the entry's fixed face; the others: decided per call
 static_assert(kPlain == (int)Face::Plain && kSpans == (int)Face::Spans && kWindows == (int)Face::Windows, "kEntries rows follow Face");
 constexpr char kOverLanes[] = "%s: max_labels %d exceeds 511", kOverStrip[] = "%s: max_labels %d exceeds 4095 (8192 lattice states per workgroup)";
 constexpr char kOverLanesQuery[] = "%s: max_labels %d exceeds 511 (one lane per lattice state, 1024 states per workgroup)";
-const Entry kEntries[5] = {
-    {face_names(Sweep::Posteriors, Face::Plain), 511, 8, false, false, kOverLanes, kOverLanesQuery},
-    {face_names(Sweep::Posteriors, Face::Spans), 511, 8, true, false, kOverLanes, kOverLanesQuery},
-    {face_names(Sweep::Posteriors, Face::Windows), 511, 8, true, false, kOverLanes, kOverLanesQuery},
-    {{"alignment_posteriors_lattice", "alignment_posteriors_lattice", "posterior_lattice"}, 4095, 16, true, true, kOverStrip, kOverStrip},
-    {{"alignment_posteriors_repeats", "alignment_posteriors_repeats", "posterior_repeats"}, 511, 8, true, true, kOverLanes, kOverLanesQuery}};
+// (la_alignment_posteriors_song is la_alignment_posteriors_repeats without the 511-label limit: up to 511 labels its call IS that
+// entry's sweep, under that entry's timer)
+const Entry kEntries[6] = {
+    {face_names(Sweep::Posteriors, Face::Plain), 511, 8, false, false, false, kOverLanes, kOverLanesQuery},
+    {face_names(Sweep::Posteriors, Face::Spans), 511, 8, true, false, false, kOverLanes, kOverLanesQuery},
+    {face_names(Sweep::Posteriors, Face::Windows), 511, 8, true, false, false, kOverLanes, kOverLanesQuery},
+    {{"alignment_posteriors_lattice", "alignment_posteriors_lattice", "posterior_lattice"}, 4095, 16, true, true, false, kOverStrip, kOverStrip},
+    {{"alignment_posteriors_repeats", "alignment_posteriors_repeats", "posterior_repeats"}, 511, 8, true, true, true, kOverLanes, kOverLanesQuery},
+    {{"alignment_posteriors_song", "alignment_posteriors_song", "posterior_song"}, 4095, 16, true, true, true, kOverStrip, kOverStrip}};
 
 int query_workspace(EntryId id, int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     const Entry &e = kEntries[id];
     LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "%s_workspace_bytes: bad arguments", e.names.query);
     PostPlan pl;
-    if (!plan_posterior(batch, max_frames, max_labels, e.label_limit, &pl)) {
+    if (!plan_posterior(batch, max_frames, max_labels, e.label_limit, &pl, e.repeats)) {
         la::set_error(e.over_query, e.names.query, max_labels);
         return LA_EUNSUPPORTED;
     }
@@ -1183,15 +1312,15 @@ int query_workspace(EntryId id, int32_t batch, int32_t max_frames, int32_t max_l
     return LA_OK;
 }
 
-// the five la_alignment_posteriors* entry points: p holds the caller's arguments, null / zero standing in for what the entry does not
+// the six la_alignment_posteriors* entry points: p holds the caller's arguments, null / zero standing in for what the entry does not
 // have (Windows: skip_from may be null, skip_stride stays the row pitch of span_skip_prob); the workspace fields are set here.  The
-// RepParams part is read for kRepeats only
+// RepParams part is read for kRepeats and kSong only
 int run_posteriors(EntryId id, RepParams p, int32_t batch, void *workspace, size_t workspace_bytes, hipStream_t stream) {
     const Entry &e = kEntries[id];
     const char *who = e.names.entry;
     if (batch == 0) return LA_OK;
-    Face face = (id == kLattice || id == kRepeats) ? Face::Plain : (Face)id;
-    if (id == kLattice || id == kRepeats) {
+    Face face = id >= kLattice ? Face::Plain : (Face)id;
+    if (id >= kLattice) {
         LA_CHECK_ARG((p.win_lo == nullptr) == (p.win_hi == nullptr), "%s: win_lo and win_hi go together (both null: no windows)", who);
         face = p.win_lo ? Face::Windows : p.skip_from ? Face::Spans : Face::Plain;
     }
@@ -1202,19 +1331,19 @@ int run_posteriors(EntryId id, RepParams p, int32_t batch, void *workspace, size
     LA_CHECK_ARG(p.window >= 0, "%s: negative boundary_window", who);
     // (la_alignment_posteriors has no penalty: 0.  The lattice entry checks the one it was given whatever the face)
     LA_CHECK_ARG(p.penalty >= 0.0, "%s: skip_penalty must be >= 0 (and not NaN)", who);
-    if (id == kRepeats) {
+    if (e.repeats) {
         LA_CHECK_ARG(p.repeat_count, "%s: null output pointer", who);
         LA_CHECK_ARG(p.repeat_penalty >= 0.0, "%s: repeat_penalty must be >= 0 (and not NaN)", who);
         LA_CHECK_ARG(!p.path_prob || p.path, "%s: path_prob needs the path it is asked about", who);
     }
     PostPlan pl;
-    const bool planned = plan_posterior(batch, p.max_frames, p.max_labels, e.label_limit, &pl);
+    const bool planned = plan_posterior(batch, p.max_frames, p.max_labels, e.label_limit, &pl, e.repeats);
     if (planned || !e.limit_first) {
         LA_CHECK_ARG(p.strides_ok(face, p.out_stride, true) && (!e.span_outputs || p.skip_stride >= p.max_labels + 1),
                      "%s: strides smaller than max_labels", who);
         LA_CHECK_ARG(!p.gamma || (p.gamma_rs >= 2 * (int64_t)p.max_labels + 1 && (batch == 1 || p.gamma_bs >= (int64_t)p.max_frames * p.gamma_rs)),
                      "%s: gamma strides smaller than [max_frames][2 max_labels + 1]", who);
-        if (id == kRepeats) {
+        if (e.repeats) {
             LA_CHECK_ARG(!p.repeat_from || p.repeat_stride >= p.max_labels, "%s: repeat_stride smaller than max_labels", who);
             LA_CHECK_ARG(!(p.path || p.path_prob) || p.path_stride >= p.max_frames, "%s: path_stride smaller than max_frames", who);
         }
@@ -1232,7 +1361,7 @@ int run_posteriors(EntryId id, RepParams p, int32_t batch, void *workspace, size
         p.acc_ws = reinterpret_cast<double *>(ws + pl.alpha_bytes);
         p.csr_ws = reinterpret_cast<int32_t *>(ws + pl.alpha_bytes + pl.acc_bytes);
     }
-    if (id == kRepeats) return launch_repeats(e.names.timer, p, pl, batch, stream);
+    if (e.repeats) return launch_repeats(pl.R ? e.names.timer : kEntries[kRepeats].names.timer, p, pl, batch, stream);
     const char *timer = pl.R ? e.names.timer : kEntries[(int)face].names.timer;
     int st = LA_EUNSUPPORTED;
     switch (face) {
@@ -1295,6 +1424,49 @@ extern "C" int la_alignment_posteriors_repeats_workspace_bytes(int32_t batch, in
     return query_workspace(kRepeats, batch, max_frames, max_labels, bytes);
 }
 
+extern "C" int la_alignment_posteriors_song_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
+    return query_workspace(kSong, batch, max_frames, max_labels, bytes);
+}
+
+namespace {
+// la_alignment_posteriors_repeats and la_alignment_posteriors_song: one argument list, two label limits
+int run_repeat_entry(EntryId id, const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels, int32_t labels_stride,
+                     const int32_t *n_labels, const int32_t *n_frames, int32_t batch, int32_t max_frames, int32_t max_labels,
+                     const int32_t *onset, const int32_t *offset, int32_t out_stride, int32_t boundary_window, const int32_t *skip_from,
+                     int32_t skip_stride, double skip_penalty, const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                     const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty, const int32_t *path, int32_t path_stride,
+                     float *occupancy, float *onset_prob, float *offset_prob, float *visits, float *span_skip_prob, float *repeat_count,
+                     float *path_prob, double *log_z, int32_t *status, float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                     void *workspace, size_t workspace_bytes, void *stream_) {
+    RepParams p{};
+    static_cast<PostParams &>(p) =
+        shared_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset, offset,
+                      out_stride, boundary_window, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride, occupancy, onset_prob,
+                      offset_prob, visits, span_skip_prob, log_z, status, gamma_out, gamma_batch_stride, gamma_row_stride);
+    p.repeat_from = repeat_from, p.repeat_stride = repeat_stride, p.repeat_penalty = repeat_penalty;
+    p.path = path, p.path_stride = path_stride, p.repeat_count = repeat_count, p.path_prob = path_prob;
+    return run_posteriors(id, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+}  // namespace
+
+extern "C" int la_alignment_posteriors_song(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
+                                            int32_t labels_stride, const int32_t *n_labels, const int32_t *n_frames, int32_t batch,
+                                            int32_t max_frames, int32_t max_labels, const int32_t *onset, const int32_t *offset,
+                                            int32_t out_stride, int32_t boundary_window, const int32_t *skip_from, int32_t skip_stride,
+                                            double skip_penalty, const int32_t *win_lo, const int32_t *win_hi, int32_t win_stride,
+                                            const int32_t *repeat_from, int32_t repeat_stride, double repeat_penalty,
+                                            const int32_t *path, int32_t path_stride, float *occupancy, float *onset_prob,
+                                            float *offset_prob, float *visits, float *span_skip_prob, float *repeat_count,
+                                            float *path_prob, double *log_z, int32_t *status, float *gamma_out,
+                                            int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
+                                            size_t workspace_bytes, void *stream_) {
+    return run_repeat_entry(kSong, em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, batch, max_frames,
+                            max_labels, onset, offset, out_stride, boundary_window, skip_from, skip_stride, skip_penalty, win_lo, win_hi,
+                            win_stride, repeat_from, repeat_stride, repeat_penalty, path, path_stride, occupancy, onset_prob, offset_prob,
+                            visits, span_skip_prob, repeat_count, path_prob, log_z, status, gamma_out, gamma_batch_stride, gamma_row_stride,
+                            workspace, workspace_bytes, stream_);
+}
+
 extern "C" int la_alignment_posteriors_repeats(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,
                                                int32_t labels_stride, const int32_t *n_labels, const int32_t *n_frames, int32_t batch,
                                                int32_t max_frames, int32_t max_labels, const int32_t *onset, const int32_t *offset,
@@ -1306,14 +1478,11 @@ extern "C" int la_alignment_posteriors_repeats(const float *em, int64_t em_batch
                                                float *path_prob, double *log_z, int32_t *status, float *gamma_out,
                                                int64_t gamma_batch_stride, int64_t gamma_row_stride, void *workspace,
                                                size_t workspace_bytes, void *stream_) {
-    RepParams p{};
-    static_cast<PostParams &>(p) =
-        shared_params(em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, max_frames, max_labels, onset, offset,
-                      out_stride, boundary_window, skip_from, skip_stride, skip_penalty, win_lo, win_hi, win_stride, occupancy, onset_prob,
-                      offset_prob, visits, span_skip_prob, log_z, status, gamma_out, gamma_batch_stride, gamma_row_stride);
-    p.repeat_from = repeat_from, p.repeat_stride = repeat_stride, p.repeat_penalty = repeat_penalty;
-    p.path = path, p.path_stride = path_stride, p.repeat_count = repeat_count, p.path_prob = path_prob;
-    return run_posteriors(kRepeats, p, batch, workspace, workspace_bytes, (hipStream_t)stream_);
+    return run_repeat_entry(kRepeats, em, em_batch_stride, em_row_stride, labels, labels_stride, n_labels, n_frames, batch, max_frames,
+                            max_labels, onset, offset, out_stride, boundary_window, skip_from, skip_stride, skip_penalty, win_lo, win_hi,
+                            win_stride, repeat_from, repeat_stride, repeat_penalty, path, path_stride, occupancy, onset_prob, offset_prob,
+                            visits, span_skip_prob, repeat_count, path_prob, log_z, status, gamma_out, gamma_batch_stride, gamma_row_stride,
+                            workspace, workspace_bytes, stream_);
 }
 
 extern "C" int la_alignment_posteriors(const float *em, int64_t em_batch_stride, int64_t em_row_stride, const int32_t *labels,

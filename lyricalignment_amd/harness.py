@@ -245,6 +245,21 @@ def _sheet_confidence(res, scores, lines: Sequence[str]):
     return out, {"sung": sung, "line_onset_prob": line_onset, "window_log_prob": float(scores["window_log_prob"])}
 
 
+def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable):
+    """-> (occurrences, conf) of align_record_lines(with_visit_confidence=True) from one clip's visits and its repeat / song score dict."""
+    occurrences = _line_occurrences(segments, lines)
+    per = [[[] for _ in occ] for occ in occurrences]
+    for v, (i, k, _) in zip(scores["visit_occupancy"], _occurrence_of_visits(segments, lines)):
+        per[i][k].append(v)
+    conf, pos = [], 0
+    for i, line in enumerate(lines):
+        conf.append({"visits": float(scores["visits"][pos]),
+                     "repeat_count": scores["repeat_count"].get((pos, pos + len(ids[i]))) if repeatable[i] else None,
+                     "occurrence_occupancy": [float(np.mean(v)) for v in per[i]]})
+        pos += len(ids[i])
+    return occurrences, conf
+
+
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
                        repeat_penalty: float = 0.0, with_visit_confidence: bool = False):
@@ -260,7 +275,7 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     chorus marked "x2"; AlignModel.align(repeat_spans=...), repeat_penalty >= 0 per return).  Each line's entry is then the LIST of its
     occurrences in time order, each [[onset, offset, char], ...] -- empty if the alignment left the line out.  Not with with_confidence
     (ValueError).
-    with_visit_confidence (with repeatable; at most 511 characters): -> (occurrences, conf), conf[i] = {"visits": the expected number of
+    with_visit_confidence (with repeatable; at most 511 characters -- align_song(repeatable=...) takes whole songs): -> (occurrences, conf), conf[i] = {"visits": the expected number of
     times line i was sung (AlignModel.align(return_repeat_confidence=True)'s `visits` of its first character: an expected count, it can
     exceed 1), "repeat_count": the expected number of returns of a repeatable line (None for the others), "occurrence_occupancy": one
     number per listed occurrence, the mean visit_occupancy of its characters}."""
@@ -279,17 +294,7 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
                 _, segments, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                                   repeat_spans=[repeat_spans], repeat_penalty=repeat_penalty, return_segments=True,
                                                   return_repeat_confidence=True)
-            occurrences = _line_occurrences(segments[0], lines)
-            per = [[[] for _ in occ] for occ in occurrences]
-            for v, (i, k, _) in zip(scores[0]["visit_occupancy"], _occurrence_of_visits(segments[0], lines)):
-                per[i][k].append(v)
-            conf, pos = [], 0
-            for i, line in enumerate(lines):
-                conf.append({"visits": float(scores[0]["visits"][pos]),
-                             "repeat_count": scores[0]["repeat_count"].get((pos, pos + len(ids[i]))) if repeatable[i] else None,
-                             "occurrence_occupancy": [float(np.mean(v)) for v in per[i]]})
-                pos += len(ids[i])
-            return occurrences, conf
+            return _visit_confidence(segments[0], scores[0], lines, ids, repeatable)
         with torch.no_grad():
             _, segments = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                       repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty,
@@ -361,7 +366,7 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
 
 
 def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
-               use_ctc_loss: bool = True, skip_penalty: float = 0.0):
+               use_ctc_loss: bool = True, skip_penalty: float = 0.0, repeatable: Optional[Sequence[bool]] = None, repeat_penalty: float = 0.0):
     """A whole song against its whole sheet, timing and confidences in one call (addition): up to 4095 characters.  `sheet` is LRC text
     (parse_lrc), a list of (start_seconds, line) pairs -- every line's first character anchored at its start time with tolerance_s, as in
     align_record_lrc -- or a list of plain lines (no times: no anchors, as in align_record_lines).  optional[i] marks lines that may be
@@ -369,7 +374,14 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     AlignModel.align(return_sheet_confidence=True): lines_out has one entry per line (None for a line left out), conf = {"sung": [per line],
     "line_onset_prob": [per line, None for a line left out], "window_log_prob": float <= 0 (0.0 for a sheet without times)}.  Up to 511
     characters the numbers are align_record_lrc's exactly.  The posterior sweep keeps every alpha row on the device: frames * 1024 R * 8
-    bytes beyond 511 characters (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095): 197 MB for a four-minute song of 800 characters."""
+    bytes beyond 511 characters (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095): 197 MB for a four-minute song of 800 characters.
+    repeatable (one flag per line; None: the call and its result as above): lines with repeatable[i] may be sung again right after they
+    were sung (a chorus printed once and marked "x2"; repeat_penalty >= 0 per return), as in align_record_lines(repeatable=...);
+    AlignModel.align(repeat_spans=..., return_song_confidence=True).  Each entry of lines_out is then the LIST of that line's occurrences
+    in time order, each [[onset, offset, char], ...] -- empty for a line left out.  conf keeps "sung" (the probability that the line was
+    sung at all: the expected visits of its first character that are not returns, visits - repeat_count), "line_onset_prob" (about the
+    first occurrence; None for a line left out) and "window_log_prob", and gains "visits", "repeat_count" and "occurrence_occupancy",
+    one value per line as align_record_lines(with_visit_confidence=True) defines them.  ValueError unless one flag per line."""
     if isinstance(sheet, str) or (len(sheet) > 0 and not isinstance(sheet[0], str)):
         pairs = _timed_lines("align_song", sheet)
         lines, starts = [line for _, line in pairs], [start for start, _ in pairs]
@@ -377,9 +389,24 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
         lines, starts = [str(line) for line in sheet], None
         if not lines:
             raise ValueError("align_song: no line in the sheet")
+    if repeatable is not None and len(repeatable) != len(lines):
+        raise ValueError(f"align_song: {len(repeatable)} repeatable flags for {len(lines)} lines")
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_song", lines, optional, lut, tokenize)
     kw = {} if starts is None else {"onset_anchors": [_line_anchors(starts, ids, tolerance_s)]}
+    if repeatable is not None:
+        from .utils.alignment import repeats_from_lines
+        repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
+        with torch.no_grad():
+            res, segments, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                                repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]],
+                                                repeat_penalty=repeat_penalty, return_segments=True, return_song_confidence=True, **kw)
+        occurrences, per_line = _visit_confidence(segments[0], scores[0], lines, ids, repeatable)
+        _, line_onset = _sheet_lines_out(res[0], lines, (lambda pos, first: None if first is None else float(scores[0]["onset_prob"][pos]),))
+        return occurrences, {"sung": [c["visits"] - (c["repeat_count"] or 0.0) for c in per_line], "line_onset_prob": line_onset,
+                             "window_log_prob": float(scores[0].get("window_log_prob", 0.0)),
+                             "visits": [c["visits"] for c in per_line], "repeat_count": [c["repeat_count"] for c in per_line],
+                             "occurrence_occupancy": [c["occurrence_occupancy"] for c in per_line]}
     with torch.no_grad():
         res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                   return_sheet_confidence=True, **kw)

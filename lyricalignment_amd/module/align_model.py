@@ -338,7 +338,8 @@ class AlignModel(torch.nn.Module):
               return_confidence: bool = False, boundary_window: int = 2, per_clip: bool = False, optional_spans=None,
               skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
-              repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False):
+              repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False,
+              return_song_confidence: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -400,8 +401,12 @@ class AlignModel(torch.nn.Module):
         optional_spans[b]), "visit_occupancy" (one number per entry of segments[b]: the mean posterior of the reported state over that
         visit's frames) and, where windows are given, "window_log_prob" (from a second sweep without them).  With no repeat span anywhere
         the numbers it shares with return_sheet_confidence are that keyword's exactly.  Up to 511 labels (NotImplementedError before
-        anything is launched).  With return_frames the DP's four tensors, (occupancy, onset_prob, offset_prob, log_z, visits,
-        span_skip_prob [, log_z_free with windows]) and path.  Not together with another confidence keyword (ValueError)."""
+        anything is launched; return_song_confidence takes whole songs).  With return_frames the DP's four tensors, (occupancy, onset_prob, offset_prob, log_z, visits,
+        span_skip_prob [, log_z_free with windows]) and path.  Not together with another confidence keyword (ValueError).
+        return_song_confidence (addition): whole songs -- return_repeat_confidence's return, with or without return_segments, for up to 4095
+        labels (ops.alignment_posteriors_song), with optional_spans, onset_anchors / char_windows, per_clip and the long form.  Up to 511
+        labels its numbers are return_repeat_confidence's exactly.  The sweep keeps every alpha row: T * 1024 R * 8 bytes per clip beyond
+        511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels).  Not together with another confidence keyword (ValueError)."""
         from ..utils.alignment import (POSTERIOR_MAX_LABELS, LatticeResult, _formatted, _formatted_repeat, _label_lists, _labels_to_device,
                                        _repeat_from_of_spans, _repeat_rows, _segments_from_path, _skip_from_of_spans, _windows_of, run_lattice)
         if return_anchored_confidence and (return_confidence or return_span_confidence):
@@ -410,6 +415,9 @@ class AlignModel(torch.nn.Module):
         if return_sheet_confidence and (return_confidence or return_span_confidence or return_anchored_confidence):
             raise ValueError("align: return_sheet_confidence does not go with return_confidence / return_span_confidence / "
                              "return_anchored_confidence (it returns their numbers at any size up to 4095 labels)")
+        if return_song_confidence and (return_confidence or return_span_confidence or return_anchored_confidence or return_sheet_confidence
+                                       or return_repeat_confidence):
+            raise ValueError("align: return_song_confidence does not go with another confidence keyword")
         if return_repeat_confidence:
             if return_confidence or return_span_confidence or return_anchored_confidence or return_sheet_confidence:
                 raise ValueError("align: return_repeat_confidence does not go with another confidence keyword")
@@ -439,8 +447,8 @@ class AlignModel(torch.nn.Module):
                              "keyword: return_span_confidence=True gives them)")
         confidence = ("sheet" if return_sheet_confidence else "anchored" if return_anchored_confidence else "span" if return_span_confidence
                       else "plain" if return_confidence else None)
-        if return_repeat_confidence:
-            confidence, repeat_from = "repeat", _repeat_from_of_spans(repeat_spans, lab_lists)
+        if return_repeat_confidence or return_song_confidence:
+            confidence, repeat_from = "song" if return_song_confidence else "repeat", _repeat_from_of_spans(repeat_spans, lab_lists)
         else:
             repeat_from = _repeat_rows("align", repeat_spans, return_segments, lab_lists, confidence is not None)
         # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
@@ -457,7 +465,7 @@ class AlignModel(torch.nn.Module):
             r = LatticeResult(*head)
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path)
             return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,))
-        if return_repeat_confidence:
+        if return_repeat_confidence or return_song_confidence:
             seconds, segments, scores = _formatted_repeat(r, lab_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
             return (seconds, segments, scores) if return_segments else (seconds, scores)
         seconds = _formatted(r, lab_lists, hop_size_second, optional_spans)

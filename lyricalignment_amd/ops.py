@@ -276,7 +276,26 @@ def alignment_posteriors_repeats(em: torch.Tensor, labels: torch.Tensor, n_label
     bit for bit, visits = its present_prob, repeat_count 0.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, visits [B,Lmax] f32, span_skip_prob [B,Lmax+1] f32,
     repeat_count [B,Lmax] f32, path_prob [B,T] f32 (gamma at the given path; None without a path) [, gamma [B,T,2*Lmax+1] f32]."""
-    who = "alignment_posteriors_repeats"
+    return _posteriors_repeats("alignment_posteriors_repeats", em, labels, n_labels, n_frames, onset, offset, skip_from, skip_penalty, win_lo,
+                               win_hi, repeat_from, repeat_penalty, path, boundary_window, want_gamma)
+
+
+def alignment_posteriors_song(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                              onset: torch.Tensor, offset: torch.Tensor, skip_from: Optional[torch.Tensor] = None,
+                              skip_penalty: float = 0.0, win_lo: Optional[torch.Tensor] = None, win_hi: Optional[torch.Tensor] = None,
+                              repeat_from: Optional[torch.Tensor] = None, repeat_penalty: float = 0.0,
+                              path: Optional[torch.Tensor] = None, boundary_window: int = 2, want_gamma: bool = False):
+    """la_alignment_posteriors_song: alignment_posteriors_repeats for whole songs, up to 4095 labels (NotImplementedError above, before a
+    launch); the same arguments and the same tuple.  Up to 511 labels the same kernel and the same bits; beyond, the strip form (R = 2 /
+    4 / 8 states per thread for up to 1023 / 2047 / 4095 labels), whose workspace holds every alpha row: B * T * 1024 R * 8 bytes."""
+    return _posteriors_repeats("alignment_posteriors_song", em, labels, n_labels, n_frames, onset, offset, skip_from, skip_penalty, win_lo,
+                               win_hi, repeat_from, repeat_penalty, path, boundary_window, want_gamma)
+
+
+def _posteriors_repeats(who, em, labels, n_labels, n_frames, onset, offset, skip_from, skip_penalty, win_lo, win_hi, repeat_from,
+                        repeat_penalty, path, boundary_window, want_gamma):
+    """The posteriors of the lattice with repeatable spans through one of its two entries (`who`, the stem of the C symbols): checks,
+    outputs, workspace and the C call."""
     if (win_lo is None) != (win_hi is None):
         raise ValueError(f"{who}: win_lo and win_hi go together")
     windows = None if win_lo is None else (win_lo, win_hi)
@@ -293,8 +312,10 @@ def alignment_posteriors_repeats(em: torch.Tensor, labels: torch.Tensor, n_label
     repeat_penalty = float(repeat_penalty)
     if not repeat_penalty >= 0.0:
         raise ValueError(f"{who}: repeat_penalty must be >= 0")
-    if Lmax > 511:
+    if who == "alignment_posteriors_repeats" and Lmax > 511:
         raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds 511 (the repeat lattice's posteriors are one lane per state)")
+    if Lmax > 4095:
+        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds 4095 (8192 lattice states per workgroup)")
     onset = onset.contiguous(); offset = offset.contiguous()
     dev = em.device
     occupancy, onset_prob, offset_prob, visits, repeat_count = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(5))
@@ -305,7 +326,7 @@ def alignment_posteriors_repeats(em: torch.Tensor, labels: torch.Tensor, n_label
     span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
     path_prob = torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None
     ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
-    check(lib().la_alignment_posteriors_repeats(
+    check(getattr(lib(), "la_" + who)(
         ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
         ptr(onset), ptr(offset), Lmax, int(boundary_window), *_face_args("lattice", skip_from, skip_stride, skip_penalty, windows),
         ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty,

@@ -319,12 +319,15 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     "repeat": the posteriors of that lattice (ops.alignment_posteriors_repeats on the DP's onset / offset / path; repeat_from None = no
     repeat span), up to 511 labels (NotImplementedError before anything is launched).  The eleven fields are filled as for "sheet" with
     `visits` (an expected count) in present_prob's place -- log_z_free from a second sweep without windows where windows were given,
-    None otherwise -- and repeat_count / path_prob are attributes of the result."""
-    if confidence not in (None, "plain", "span", "anchored", "sheet", "repeat"):
+    None otherwise -- and repeat_count / path_prob are attributes of the result.
+    "song": "repeat" without the label limit (whole songs, up to 4095 labels): ops.viterbi_repeats_batch, then ONE call of
+    ops.alignment_posteriors_song, and a second one without windows for log_z_free where windows were given.  Up to 511 labels its
+    numbers are "repeat"'s exactly."""
+    if confidence not in (None, "plain", "span", "anchored", "sheet", "repeat", "song"):
         raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
-    if repeat_from is not None or confidence == "repeat":
-        if confidence not in (None, "repeat"):
-            raise ValueError("run_lattice: on the lattice with repeatable spans the posteriors are confidence=\"repeat\" "
+    if repeat_from is not None or confidence in ("repeat", "song"):
+        if confidence not in (None, "repeat", "song"):
+            raise ValueError("run_lattice: on the lattice with repeatable spans the posteriors are confidence=\"repeat\" or \"song\" "
                              "(repeat_from does not go with the four older kinds)")
         if confidence == "repeat" and lab.shape[1] > POSTERIOR_MAX_LABELS:
             raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posteriors "
@@ -336,12 +339,13 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
         out = ops.viterbi_repeats_batch(em, lab, n_lab, nf, skip_dev, skip_penalty, *win, rep_dev, repeat_penalty)
         if confidence is None:
             return RepeatLatticeResult(*out)
-        post = ops.alignment_posteriors_repeats(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, *win, rep_dev, repeat_penalty,
-                                                out[4], boundary_window=boundary_window)
+        sweep = ops.alignment_posteriors_song if confidence == "song" else ops.alignment_posteriors_repeats
+        post = sweep(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, *win, rep_dev, repeat_penalty, out[4],
+                     boundary_window=boundary_window)
         log_z_free = None
         if windows is not None:
-            log_z_free = ops.alignment_posteriors_repeats(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, None, None, rep_dev,
-                                                          repeat_penalty, boundary_window=boundary_window)[3]
+            log_z_free = sweep(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, None, None, rep_dev, repeat_penalty,
+                               boundary_window=boundary_window)[3]
         return RepeatLatticeResult(*out, posteriors=(*post[:4], *post[5:7], log_z_free), repeat_count=post[7], path_prob=post[8])
     wide = lab.shape[1] > POSTERIOR_MAX_LABELS
     if wide and confidence not in (None, "sheet"):
@@ -441,7 +445,7 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, anchored=False, sheet=False, repeat_spans=None, repeat_penalty=0.0,
-             return_segments=False, repeat_scored=False):
+             return_segments=False, repeat_scored=False, song_scored=False):
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -458,13 +462,14 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     # (additions) optional spans and per-state frame windows; None / all-empty keywords take the reference's lattice unchanged
     skip_from = _skip_from_of_spans(optional_spans, lists)
     windows = _windows_of(char_windows, onset_anchors, lists, counts, hop_size_second)
+    repeat_scored = repeat_scored or song_scored
     if windows is not None and boundary_window is not None and not (anchored or sheet or repeat_scored):
         raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
                          "(perform_viterbi(_ctc)_anchored_scored give them)")
     confidence = "sheet" if sheet else "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
     if repeat_scored:
-        confidence, repeat_from = "repeat", _repeat_from_of_spans(repeat_spans, lists)
-        if lab.shape[1] > POSTERIOR_MAX_LABELS:
+        confidence, repeat_from = "song" if song_scored else "repeat", _repeat_from_of_spans(repeat_spans, lists)
+        if lab.shape[1] > POSTERIOR_MAX_LABELS and not song_scored:
             raise NotImplementedError(f"perform_viterbi_repeat_scored: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of "
                                       "the posteriors on the lattice with repeatable spans")
     else:
@@ -497,7 +502,7 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     The result keeps its shape: the FIRST visit per character, None for a character never visited.  ValueError for a < 0, a >= e, e > L
     or two spans with one start.  With optional_spans, char_windows / onset_anchors and n_frames, up to 4095 labels; the older _scored
     functions and anchored_alignment_loss raise ValueError with it (perform_viterbi(_ctc)_repeat_scored: its confidence, up to 511
-    labels).  None or all-empty: the call as it was.
+    labels; perform_viterbi(_ctc)_song_scored: up to 4095).  None or all-empty: the call as it was.
     return_segments (addition): -> (predicted_onset_offset, segments), segments[b] = the time-ordered list of (char_index, onset_s,
     offset_s) of EVERY visit, with or without repeat_spans."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
@@ -589,7 +594,7 @@ def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boun
     """perform_viterbi with repeat_spans plus the confidence of that lattice (addition): -> (predicted_onset_offset, scores), or
     (predicted_onset_offset, segments, scores) with return_segments.  The DP is la_viterbi_repeats_batch, the sweep
     la_alignment_posteriors_repeats, with or without optional_spans, char_windows / onset_anchors and n_frames; up to 511 labels
-    (NotImplementedError before anything is launched).  A path may visit a character more than once on this lattice, so some numbers are
+    (NotImplementedError before anything is launched; perform_viterbi_song_scored takes whole songs).  A path may visit a character more than once on this lattice, so some numbers are
     EXPECTED COUNTS, can exceed 1 and are not clamped.  scores[b] holds
       "occupancy", "onset_prob", "offset_prob" [L]: about the reported (first) visit; onset_prob / offset_prob count the visits that begin /
           end within boundary_window frames of the reported boundary (probabilities unless two visits can begin that close together);
@@ -614,6 +619,27 @@ def perform_viterbi_ctc_repeat_scored(prediction, labels, hop_size_second=0.02, 
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True)
+
+
+def perform_viterbi_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
+                                return_segments=False):
+    """Whole-song timing with repeated lines and its confidences (addition): perform_viterbi_repeat_scored's arguments and return values
+    for up to 4095 labels (la_viterbi_repeats_batch for the DP, la_alignment_posteriors_song for the posteriors).  Up to 511 labels
+    the numbers are perform_viterbi_repeat_scored's exactly.  The sweep's workspace holds every alpha row: T * 1024 R * 8 bytes per
+    utterance beyond 511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True)
+
+
+def perform_viterbi_ctc_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
+                                    skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
+                                    return_segments=False):
+    """perform_viterbi_ctc plus the whole-song confidences of the lattice with repeatable spans: see perform_viterbi_song_scored."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
+                    optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
