@@ -144,8 +144,9 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 
 // acc[mi][ni]: rows m = m0 + wm*64 + mi*16 + (lane & 15); cols n = n0 + wn*64 + ni*16 + (lane >> 4)*4 + reg
 // TA / TW (float32 only): that operand is stored transposed, [K][rows] with pitch lda / ldw (see stage_tile_t).  With a
-// transposed operand K need not be a multiple of the 32-element stage: the last stage's k >= K are masked out of the A
-// fragments (a K-contiguous operand must then have a row pitch that covers the rounded-up K: its tail reads stay in the row).
+// transposed operand K need not be a multiple of the 32-element stage: the last stage's k >= K are masked out of both
+// fragments (a K-contiguous operand must then have a row pitch that covers the rounded-up K: its tail reads stay in the row,
+// and what they return -- NaN and Inf included -- does not reach the result).
 template <typename T, typename C, bool TA = false, bool TW = false>
 __device__ __forceinline__ void mainloop(const T *A, int64_t lda, int M, const T *W, int64_t ldw, int N, int K,
                                          int m0, int n0, unsigned char *lds, f32x4 (&acc)[4][4]) {
@@ -199,6 +200,11 @@ __device__ __forceinline__ void mainloop(const T *A, int64_t lda, int M, const T
                         if (kb + 1 >= kvalid) af[i].y = 0u;
                         if (kb + 2 >= kvalid) af[i].z = 0u;
                         if (kb + 3 >= kvalid) af[i].w = 0u;
+                        // W too: behind column K a K-contiguous W holds whatever its pitch holds, and 0 x Inf, 0 x NaN are NaN
+                        if (kb + 0 >= kvalid) wf[i].x = 0u;
+                        if (kb + 1 >= kvalid) wf[i].y = 0u;
+                        if (kb + 2 >= kvalid) wf[i].z = 0u;
+                        if (kb + 3 >= kvalid) wf[i].w = 0u;
                     }
                 }
             }
