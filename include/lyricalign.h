@@ -137,6 +137,16 @@ int la_timer_read_work(double *total_ms, int64_t *timed_launches, double *timed_
  *   "gemm_epi16"      LA_GEMM_EPI16       1 = interior output tiles of the 256 x 256 kernel with a 16-bit result and no residual (plain / LayerNorm-
  *                                         consumer epilogues) run the epilogue arithmetic in the accumulator layout and cross the LDS transpose as
  *                                         16-bit values (default) | 0 = every tile crosses it as float32 (twice the staging; identical bits: A/B partner)
+ *   Cache policy of the streamed stores and loads of the 16-bit encoder's hot kernels, one option per site: a modifier bit of the same
+ *   instruction (where a line is kept, never what is written; identical bits under every value).  0 = the default cache policy (the
+ *   default of every option but cp_epi16); 1 = nt, the streaming hint; any other value -> LA_EINVAL.  Measurements: profiles/cache_policy.txt.
+ *   "cp_epi16"        LA_CP_EPI16         the 16-byte result stores of the 256 x 256 kernel's 16-bit staging (QKV, MLP-up): 1 = nt (default:
+ *                                         -0.8 ms of the 40 ms bf16 step) | 0 | 2 = sc1, write-through: the line leaves the XCD's L2 with the store
+ *   "cp_split_st"     LA_CP_SPLIT_ST      la_gemm_split: the interior tiles' stores of the hi and lo planes
+ *   "cp_split_ld"     LA_CP_SPLIT_LD      la_gemm_split in place: the interior tiles' loads of the incoming planes
+ *   "cp_gemm_a"       LA_CP_GEMM_A        the hand-placed main loop's LDS-DMA pieces of the A operand (16-bit and split-stream results); W keeps the default
+ *   "cp_attn_qo"      LA_CP_ATTN_QO       16-bit attention: the Q fragment loads and the output stores
+ *   "cp_attn_kv"      LA_CP_ATTN_KV       16-bit attention: the LDS-DMA pieces of the K / V tiles
  * A library built with -DLA_EXPERIMENTS (tools/build_variant.sh; la_has_experiments() == 1) additionally carries the measured-slower
  * GEMM kernel structures of rounds 2-4 and their per-launch developer switches; the shipped library has neither.  The attention
  * kernels have one form per (element type, workgroup size, LA_Q_LOG2) in every build; their timing knock-outs are compile-time masks

@@ -68,14 +68,14 @@ __device__ __forceinline__ KvOff<PER> kv_offsets(int64_t pitch, int key0, int T,
 }
 // this wave's pieces of two images that travel together -- a K and a V tile (skip1 = 0), or the hi and the lo plane of one operand tile
 // (src1 = src0, skip1 = the elements from a token's hi to its lo plane): src = the tile's first token row at the head's columns, buf = the
-// image's LDS address
-template <int PER>
+// image's LDS address.  POL (la_common.h CachePol, option cp_attn_kv): the cache policy in the text of the LDS-DMA pieces
+template <int PER, int POL = 0>
 __device__ __forceinline__ void stage_pair(const unsigned short *src0, const unsigned (&off0)[PER], unsigned buf0, const unsigned short *src1,
                                            int64_t skip1, const unsigned (&off1)[PER], unsigned buf1, int wave) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-        la::glds16_so(off0[i], src0, buf0 + (wave * PER + i) * 1024);
-        la::glds16_so(off1[i], src1 + skip1, buf1 + (wave * PER + i) * 1024);
+        la::glds16_so_pol<POL>(off0[i], src0, buf0 + (wave * PER + i) * 1024);
+        la::glds16_so_pol<POL>(off1[i], src1 + skip1, buf1 + (wave * PER + i) * 1024);
     }
 }
 

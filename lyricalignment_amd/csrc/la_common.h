@@ -48,6 +48,10 @@ void *stream_scratch(hipStream_t stream, int purpose, size_t bytes);
 struct Options {
     int gemm_tile = 0, gemm_loop = 0, gemm_splitk = 1, attn_nw = 0, gru_nw = 0, gru_fence = 0, gru_handoff = 0, gru_poll_delay = 0, viterbi_dpp = 1,
         head_clip_cap = 0, ln_fusion = 1, resid_split = 1, x2_inference = 1, gru_timeout_us = 0, gru_fault_step = 0, x2_small = 0, gemm_epi16 = 1;
+    // cache policy of the streamed stores and loads of the encoder's hot kernels, one field per site (CachePol below; DESIGN.md section 4,
+    // profiles/cache_policy.txt): 0 = the instruction as it always was.  cp_epi16 = 1 (nt on the QKV / MLP-up result stores) is the one
+    // setting that was faster inside the pipeline in every round (-0.8 ms of 40.3 per step); the others measured flat or slower and stay 0.
+    int cp_epi16 = 1, cp_split_st = 0, cp_split_ld = 0, cp_attn_qo = 0, cp_gemm_a = 0, cp_attn_kv = 0;
 };
 Options &opts();
 // Developer switches of the experiment build (-DLA_EXPERIMENTS, tools/build_variant.sh): re-read on every launch there, so that
@@ -306,8 +310,57 @@ __device__ __forceinline__ void glds16_so(unsigned voff, const void *sbase, unsi
                  : "v"(voff), "s"(sbase), "s"(m0_dst)
                  : "memory");
 }
+// the same with a cache policy in the instruction text (CP_NT: the streaming bit)
+template <int POL>
+__device__ __forceinline__ void glds16_so_pol(unsigned voff, const void *sbase, unsigned m0_dst) {
+    if constexpr (POL == 0) glds16_so(voff, sbase, m0_dst);
+    else {
+        static_assert(POL == 1, "LDS-DMA loads take the default policy or nt");
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt"
+                     :
+                     : "v"(voff), "s"(sbase), "s"(m0_dst)
+                     : "memory");
+    }
+}
 __device__ __forceinline__ unsigned lds_addr_u32(const void *p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
+}
+
+// ---- cache policy of a streamed vector-memory access (options cp_*) ----
+// A modifier bit of the instruction itself: where the line is kept, never what is written or read.  CP_NT = nt, the streaming hint; CP_WT =
+// sc1 on a store, agent-scope write-through: the line leaves the XCD's L2 with the store (16-byte stores only: narrower write-through stores
+// are one fabric write each).  Hand-off, flag and counter traffic never goes through these (la_gru.hip has its own forms).
+enum CachePol { CP_DEFAULT = 0, CP_NT = 1, CP_WT = 2 };
+typedef unsigned cp_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned cp_u32x4 __attribute__((ext_vector_type(4)));
+template <int BYTES> struct CpWord;
+template <> struct CpWord<4> { typedef unsigned type; };
+template <> struct CpWord<8> { typedef cp_u32x2 type; };
+template <> struct CpWord<16> { typedef cp_u32x4 type; };
+// *p = v with policy POL; V = a 4-, 8- or 16-byte value (one global_store_dword / dwordx2 / dwordx4 as before)
+template <int POL, typename P, typename V>
+__device__ __forceinline__ void store_pol(P *p, const V &v) {
+    if constexpr (POL == CP_DEFAULT) *reinterpret_cast<V *>(p) = v;
+    else {
+        typedef typename CpWord<sizeof(V)>::type W;
+        const W w = __builtin_bit_cast(W, v);
+        if constexpr (POL == CP_NT) __builtin_nontemporal_store(w, reinterpret_cast<W *>(p));
+        else {
+            static_assert(POL == CP_WT && sizeof(V) == 16, "write-through stores are 16 bytes wide");
+            // (s_nop 1: a store of more than 8 bytes reads its data registers for two more cycles; hipcc pads its own stores against an
+            //  overwrite by the next vector instruction and cannot see into this one)
+            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(w) : "memory");
+        }
+    }
+}
+template <int POL, typename V, typename P>
+__device__ __forceinline__ V load_pol(const P *p) {
+    if constexpr (POL == CP_DEFAULT) return *reinterpret_cast<const V *>(p);
+    else {
+        static_assert(POL == CP_NT, "loads take the default policy or nt");
+        typedef typename CpWord<sizeof(V)>::type W;
+        return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const W *>(p)));
+    }
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -106,7 +106,8 @@ __device__ __forceinline__ void epi_quad(f32x4 &v, const float (&b4)[4], const f
 // Rows 8-15 come back with their two quads exchanged (the half bit): the second read's registers are stored in the other order.
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-template <typename T16, int EQ>
+// POL (la_common.h CachePol, option cp_epi16): the cache policy of the tile's 16-byte row stores -- the same stores, another modifier bit.
+template <typename T16, int EQ, int POL = 0>
 __device__ __forceinline__ void wave_epilogue16(T16 *cw0, int64_t ldc, f32x4 (&acc)[8][4], bool has_bias, bool do_gelu, int epi, float bias_l,
                                                 float csum_l, unsigned char *reg, const float2 *stats_row, int lane) {
     // (opaque lane: hipcc must not start the 32 column fetches above the caller's main loop, where every register is spoken for)
@@ -151,8 +152,8 @@ __device__ __forceinline__ void wave_epilogue16(T16 *cw0, int64_t ldc, f32x4 (&a
                 }
             }
             if (mi > 0) {
-                *reinterpret_cast<u32x4 *>(cw + (int64_t)(mi * 16 - 16) * ldc) = lo;
-                *reinterpret_cast<u32x4 *>(cw + (int64_t)(mi * 16 - 8) * ldc) = u32x4{hi.z, hi.w, hi.x, hi.y};
+                la::store_pol<POL>(cw + (int64_t)(mi * 16 - 16) * ldc, lo);
+                la::store_pol<POL>(cw + (int64_t)(mi * 16 - 8) * ldc, u32x4{hi.z, hi.w, hi.x, hi.y});
             }
             asm volatile("" ::: "memory");
         }
@@ -176,7 +177,8 @@ __device__ __forceinline__ void wave_epilogue16(T16 *cw0, int64_t ldc, f32x4 (&a
 // (chunk c of row r at c ^ r: conflict-free for the transposing b128 writes and the row-major b128 reads) -- the persistent kernel's
 // form: 8 x 4 KiB = 32 KiB beside the four ring slots, so the NEXT tile's first stages can land in the ring under this epilogue.
 // Edge wave tiles always take the element-wise path below with the 32-row staging.
-template <bool OUT_F32, typename T16, int LNM, int STG = 0>
+// POL16: wave_epilogue16's POL (gemm_pp_kernel_cp's instantiations).
+template <bool OUT_F32, typename T16, int LNM, int STG = 0, int POL16 = 0>
 __device__ __forceinline__ void wave_epilogue(const GemmParams &p, int z, f32x4 (&acc)[8][4], int wrow0, int wcol0, bool has_bias,
                                               float bias_l, float csum_l, unsigned char *reg, const float2 *stats_tab = nullptr,
                                               int tile_m0 = 0, unsigned char *reg_edge = nullptr, float2 sr0 = float2{0.f, 1.f},
@@ -200,8 +202,8 @@ __device__ __forceinline__ void wave_epilogue(const GemmParams &p, int z, f32x4 
     // 16-byte stores go through the 16-bit staging; edge tiles and unaligned C stay on the forms below
     if constexpr (!OUT_F32 && STG == 0 && (LNM == 0 || LNM == 4)) {
         if ((epi & LA_EPI_STAGE16) && wrow0 + 128 <= p.M && wcol0 + 64 <= p.N && (p.ldc * (int64_t)sizeof(TC)) % 16 == 0 && (uintptr_t)C % 16 == 0) {
-            wave_epilogue16<T16, LNC ? 2 : 0>(C + (int64_t)wrow0 * p.ldc + wcol0, p.ldc, acc, has_bias, do_gelu, epi, bias_l, csum_l, reg,
-                                              LNC ? stats_tab + (wrow0 - tile_m0) : nullptr, lane);
+            wave_epilogue16<T16, LNC ? 2 : 0, POL16>(C + (int64_t)wrow0 * p.ldc + wcol0, p.ldc, acc, has_bias, do_gelu, epi, bias_l, csum_l, reg,
+                                                     LNC ? stats_tab + (wrow0 - tile_m0) : nullptr, lane);
             return;
         }
     }
@@ -373,7 +375,9 @@ __device__ __forceinline__ void wave_epilogue(const GemmParams &p, int z, f32x4 
 // leaves as hi = x rounded to T16 (p.C2: the next GEMM's raw A operand) and lo = one byte per element (p.C) -- 3 + 3 bytes per
 // element through HBM instead of the 4 + 4 + 2 of wave_epilogue's f32 stream with a 16-bit copy.  Same staging (through the
 // wave's LDS region, row-major quads), same order of operations on the f32 values as wave_epilogue<true, T16, 1>.
-template <typename T16, int STG = 0>
+// PST / PLD (la_common.h CachePol; options cp_split_st, cp_split_ld; gemm_pp_kernel_cp's instantiations): the cache policy of the interior
+// tiles' stores of the two planes and of their loads of the incoming planes (the stream in place: each row is read once per launch).
+template <typename T16, int STG = 0, int PST = 0, int PLD = 0>
 __device__ __forceinline__ void wave_epilogue_split(const GemmParams &p, int z, f32x4 (&acc)[8][4], int wrow0, int wcol0, bool has_bias,
                                                     float bias_l, unsigned char *reg, unsigned char *reg_edge = nullptr, int lane_in = -1) {
     constexpr int NPASS = STG ? 8 : 4, NIT = STG ? 4 : 8, RP = STG ? 16 : 32;    // as wave_epilogue
@@ -417,8 +421,14 @@ __device__ __forceinline__ void wave_epilogue_split(const GemmParams &p, int z, 
 #pragma unroll
                     for (int it = 0; it < NIT; ++it) {
                         const int64_t off = (int64_t)(h * RP + it * 4 + q) * p.ldc;
-                        tth[S][it] = *reinterpret_cast<const ushort4 *>(hiw + off);
-                        ttl[S][it] = *reinterpret_cast<const unsigned *>(low + off);
+                        // (policy 0 keeps its statements as they were written: the default kernel's code is the same to the instruction)
+                        if constexpr (PLD == 0) {
+                            tth[S][it] = *reinterpret_cast<const ushort4 *>(hiw + off);
+                            ttl[S][it] = *reinterpret_cast<const unsigned *>(low + off);
+                        } else {
+                            tth[S][it] = la::load_pol<PLD, ushort4>(hiw + off);
+                            ttl[S][it] = la::load_pol<PLD, unsigned>(low + off);
+                        }
                     }
                 }
             };
@@ -461,8 +471,13 @@ __device__ __forceinline__ void wave_epilogue_split(const GemmParams &p, int z, 
                     pk.x = la::split_encode<T16>(v[0], q0); pk.y = la::split_encode<T16>(v[1], q1);
                     pk.z = la::split_encode<T16>(v[2], q2); pk.w = la::split_encode<T16>(v[3], q3);
                     const int64_t off = (int64_t)(h * RP + rl) * p.ldc;
-                    *reinterpret_cast<ushort4 *>(hiw + off) = pk;
-                    *reinterpret_cast<unsigned *>(low + off) = la::pack_u8x4(q0, q1, q2, q3);
+                    if constexpr (PST == 0) {
+                        *reinterpret_cast<ushort4 *>(hiw + off) = pk;
+                        *reinterpret_cast<unsigned *>(low + off) = la::pack_u8x4(q0, q1, q2, q3);
+                    } else {
+                        la::store_pol<PST>(hiw + off, pk);
+                        la::store_pol<PST>(low + off, la::pack_u8x4(q0, q1, q2, q3));
+                    }
                     if (part) {
                         const float2 sg = segment_stats<T16>(pk);
                         if (r == 0) part[h * RP + rl] = sg;

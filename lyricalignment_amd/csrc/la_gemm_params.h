@@ -50,6 +50,12 @@ constexpr int LA_EPI_SPLIT_INPLACE = 1 << 20;    // the residual is the split st
 constexpr int LA_EPI_SPLIT_PASS32 = 1 << 21;     // (experiment build, LA_EPI_SPLIT_PASS=32) the 32-row passes without the one-pass-ahead requests
 constexpr int LA_EPI_STAGE16 = 1 << 22;         // option gemm_epi16: interior tiles of a 16-bit result without residual take wave_epilogue16
 constexpr int LA_EPI_Q4_PRIO = 1 << 23;          // (experiment build, LA_GEMM_Q4_PRIO=1) gemm_q4_kernel's prologue / epilogue at wave priority 3
+// Cache policy of a 256 x 256 launch (la_common.h CachePol; options cp_epi16, cp_split_st, cp_split_ld, cp_gemm_a), packed: the template
+// argument of gemm_pp_kernel_cp, whose instantiations are built in la_gemm_pp_cp_bf16.hip / la_gemm_pp_cp_f16.hip.  0 = gemm_pp_kernel itself.
+constexpr int PPCP_EPI16_MASK = 3;               // bits 0-1: stores of wave_epilogue16 (CP_NT | CP_WT)
+constexpr int PPCP_SPLIT_ST = 4;                 // the split-stream epilogue's stores of the hi and lo planes: nt
+constexpr int PPCP_SPLIT_LD = 8;                 // its loads of the incoming planes (in place): nt
+constexpr int PPCP_GEMM_A = 16;                  // the hand-placed loop's LDS-DMA pieces of the A operand (waves 4-7): nt
 
 // The 256 x 256 kernel by operand type (dtype: LA_BF16 | LA_F16).  launch_pp16: plain / LayerNorm-producer (p.C2) / LayerNorm-consumer
 // (p.ln_stats) epilogues by p's fields; launch_split16: the split residual stream's producers (la_gemm_split; p.C = lo, p.C2 = hi).
@@ -57,6 +63,10 @@ int launch_pp_bf16(GemmParams p, int batch, bool out_f32, hipStream_t stream);
 int launch_pp_f16(GemmParams p, int batch, bool out_f32, hipStream_t stream);
 int launch_split_bf16(GemmParams p, int batch, hipStream_t stream);
 int launch_split_f16(GemmParams p, int batch, hipStream_t stream);
+// the same launches with a non-zero cache policy cp (PPCP_* above); lnm = 0 plain 16-bit result | 2 LayerNorm consumer | 3 split stream;
+// p, duo as launch_pp / launch_split have prepared them
+int launch_pp_cp_bf16(GemmParams p, int batch, int lnm, bool duo, int cp, hipStream_t stream);
+int launch_pp_cp_f16(GemmParams p, int batch, int lnm, bool duo, int cp, hipStream_t stream);
 // la_gemm_f16x2 (la_f32x2.hip): float32 products as three f16 products over segmented K, f32 out, scale epilogue; batch = split-K slots
 int launch_x2_f16(GemmParams p, int batch, hipStream_t stream);
 

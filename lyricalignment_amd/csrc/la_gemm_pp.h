@@ -344,13 +344,15 @@ __device__ __forceinline__ void duo_setup(DuoCtx &c, const T16 *A, int64_t lda, 
 #ifndef LA_DUO_DIST
 #define LA_DUO_DIST 4
 #endif
-template <bool SEG = false>
+// DMAP (la_common.h CachePol, option cp_gemm_a): the cache policy in the text of this wave's LDS-DMA pieces, here and in duo_run -- a second
+// instantiation of the same stream, taken by the waves that carry the A image (4-7) of a launch that asks for it; never a branch inside it.
+template <bool SEG = false, int DMAP = 0>
 __device__ __forceinline__ void duo_issue_prologue(const DuoCtx &c) {
     constexpr int STAGE = 32768;
 #pragma unroll
     for (int st = 0; st < LA_DUO_DIST; ++st) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) glds16_so(c.voff[i], duo_stage_src<SEG>(c, st), c.piece0 + st * STAGE + i * 1024);
+        for (int i = 0; i < 4; ++i) glds16_so_pol<DMAP>(c.voff[i], duo_stage_src<SEG>(c, st), c.piece0 + st * STAGE + i * 1024);
     }
 }
 // PREFETCHED: stages 0 .. 3 were issued BEFORE the previous tile's epilogue (whose >= 24 vector-memory operations -- its stores --
@@ -362,7 +364,7 @@ __device__ __forceinline__ void duo_issue_prologue(const DuoCtx &c) {
 #ifndef LA_DUO_PROBE
 #define LA_DUO_PROBE 0
 #endif
-template <typename T16 = bf16_t, int STAT_WC = -1, bool PREFETCHED = false, bool SEG = false>
+template <typename T16 = bf16_t, int STAT_WC = -1, bool PREFETCHED = false, bool SEG = false, int DMAP = 0>
 __device__ __forceinline__ void duo_run(const DuoCtx &c, int K, f32x4 (&acc)[8][4] LA_STAMP_PARAM, float *sacc = nullptr) {
     constexpr int STAGE = 32768;
     const int ns = K / 32;
@@ -374,7 +376,7 @@ __device__ __forceinline__ void duo_run(const DuoCtx &c, int K, f32x4 (&acc)[8][
     const unsigned piece0 = c.piece0;
     unsigned voff[4] = {c.voff[0], c.voff[1], c.voff[2], c.voff[3]};
     auto issue1 = [&](const unsigned char *src, int slot, int i) __attribute__((always_inline)) {
-        glds16_so(voff[i], src, piece0 + slot * STAGE + i * 1024);
+        glds16_so_pol<DMAP>(voff[i], src, piece0 + slot * STAGE + i * 1024);
     };
     // (PREFETCHED -- the persistent kernel -- has its entry waits counted for distance 4: not to be run from a -DLA_DUO_DIST=3 build)
     if constexpr (PREFETCHED) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
@@ -461,7 +463,7 @@ __device__ __forceinline__ void duo_run(const DuoCtx &c, int K, f32x4 (&acc)[8][
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     LA_PP_BARRIER();
 }
-template <typename T16 = bf16_t, int STAT_WC = -1>
+template <typename T16 = bf16_t, int STAT_WC = -1, int DMAP = 0>
 __device__ __forceinline__ void mainloop_duo_asm(const T16 *A, int64_t lda, int M, const T16 *W, int64_t ldw, int N, int K,
                                                  int m0, int n0, unsigned char *lds, f32x4 (&acc)[8][4] LA_STAMP_PARAM,
                                                  float *sacc = nullptr) {
@@ -470,11 +472,11 @@ __device__ __forceinline__ void mainloop_duo_asm(const T16 *A, int64_t lda, int 
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_u32(lds));
     DuoCtx c;
     duo_setup<T16>(c, A, lda, M, W, ldw, N, m0, n0, lds0, wave, lane);
-    duo_issue_prologue(c);
+    duo_issue_prologue<false, DMAP>(c);
 #ifdef LA_TILE_STAMPS
-    duo_run<T16, STAT_WC, false>(c, K, acc, stamp_t1, sacc);
+    duo_run<T16, STAT_WC, false, false, DMAP>(c, K, acc, stamp_t1, sacc);
 #else
-    duo_run<T16, STAT_WC, false>(c, K, acc, sacc);
+    duo_run<T16, STAT_WC, false, false, DMAP>(c, K, acc, sacc);
 #endif
 }
 

@@ -20,107 +20,25 @@ static inline int set_tile_stamps_here(void *buf) {
 }
 #endif
 
+// The kernel's program is la_gemm_pp_kernel_body.h.  CP (la_gemm_params.h PPCP_*): the cache policy of its streamed accesses, compiled into
+// the instruction text -- gemm_pp_kernel is CP = 0, the instructions as they always were; gemm_pp_kernel_cp carries the other values
+// (options cp_epi16, cp_split_st, cp_split_ld, cp_gemm_a), one instantiation per combination, chosen per launch.
 template <bool OUT_F32, bool DUO, typename T16, int LNM = 0>
 __global__ __launch_bounds__(PP::THREADS, 2) void gemm_pp_kernel(GemmParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-#ifdef LA_TILE_STAMPS
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long stamp_t1 = stamp_t0;
-#endif
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int tile = xcd_remap(blockIdx.x, nwg);
-    const TileCoord tc = tile_coord_mb(tile, p.tiles_m, p.tiles_n, p.group, p.mblock);
-    const int m0 = tc.tm * PP::TM, n0 = tc.tn * PP::TN;
-    const int z = blockIdx.y;
-    const T16 *A = reinterpret_cast<const T16 *>(p.A) + (int64_t)z * p.strideA;
-    const T16 *W = reinterpret_cast<const T16 *>(p.W) + (int64_t)z * p.strideW;
-    const float *bias = p.bias ? p.bias + (int64_t)z * p.strideBias : nullptr;
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 2, wc = wave & 3;
-    const bool has_bias = (p.epilogue & LA_EPI_BIAS) && bias;
-    // Per-column epilogue operands are requested BEFORE the main loop, one column per lane (this wave's 64 columns), and
-    // handed to the row-major epilogue layout with ds_bpermute afterwards: all eight waves reach the epilogue together, so a load
-    // issued there is a fully exposed L2 round trip per tile.
-    const int ncol = min(n0 + wc * 64 + lane, p.N - 1);
-    const float bias_l = has_bias ? bias[ncol] : 0.f;
-    float csum_l = 0.f;
-    if constexpr (LNM == 2 || LNM == 4 || LNM == 6) csum_l = p.ln_csum[ncol];
-    // LNM == 2: the tile's 256 row statistics are requested here too (32 rows per wave) and handed to the epilogue through LDS after
-    // the main loop: loaded inside the epilogue they were one exposed L2 round trip per pass of 32 rows, four per tile.
-    float2 st_pre = make_float2(0.f, 1.f);
-    if constexpr (LNM == 2) {
-        if (lane < 32) st_pre = reinterpret_cast<const float2 *>(p.ln_stats)[min(m0 + wr * 128 + wc * 32 + lane, p.M - 1)];
-    }
-    if constexpr (LNM == 6) {                                                 // f16x2 products: (0, row scale) in the statistics' place
-        if (lane < 32) st_pre = make_float2(0.f, p.ln_stats[min(m0 + wr * 128 + wc * 32 + lane, p.M - 1)]);
-    }
-
-    f32x4 acc[8][4];
-#ifdef LA_TILE_STAMPS
-#define LA_STAMP_ARG , stamp_t1
-#else
-#define LA_STAMP_ARG
-#endif
-    float sacc[4] = {0.f, 0.f, 0.f, 0.f};
-    float2 *stats_tab = reinterpret_cast<float2 *>(lds + 120 * 1024);        // LNM == 4: inside ring slot 3, clear of the epilogue staging
-    if constexpr (LNM == 4) {
-        static_assert(DUO || LNM != 4, "the main loop takes the row statistics only in its hand-placed form");
-        const int wc_u = __builtin_amdgcn_readfirstlane(wc);
-        switch (wc_u) {                                                       // (the fragment registers are named at compile time)
-            case 0: mainloop_duo_asm<T16, 0>(A, p.lda, p.M, W, p.ldw, p.N, p.K, m0, n0, lds, acc LA_STAMP_ARG, sacc); break;
-            case 1: mainloop_duo_asm<T16, 1>(A, p.lda, p.M, W, p.ldw, p.N, p.K, m0, n0, lds, acc LA_STAMP_ARG, sacc); break;
-            case 2: mainloop_duo_asm<T16, 2>(A, p.lda, p.M, W, p.ldw, p.N, p.K, m0, n0, lds, acc LA_STAMP_ARG, sacc); break;
-            default: mainloop_duo_asm<T16, 3>(A, p.lda, p.M, W, p.ldw, p.N, p.K, m0, n0, lds, acc LA_STAMP_ARG, sacc); break;
-        }
-        // sum over the four lanes that hold one row's four k chunks, then (mean, rstd) of rows wr * 128 + (2 wc + i) * 16 + r
-        const float inv_k = 1.0f / (float)p.K;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float s1 = sacc[2 * i], s2 = sacc[2 * i + 1];
-            s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-            s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-            const float mean = s1 * inv_k;
-            const float var = fmaxf(fmaf(-mean, mean, s2 * inv_k), 0.f);
-            if (lane < 16) stats_tab[wr * 128 + (2 * wc + i) * 16 + lane] = make_float2(mean, 1.0f / sqrtf(var + 1e-5f));
-        }
-    } else if constexpr (LNM == 6) {
-        static_assert(DUO || LNM != 6, "the segmented-K loop is the hand-placed one");
-        mainloop_duo_seg_asm<T16>(A, p.lda, p.M, W, p.ldw, p.N, p.K, p.plane_a, p.plane_w, m0, n0, lds, acc);
-    } else if constexpr (DUO) {
-        mainloop_duo_asm<T16>(A, p.lda, p.M, W, p.ldw, p.N, p.K, m0, n0, lds, acc LA_STAMP_ARG);
-    } else {
-        mainloop_pp<T16>(A, p.lda, p.M, W, p.ldw, p.N, p.K, m0, n0, lds, acc);
-    }
-    if constexpr (LNM == 2 || LNM == 6) {
-        if (lane < 32) stats_tab[wr * 128 + wc * 32 + lane] = st_pre;       // (both main loops end behind a barrier: slot 3 is free)
-    }
-#ifdef LA_TILE_STAMPS
-    const unsigned long long stamp_t2 = __builtin_amdgcn_s_memrealtime();
-#endif
-
-    __syncthreads();
-    if constexpr (LNM == 3) {
-        // 16-row passes with the residual rows requested one pass ahead (default), or the 32-row passes (LA_EPI_SPLIT_PASS=32: A/B)
-        if (p.epilogue & LA_EPI_SPLIT_PASS32) wave_epilogue_split<T16, 0>(p, z, acc, m0 + wr * 128, n0 + wc * 64, has_bias, bias_l, lds + wave * (32 * EPI_PITCH));
-        else wave_epilogue_split<T16, 1>(p, z, acc, m0 + wr * 128, n0 + wc * 64, has_bias, bias_l, lds + wave * (32 * EPI_PITCH), lds + wave * (32 * EPI_PITCH));
-    } else wave_epilogue<OUT_F32, T16, LNM == 2 ? 4 : LNM>(p, z, acc, m0 + wr * 128, n0 + wc * 64, has_bias, bias_l, csum_l, lds + wave * (32 * EPI_PITCH), stats_tab, m0);
-#ifdef LA_TILE_STAMPS
-    if (threadIdx.x == 0 && g_tile_stamps) {
-        unsigned long long *o = g_tile_stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
-        o[0] = stamp_t0; o[1] = stamp_t1; o[2] = stamp_t2; o[3] = __builtin_amdgcn_s_memrealtime();
-        unsigned hw_id, xcc_id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
-        o[4] = hw_id; o[5] = xcc_id;
-        o[6] = tile;
-    }
-#endif
+    constexpr int CP = 0;
+#include "la_gemm_pp_kernel_body.h"
+}
+template <bool OUT_F32, bool DUO, typename T16, int LNM, int CP>
+__global__ __launch_bounds__(PP::THREADS, 2) void gemm_pp_kernel_cp(GemmParams p) {
+    static_assert(CP != 0, "CP = 0 is gemm_pp_kernel");
+#include "la_gemm_pp_kernel_body.h"
 }
 
-template <bool OUT_F32, bool DUO, typename T16, int LNM = 0>
+template <bool OUT_F32, bool DUO, typename T16, int LNM = 0, int CP = 0>
 int launch_pp_loop(GemmParams p, int batch, hipStream_t stream) {
-    auto kern = gemm_pp_kernel<OUT_F32, DUO, T16, LNM>;
+    void (*kern)(GemmParams);
+    if constexpr (CP == 0) kern = gemm_pp_kernel<OUT_F32, DUO, T16, LNM>;
+    else kern = gemm_pp_kernel_cp<OUT_F32, DUO, T16, LNM, CP>;
     static la::DeviceOnce attr_once;
     if (attr_once.pending()) {
         LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS));
@@ -170,6 +88,12 @@ int launch_pp(GemmParams p, int batch, hipStream_t stream) {
     }
     // option gemm_epi16: 16-bit results without a residual cross the epilogue's LDS transpose as 16-bit values (wave_epilogue16)
     if (!OUT_F32 && la::opts().gemm_epi16 && !((p.epilogue & LA_EPI_RESIDUAL) && p.residual)) p.epilogue |= LA_EPI_STAGE16;
+    // cache-policy options of the 16-bit results (the encoder's QKV and MLP-up launches): a launch that sets one runs gemm_pp_kernel_cp
+    if constexpr (!OUT_F32) {
+        const int cp = ((p.epilogue & LA_EPI_STAGE16) ? (la::opts().cp_epi16 & PPCP_EPI16_MASK) : 0) | (duo && la::opts().cp_gemm_a ? PPCP_GEMM_A : 0);
+        if (cp && (lnm == 0 || lnm == 2))
+            return std::is_same<T16, bf16_t>::value ? launch_pp_cp_bf16(p, batch, lnm, duo, cp, stream) : launch_pp_cp_f16(p, batch, lnm, duo, cp, stream);
+    }
     if (lnm == 2) return duo ? launch_pp_loop<OUT_F32, true, T16, 2>(p, batch, stream) : launch_pp_loop<OUT_F32, false, T16, 2>(p, batch, stream);
     if constexpr (OUT_F32) {
         if (lnm == 1) return duo ? launch_pp_loop<OUT_F32, true, T16, 1>(p, batch, stream) : launch_pp_loop<OUT_F32, false, T16, 1>(p, batch, stream);
@@ -188,7 +112,35 @@ int launch_split(GemmParams p, int batch, hipStream_t stream) {
         if (lab_try_launch(p, batch, true, 3, duo, stream, &rc)) return rc;
     }
 #endif
+    // cache-policy options of the split stream's producers (out-proj, MLP-down, the stem)
+    const int cp = (la::opts().cp_split_st ? PPCP_SPLIT_ST : 0) | (la::opts().cp_split_ld && (p.epilogue & LA_EPI_SPLIT_INPLACE) ? PPCP_SPLIT_LD : 0) |
+                   (duo && la::opts().cp_gemm_a ? PPCP_GEMM_A : 0);
+    if (cp) return std::is_same<T16, bf16_t>::value ? launch_pp_cp_bf16(p, batch, 3, duo, cp, stream) : launch_pp_cp_f16(p, batch, 3, duo, cp, stream);
     return duo ? launch_pp_loop<true, true, T16, 3>(p, batch, stream) : launch_pp_loop<true, false, T16, 3>(p, batch, stream);
+}
+
+// The policy instantiations' dispatch (la_gemm_pp_cp_bf16.hip / la_gemm_pp_cp_f16.hip): cp's combinations per epilogue family.
+template <bool OUT_F32, typename T16, int LNM, int CP>
+int launch_pp_cp_one(const GemmParams &p, int batch, bool duo, hipStream_t stream) {
+    if constexpr ((CP & PPCP_GEMM_A) != 0) return launch_pp_loop<OUT_F32, true, T16, LNM, CP>(p, batch, stream);      // (set for the hand-placed loop only)
+    else return duo ? launch_pp_loop<OUT_F32, true, T16, LNM, CP>(p, batch, stream) : launch_pp_loop<OUT_F32, false, T16, LNM, CP>(p, batch, stream);
+}
+template <typename T16>
+int launch_pp_cp(const GemmParams &p, int batch, int lnm, bool duo, int cp, hipStream_t stream) {
+#define LA_PPCP_CASE(OUT_F32, LNM, CP) case CP: return launch_pp_cp_one<OUT_F32, T16, LNM, CP>(p, batch, duo, stream);
+    if (lnm == 3) {
+        switch (cp) {
+            LA_PPCP_CASE(true, 3, 4) LA_PPCP_CASE(true, 3, 8) LA_PPCP_CASE(true, 3, 12) LA_PPCP_CASE(true, 3, 16)
+            LA_PPCP_CASE(true, 3, 20) LA_PPCP_CASE(true, 3, 24) LA_PPCP_CASE(true, 3, 28)
+        }
+    } else if (lnm == 2) {
+        switch (cp) { LA_PPCP_CASE(false, 2, 1) LA_PPCP_CASE(false, 2, 2) LA_PPCP_CASE(false, 2, 16) LA_PPCP_CASE(false, 2, 17) LA_PPCP_CASE(false, 2, 18) }
+    } else if (lnm == 0) {
+        switch (cp) { LA_PPCP_CASE(false, 0, 1) LA_PPCP_CASE(false, 0, 2) LA_PPCP_CASE(false, 0, 16) LA_PPCP_CASE(false, 0, 17) LA_PPCP_CASE(false, 0, 18) }
+    }
+#undef LA_PPCP_CASE
+    la::set_error("gemm: no kernel for cache policy %d of epilogue family %d", cp, lnm);
+    return LA_EINVAL;
 }
 
 }  // namespace gemm

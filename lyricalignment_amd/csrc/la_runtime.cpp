@@ -51,8 +51,9 @@ void *stream_scratch(hipStream_t stream, int purpose, size_t bytes) {
 
 // ---- options --------------------------------------------------------------------
 namespace {
-struct OptionDesc { const char *name, *env; int Options::*field; bool env_inverts; };
+struct OptionDesc { const char *name, *env; int Options::*field; bool env_inverts; int max_value = -1; };
 // env_inverts: the variable's presence (LA_GEMM_NO_SPLITK, LA_VITERBI_NO_DPP) switches the option OFF
+// max_value >= 0: the option takes 0 .. max_value and la_set_option refuses anything else (an environment value outside is ignored)
 const OptionDesc kOptions[] = {
     {"gemm_tile", "LA_GEMM_TILE", &Options::gemm_tile, false},       {"gemm_loop", "LA_PP_DBG", &Options::gemm_loop, false},
     {"gemm_splitk", "LA_GEMM_NO_SPLITK", &Options::gemm_splitk, true}, {"attn_nw", "LA_ATTN_NW", &Options::attn_nw, false},
@@ -63,6 +64,10 @@ const OptionDesc kOptions[] = {
     {"x2_inference", "LA_X2_INFERENCE", &Options::x2_inference, false}, {"x2_small", "LA_X2_SMALL", &Options::x2_small, false},
     {"gru_timeout_us", "LA_GRU_TIMEOUT_US", &Options::gru_timeout_us, false}, {"gru_fault_step", "LA_GRU_FAULT_STEP", &Options::gru_fault_step, false},
     {"gemm_epi16", "LA_GEMM_EPI16", &Options::gemm_epi16, false},
+    // cache policy per site (la_common.h CachePol): 1 = nt; cp_epi16 also 2 = write-through (its stores are 16 bytes wide)
+    {"cp_epi16", "LA_CP_EPI16", &Options::cp_epi16, false, 2},       {"cp_split_st", "LA_CP_SPLIT_ST", &Options::cp_split_st, false, 1},
+    {"cp_split_ld", "LA_CP_SPLIT_LD", &Options::cp_split_ld, false, 1}, {"cp_attn_qo", "LA_CP_ATTN_QO", &Options::cp_attn_qo, false, 1},
+    {"cp_gemm_a", "LA_CP_GEMM_A", &Options::cp_gemm_a, false, 1},    {"cp_attn_kv", "LA_CP_ATTN_KV", &Options::cp_attn_kv, false, 1},
 };
 }  // namespace
 
@@ -72,6 +77,7 @@ Options &opts() {
         for (const OptionDesc &d : kOptions) {
             const char *e = getenv(d.env);
             if (!e) continue;
+            if (d.max_value >= 0 && (atoi(e) < 0 || atoi(e) > d.max_value)) continue;
             v.*(d.field) = d.env_inverts ? 0 : atoi(e);
         }
         return v;
@@ -145,6 +151,10 @@ extern "C" int la_set_option(const char *name, int64_t value) {
     LA_CHECK_ARG(name, "set_option: null name");
     for (const la::OptionDesc &d : la::kOptions)
         if (strcmp(d.name, name) == 0) {
+            if (d.max_value >= 0 && (value < 0 || value > d.max_value)) {
+                la::set_error("set_option: '%s' takes 0 .. %d", name, d.max_value);
+                return LA_EINVAL;
+            }
             la::opts().*(d.field) = (int)value;
             return LA_OK;
         }

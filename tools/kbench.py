@@ -2,6 +2,8 @@
 """Kernel micro-benchmarks on the config-2 shapes (developer tool; run on the GPU box).
     python tools/kbench.py gemm|attn|gru|fc|all [--iters N]
     python tools/kbench.py epi16      option gemm_epi16 off / on on the QKV, MLP-up and plain 16-bit launches (shipped library)
+    python tools/kbench.py cp --cp cp_epi16=1,cp_gemm_a=1,cp_epi16=2+cp_gemm_a=1      cache-policy options (shipped library): each
+                                      comma-separated setting (+ joins options set together) against policy 0 and policy 0 against itself
 Interleaved rounds in one process, random operands (cdna guide rules 24/25).
 The A/B modes that flip developer switches per launch (gemm --variants 73, persist, q4, q4w, order, epi) need
 the EXPERIMENT build of the library: bash tools/build_variant.sh lab -DLA_EXPERIMENTS; LA_LIB_PATH=$PWD/ab/lab/liblyricalign_hip.so."""
@@ -280,6 +282,83 @@ def bench_epi16(iters, rounds=5):
         o_, n_ = sorted(res[0])[rounds // 2], sorted(res[1])[rounds // 2]
         print(f"epi16 {name:28s} 16-bit staging vs float32 staging: {100 * (o_ / n_ - 1):+.2f} % | identical bits: {same}", flush=True)
     _lib.set_option("gemm_epi16", prev)
+
+
+CP_OPTIONS = ("cp_epi16", "cp_split_st", "cp_split_ld", "cp_gemm_a", "cp_attn_qo", "cp_attn_kv")
+
+
+def bench_cp(iters, settings, rounds=7):
+    """Cache-policy options (include/lyricalign.h cp_*) on the launches they reach: the four GEMMs of an encoder block at M = 48000 with their
+    epilogues (QKV: LayerNorm consumer; MLP-up: + GELU; out-proj, MLP-down: the split stream in place) and the attention at 32 x 16 x 1500.
+    Per case and setting, interleaved rounds of three legs in one process -- policy 0, the setting, policy 0 again (the control: the same value
+    against itself) -- each leg `iters` launches back to back between two events, so that the chip sits at its power cap as inside the
+    pipeline.  Per leg: median and min..max over the rounds of the time per launch; raw outputs of the setting compared with policy 0's."""
+    M, B, T, H = 48000, 32, 1500, 16
+
+    def apply(setting):
+        for name in CP_OPTIONS:
+            _lib.set_option(name, setting.get(name, 0))
+
+    def leg(fn):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fn(); torch.cuda.synchronize()
+        s.record()
+        for _ in range(iters):
+            fn()
+        e.record(); torch.cuda.synchronize()
+        return s.elapsed_time(e) / iters * 1e3                   # us per launch
+
+    cases = []
+    for name, N, K, kind in (("qkv (LN consumer)", 3072, 1024, "ln"), ("mlp_up (LN consumer + GELU)", 4096, 1024, "ln_gelu"),
+                             ("out_proj (split stream)", 1024, 1024, "split"), ("mlp_down (split stream)", 1024, 4096, "split")):
+        def make(N=N, K=K, kind=kind):
+            a, w = rnd(M, K), rnd(N, K, scale=K ** -0.5)
+            bias = torch.randn(N, device="cuda")
+            if kind == "split":
+                hi0 = torch.randn(M, N, device="cuda").bfloat16()
+                hi, lo = hi0.clone(), torch.full((M, N), 128, dtype=torch.uint8, device="cuda")
+                def fresh():
+                    hi.copy_(hi0); lo.fill_(128)
+                return (lambda: ops.gemm_split(a, w, hi, lo, bias=bias * 1e-3, in_place=True)), fresh, (lambda: (hi.clone(), lo.clone()))
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            stats = torch.stack([torch.randn(M, device="cuda") * 0.01, torch.rand(M, device="cuda") + 0.5], dim=1).contiguous()
+            csum = torch.randn(N, device="cuda") * 0.1
+            return (lambda: ops.gemm(a, w, out, bias=bias, gelu=kind == "ln_gelu", ln_stats=stats, ln_csum=csum)), (lambda: None), (lambda: (out.clone(),))
+        sites = ("cp_split_st", "cp_split_ld", "cp_gemm_a") if kind == "split" else ("cp_epi16", "cp_gemm_a")
+        cases.append((f"gemm {name} N={N} K={K}", make, sites))
+
+    def make_attn():
+        qkv = rnd(B * T, 3 * H * 64)
+        qkv[:, : H * 64] *= 0.125
+        out = torch.empty(B * T, H * 64, device="cuda", dtype=torch.bfloat16)
+        return (lambda: ops.attention(qkv, B, T, H, out=out)), (lambda: None), (lambda: (out.clone(),))
+    cases.append((f"attention B={B} T={T} H={H}", make_attn, ("cp_attn_qo", "cp_attn_kv")))
+
+    try:
+        for cname, make, sites in cases:
+            todo = [st for st in settings if any(k in sites for k in st)]
+            if not todo:
+                continue
+            fn, fresh, snapshot = make()
+            for st in todo:
+                label = "+".join(f"{k}={v}" for k, v in st.items())
+                apply({}); fresh(); fn(); torch.cuda.synchronize(); ref = snapshot()
+                apply(st); fresh(); fn(); torch.cuda.synchronize(); got = snapshot()
+                same = all(torch.equal(r.view(torch.uint8), g.view(torch.uint8)) for r, g in zip(ref, got))
+                res = {"policy 0": [], label: [], "policy 0 again": []}
+                for rd in range(rounds):
+                    for key, setting in (("policy 0", {}), (label, st), ("policy 0 again", {})):
+                        apply(setting)
+                        res[key].append(leg(fn))
+                for key, ts in res.items():
+                    t = sorted(ts)
+                    print(f"cp {cname:45s} {key:40s}: median {t[len(t) // 2]:7.1f} us  min..max {t[0]:7.1f}..{t[-1]:7.1f}", flush=True)
+                m0, m1, m2 = (sorted(res[k])[rounds // 2] for k in ("policy 0", label, "policy 0 again"))
+                print(f"cp {cname:45s} {label}: {100 * (m1 / m0 - 1):+.2f} % against policy 0 | control (0 against 0) {100 * (m2 / m0 - 1):+.2f} % | identical bits: {same}", flush=True)
+            del fn, fresh, snapshot
+            torch.cuda.empty_cache()
+    finally:
+        apply({})
 
 
 def bench_f32emu(iters):
@@ -592,6 +671,8 @@ if __name__ == "__main__":
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--variants", default="", help="gemm: comma-separated LA_PP_DBG values to A/B in one process (first = reference)")
+    ap.add_argument("--cp", default="", help="cp: comma-separated cache-policy settings, e.g. cp_epi16=1,cp_epi16=2+cp_gemm_a=1")
+    ap.add_argument("--rounds", type=int, default=7, help="cp: interleaved rounds per setting")
     a = ap.parse_args()
     torch.manual_seed(0)
     if a.what == "gemm" and a.variants:
@@ -614,6 +695,10 @@ if __name__ == "__main__":
         sys.exit(0)
     if a.what == "epi16":
         bench_epi16(a.iters)
+        sys.exit(0)
+    if a.what == "cp":
+        specs = a.cp.split(",") if a.cp else [f"{n}=1" for n in CP_OPTIONS] + ["cp_epi16=2"]
+        bench_cp(a.iters, [{kv.split("=")[0]: int(kv.split("=")[1]) for kv in sp.split("+")} for sp in specs], a.rounds)
         sys.exit(0)
     if a.what == "attn_fwd":
         bench_attn_fwd(a.iters)
