@@ -593,7 +593,54 @@ int la_emissions_from_logits(const float *logits, int64_t batch_stride, int64_t 
                              float *em, int64_t em_batch_stride, int64_t em_row_stride, void *stream);
 
 /* ------------------------------------------------------------------------- */
-/* log-mel front end   (replaces whisper.audio.log_mel_spectrogram + pad_or_trim, */
+/* pronunciation alternatives: characters with several readings               */
+/*   (addition; the reference maps every character to one class)              */
+/* ------------------------------------------------------------------------- */
+/*
+ * A label position n of clip b may have a set of readings R_n = [labels[b][n], extra_1, ...] (class ids, the sheet's own class
+ * first).  Its lattice state is scored on the MERGED class: em[t][1+n] = log sum_a exp(em_a[t]) over its readings, a per-frame
+ * merge.  The emissions of every reading come from la_fc_emissions / la_emissions_from_logits run on the EXPANDED label list (all
+ * readings of position 0, then of position 1, ...); the two entries below sit in front of and behind the lattice entries, which run
+ * on the folded matrix unchanged.
+ *
+ * Expanded layout: em_x[b][t][0] is silence; columns 1 + alt_start[b][n] .. alt_start[b][n+1] are position n's readings in order.
+ * alt_start (device) is a CSR row of n_labels[b] + 1 int32 per clip, alt_start[b][0] = 0, non-decreasing, alt_start[b][n_labels[b]]
+ * <= max_columns; alt_stride is its row pitch in elements.  (Entries outside 0 .. max_columns are clamped into it, so a malformed
+ * row reads no memory outside the expanded row; an empty group folds to -inf.)
+ *
+ * la_emissions_merge_readings: em[b][t][0] = em_x[b][t][0] bit for bit; a position with one reading is copied bit for bit; with
+ * A >= 2 readings x_0 .. x_{A-1}: m = their float maximum, the result is -inf if m is -inf, otherwise
+ *     (float)((double)m + log(sum_a exp((double)x_a - (double)m)))
+ * summed in float64 in ascending a and rounded once.  Written: rows t < n_frames[b], columns 0 .. n_labels[b]; rows beyond, columns
+ * beyond and the stride padding are left untouched.  Strides are in elements and arbitrary (rows need no alignment; em_x rows hold
+ * max_columns + 1, em rows max_labels + 1 entries); em must not overlap em_x.  One read of the expanded rows, one write of the folded
+ * rows; no atomics and nothing shared between clips, so a clip's bits are the same alone and in a batch.
+ *
+ * la_reading_scores: which reading was sung, decided on the boundaries the DP chose (onset / offset [batch][out_stride], the lattice
+ * entries' outputs; with repeat spans the reported, first visit).  col_score[b][j] for every expanded column j <
+ * alt_start[b][n_labels[b]] = the float64 sum of em_x[b][t][1+j] over t ascending in [onset, offset) of the column's position: the
+ * segment's log-likelihood had the character been that reading throughout (sequential, so two calls agree bit for bit).
+ * reading[b][n] = the smallest a (0 = the sheet's own class) with the largest col_score[b][alt_start[b][n] + a].  A skipped position
+ * (onset -1) gets reading -1 and scores 0.  col_score rows hold max_columns doubles (col_stride), reading rows max_labels int32.
+ *
+ * Both: batch, max_frames, max_labels <= 0, a null pointer, max_columns < max_labels or a stride smaller than its width ->
+ * LA_EINVAL; more than 4095 labels or columns -> LA_EUNSUPPORTED (reported before the stride checks); answered on the host under the
+ * entry's name before anything is enqueued.  Neither entry synchronises, allocates or frees.
+ */
+int la_emissions_merge_readings(const float *em_x, int64_t emx_batch_stride, int64_t emx_row_stride,
+                                const int32_t *alt_start, int32_t alt_stride,
+                                const int32_t *n_labels, const int32_t *n_frames,
+                                int32_t batch, int32_t max_frames, int32_t max_labels, int32_t max_columns,
+                                float *em, int64_t em_batch_stride, int64_t em_row_stride, void *stream);
+
+int la_reading_scores(const float *em_x, int64_t emx_batch_stride, int64_t emx_row_stride,
+                      const int32_t *alt_start, int32_t alt_stride, const int32_t *n_labels,
+                      const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                      int32_t batch, int32_t max_frames, int32_t max_labels, int32_t max_columns,
+                      double *col_score, int32_t col_stride, int32_t *reading, int32_t reading_stride, void *stream);
+
+/* ------------------------------------------------------------------------- */
+/* log-mel front end  (replaces whisper.audio.log_mel_spectrogram + pad_or_trim, */
 /*                      call sites module/align_model.py:84,89,100,109)           */
 /* ------------------------------------------------------------------------- */
 /*

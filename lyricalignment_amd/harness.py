@@ -25,12 +25,38 @@ class PinyinClassLUT:
 
     def __init__(self, token_pinyin: Sequence[str], pinyin_lookup_table: dict):
         self.table = np.asarray([pinyin_lookup_table[p] for p in token_pinyin], dtype=np.int64)
+        self.lookup = dict(pinyin_lookup_table)
 
     def __call__(self, tokens) -> torch.Tensor:
         t = torch.as_tensor(tokens).clone().long()
         keep = t != -100
         t[keep] = torch.from_numpy(self.table)[t[keep]]
         return t
+
+    def readings_of(self, tokens, heteronyms) -> List[list]:
+        """Characters with several readings (addition; the table holds one syllable per character): tokens [B, L] token ids with -100 padding,
+        heteronyms = {token id: [syllable, ...]}, a caller-supplied dict of the further syllables a character may be sung as, resolved
+        through pinyin_lookup_table -> AlignModel.align's `alternatives`: per row the list of (position among the row's labels, [class id,
+        ...]) for every character with at least one class beside its own (the table's class and repeats are dropped).  ValueError for a
+        syllable the lookup table does not hold."""
+        out = []
+        for row in torch.as_tensor(tokens).long().tolist():
+            alts, n = [], 0
+            for tok in row:
+                if tok == -100:
+                    continue
+                own, extras = int(self.table[tok]), []
+                for syllable in heteronyms.get(tok, ()):
+                    if syllable not in self.lookup:
+                        raise ValueError(f"readings_of: syllable {syllable!r} of token {tok} is not in the pinyin lookup table")
+                    c = int(self.lookup[syllable])
+                    if c != own and c not in extras:
+                        extras.append(c)
+                if extras:
+                    alts.append((n, extras))
+                n += 1
+            out.append(alts)
+        return out
 
 
 PER_CLIP_MAX_SAMPLES = 3000 * 160 + 159        # the longest clip AlignModel.align(per_clip=True) takes: 3000 mel frames = 30 s
@@ -188,9 +214,27 @@ def _line_anchors(starts: Sequence[float], ids, tolerance_s: float) -> list:
     return anchors
 
 
-def _sheet_lines_out(res, lines: Sequence[str], per_line=()):
+def _reading_kw(lut: PinyinClassLUT, ids, heteronyms) -> dict:
+    """The keywords the sheet functions add to AlignModel.align for heteronyms (None: none): the alternatives of the one clip and
+    return_readings, so that every character entry can name the class that was sung."""
+    if heteronyms is None:
+        return {}
+    return {"alternatives": lut.readings_of(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long), heteronyms), "return_readings": True}
+
+
+def _align_sheet(model, reading_kw: dict, audio, labels, **kw):
+    """model.align on the one clip with _reading_kw's keywords -> (what the call returns without them, the clip's readings or None)."""
+    out = model.align([audio], labels, **kw, **reading_kw)
+    if not reading_kw:
+        return out, None
+    *rest, readings = out
+    return (rest[0] if len(rest) == 1 else tuple(rest)), readings[0]
+
+
+def _sheet_lines_out(res, lines: Sequence[str], per_line=(), readings=None):
     """One clip's per-character result -> one entry per line (None for a line left out: a span is taken or left as a whole, its characters
-    are None together), and for every f of per_line the list of f(position of the line's first character, its result)."""
+    are None together), and for every f of per_line the list of f(position of the line's first character, its result).  readings (the
+    clip's, AlignModel.align(return_readings=True)): every character entry gains the class id that was sung."""
     out: List[Optional[list]] = []
     extra = [[] for _ in per_line]
     pos = 0
@@ -198,19 +242,20 @@ def _sheet_lines_out(res, lines: Sequence[str], per_line=()):
         part = res[pos: pos + len(line)]
         for values, f in zip(extra, per_line):
             values.append(f(pos, part[0]))
+        out.append(None if part[0] is None else
+                   [[part[j][0], part[j][1], line[j]] + ([] if readings is None else [readings[pos + j][0]]) for j in range(len(line))])
         pos += len(line)
-        out.append(None if part[0] is None else [[part[j][0], part[j][1], line[j]] for j in range(len(line))])
     return (out, *extra)
 
 
-def _line_occurrences(segments, lines: Sequence[str]) -> List[list]:
+def _line_occurrences(segments, lines: Sequence[str], readings=None) -> List[list]:
     """One clip's visits (char_index, onset_s, offset_s) in time order -> per line the list of its occurrences, each [[onset, offset, char],
     ...]: a new occurrence of a line begins where a visit does not continue the line's last one (its character index does not go up)."""
     out: List[list] = [[] for _ in lines]
     for (n, on, off), (i, k, j) in zip(segments, _occurrence_of_visits(segments, lines)):
         if k == len(out[i]):
             out[i].append([])
-        out[i][k].append([on, off, lines[i][j]])
+        out[i][k].append([on, off, lines[i][j]] + ([] if readings is None else [readings[n][0]]))
     return out
 
 
@@ -238,16 +283,17 @@ def _timed_lines(who: str, lrc) -> List[tuple]:
     return pairs
 
 
-def _sheet_confidence(res, scores, lines: Sequence[str]):
+def _sheet_confidence(res, scores, lines: Sequence[str], readings=None):
     """-> (lines_out, conf) of align_record_lrc(with_confidence=True) from one clip's seconds and its anchored / sheet score dict."""
     out, sung, line_onset = _sheet_lines_out(res, lines, (lambda pos, first: float(scores["sung_prob"][pos]),
-                                                          lambda pos, first: None if first is None else float(scores["onset_prob"][pos])))
+                                                          lambda pos, first: None if first is None else float(scores["onset_prob"][pos])),
+                                                  readings)
     return out, {"sung": sung, "line_onset_prob": line_onset, "window_log_prob": float(scores["window_log_prob"])}
 
 
-def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable):
+def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable, readings=None):
     """-> (occurrences, conf) of align_record_lines(with_visit_confidence=True) from one clip's visits and its repeat / song score dict."""
-    occurrences = _line_occurrences(segments, lines)
+    occurrences = _line_occurrences(segments, lines, readings)
     per = [[[] for _ in occ] for occ in occurrences]
     for v, (i, k, _) in zip(scores["visit_occupancy"], _occurrence_of_visits(segments, lines)):
         per[i][k].append(v)
@@ -262,7 +308,7 @@ def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable):
 
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
-                       repeat_penalty: float = 0.0, with_visit_confidence: bool = False):
+                       repeat_penalty: float = 0.0, with_visit_confidence: bool = False, heteronyms=None):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
@@ -278,9 +324,13 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     with_visit_confidence (with repeatable; at most 511 characters -- align_song(repeatable=...) takes whole songs): -> (occurrences, conf), conf[i] = {"visits": the expected number of
     times line i was sung (AlignModel.align(return_repeat_confidence=True)'s `visits` of its first character: an expected count, it can
     exceed 1), "repeat_count": the expected number of returns of a repeatable line (None for the others), "occurrence_occupancy": one
-    number per listed occurrence, the mean visit_occupancy of its characters}."""
+    number per listed occurrence, the mean visit_occupancy of its characters}.
+    heteronyms (here, in align_record_lrc and in align_song; None: the outputs as above): {token id: [syllable, ...]}, the further syllables
+    a character may be sung as (PinyinClassLUT.readings_of; AlignModel.align(alternatives=..., return_readings=True)).  Every character
+    entry is then [onset, offset, char, class_id_sung]."""
     lines = list(lines)
     ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
+    rk = _reading_kw(lut, ids, heteronyms)
     if with_visit_confidence and repeatable is None:
         raise ValueError("align_record_lines: with_visit_confidence goes with repeatable (with_confidence is the keyword without it)")
     if repeatable is not None:
@@ -291,23 +341,23 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
         if with_visit_confidence:
             repeat_spans = [(a, e) for a, e in enumerate(repeat_from) if e >= 0]
             with torch.no_grad():
-                _, segments, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                                                  repeat_spans=[repeat_spans], repeat_penalty=repeat_penalty, return_segments=True,
-                                                  return_repeat_confidence=True)
-            return _visit_confidence(segments[0], scores[0], lines, ids, repeatable)
+                (_, segments, scores), readings = _align_sheet(
+                    model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                    repeat_spans=[repeat_spans], repeat_penalty=repeat_penalty, return_segments=True, return_repeat_confidence=True)
+            return _visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings)
         with torch.no_grad():
-            _, segments = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                                      repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty,
-                                      return_segments=True)
-        return _line_occurrences(segments[0], lines)
+            (_, segments), readings = _align_sheet(
+                model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty, return_segments=True)
+        return _line_occurrences(segments[0], lines, readings)
     with torch.no_grad():
         if with_confidence:
-            res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                                      return_span_confidence=True)
+            (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
+                                                   skip_penalty=skip_penalty, return_span_confidence=True)
             present = scores[0]["sung_prob"]
-            return _sheet_lines_out(res[0], lines, (lambda pos, first: float(present[pos]),))
-        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)[0]
-    return _sheet_lines_out(res, lines)[0]
+            return _sheet_lines_out(res[0], lines, (lambda pos, first: float(present[pos]),), readings)
+        res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)
+    return _sheet_lines_out(res[0], lines, (), readings)[0]
 
 
 _LRC_TAG = re.compile(r"\[([^\[\]]*)\]")
@@ -337,7 +387,7 @@ def parse_lrc(text: str) -> List[tuple]:
 
 
 def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
-                     use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False):
+                     use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, heteronyms=None):
     """One recording against an LRC sheet (addition): per-character timing from per-line start times.  `lrc` is LRC text (parse_lrc) or a
     list of (start_seconds, line) pairs; the first character of every line gets an onset anchor at the line's start time with tolerance_s
     (AlignModel.align(onset_anchors=...): the line starts within tolerance_s of its tag, and everything before it has ended by then).
@@ -350,23 +400,27 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
                                 the reported onset, None for a line that was left out],
             "window_log_prob": float <= 0, the log-probability the unanchored model gives to "the path respects every tag" -- near 0
                                when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}.
-    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song)."""
+    Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song).
+    heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung]."""
     pairs = _timed_lines("align_record_lrc", lrc)
     lines = [line for _, line in pairs]
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_record_lrc", lines, optional, lut, tokenize)
     anchors = _line_anchors([start for start, _ in pairs], ids, tolerance_s)
+    rk = _reading_kw(lut, ids, heteronyms)
     with torch.no_grad():
         if with_confidence:
-            res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                                      onset_anchors=[anchors], return_anchored_confidence=True)
-            return _sheet_confidence(res[0], scores[0], lines)
-        res = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty, onset_anchors=[anchors])[0]
-    return _sheet_lines_out(res, lines)[0]
+            (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
+                                                   skip_penalty=skip_penalty, onset_anchors=[anchors], return_anchored_confidence=True)
+            return _sheet_confidence(res[0], scores[0], lines, readings)
+        res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                     onset_anchors=[anchors])
+    return _sheet_lines_out(res[0], lines, (), readings)[0]
 
 
 def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
-               use_ctc_loss: bool = True, skip_penalty: float = 0.0, repeatable: Optional[Sequence[bool]] = None, repeat_penalty: float = 0.0):
+               use_ctc_loss: bool = True, skip_penalty: float = 0.0, repeatable: Optional[Sequence[bool]] = None, repeat_penalty: float = 0.0,
+               heteronyms=None):
     """A whole song against its whole sheet, timing and confidences in one call (addition): up to 4095 characters.  `sheet` is LRC text
     (parse_lrc), a list of (start_seconds, line) pairs -- every line's first character anchored at its start time with tolerance_s, as in
     align_record_lrc -- or a list of plain lines (no times: no anchors, as in align_record_lines).  optional[i] marks lines that may be
@@ -381,7 +435,9 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     in time order, each [[onset, offset, char], ...] -- empty for a line left out.  conf keeps "sung" (the probability that the line was
     sung at all: the expected visits of its first character that are not returns, visits - repeat_count), "line_onset_prob" (about the
     first occurrence; None for a line left out) and "window_log_prob", and gains "visits", "repeat_count" and "occurrence_occupancy",
-    one value per line as align_record_lines(with_visit_confidence=True) defines them.  ValueError unless one flag per line."""
+    one value per line as align_record_lines(with_visit_confidence=True) defines them.  ValueError unless one flag per line.
+    heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung], and the confidences are
+    posteriors of the merged classes."""
     if isinstance(sheet, str) or (len(sheet) > 0 and not isinstance(sheet[0], str)):
         pairs = _timed_lines("align_song", sheet)
         lines, starts = [line for _, line in pairs], [start for start, _ in pairs]
@@ -394,23 +450,25 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_song", lines, optional, lut, tokenize)
     kw = {} if starts is None else {"onset_anchors": [_line_anchors(starts, ids, tolerance_s)]}
+    rk = _reading_kw(lut, ids, heteronyms)
     if repeatable is not None:
         from .utils.alignment import repeats_from_lines
         repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
         with torch.no_grad():
-            res, segments, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                                                repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]],
-                                                repeat_penalty=repeat_penalty, return_segments=True, return_song_confidence=True, **kw)
-        occurrences, per_line = _visit_confidence(segments[0], scores[0], lines, ids, repeatable)
+            (res, segments, scores), readings = _align_sheet(
+                model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty, return_segments=True,
+                return_song_confidence=True, **kw)
+        occurrences, per_line = _visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings)
         _, line_onset = _sheet_lines_out(res[0], lines, (lambda pos, first: None if first is None else float(scores[0]["onset_prob"][pos]),))
         return occurrences, {"sung": [c["visits"] - (c["repeat_count"] or 0.0) for c in per_line], "line_onset_prob": line_onset,
                              "window_log_prob": float(scores[0].get("window_log_prob", 0.0)),
                              "visits": [c["visits"] for c in per_line], "repeat_count": [c["repeat_count"] for c in per_line],
                              "occurrence_occupancy": [c["occurrence_occupancy"] for c in per_line]}
     with torch.no_grad():
-        res, scores = model.align([audio], labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                                  return_sheet_confidence=True, **kw)
-    return _sheet_confidence(res[0], scores[0], lines)
+        (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
+                                               skip_penalty=skip_penalty, return_sheet_confidence=True, **kw)
+    return _sheet_confidence(res[0], scores[0], lines, readings)
 
 
 def lrc_training_clips(audio, lrc, tokenize, max_seconds: float = 30.0, tolerance_s: float = 1.0, sample_rate: int = 16000) -> List[dict]:

@@ -339,7 +339,7 @@ class AlignModel(torch.nn.Module):
               skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
               repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False,
-              return_song_confidence: bool = False):
+              return_song_confidence: bool = False, alternatives=None, return_readings: bool = False):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -406,9 +406,24 @@ class AlignModel(torch.nn.Module):
         return_song_confidence (addition): whole songs -- return_repeat_confidence's return, with or without return_segments, for up to 4095
         labels (ops.alignment_posteriors_song), with optional_spans, onset_anchors / char_windows, per_clip and the long form.  Up to 511
         labels its numbers are return_repeat_confidence's exactly.  The sweep keeps every alpha row: T * 1024 R * 8 bytes per clip beyond
-        511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels).  Not together with another confidence keyword (ValueError)."""
+        511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels).  Not together with another confidence keyword (ValueError).
+        alternatives (addition): characters with several readings -- alternatives[b] = [(n, [class, ...]), ...]: label n of clip b may also be
+        sung as one of these classes (at most 8 readings per position, the sheet's own class included, and at most 4095 expanded columns
+        per clip: ValueError / NotImplementedError before anything is launched).  The head runs on the expanded label list, its emissions
+        are folded per frame into the merged class, log sum exp over the position's readings (ops.merge_readings), and the lattice runs on
+        the folded matrix; two neighbouring positions count as the same label exactly when their reading sets are equal.  With every other
+        keyword, per_clip and the long form; occupancy, sung_prob and the other confidences are then posteriors of the merged class.  None
+        or all-empty: the call as it was.
+        return_readings (addition; with alternatives, ValueError without): the return gains `readings` as its last element (a bare seconds
+        becomes (seconds, readings)): readings[b][n] = (class id sung, [score per reading, the sheet's own class first]), None for a skipped
+        character; a reading's score is the sum of its emissions over the segment the DP chose (the reported, first visit), the class the
+        smallest index with the largest score (ops.reading_scores).  With return_frames two more tensors: reading [B, Lmax] int32 (index
+        into the position's readings, -1 = skipped) and col_score [B, columns] float64."""
         from ..utils.alignment import (POSTERIOR_MAX_LABELS, LatticeResult, _formatted, _formatted_repeat, _label_lists, _labels_to_device,
-                                       _repeat_from_of_spans, _repeat_rows, _segments_from_path, _skip_from_of_spans, _windows_of, run_lattice)
+                                       _readings_from_scores, _readings_of, _repeat_from_of_spans, _repeat_rows, _segments_from_path,
+                                       _skip_from_of_spans, _windows_of, readings_route, run_lattice)
+        if return_readings and alternatives is None:
+            raise ValueError("align: return_readings goes with alternatives (without them every character has the one reading of its label)")
         if return_anchored_confidence and (return_confidence or return_span_confidence):
             raise ValueError("align: return_anchored_confidence does not go with return_confidence / return_span_confidence (it returns "
                              "their numbers on the windowed lattice)")
@@ -424,6 +439,7 @@ class AlignModel(torch.nn.Module):
             widest = max((len(l) for l in _label_lists(labels, len(labels))), default=0)
             if widest > POSTERIOR_MAX_LABELS:
                 raise NotImplementedError(f"align: {widest} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
+        rd = None if alternatives is None else _readings_of(alternatives, _label_lists(labels, len(labels)), keep_empty=return_readings)
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -453,23 +469,40 @@ class AlignModel(torch.nn.Module):
             repeat_from = _repeat_rows("align", repeat_spans, return_segments, lab_lists, confidence is not None)
         # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
         need_em = confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
-        head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN,
-                                       want_emissions=need_em, **kw)
-        if need_em:
+        variant = _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN
+        route = None
+        if rd is not None:
+            # pronunciation alternatives: the fused head runs on the EXPANDED labels for their emissions (with its time-out recovery); its own
+            # DP result on that list is meaningless and is dropped without looking at its status.  The folded matrix goes through the
+            # lattice with the set-equality ids in the labels' place.
             nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same bits;
-            # the sheet confidence keeps the fused head's, which run_lattice uses only where there is neither a span nor a window)
-            r = run_lattice(head[4], lab_dev, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
-                            dp=None if return_anchored_confidence else head[:4], repeat_from=repeat_from, repeat_penalty=repeat_penalty)
+            route = readings_route(rd, lambda lab_x, n_x: eng.align_feats_checked(feats, B, T, stride, lab_x, n_x, variant,
+                                                                                 want_emissions=True, **kw)[4], n_lab, nf, eng.device)
+            r = run_lattice(route.em, route.lattice_ids, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
+                            repeat_from=repeat_from, repeat_penalty=repeat_penalty)
         else:
-            r = LatticeResult(*head)
-        if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path)
-            return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,))
+            head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, variant, want_emissions=need_em, **kw)
+            if need_em:
+                nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
+                # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same
+                # bits; the sheet confidence keeps the fused head's, which run_lattice uses only where there is neither a span nor a window)
+                r = run_lattice(head[4], lab_dev, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
+                                dp=None if return_anchored_confidence else head[:4], repeat_from=repeat_from, repeat_penalty=repeat_penalty)
+            else:
+                r = LatticeResult(*head)
+        picked = route.scores(n_lab, r.onset, r.offset) if return_readings else ()
+        if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path);
+            return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,)) + picked     # reading, col_score last
         if return_repeat_confidence or return_song_confidence:
             seconds, segments, scores = _formatted_repeat(r, lab_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
-            return (seconds, segments, scores) if return_segments else (seconds, scores)
-        seconds = _formatted(r, lab_lists, hop_size_second, optional_spans)
-        return (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
+            out = (seconds, segments, scores) if return_segments else (seconds, scores)
+        else:
+            seconds = _formatted(r, lab_lists, hop_size_second, optional_spans)
+            out = (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
+        if not return_readings:
+            return out
+        readings = _readings_from_scores(*picked, rd)
+        return (*out, readings) if isinstance(out, tuple) else (out, readings)
 
 
 def encoder_only_engine(whisper_model, mel: torch.Tensor) -> torch.Tensor:

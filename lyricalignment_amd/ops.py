@@ -354,6 +354,65 @@ def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: 
     return em
 
 
+def _readings_inputs(who: str, em_x: torch.Tensor, alt_start: torch.Tensor, n_labels: torch.Tensor):
+    """The checks merge_readings and reading_scores share: em_x [B,T,>=1+max_columns] f32, alt_start [B,>=Lmax+1] i32, n_labels [B] i32
+    (device, unit inner strides) -> B, T, max_columns (what the expanded rows hold)."""
+    _dev(em_x, "em_x", torch.float32); _dev(alt_start, "alt_start", torch.int32); _dev(n_labels, "n_labels", torch.int32)
+    if em_x.dim() != 3 or alt_start.dim() != 2 or em_x.stride(2) != 1 or alt_start.stride(1) != 1:
+        raise ValueError(f"{who}: em_x [B,T,E] / alt_start [B,Lmax+1] with unit inner stride expected")
+    B, T, E = em_x.shape
+    if alt_start.shape[0] != B or alt_start.shape[1] < 2 or n_labels.shape != (B,) or E < alt_start.shape[1]:
+        raise ValueError(f"{who}: inconsistent shapes")
+    return B, T, E - 1
+
+
+def merge_readings(em_x: torch.Tensor, alt_start: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """la_emissions_merge_readings: the expanded compact emissions em_x [B,T,1+columns] f32 (silence, then every position's readings in
+    order) folded into the matrix the lattice reads, em [B,T,Lmax+1]: a position's column is log sum exp over its readings (float64,
+    rounded once; one reading: copied bit for bit).  alt_start [B,Lmax+1] i32: the CSR rows (columns 1 + alt_start[b,n] ..
+    alt_start[b,n+1] are position n's), n_labels / n_frames [B] i32; all on the device.  Rows t >= n_frames[b] and columns beyond
+    n_labels[b] are not written (out: a caller's [B,T,>=Lmax+1] tensor, e.g. to keep what it holds there)."""
+    who = "merge_readings"
+    B, T, max_columns = _readings_inputs(who, em_x, alt_start, n_labels)
+    _dev(n_frames, "n_frames", torch.int32)
+    Lmax = alt_start.shape[1] - 1
+    if n_frames.shape != (B,):
+        raise ValueError(f"{who}: inconsistent shapes")
+    if out is None:
+        out = torch.empty((B, T, Lmax + 1), dtype=torch.float32, device=em_x.device)
+    else:
+        _dev(out, "out", torch.float32)
+        if out.dim() != 3 or out.shape[0] != B or out.shape[1] != T or out.shape[2] < Lmax + 1 or out.stride(2) != 1:
+            raise ValueError(f"{who}: out [B,T,>=Lmax+1] with unit inner stride expected")
+    check(lib().la_emissions_merge_readings(ptr(em_x), em_x.stride(0), em_x.stride(1), ptr(alt_start), alt_start.stride(0),
+                                            ptr(n_labels.contiguous()), ptr(n_frames.contiguous()), B, T, Lmax, max_columns, ptr(out),
+                                            out.stride(0), out.stride(1), stream_ptr()), who)
+    return out
+
+
+def reading_scores(em_x: torch.Tensor, alt_start: torch.Tensor, n_labels: torch.Tensor, onset: torch.Tensor, offset: torch.Tensor
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """la_reading_scores: which reading was sung, on the boundaries the DP chose.  em_x / alt_start / n_labels as merge_readings, onset /
+    offset [B,Lmax] i32 (a lattice entry's outputs).  -> reading [B,Lmax] i32 (index into the position's readings, 0 = the sheet's own
+    class, the smallest index with the largest score; -1 for a skipped position) and col_score [B,columns] f64 (per expanded column the
+    sequential float64 sum of its emissions over its position's segment; 0 for a skipped position).  Entries beyond a clip's own labels
+    / columns are unspecified."""
+    who = "reading_scores"
+    B, T, max_columns = _readings_inputs(who, em_x, alt_start, n_labels)
+    _dev(onset, "onset", torch.int32); _dev(offset, "offset", torch.int32)
+    Lmax = alt_start.shape[1] - 1
+    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
+        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
+    onset = onset.contiguous(); offset = offset.contiguous()
+    reading = torch.empty((B, Lmax), dtype=torch.int32, device=em_x.device)
+    col_score = torch.empty((B, max_columns), dtype=torch.float64, device=em_x.device)
+    check(lib().la_reading_scores(ptr(em_x), em_x.stride(0), em_x.stride(1), ptr(alt_start), alt_start.stride(0),
+                                  ptr(n_labels.contiguous()), ptr(onset), ptr(offset), Lmax, B, T, Lmax, max_columns, ptr(col_score),
+                                  max_columns, ptr(reading), Lmax, stream_ptr()), who)
+    return reading, col_score
+
+
 # --------------------------------------------------------------------------- #
 # encoder / head building blocks                                                #
 # --------------------------------------------------------------------------- #

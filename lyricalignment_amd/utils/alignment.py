@@ -123,6 +123,106 @@ def _repeat_from_of_spans(repeat_spans, label_lists: List[List[int]]):
     return rows if any_span else None
 
 
+MAX_READINGS = 8                # readings per label position, the sheet's own class included
+MAX_READING_COLUMNS = 4095      # expanded columns per clip: what the head, the prep and the fold take
+READING_SET_ID = 1 << 24        # lattice id of a clip's k-th distinct multi-reading set: READING_SET_ID + k (class ids lie far below)
+
+
+class Readings(NamedTuple):
+    """_readings_of's result (host): what the route with pronunciation alternatives needs beside the labels."""
+    labels_x: torch.Tensor          # [B, Xmax] int32: the expanded label rows -- every position's readings in order, the sheet's class first
+    alt_start: torch.Tensor         # [B, Lmax + 1] int32: CSR rows into them (alt_start[b, n] .. alt_start[b, n+1]); past L_b the last value
+    lattice_ids: torch.Tensor       # [B, Lmax] int32: what the lattice compares -- equal exactly where the reading SETS are equal
+    n_columns: List[int]            # per clip the number of expanded columns
+    sets: List[List[List[int]]]     # sets[b][n] = position n's class ids, the sheet's own first
+
+
+def _readings_of(alternatives, label_lists: List[List[int]], keep_empty: bool = False) -> Optional[Readings]:
+    """alternatives[b] = [(n, [class, ...]), ...]: label n of utterance b may also be sung as one of these classes -> Readings, or None when
+    alternatives is None or all-empty (keep_empty: the Readings of a sheet without extras instead).  The lattice id of a position is its
+    class id where it has no extras and READING_SET_ID + k for the k-th distinct multi-reading set of the clip (sets compared as sets),
+    so that the equal-neighbour rule and the span rule see "the same label" exactly where the reading sets are equal; without extras the
+    ids are the labels.  ValueError for a wrong list count, n outside 0 .. L_b-1, two entries for one n, an empty extras list, a class
+    repeated within a set (the sheet's own included) or more than MAX_READINGS readings; NotImplementedError when a clip's expanded
+    columns exceed MAX_READING_COLUMNS.  Host only."""
+    if alternatives is None:
+        return None
+    if len(alternatives) != len(label_lists):
+        raise ValueError(f"alternatives: {len(label_lists)} lists expected, one per utterance")
+    sets, any_extra = [], False
+    for b, labs in enumerate(label_lists):
+        row = [[int(c)] for c in labs]
+        seen = set()
+        for n, extras in (alternatives[b] or ()):
+            if int(n) != n or not 0 <= int(n) < len(labs):
+                raise ValueError(f"alternatives[{b}]: position {n} outside 0..{len(labs) - 1}")
+            n = int(n)
+            if n in seen:
+                raise ValueError(f"alternatives[{b}]: two entries for position {n}")
+            seen.add(n)
+            extras = [int(c) for c in extras]
+            if not extras:
+                raise ValueError(f"alternatives[{b}]: position {n} has an empty list of extra readings")
+            row[n] = row[n] + extras
+            if len(set(row[n])) != len(row[n]):
+                raise ValueError(f"alternatives[{b}]: position {n} names a class twice (the sheet's own class {row[n][0]} included)")
+            if len(row[n]) > MAX_READINGS:
+                raise ValueError(f"alternatives[{b}]: position {n} has {len(row[n])} readings, at most {MAX_READINGS}")
+            any_extra = True
+        if sum(len(r) for r in row) > MAX_READING_COLUMNS:
+            raise NotImplementedError(f"alternatives[{b}]: {sum(len(r) for r in row)} expanded columns exceed {MAX_READING_COLUMNS}")
+        sets.append(row)
+    if not any_extra and not keep_empty:
+        return None
+    B = len(label_lists)
+    Lmax = max(1, max((len(l) for l in label_lists), default=1))
+    n_columns = [sum(len(r) for r in row) for row in sets]
+    labels_x = torch.zeros((B, max(1, max(n_columns, default=1))), dtype=torch.int32)
+    alt_start = torch.zeros((B, Lmax + 1), dtype=torch.int32)
+    lattice_ids = torch.zeros((B, Lmax), dtype=torch.int32)
+    for b, row in enumerate(sets):
+        flat = [c for r in row for c in r]
+        if flat:
+            labels_x[b, : len(flat)] = torch.tensor(flat, dtype=torch.int32)
+        starts, known = [0], {}
+        for r in row:
+            starts.append(starts[-1] + len(r))
+        alt_start[b] = torch.tensor(starts + [starts[-1]] * (Lmax + 1 - len(starts)), dtype=torch.int32)
+        ids = [r[0] if len(r) == 1 else READING_SET_ID + known.setdefault(frozenset(r), len(known)) for r in row]
+        if ids:
+            lattice_ids[b, : len(ids)] = torch.tensor(ids, dtype=torch.int32)
+    return Readings(labels_x, alt_start, lattice_ids, n_columns, sets)
+
+
+def _readings_from_scores(reading, col_score, rd: Readings):
+    """Device outputs of ops.reading_scores -> readings[b][n] = (class id of the reading with the largest segment score, [score per
+    reading, the sheet's own class first]), or None for a skipped character."""
+    pick, score, alt = reading.cpu().numpy(), col_score.cpu().numpy(), rd.alt_start.numpy()
+    return [[None if pick[b, n] < 0 else (int(r[pick[b, n]]), [float(v) for v in score[b, alt[b, n]: alt[b, n + 1]]])
+             for n, r in enumerate(row)] for b, row in enumerate(rd.sets)]
+
+
+class ReadingRoute(NamedTuple):
+    """The device side of one call with pronunciation alternatives (readings_route): the expanded emissions stay for the scores."""
+    rd: Readings
+    em_x: torch.Tensor
+    alt_start: torch.Tensor
+    em: torch.Tensor                # the folded matrix: run_lattice's input, with lattice_ids in the labels' place
+    lattice_ids: torch.Tensor
+
+    def scores(self, n_lab, onset, offset):
+        """-> reading [B, Lmax] int32, col_score [B, columns] float64 (ops.reading_scores on the DP's boundaries)."""
+        return ops.reading_scores(self.em_x, self.alt_start, n_lab, onset, offset)
+
+
+def readings_route(rd: Readings, emissions_of, n_lab, nf, device) -> ReadingRoute:
+    """The one route every caller takes: emissions_of(labels_x, n_columns) -- the existing head or prep, run on the expanded labels (device
+    int32 tensors) -> the expanded compact matrix; ops.merge_readings folds it for the lattice."""
+    em_x = emissions_of(rd.labels_x.to(device), torch.tensor(rd.n_columns, dtype=torch.int32).to(device))
+    alt = rd.alt_start.to(device)
+    return ReadingRoute(rd, em_x, alt, ops.merge_readings(em_x, alt, n_lab, nf), rd.lattice_ids.to(device))
+
+
 def _visits_of_row(row):
     """One clip's lattice state per frame -> the time-ordered list of (char_index, first frame, last frame + 1) of every visit: the maximal
     runs of frames in one odd lattice state."""
@@ -445,7 +545,9 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, anchored=False, sheet=False, repeat_spans=None, repeat_penalty=0.0,
-             return_segments=False, repeat_scored=False, song_scored=False):
+             return_segments=False, repeat_scored=False, song_scored=False, alternatives=None, return_readings=False):
+    if return_readings and alternatives is None:
+        raise ValueError("return_readings goes with alternatives (without them every character has the one reading of its label)")
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -474,19 +576,36 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
                                       "the posteriors on the lattice with repeatable spans")
     else:
         repeat_from = _repeat_rows("perform_viterbi", repeat_spans, return_segments, lists, confidence is not None)
-    em = ops.emissions_from_logits(pred, lab, n_lab, variant)
-    nf = torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
+    # (addition) pronunciation alternatives: the prep runs on the expanded labels and its matrix is folded in front of the lattice, which
+    # sees the set-equality ids in the labels' place; None / all-empty takes the call as it was
+    rd = _readings_of(alternatives, lists, keep_empty=return_readings)
+    def frame_counts_on_device():
+        return torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
+
+    route = None
+    if rd is None:
+        em = ops.emissions_from_logits(pred, lab, n_lab, variant)
+        nf = frame_counts_on_device()
+    else:
+        nf = frame_counts_on_device()
+        route = readings_route(rd, lambda lab_x, n_x: ops.emissions_from_logits(pred, lab_x, n_x, variant), n_lab, nf, dev)
+        em, lab = route.em, route.lattice_ids
     r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, repeat_from=repeat_from,
                     repeat_penalty=repeat_penalty)
     if repeat_scored:
         seconds, segments, scores = _formatted_repeat(r, lists, counts, hop_size_second, optional_spans, repeat_spans)
-        return (seconds, segments, scores) if return_segments else (seconds, scores)
-    seconds = _formatted(r, lists, hop_size_second, optional_spans)
-    return (seconds, _segments_from_path(r.path, counts, hop_size_second)) if return_segments else seconds
+        out = (seconds, segments, scores) if return_segments else (seconds, scores)
+    else:
+        seconds = _formatted(r, lists, hop_size_second, optional_spans)
+        out = (seconds, _segments_from_path(r.path, counts, hop_size_second)) if return_segments else seconds
+    if not return_readings:
+        return out
+    readings = _readings_from_scores(*route.scores(n_lab, r.onset, r.offset), rd)
+    return (*out, readings) if isinstance(out, tuple) else (out, readings)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                    char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False):
+                    char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
     aligned over its first n_frames[b] rows, as if it had been handed over alone.
     optional_spans (addition): optional_spans[b] = list of (a, n) pairs, labels a .. n-1 of utterance b may be left out by the path
@@ -504,21 +623,31 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     functions and anchored_alignment_loss raise ValueError with it (perform_viterbi(_ctc)_repeat_scored: its confidence, up to 511
     labels; perform_viterbi(_ctc)_song_scored: up to 4095).  None or all-empty: the call as it was.
     return_segments (addition): -> (predicted_onset_offset, segments), segments[b] = the time-ordered list of (char_index, onset_s,
-    offset_s) of EVERY visit, with or without repeat_spans."""
+    offset_s) of EVERY visit, with or without repeat_spans.
+    alternatives (addition; here and in perform_viterbi_ctc and every _scored function): alternatives[b] = [(n, [class, ...]), ...] -- label n
+    of utterance b may also be sung as one of these classes (a character with several readings; at most 8 readings per position, the
+    sheet's own included, at most 4095 expanded columns per utterance: _readings_of).  The position's lattice state is scored on the
+    merged class, log sum exp over its readings per frame (la_emissions_merge_readings on the prep's emissions for the expanded labels);
+    two neighbouring positions count as the same label exactly when their reading sets are equal.  With every other keyword; the
+    confidences are then posteriors of the merged class.  None or all-empty: the call as it was.
+    return_readings (with alternatives; ValueError without): the return gains `readings` as its last element (a bare result becomes
+    (result, readings)): readings[b][n] = (class id sung, [score per reading, the sheet's own class first]) -- the score of a reading is
+    the sum of its emissions over the segment the DP chose (the reported visit), the class the smallest index with the largest score
+    (la_reading_scores) -- or None for a skipped character."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
-                    repeat_penalty=repeat_penalty, return_segments=return_segments)
+                    repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                        char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False):
+                        char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
-                    repeat_penalty=repeat_penalty, return_segments=return_segments)
+                    repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                           char_windows=None, onset_anchors=None, repeat_spans=None):
+                           char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
     """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
     scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
     sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi.
@@ -530,19 +659,19 @@ def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_wi
     (perform_viterbi(_ctc)_repeat_scored give the posteriors of that lattice)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                               skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
+                               skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                    skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
+                                    skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
     """perform_viterbi with char_windows / onset_anchors plus the confidence GIVEN them (addition): -> (predicted_onset_offset, scores).
     The DP and the forward-backward sweep run on the lattice with per-state frame windows (la_viterbi_windows_batch,
     la_alignment_posteriors_windows), with or without optional_spans.  scores[b] holds perform_viterbi_scored's keys with optional_spans
@@ -554,20 +683,20 @@ def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, bo
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     anchored=True,
-                    repeat_spans=repeat_spans)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                        skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
+                                        skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
     """perform_viterbi_ctc plus the confidence given the windows: see perform_viterbi_anchored_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     anchored=True,
-                    repeat_spans=repeat_spans)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
+                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
     """Whole-song timing with its confidences (addition): perform_viterbi_anchored_scored's (predicted_onset_offset, scores) for up to 4095
     labels, with or without optional_spans and char_windows / onset_anchors (la_viterbi_lattice_batch's routing for the DP,
     la_alignment_posteriors_lattice for the posteriors).  window_log_prob is 0.0 without windows.  Up to 511 labels the numbers are
@@ -576,21 +705,21 @@ def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, bound
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     sheet=True,
-                    repeat_spans=repeat_spans)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None):
+                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
     """perform_viterbi_ctc plus the whole-song confidences: see perform_viterbi_sheet_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     sheet=True,
-                    repeat_spans=repeat_spans)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                   skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                  return_segments=False):
+                                  return_segments=False, alternatives=None, return_readings=False):
     """perform_viterbi with repeat_spans plus the confidence of that lattice (addition): -> (predicted_onset_offset, scores), or
     (predicted_onset_offset, segments, scores) with return_segments.  The DP is la_viterbi_repeats_batch, the sweep
     la_alignment_posteriors_repeats, with or without optional_spans, char_windows / onset_anchors and n_frames; up to 511 labels
@@ -609,37 +738,37 @@ def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boun
     With no repeat span anywhere the numbers it shares with perform_viterbi_sheet_scored are that function's exactly."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                       skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                      return_segments=False):
+                                      return_segments=False, alternatives=None, return_readings=False):
     """perform_viterbi_ctc plus the confidence of the lattice with repeatable spans: see perform_viterbi_repeat_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                return_segments=False):
+                                return_segments=False, alternatives=None, return_readings=False):
     """Whole-song timing with repeated lines and its confidences (addition): perform_viterbi_repeat_scored's arguments and return values
     for up to 4095 labels (la_viterbi_repeats_batch for the DP, la_alignment_posteriors_song for the posteriors).  Up to 511 labels
     the numbers are perform_viterbi_repeat_scored's exactly.  The sweep's workspace holds every alpha row: T * 1024 R * 8 bytes per
     utterance beyond 511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                    return_segments=False):
+                                    return_segments=False, alternatives=None, return_readings=False):
     """perform_viterbi_ctc plus the whole-song confidences of the lattice with repeatable spans: see perform_viterbi_song_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True, alternatives=alternatives, return_readings=return_readings)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
@@ -684,7 +813,7 @@ def anchored_loss_inputs(labels, frame_counts: Sequence[int], onset_anchors=None
 
 
 def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_windows=None, optional_spans=None, skip_penalty=0.0,
-                            hop_size_second=0.02, n_frames=None, on_infeasible="raise", repeat_spans=None):
+                            hop_size_second=0.02, n_frames=None, on_infeasible="raise", repeat_spans=None, alternatives=None):
     """Training from line times (addition; the reference's losses need a label for every frame): -log of the total weight of the alignments
     that char_windows / onset_anchors (per utterance, in windows_from_anchors' form, seconds in the utterance's own frames) and
     optional_spans (as perform_viterbi) allow, per frame and averaged over the batch -- include/lyricalign.h la_anchored_alignment_loss.
@@ -696,9 +825,12 @@ def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_window
     on_infeasible: "raise" reads the per-clip status once (ONE host synchronisation per call) and raises ValueError naming the first clip
     without a path inside its windows (or without labels); "skip" does not read it: such a clip adds nothing to the loss (still divided by
     B) and gets a zero gradient.
-    repeat_spans: ValueError unless None or all-empty (the loss does not know the lattice with repeatable spans)."""
+    repeat_spans: ValueError unless None or all-empty (the loss does not know the lattice with repeatable spans).
+    alternatives: ValueError unless None or all-empty (training on merged classes is not part of the pronunciation alternatives)."""
     if repeat_spans is not None and any(len(v or ()) for v in repeat_spans):
         raise ValueError("anchored_alignment_loss: repeat_spans are not supported (no sum-product sweep on the lattice with repeatable spans)")
+    if alternatives is not None and any(len(v or ()) for v in alternatives):
+        raise ValueError("anchored_alignment_loss: alternatives are not supported (the loss is not defined on merged classes)")
     if on_infeasible not in ("raise", "skip"):
         raise ValueError('anchored_alignment_loss: on_infeasible must be "raise" or "skip"')
     if not torch.is_tensor(align_logit) or align_logit.dim() != 3 or not align_logit.is_cuda or align_logit.dtype != torch.float32:
