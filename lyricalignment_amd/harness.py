@@ -231,6 +231,17 @@ def _align_sheet(model, reading_kw: dict, audio, labels, **kw):
     return (rest[0] if len(rest) == 1 else tuple(rest)), readings[0]
 
 
+def _align_repeat_sheet(model, reading_kw: dict, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty, repeat_penalty, **kw):
+    """_align_sheet on the lattice where the lines with repeatable[i] may be sung again (repeat_spans from the flags: repeats_from_lines),
+    with every visit as segments; kw: the confidence keyword and the anchors, if any."""
+    from .utils.alignment import repeats_from_lines
+    repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
+    with torch.no_grad():
+        return _align_sheet(model, reading_kw, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                            repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty,
+                            return_segments=True, **kw)
+
+
 def _sheet_lines_out(res, lines: Sequence[str], per_line=(), readings=None):
     """One clip's per-character result -> one entry per line (None for a line left out: a span is taken or left as a whole, its characters
     are None together), and for every f of per_line the list of f(position of the line's first character, its result).  readings (the
@@ -334,21 +345,13 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     if with_visit_confidence and repeatable is None:
         raise ValueError("align_record_lines: with_visit_confidence goes with repeatable (with_confidence is the keyword without it)")
     if repeatable is not None:
-        from .utils.alignment import repeats_from_lines
         if with_confidence:
             raise ValueError("align_record_lines: repeatable does not go with with_confidence (no posteriors on the lattice with repeatable spans)")
-        repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
+        sheet = (model, rk, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty, repeat_penalty)
         if with_visit_confidence:
-            repeat_spans = [(a, e) for a, e in enumerate(repeat_from) if e >= 0]
-            with torch.no_grad():
-                (_, segments, scores), readings = _align_sheet(
-                    model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                    repeat_spans=[repeat_spans], repeat_penalty=repeat_penalty, return_segments=True, return_repeat_confidence=True)
+            (_, segments, scores), readings = _align_repeat_sheet(*sheet, return_repeat_confidence=True)
             return _visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings)
-        with torch.no_grad():
-            (_, segments), readings = _align_sheet(
-                model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty, return_segments=True)
+        (_, segments), readings = _align_repeat_sheet(*sheet)
         return _line_occurrences(segments[0], lines, readings)
     with torch.no_grad():
         if with_confidence:
@@ -452,13 +455,8 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     kw = {} if starts is None else {"onset_anchors": [_line_anchors(starts, ids, tolerance_s)]}
     rk = _reading_kw(lut, ids, heteronyms)
     if repeatable is not None:
-        from .utils.alignment import repeats_from_lines
-        repeat_from = repeats_from_lines([len(t) for t in ids], repeatable)
-        with torch.no_grad():
-            (res, segments, scores), readings = _align_sheet(
-                model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
-                repeat_spans=[[(a, e) for a, e in enumerate(repeat_from) if e >= 0]], repeat_penalty=repeat_penalty, return_segments=True,
-                return_song_confidence=True, **kw)
+        (res, segments, scores), readings = _align_repeat_sheet(model, rk, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty,
+                                                                repeat_penalty, return_song_confidence=True, **kw)
         occurrences, per_line = _visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings)
         _, line_onset = _sheet_lines_out(res[0], lines, (lambda pos, first: None if first is None else float(scores[0]["onset_prob"][pos]),))
         return occurrences, {"sung": [c["visits"] - (c["repeat_count"] or 0.0) for c in per_line], "line_onset_prob": line_onset,

@@ -419,9 +419,7 @@ class AlignModel(torch.nn.Module):
         character; a reading's score is the sum of its emissions over the segment the DP chose (the reported, first visit), the class the
         smallest index with the largest score (ops.reading_scores).  With return_frames two more tensors: reading [B, Lmax] int32 (index
         into the position's readings, -1 = skipped) and col_score [B, columns] float64."""
-        from ..utils.alignment import (POSTERIOR_MAX_LABELS, LatticeResult, _formatted, _formatted_repeat, _label_lists, _labels_to_device,
-                                       _readings_from_scores, _readings_of, _repeat_from_of_spans, _repeat_rows, _segments_from_path,
-                                       _skip_from_of_spans, _windows_of, readings_route, run_lattice)
+        from ..utils import alignment as ua
         if return_readings and alternatives is None:
             raise ValueError("align: return_readings goes with alternatives (without them every character has the one reading of its label)")
         if return_anchored_confidence and (return_confidence or return_span_confidence):
@@ -436,10 +434,10 @@ class AlignModel(torch.nn.Module):
         if return_repeat_confidence:
             if return_confidence or return_span_confidence or return_anchored_confidence or return_sheet_confidence:
                 raise ValueError("align: return_repeat_confidence does not go with another confidence keyword")
-            widest = max((len(l) for l in _label_lists(labels, len(labels))), default=0)
-            if widest > POSTERIOR_MAX_LABELS:
-                raise NotImplementedError(f"align: {widest} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
-        rd = None if alternatives is None else _readings_of(alternatives, _label_lists(labels, len(labels)), keep_empty=return_readings)
+            widest = max((len(l) for l in ua._label_lists(labels, len(labels))), default=0)
+            if widest > ua.POSTERIOR_MAX_LABELS:
+                raise NotImplementedError(f"align: {widest} labels exceed the {ua.POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
+        rd = None if alternatives is None else ua._readings_of(alternatives, ua._label_lists(labels, len(labels)), keep_empty=return_readings)
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -452,57 +450,36 @@ class AlignModel(torch.nn.Module):
                 mel = self._mel_of(audios)
             feats, B, T, stride = self._features(mel.to(eng.device), get_orig_len)
             frame_counts = [T] * B
-        lab_dev, n_lab, lab_lists = _labels_to_device(labels, B, eng.device)
-        skip_from = _skip_from_of_spans(optional_spans, lab_lists)
-        windows = _windows_of(char_windows, onset_anchors, lab_lists, frame_counts, hop_size_second)
+        lab_dev, n_lab, lab_lists = ua._labels_to_device(labels, B, eng.device)
+        skip_from = ua._skip_from_of_spans(optional_spans, lab_lists)
+        windows = ua._windows_of(char_windows, onset_anchors, lab_lists, frame_counts, hop_size_second)
         if windows is not None and (return_confidence or return_span_confidence):
             raise ValueError("align: char_windows / onset_anchors do not go with return_confidence / return_span_confidence "
                              "(return_anchored_confidence=True gives the posteriors on the windowed lattice)")
         if skip_from is not None and return_confidence:
             raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice by that "
                              "keyword: return_span_confidence=True gives them)")
-        confidence = ("sheet" if return_sheet_confidence else "anchored" if return_anchored_confidence else "span" if return_span_confidence
-                      else "plain" if return_confidence else None)
-        if return_repeat_confidence or return_song_confidence:
-            confidence, repeat_from = "song" if return_song_confidence else "repeat", _repeat_from_of_spans(repeat_spans, lab_lists)
-        else:
-            repeat_from = _repeat_rows("align", repeat_spans, return_segments, lab_lists, confidence is not None)
-        # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them
-        need_em = confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
+        confidence = ("song" if return_song_confidence else "repeat" if return_repeat_confidence else "sheet" if return_sheet_confidence
+                      else "anchored" if return_anchored_confidence else "span" if return_span_confidence else "plain" if return_confidence
+                      else None)
         variant = _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN
-        route = None
-        if rd is not None:
-            # pronunciation alternatives: the fused head runs on the EXPANDED labels for their emissions (with its time-out recovery); its own
-            # DP result on that list is meaningless and is dropped without looking at its status.  The folded matrix goes through the
-            # lattice with the set-equality ids in the labels' place.
-            nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-            route = readings_route(rd, lambda lab_x, n_x: eng.align_feats_checked(feats, B, T, stride, lab_x, n_x, variant,
-                                                                                 want_emissions=True, **kw)[4], n_lab, nf, eng.device)
-            r = run_lattice(route.em, route.lattice_ids, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
-                            repeat_from=repeat_from, repeat_penalty=repeat_penalty)
-        else:
-            head = eng.align_feats_checked(feats, B, T, stride, lab_dev, n_lab, variant, want_emissions=need_em, **kw)
-            if need_em:
-                nf = kw["n_frames"] if per_clip else torch.full((B,), T, dtype=torch.int32, device=eng.device)
-                # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same
-                # bits; the sheet confidence keeps the fused head's, which run_lattice uses only where there is neither a span nor a window)
-                r = run_lattice(head[4], lab_dev, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window,
-                                dp=None if return_anchored_confidence else head[:4], repeat_from=repeat_from, repeat_penalty=repeat_penalty)
-            else:
-                r = LatticeResult(*head)
-        picked = route.scores(n_lab, r.onset, r.offset) if return_readings else ()
+
+        def head(lab, n, needed=True):
+            # the head is fused with the plain lattice's DP; its emissions leave it only where another lattice or a sweep needs them.  With
+            # pronunciation alternatives it runs on the EXPANDED labels for their emissions (with its time-out recovery); its own DP result on
+            # that list is meaningless and is dropped without looking at its status.
+            # (the anchored confidence runs the plain lattice's DP on the emissions, as perform_viterbi_anchored_scored does: the same
+            # bits; the sheet confidence keeps the fused head's, which run_lattice uses only where there is neither a span nor a window)
+            out = eng.align_feats_checked(feats, B, T, stride, lab, n, variant, want_emissions=needed, **kw)
+            return None if return_anchored_confidence else out[:4], out[4] if needed else None
+
+        out = ua.align_labels("align", head, lab_dev, n_lab, lab_lists, frame_counts, T, kw.get("n_frames"), hop_size_second, confidence,
+                              boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
+                              alternatives, return_readings, rd, raw=return_frames)
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path);
+            r, picked = out
             return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,)) + picked     # reading, col_score last
-        if return_repeat_confidence or return_song_confidence:
-            seconds, segments, scores = _formatted_repeat(r, lab_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
-            out = (seconds, segments, scores) if return_segments else (seconds, scores)
-        else:
-            seconds = _formatted(r, lab_lists, hop_size_second, optional_spans)
-            out = (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
-        if not return_readings:
-            return out
-        readings = _readings_from_scores(*picked, rd)
-        return (*out, readings) if isinstance(out, tuple) else (out, readings)
+        return out
 
 
 def encoder_only_engine(whisper_model, mel: torch.Tensor) -> torch.Tensor:

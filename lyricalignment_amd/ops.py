@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -58,86 +58,128 @@ def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device) -> Tuple[t
     return torch.empty((max(need.value, 16),), dtype=torch.uint8, device=device), need.value
 
 
-# The face of a lattice call (csrc/la_lattice.h Face) is chosen by the public function: "plain", "spans" (skip_from given) or
-# "windows" (win_lo / win_hi given, skip_from may be None); "lattice" is the general entry (la_viterbi_lattice_batch and
-# la_alignment_posteriors_lattice: skip_from and the windows may each be None, up to 4095 labels).  -> the stem of its C symbols, DP and posteriors
-_DP_ENTRY = {"plain": "viterbi", "spans": "viterbi_spans", "windows": "viterbi_windows", "lattice": "viterbi_lattice"}
-_POSTERIOR_ENTRY = {"plain": "alignment_posteriors", "spans": "alignment_posteriors_spans", "windows": "alignment_posteriors_windows",
-                    "lattice": "alignment_posteriors_lattice"}
+# One row per C lattice entry (csrc/la_lattice.h Face chooses the kernel; here only what the Python side must know): the stem of its C
+# symbols (la_<stem>_batch for a DP, la_<stem> for a sweep, la_<stem>_workspace_bytes), whether it takes the span arguments (skip_from,
+# skip_stride, skip_penalty), the window arguments (win_lo, win_hi, win_stride; null = no windows where the public function lets them
+# be None) and the repeat / path arguments, whether a sweep writes the span outputs (present_prob, span_skip_prob), and the label limit
+# the Python side refuses beyond (NotImplementedError before a launch; None: the C entry's own).
+class _Entry(NamedTuple):
+    stem: str
+    spans: bool = False
+    windows: bool = False
+    repeats: bool = False
+    span_out: bool = False
+    max_labels: Optional[int] = None
 
 
-def _lattice_checked(who: str, face: str, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows, path=None, boundary_window=None):
-    """_lattice_inputs plus the checks of the face's own arguments (path = the (onset, offset) the posteriors are asked about)
-    -> B, T, Lmax, the contiguous count tensors and skip_penalty as a float."""
-    more = {} if path is None else dict(onset=path[0], offset=path[1])
+_ENTRIES = {e.stem: e for e in (
+    _Entry("viterbi"), _Entry("viterbi_spans", True), _Entry("viterbi_windows", True, True), _Entry("viterbi_lattice", True, True),
+    _Entry("viterbi_repeats", True, True, True),
+    _Entry("alignment_posteriors"), _Entry("alignment_posteriors_spans", True, span_out=True),
+    _Entry("alignment_posteriors_windows", True, True, span_out=True), _Entry("alignment_posteriors_lattice", True, True, span_out=True),
+    _Entry("alignment_posteriors_repeats", True, True, True, True, 511), _Entry("alignment_posteriors_song", True, True, True, True, 4095))}
+_LABEL_LIMIT_WHY = {511: "the repeat lattice's posteriors are one lane per state", 4095: "8192 lattice states per workgroup"}
+
+
+def _lattice_checked(who: str, e: _Entry, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty,
+                     frames=None, path=None, boundary_window=None):
+    """_lattice_inputs plus the checks of the entry's own arguments (frames = the (onset, offset) the posteriors are asked about)
+    -> B, T, Lmax, the contiguous count tensors, skip_penalty as a float, the windows as a pair or None, repeat_penalty as a float."""
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError(f"{who}: win_lo and win_hi go together")
+    windows = None if win_lo is None else (win_lo, win_hi)
+    more = {} if frames is None else dict(onset=frames[0], offset=frames[1])
     if windows is not None:
-        more.update(win_lo=windows[0], win_hi=windows[1])
+        more.update(win_lo=win_lo, win_hi=win_hi)
     if skip_from is not None:
         more["skip_from"] = skip_from
     B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
-    if path is not None and (path[0].shape != (B, Lmax) or path[1].shape != (B, Lmax)):
+    if frames is not None and (frames[0].shape != (B, Lmax) or frames[1].shape != (B, Lmax)):
         raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
     for t in windows or ():
-        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != windows[0].stride(0):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 2 * Lmax + 1 or t.stride(1) != 1 or t.stride(0) != win_lo.stride(0):
             raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
     if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
         raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
     if boundary_window is not None and int(boundary_window) < 0:
         raise ValueError(f"{who}: boundary_window must be >= 0")
     skip_penalty = float(skip_penalty)
-    if face != "plain" and not skip_penalty >= 0.0:
+    if e.spans and not skip_penalty >= 0.0:
         raise ValueError(f"{who}: skip_penalty must be >= 0")
-    return B, T, Lmax, n_labels, n_frames, skip_penalty
+    for name, t, least in (("repeat_from", repeat_from, "Lmax"), ("path", path, "T")):
+        if t is not None:
+            _dev(t, name, torch.int32)
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] < (Lmax if least == "Lmax" else T) or t.stride(1) != 1:
+                raise ValueError(f"{who}: {name} [B, >= {least}] with unit inner stride expected")
+    repeat_penalty = float(repeat_penalty)
+    if e.repeats and not repeat_penalty >= 0.0:
+        raise ValueError(f"{who}: repeat_penalty must be >= 0")
+    if e.max_labels is not None and Lmax > e.max_labels:
+        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {e.max_labels} ({_LABEL_LIMIT_WHY[e.max_labels]})")
+    return B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty
 
 
-def _face_args(face: str, skip_from, skip_stride: int, skip_penalty: float, windows) -> tuple:
-    """The C arguments a face adds to the plain one's: (skip_from, skip_stride, skip_penalty) and (win_lo, win_hi, win_stride)."""
-    spans = () if face == "plain" else (ptr(skip_from), skip_stride, skip_penalty)
-    if face == "lattice" and windows is None:                # the general entry always takes the window arguments: null = no windows
-        return spans + (0, 0, 0)
-    return spans + ((ptr(windows[0]), ptr(windows[1]), windows[0].stride(0)) if face in ("windows", "lattice") else ())
+def _face_args(e: _Entry, skip_from, skip_stride: int, skip_penalty: float, windows, repeat_from, repeat_penalty: float) -> tuple:
+    """The C arguments an entry adds to the plain one's: (skip_from, skip_stride, skip_penalty), (win_lo, win_hi, win_stride) -- null and 0
+    without windows -- and (repeat_from, repeat_stride, repeat_penalty)."""
+    lo, hi = windows or (None, None)
+    return (((ptr(skip_from), skip_stride, skip_penalty) if e.spans else ())
+            + ((ptr(lo), ptr(hi), lo.stride(0) if lo is not None else 0) if e.windows else ())
+            + ((ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty) if e.repeats else ()))
 
 
-def _viterbi(who: str, face: str, em, labels, n_labels, n_frames, skip_from=None, skip_penalty=0.0, windows=None):
-    """The alignment DP of one face: checks, outputs, workspace and the C call -> onset, offset, final_score, status."""
-    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, face, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows)
+def _viterbi(stem: str, em, labels, n_labels, n_frames, skip_from=None, skip_penalty=0.0, win_lo=None, win_hi=None, repeat_from=None,
+             repeat_penalty=0.0):
+    """The alignment DP through one entry: checks, outputs, workspace and the C call -> onset, offset, final_score, status [, path]."""
+    e, who = _ENTRIES[stem], stem + "_batch"
+    B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty = _lattice_checked(
+        who, e, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty)
     dev = em.device
     onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
     score = torch.empty((B,), dtype=torch.float64, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
-    ws, need = _lattice_workspace(_DP_ENTRY[face] + "_workspace_bytes", B, T, Lmax, dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev) if e.repeats else None
+    ws, need = _lattice_workspace(stem + "_workspace_bytes", B, T, Lmax, dev)
     skip_stride = skip_from.stride(0) if skip_from is not None else 0
-    check(getattr(lib(), "la_" + _DP_ENTRY[face] + "_batch")(
+    check(getattr(lib(), "la_" + who)(
         ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), *_face_args(face, skip_from, skip_stride, skip_penalty, windows),
+        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
+        *_face_args(e, skip_from, skip_stride, skip_penalty, windows, repeat_from, repeat_penalty), *((ptr(path), T) if e.repeats else ()),
         ptr(ws), need, stream_ptr()), who)
-    return onset, offset, score, status
+    return (onset, offset, score, status, path) if e.repeats else (onset, offset, score, status)
 
 
-def _posteriors(who: str, face: str, em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
-                skip_from=None, skip_penalty=0.0, windows=None):
-    """The forward-backward sweep of one face: checks, outputs, workspace and the C call -> occupancy, onset_prob, offset_prob, log_z,
-    status [, present_prob, span_skip_prob unless plain] [, gamma]."""
-    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, face, em, labels, n_labels, n_frames, skip_from, skip_penalty, windows,
-                                                                    (onset, offset), boundary_window)
+def _posteriors(who: str, em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma, skip_from=None, skip_penalty=0.0,
+                win_lo=None, win_hi=None, repeat_from=None, repeat_penalty=0.0, path=None):
+    """The forward-backward sweep through one entry (`who`, the stem of its C symbols): checks, outputs, workspace and the C call ->
+    occupancy, onset_prob, offset_prob, log_z, status [, present_prob, span_skip_prob [, repeat_count, path_prob]] [, gamma]."""
+    e = _ENTRIES[who]
+    B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty = _lattice_checked(
+        who, e, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty, (onset, offset), path,
+        boundary_window)
     onset = onset.contiguous(); offset = offset.contiguous()
     dev = em.device
     occupancy, onset_prob, offset_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(3))
     log_z = torch.empty((B,), dtype=torch.float64, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    res, span_out = (occupancy, onset_prob, offset_prob, log_z, status), ()
+    more = ()                               # what the entry writes beside the plain five, in the C call's order and the result's
     skip_stride = skip_from.stride(0) if skip_from is not None else Lmax + 1
-    if face != "plain":                     # skip_stride is the row pitch the kernel is told for skip_from AND for span_skip_prob
-        present_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
-        span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
-        res, span_out = res + (present_prob, span_skip_prob), (ptr(present_prob), ptr(span_skip_prob))
-    ws, need = _lattice_workspace(_POSTERIOR_ENTRY[face] + "_workspace_bytes", B, T, Lmax, dev)
-    check(getattr(lib(), "la_" + _POSTERIOR_ENTRY[face])(
+    if e.span_out:                          # skip_stride is the row pitch the kernel is told for skip_from AND for span_skip_prob
+        present_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)          # (`visits` on the repeat lattice)
+        more = (present_prob, torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1])
+    if e.repeats:                           # path_prob has the row pitch of path
+        more += (torch.empty((B, Lmax), dtype=torch.float32, device=dev),
+                 torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None)
+    ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
+    check(getattr(lib(), "la_" + who)(
         ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, int(boundary_window), *_face_args(face, skip_from, skip_stride, skip_penalty, windows),
-        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), *span_out, ptr(log_z), ptr(status), ptr(gamma),
+        ptr(onset), ptr(offset), Lmax, int(boundary_window),
+        *_face_args(e, skip_from, skip_stride, skip_penalty, windows, repeat_from, repeat_penalty),
+        *((ptr(path), path.stride(0) if path is not None else 0) if e.repeats else ()),
+        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), *(ptr(t) for t in more), ptr(log_z), ptr(status), ptr(gamma),
         gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0, ptr(ws), need, stream_ptr()), who)
+    res = (occupancy, onset_prob, offset_prob, log_z, status) + more
     return res + (gamma,) if want_gamma else res
 
 
@@ -145,7 +187,7 @@ def viterbi_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """em [B,T,E] f32 (E >= Lmax+1), labels [B,Lmax] i32, n_labels [B] i32, n_frames [B] i32 (device).
     -> onset [B,Lmax] i32, offset [B,Lmax] i32, final_score [B] f64, status [B] i32 (device)."""
-    return _viterbi("viterbi_batch", "plain", em, labels, n_labels, n_frames)
+    return _viterbi("viterbi", em, labels, n_labels, n_frames)
 
 
 def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -154,7 +196,7 @@ def viterbi_spans_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.
     """la_viterbi_spans_batch: viterbi_batch on the lattice with optional label spans.  skip_from [B, >= Lmax+1] i32 (device):
     skip_from[b, n] = a (0 <= a < n) makes labels a..n-1 of clip b optional, anything else = no span ends at n.
     -> the tuple of viterbi_batch; labels inside a taken jump have onset = offset = -1 under status LA_OK."""
-    return _viterbi("viterbi_spans_batch", "spans", em, labels, n_labels, n_frames, skip_from, skip_penalty)
+    return _viterbi("viterbi_spans", em, labels, n_labels, n_frames, skip_from, skip_penalty)
 
 
 def viterbi_windows_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -164,7 +206,7 @@ def viterbi_windows_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     win_lo / win_hi [B, >= 2*Lmax+1] i32 (device, one row pitch): state s of clip b may hold the path at frame t only if
     win_lo[b, s] <= t < win_hi[b, s].  -> the tuple of viterbi_batch; a clip without a path inside its windows has status
     LA_EINFEASIBLE, score -inf and every onset / offset -1."""
-    return _viterbi("viterbi_windows_batch", "windows", em, labels, n_labels, n_frames, skip_from, skip_penalty, (win_lo, win_hi))
+    return _viterbi("viterbi_windows", em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi)
 
 
 def viterbi_lattice_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -173,10 +215,7 @@ def viterbi_lattice_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     """la_viterbi_lattice_batch: the DP on the lattice that skip_from (None: no span) and win_lo / win_hi (both None: no windows)
     describe, for up to 4095 labels.  Up to 511 labels the outputs are viterbi_windows_batch's, viterbi_spans_batch's or viterbi_batch's
     bit for bit, according to what is given.  -> the tuple of viterbi_batch."""
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError("viterbi_lattice_batch: win_lo and win_hi go together")
-    return _viterbi("viterbi_lattice_batch", "lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty,
-                    None if win_lo is None else (win_lo, win_hi))
+    return _viterbi("viterbi_lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi)
 
 
 def viterbi_repeats_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -189,31 +228,7 @@ def viterbi_repeats_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     and status are viterbi_lattice_batch's bit for bit.
     -> onset, offset (a label's FIRST visit in time), final_score, status, path [B,T] i32 (the lattice state at every frame t < T_b;
     -1 for t >= T_b and for a clip whose status is LA_EEMPTY or LA_EINVAL or that has no path inside its windows)."""
-    who = "viterbi_repeats_batch"
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError(f"{who}: win_lo and win_hi go together")
-    windows = None if win_lo is None else (win_lo, win_hi)
-    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, "lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty, windows)
-    if repeat_from is not None:
-        _dev(repeat_from, "repeat_from", torch.int32)
-        if repeat_from.dim() != 2 or repeat_from.shape[0] != B or repeat_from.shape[1] < Lmax or repeat_from.stride(1) != 1:
-            raise ValueError(f"{who}: repeat_from [B, >= Lmax] with unit inner stride expected")
-    repeat_penalty = float(repeat_penalty)
-    if not repeat_penalty >= 0.0:
-        raise ValueError(f"{who}: repeat_penalty must be >= 0")
-    dev = em.device
-    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
-    score = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev)
-    ws, need = _lattice_workspace("viterbi_repeats_workspace_bytes", B, T, Lmax, dev)
-    skip_stride = skip_from.stride(0) if skip_from is not None else 0
-    check(lib().la_viterbi_repeats_batch(
-        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), *_face_args("lattice", skip_from, skip_stride, skip_penalty, windows),
-        ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty, ptr(path), T,
-        ptr(ws), need, stream_ptr()), who)
-    return onset, offset, score, status, path
+    return _viterbi("viterbi_repeats", em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty)
 
 
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -221,7 +236,7 @@ def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,
     onset / offset [B,Lmax] i32 = viterbi_batch's (or align_head_forward's) outputs for the same emissions.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32 [, gamma [B,T,2*Lmax+1] f32] (device)."""
-    return _posteriors("alignment_posteriors", "plain", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma)
+    return _posteriors("alignment_posteriors", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma)
 
 
 def alignment_posteriors_spans(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -231,7 +246,7 @@ def alignment_posteriors_spans(em: torch.Tensor, labels: torch.Tensor, n_labels:
     offset = viterbi_spans_batch's outputs for the same skip_from [B, >= Lmax+1] i32 and skip_penalty.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, present_prob [B,Lmax] f32 (label n is on the path),
     span_skip_prob [B,Lmax+1] f32 (the span ending at position n is jumped) [, gamma [B,T,2*Lmax+1] f32] (device)."""
-    return _posteriors("alignment_posteriors_spans", "spans", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+    return _posteriors("alignment_posteriors_spans", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
                        skip_from, skip_penalty)
 
 
@@ -244,8 +259,8 @@ def alignment_posteriors_windows(em: torch.Tensor, labels: torch.Tensor, n_label
     win_lo / win_hi as viterbi_windows_batch.  Every output is a posterior GIVEN the windows (normalised by the windowed log_z).
     -> the tuple of alignment_posteriors_spans (skip_from None: present_prob 1 on reported labels, span_skip_prob 0); a clip without a
     path inside its windows has status LA_EINFEASIBLE, log_z -inf and every output 0."""
-    return _posteriors("alignment_posteriors_windows", "windows", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
-                       skip_from, skip_penalty, (win_lo, win_hi))
+    return _posteriors("alignment_posteriors_windows", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty, win_lo, win_hi)
 
 
 def alignment_posteriors_lattice(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -258,10 +273,8 @@ def alignment_posteriors_lattice(em: torch.Tensor, labels: torch.Tensor, n_label
     according to what is given.  The workspace holds every alpha row: B * T * 1024 R * 8 bytes beyond 511 labels (R = 2 / 4 / 8 for up to
     1023 / 2047 / 4095 labels).  -> the tuple of alignment_posteriors_spans (no span: present_prob 1 on the labels of an LA_OK clip,
     span_skip_prob 0)."""
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError("alignment_posteriors_lattice: win_lo and win_hi go together")
-    return _posteriors("alignment_posteriors_lattice", "lattice", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
-                       skip_from, skip_penalty, None if win_lo is None else (win_lo, win_hi))
+    return _posteriors("alignment_posteriors_lattice", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty, win_lo, win_hi)
 
 
 def alignment_posteriors_repeats(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -276,8 +289,8 @@ def alignment_posteriors_repeats(em: torch.Tensor, labels: torch.Tensor, n_label
     bit for bit, visits = its present_prob, repeat_count 0.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, visits [B,Lmax] f32, span_skip_prob [B,Lmax+1] f32,
     repeat_count [B,Lmax] f32, path_prob [B,T] f32 (gamma at the given path; None without a path) [, gamma [B,T,2*Lmax+1] f32]."""
-    return _posteriors_repeats("alignment_posteriors_repeats", em, labels, n_labels, n_frames, onset, offset, skip_from, skip_penalty, win_lo,
-                               win_hi, repeat_from, repeat_penalty, path, boundary_window, want_gamma)
+    return _posteriors("alignment_posteriors_repeats", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty, path)
 
 
 def alignment_posteriors_song(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -288,54 +301,8 @@ def alignment_posteriors_song(em: torch.Tensor, labels: torch.Tensor, n_labels: 
     """la_alignment_posteriors_song: alignment_posteriors_repeats for whole songs, up to 4095 labels (NotImplementedError above, before a
     launch); the same arguments and the same tuple.  Up to 511 labels the same kernel and the same bits; beyond, the strip form (R = 2 /
     4 / 8 states per thread for up to 1023 / 2047 / 4095 labels), whose workspace holds every alpha row: B * T * 1024 R * 8 bytes."""
-    return _posteriors_repeats("alignment_posteriors_song", em, labels, n_labels, n_frames, onset, offset, skip_from, skip_penalty, win_lo,
-                               win_hi, repeat_from, repeat_penalty, path, boundary_window, want_gamma)
-
-
-def _posteriors_repeats(who, em, labels, n_labels, n_frames, onset, offset, skip_from, skip_penalty, win_lo, win_hi, repeat_from,
-                        repeat_penalty, path, boundary_window, want_gamma):
-    """The posteriors of the lattice with repeatable spans through one of its two entries (`who`, the stem of the C symbols): checks,
-    outputs, workspace and the C call."""
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError(f"{who}: win_lo and win_hi go together")
-    windows = None if win_lo is None else (win_lo, win_hi)
-    B, T, Lmax, n_labels, n_frames, skip_penalty = _lattice_checked(who, "lattice", em, labels, n_labels, n_frames, skip_from, skip_penalty,
-                                                                    windows, (onset, offset), boundary_window)
-    if repeat_from is not None:
-        _dev(repeat_from, "repeat_from", torch.int32)
-        if repeat_from.dim() != 2 or repeat_from.shape[0] != B or repeat_from.shape[1] < Lmax or repeat_from.stride(1) != 1:
-            raise ValueError(f"{who}: repeat_from [B, >= Lmax] with unit inner stride expected")
-    if path is not None:
-        _dev(path, "path", torch.int32)
-        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < T or path.stride(1) != 1:
-            raise ValueError(f"{who}: path [B, >= T] with unit inner stride expected")
-    repeat_penalty = float(repeat_penalty)
-    if not repeat_penalty >= 0.0:
-        raise ValueError(f"{who}: repeat_penalty must be >= 0")
-    if who == "alignment_posteriors_repeats" and Lmax > 511:
-        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds 511 (the repeat lattice's posteriors are one lane per state)")
-    if Lmax > 4095:
-        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds 4095 (8192 lattice states per workgroup)")
-    onset = onset.contiguous(); offset = offset.contiguous()
-    dev = em.device
-    occupancy, onset_prob, offset_prob, visits, repeat_count = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(5))
-    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    skip_stride = skip_from.stride(0) if skip_from is not None else Lmax + 1   # the row pitch of skip_from AND of span_skip_prob
-    span_skip_prob = torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1]
-    path_prob = torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None
-    ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
-    check(getattr(lib(), "la_" + who)(
-        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, int(boundary_window), *_face_args("lattice", skip_from, skip_stride, skip_penalty, windows),
-        ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty,
-        ptr(path), path.stride(0) if path is not None else 0,
-        ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(visits), ptr(span_skip_prob), ptr(repeat_count), ptr(path_prob),
-        ptr(log_z), ptr(status), ptr(gamma), gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
-        ptr(ws), need, stream_ptr()), who)
-    res = (occupancy, onset_prob, offset_prob, log_z, status, visits, span_skip_prob, repeat_count, path_prob)
-    return res + (gamma,) if want_gamma else res
+    return _posteriors("alignment_posteriors_song", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma,
+                       skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty, path)
 
 
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:

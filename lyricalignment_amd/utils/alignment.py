@@ -377,7 +377,11 @@ class LatticeResult(NamedTuple):
     present_prob: Optional[torch.Tensor] = None
     span_skip_prob: Optional[torch.Tensor] = None
     log_z_free: Optional[torch.Tensor] = None
-    path = None             # (no tuple field: the eleven above are what the lattices without repeatable spans return; see below)
+    # behind the eleven tuple fields, as plain attributes (None where they do not apply; run_lattice's _result sets them)
+    path = None             # [B, T] int32, the lattice state per frame: ops.viterbi_repeats_batch's fifth output
+    visits = None           # [B, Lmax] (= present_prob, an expected count), repeat_count [B, Lmax], path_prob [B, T]: the repeat sweeps'
+    repeat_count = None
+    path_prob = None
 
 
 class RepeatLatticeResult(LatticeResult):
@@ -385,18 +389,96 @@ class RepeatLatticeResult(LatticeResult):
     asked for; present_prob then holds `visits`, an expected count) and, behind them as attributes, `path` [B, T] int32 -- the lattice
     state per frame, ops.viterbi_repeats_batch's fifth output -- and with confidence="repeat" `visits` [B, Lmax] (= present_prob),
     `repeat_count` [B, Lmax] and `path_prob` [B, T] (ops.alignment_posteriors_repeats)."""
-    visits = None
-    repeat_count = None
-    path_prob = None
 
-    def __new__(cls, onset, offset, score, status, path, posteriors=(), repeat_count=None, path_prob=None):
-        r = super().__new__(cls, onset, offset, score, status, *posteriors)
-        r.path = path
-        r.visits, r.repeat_count, r.path_prob = r.present_prob, repeat_count, path_prob
-        return r
+
+def _result(dp, post=(), log_z_free=None) -> LatticeResult:
+    """A DP entry's tuple, a sweep's (or none) and log_z_free -> the LatticeResult; a DP with a path (ops.viterbi_repeats_batch) gives a
+    RepeatLatticeResult with the path and the repeat sweep's further outputs as attributes."""
+    fields = (*dp[:4], *post[:4], *post[5:7])
+    if len(dp) == 4:
+        return LatticeResult(*fields, log_z_free=log_z_free)
+    r = RepeatLatticeResult(*fields, log_z_free=log_z_free)
+    r.path, r.visits = dp[4], r.present_prob
+    r.repeat_count, r.path_prob = post[7:9] or (None, None)
+    return r
 
 
 POSTERIOR_MAX_LABELS = 511      # one lane per lattice state in the sum-product sweeps and in the span / window entries of the DP
+
+
+class Route(NamedTuple):
+    """One row of ROUTES: the ops entries behind one (confidence, spans given, windows given)."""
+    dp: str
+    posteriors: Optional[str] = None
+    free: Optional[str] = None      # log_z_free: None, "log_z" (the sweep's own) or [3] of one more call of this entry without windows
+
+
+# THE dispatch table: (confidence, spans given, windows given) -> Route.  tests/test_gpu_lattice_dispatch.py restates eleven of its rows.
+# ("plain" is meant for the lattice without spans and windows and "span" for the one without windows; their other rows say what such a
+# call has always made.  A "span" row with windows sweeps once more for a log_z_free that its result does not hold.)
+ROUTES = {
+    (None, False, False): Route("viterbi_batch"),
+    (None, True, False): Route("viterbi_spans_batch"),
+    (None, False, True): Route("viterbi_windows_batch"),
+    (None, True, True): Route("viterbi_windows_batch"),
+    ("plain", False, False): Route("viterbi_batch", "alignment_posteriors"),
+    ("plain", True, False): Route("viterbi_spans_batch", "alignment_posteriors"),
+    ("plain", False, True): Route("viterbi_windows_batch", "alignment_posteriors"),
+    ("plain", True, True): Route("viterbi_windows_batch", "alignment_posteriors"),
+    ("span", False, False): Route("viterbi_batch", "alignment_posteriors_spans"),
+    ("span", True, False): Route("viterbi_spans_batch", "alignment_posteriors_spans"),
+    ("span", False, True): Route("viterbi_windows_batch", "alignment_posteriors_windows", "alignment_posteriors"),
+    ("span", True, True): Route("viterbi_windows_batch", "alignment_posteriors_windows", "alignment_posteriors_spans"),
+    ("anchored", False, False): Route("viterbi_batch", "alignment_posteriors_spans", "log_z"),
+    ("anchored", True, False): Route("viterbi_spans_batch", "alignment_posteriors_spans", "log_z"),
+    ("anchored", False, True): Route("viterbi_windows_batch", "alignment_posteriors_windows", "alignment_posteriors"),
+    ("anchored", True, True): Route("viterbi_windows_batch", "alignment_posteriors_windows", "alignment_posteriors_spans"),
+    ("sheet", False, False): Route("viterbi_batch", "alignment_posteriors_lattice", "log_z"),
+    ("sheet", True, False): Route("viterbi_spans_batch", "alignment_posteriors_lattice", "log_z"),
+    ("sheet", False, True): Route("viterbi_windows_batch", "alignment_posteriors_lattice", "alignment_posteriors_lattice"),
+    ("sheet", True, True): Route("viterbi_windows_batch", "alignment_posteriors_lattice", "alignment_posteriors_lattice"),
+    ("repeat", False, False): Route("viterbi_repeats_batch", "alignment_posteriors_repeats"),
+    ("repeat", True, False): Route("viterbi_repeats_batch", "alignment_posteriors_repeats"),
+    ("repeat", False, True): Route("viterbi_repeats_batch", "alignment_posteriors_repeats", "alignment_posteriors_repeats"),
+    ("repeat", True, True): Route("viterbi_repeats_batch", "alignment_posteriors_repeats", "alignment_posteriors_repeats"),
+    ("song", False, False): Route("viterbi_repeats_batch", "alignment_posteriors_song"),
+    ("song", True, False): Route("viterbi_repeats_batch", "alignment_posteriors_song"),
+    ("song", False, True): Route("viterbi_repeats_batch", "alignment_posteriors_song", "alignment_posteriors_song"),
+    ("song", True, True): Route("viterbi_repeats_batch", "alignment_posteriors_song", "alignment_posteriors_song"),
+}
+# The two rules that lie across the table.  A given repeat_from sends the DP to the lattice with repeatable spans (the rows of "repeat"
+# and "song" name it themselves); beyond POSTERIOR_MAX_LABELS the DP's span and window entries give way to the general one.
+REPEAT_DP = "viterbi_repeats_batch"
+WIDE_DP = {"viterbi_spans_batch": "viterbi_lattice_batch", "viterbi_windows_batch": "viterbi_lattice_batch"}
+# the sweeps of one lane per lattice state, and how run_lattice's refusal beyond POSTERIOR_MAX_LABELS ends for each
+NARROW_SWEEPS = {name: "the posterior sweeps (the alignment itself and the sheet confidence take up to 4095)"
+                 for name in ("alignment_posteriors", "alignment_posteriors_spans", "alignment_posteriors_windows")}
+NARROW_SWEEPS["alignment_posteriors_repeats"] = "the posteriors on the lattice with repeatable spans"
+# What an ops entry takes behind (em, labels, n_labels, n_frames [, onset, offset]), in its own order: "skip" = skip_from, skip_penalty;
+# "win" = win_lo, win_hi; "repeat" = repeat_from, repeat_penalty; "path"; "bw" = boundary_window, which the entries that do not list it
+# take by keyword.
+ENTRY_ARGS = {
+    "viterbi_batch": (), "viterbi_spans_batch": ("skip",), "viterbi_windows_batch": ("win", "skip"), "viterbi_lattice_batch": ("skip", "win"),
+    "viterbi_repeats_batch": ("skip", "win", "repeat"),
+    "alignment_posteriors": ("bw",), "alignment_posteriors_spans": ("skip", "bw"), "alignment_posteriors_windows": ("win", "skip", "bw"),
+    "alignment_posteriors_lattice": ("skip", "win"), "alignment_posteriors_repeats": ("skip", "win", "repeat", "path"),
+    "alignment_posteriors_song": ("skip", "win", "repeat", "path")}
+
+
+def route_of(confidence, spans: bool, windows: bool, wide: bool = False, repeats: bool = False) -> Route:
+    """ROUTES' row with the two rules applied: repeats = a repeat_from is given, wide = more than POSTERIOR_MAX_LABELS labels."""
+    route = ROUTES[confidence, spans, windows]
+    dp = REPEAT_DP if repeats else route.dp
+    if wide:
+        dp = WIDE_DP.get(dp, dp)
+    return route if dp == route.dp else route._replace(dp=dp)
+
+
+def _call(name: str, lattice, groups, boundary_window=None):
+    """ops.<name> on lattice = (em, lab, n_lab, nf [, onset, offset]) with the argument groups that ENTRY_ARGS lists for it."""
+    takes = ENTRY_ARGS[name]
+    kw = {} if boundary_window is None or "bw" in takes else {"boundary_window": boundary_window}
+    return getattr(ops, name)(*lattice, *(v for group in takes for v in groups[group]), **kw)
 
 
 def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0.0, confidence=None, boundary_window=2, dp=None,
@@ -423,71 +505,35 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     "song": "repeat" without the label limit (whole songs, up to 4095 labels): ops.viterbi_repeats_batch, then ONE call of
     ops.alignment_posteriors_song, and a second one without windows for log_z_free where windows were given.  Up to 511 labels its
     numbers are "repeat"'s exactly."""
-    if confidence not in (None, "plain", "span", "anchored", "sheet", "repeat", "song"):
+    key = (confidence, skip_from is not None, windows is not None)
+    if key not in ROUTES:
         raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
-    if repeat_from is not None or confidence in ("repeat", "song"):
-        if confidence not in (None, "repeat", "song"):
-            raise ValueError("run_lattice: on the lattice with repeatable spans the posteriors are confidence=\"repeat\" or \"song\" "
-                             "(repeat_from does not go with the four older kinds)")
-        if confidence == "repeat" and lab.shape[1] > POSTERIOR_MAX_LABELS:
-            raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posteriors "
-                                      "on the lattice with repeatable spans")
-        dev = em.device
-        win = (None, None) if windows is None else (windows[0].to(dev), windows[1].to(dev))
-        skip_dev = None if skip_from is None else skip_from.to(dev)
-        rep_dev = None if repeat_from is None else repeat_from.to(dev)
-        out = ops.viterbi_repeats_batch(em, lab, n_lab, nf, skip_dev, skip_penalty, *win, rep_dev, repeat_penalty)
-        if confidence is None:
-            return RepeatLatticeResult(*out)
-        sweep = ops.alignment_posteriors_song if confidence == "song" else ops.alignment_posteriors_repeats
-        post = sweep(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, *win, rep_dev, repeat_penalty, out[4],
-                     boundary_window=boundary_window)
-        log_z_free = None
-        if windows is not None:
-            log_z_free = sweep(em, lab, n_lab, nf, out[0], out[1], skip_dev, skip_penalty, None, None, rep_dev, repeat_penalty,
-                               boundary_window=boundary_window)[3]
-        return RepeatLatticeResult(*out, posteriors=(*post[:4], *post[5:7], log_z_free), repeat_count=post[7], path_prob=post[8])
+    route = ROUTES[key]
+    if repeat_from is not None and route.posteriors is not None and route.dp != REPEAT_DP:
+        raise ValueError("run_lattice: on the lattice with repeatable spans the posteriors are confidence=\"repeat\" or \"song\" "
+                         "(repeat_from does not go with the four older kinds)")
     wide = lab.shape[1] > POSTERIOR_MAX_LABELS
-    if wide and confidence not in (None, "sheet"):
-        raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of the posterior sweeps "
-                                  "(the alignment itself and the sheet confidence take up to 4095)")
+    if wide and route.posteriors in NARROW_SWEEPS:
+        raise NotImplementedError(f"run_lattice: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of "
+                                  + NARROW_SWEEPS[route.posteriors])
+    route = route_of(*key, wide, repeat_from is not None)
     dev = em.device
     skip_dev = None if skip_from is None else skip_from.to(dev)
-    win = None if windows is None else (windows[0].to(dev), windows[1].to(dev))
-    if wide and (win is not None or skip_dev is not None):
-        dp = ops.viterbi_lattice_batch(em, lab, n_lab, nf, skip_dev, skip_penalty, *(win or (None, None)))
-    elif win is not None:
-        dp = ops.viterbi_windows_batch(em, lab, n_lab, nf, win[0], win[1], skip_dev, skip_penalty)
-    elif skip_dev is not None:
-        dp = ops.viterbi_spans_batch(em, lab, n_lab, nf, skip_dev, skip_penalty)
-    elif dp is None:
-        dp = ops.viterbi_batch(em, lab, n_lab, nf)
-    onset, offset = dp[0], dp[1]
-    if confidence is None:
-        return LatticeResult(*dp)
-    if confidence == "sheet":
-        post = ops.alignment_posteriors_lattice(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, *(win or (None, None)),
-                                                boundary_window=boundary_window)
-        log_z_free = post[3]
-        if win is not None:
-            log_z_free = ops.alignment_posteriors_lattice(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty,
-                                                          boundary_window=boundary_window)[3]
-        return LatticeResult(*dp, *post[:4], *post[5:7], log_z_free)
-    if confidence == "plain":
-        return LatticeResult(*dp, *ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[:4])
-    span_free = skip_dev is None
-    if win is None:
-        if span_free:
-            skip_dev = torch.full((lab.shape[0], lab.shape[1] + 1), -1, dtype=torch.int32, device=dev)
-        post = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, boundary_window)
-        log_z_free = post[3]
-    else:
-        post = ops.alignment_posteriors_windows(em, lab, n_lab, nf, onset, offset, win[0], win[1], skip_dev, skip_penalty, boundary_window)
-        if span_free:
-            log_z_free = ops.alignment_posteriors(em, lab, n_lab, nf, onset, offset, boundary_window)[3]
-        else:
-            log_z_free = ops.alignment_posteriors_spans(em, lab, n_lab, nf, onset, offset, skip_dev, skip_penalty, boundary_window)[3]
-    return LatticeResult(*dp, *post[:4], *post[5:7], log_z_free if confidence == "anchored" else None)
+    groups = {"skip": (skip_dev, skip_penalty), "win": (None, None) if windows is None else (windows[0].to(dev), windows[1].to(dev)),
+              "repeat": (None if repeat_from is None else repeat_from.to(dev), repeat_penalty), "bw": (boundary_window,)}
+    if dp is None or route.dp != "viterbi_batch":
+        dp = _call(route.dp, (em, lab, n_lab, nf), groups)
+    if route.posteriors is None:
+        return _result(dp)
+    groups["path"] = dp[4:5]
+    if route.posteriors == "alignment_posteriors_spans" and skip_dev is None:          # the span entry wants its rows: none marked
+        groups["skip"] = (torch.full((lab.shape[0], lab.shape[1] + 1), -1, dtype=torch.int32, device=dev), skip_penalty)
+    frames = (em, lab, n_lab, nf, dp[0], dp[1])
+    post = _call(route.posteriors, frames, groups, boundary_window)
+    log_z_free = post[3] if route.free == "log_z" else None
+    if route.free not in (None, "log_z"):
+        log_z_free = _call(route.free, frames, {**groups, "win": (None, None), "path": (None,)}, boundary_window)[3]
+    return _result(dp, post, None if confidence == "span" else log_z_free)
 
 
 def _formatted(r: LatticeResult, label_lists, hop_size_second, optional_spans):
@@ -543,9 +589,63 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
     return rows
 
 
+def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, n_frames_max: int, nf, hop_size_second, confidence,
+                 boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
+                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False):
+    """What perform_viterbi* and AlignModel.align (`who`: "perform_viterbi" / "align") do once the labels (lab / n_lab on the device,
+    label_lists), the spans and windows (host rows, or None) and the kind of confidence are known: the repeat_from rows
+    (_repeat_from_of_spans for "repeat" / "song", whose label limit is refused here; _repeat_rows otherwise), the readings (rd: the
+    caller's _readings_of result where it has one), the emissions, run_lattice, the reading scores, and the public return value --
+    _formatted's or _formatted_repeat's, then the segments, then the readings; a bare result with readings becomes a tuple.
+    emissions_of(labels, n_labels, needed=True) -> (dp, em): the compact emissions of the device label rows given (em; it may be None
+    where `needed` is False and dp is not) and the plain lattice's (onset, offset, score, status) on them where the provider's kernel
+    has them anyway (the fused head), else None.  With alternatives it is asked once, for the expanded rows; otherwise once for lab,
+    with needed = "another lattice or a sweep reads the emissions" -- a dp without emissions is the result, and nothing else is launched.
+    nf: the device frame counts of a ragged batch, or None: every clip has n_frames_max frames (filled here, and only if needed).
+    raw: -> (the LatticeResult, ops.reading_scores' pair or ()) in place of the formatted value."""
+    repeat_kind = confidence in ("repeat", "song")
+    if repeat_kind:
+        repeat_from = _repeat_from_of_spans(repeat_spans, label_lists)
+        if lab.shape[1] > POSTERIOR_MAX_LABELS and confidence == "repeat":
+            raise NotImplementedError(f"{who}_repeat_scored: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of "
+                                      "the posteriors on the lattice with repeatable spans")
+    else:
+        repeat_from = _repeat_rows(who, repeat_spans, return_segments, label_lists, confidence is not None)
+    # pronunciation alternatives: the head or the prep runs on the expanded labels and its matrix is folded in front of the lattice, which
+    # sees the set-equality ids in the labels' place; None / all-empty takes the call as it was
+    if rd is None:
+        rd = _readings_of(alternatives, label_lists, keep_empty=return_readings)
+    route, dp, em = None, None, None
+    if rd is None:
+        dp, em = emissions_of(lab, n_lab, confidence is not None or skip_from is not None or windows is not None or repeat_from is not None)
+    if rd is None and em is None:
+        r = _result(dp)
+    else:
+        if nf is None:
+            nf = torch.full((len(label_lists),), n_frames_max, dtype=torch.int32, device=lab.device)
+        if rd is not None:
+            route = readings_route(rd, lambda lab_x, n_x: emissions_of(lab_x, n_x)[1], n_lab, nf, lab.device)
+            em, lab = route.em, route.lattice_ids
+        r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from, repeat_penalty)
+    picked = route.scores(n_lab, r.onset, r.offset) if return_readings else ()
+    if raw:
+        return r, picked
+    if repeat_kind:
+        seconds, segments, scores = _formatted_repeat(r, label_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
+        out = (seconds, segments, scores) if return_segments else (seconds, scores)
+    else:
+        seconds = _formatted(r, label_lists, hop_size_second, optional_spans)
+        out = (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
+    if not return_readings:
+        return out
+    readings = _readings_from_scores(*picked, rd)
+    return (*out, readings) if isinstance(out, tuple) else (out, readings)
+
+
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
-             char_windows=None, onset_anchors=None, anchored=False, sheet=False, repeat_spans=None, repeat_penalty=0.0,
-             return_segments=False, repeat_scored=False, song_scored=False, alternatives=None, return_readings=False):
+             char_windows=None, onset_anchors=None, confidence=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False,
+             alternatives=None, return_readings=False):
+    """confidence: the kind the public function stands for (run_lattice's); "plain" becomes "span" where a span is given."""
     if return_readings and alternatives is None:
         raise ValueError("return_readings goes with alternatives (without them every character has the one reading of its label)")
     dev = _device_of(prediction)
@@ -556,52 +656,23 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         pred = pred.contiguous()
     B, T, V = pred.shape
     lab, n_lab, lists = _labels_to_device(labels, B, dev)
-    counts = [T] * B
+    counts, nf = [T] * B, None
     if n_frames is not None:                 # (addition) utterance b owns the first n_frames[b] rows of a zero-padded [B, Tmax, V] prediction
         counts = [int(v) for v in (n_frames.tolist() if torch.is_tensor(n_frames) else n_frames)]
         if len(counts) != B or any(v < 0 or v > T for v in counts):
             raise ValueError(f"n_frames: {B} frame counts in 0..{T} expected")
+        nf = torch.tensor(counts, dtype=torch.int32).to(dev)
     # (additions) optional spans and per-state frame windows; None / all-empty keywords take the reference's lattice unchanged
     skip_from = _skip_from_of_spans(optional_spans, lists)
     windows = _windows_of(char_windows, onset_anchors, lists, counts, hop_size_second)
-    repeat_scored = repeat_scored or song_scored
-    if windows is not None and boundary_window is not None and not (anchored or sheet or repeat_scored):
+    if windows is not None and confidence == "plain":
         raise ValueError("char_windows / onset_anchors: the _scored functions have no posteriors on the windowed lattice "
                          "(perform_viterbi(_ctc)_anchored_scored give them)")
-    confidence = "sheet" if sheet else "anchored" if anchored else None if boundary_window is None else "plain" if skip_from is None else "span"
-    if repeat_scored:
-        confidence, repeat_from = "song" if song_scored else "repeat", _repeat_from_of_spans(repeat_spans, lists)
-        if lab.shape[1] > POSTERIOR_MAX_LABELS and not song_scored:
-            raise NotImplementedError(f"perform_viterbi_repeat_scored: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of "
-                                      "the posteriors on the lattice with repeatable spans")
-    else:
-        repeat_from = _repeat_rows("perform_viterbi", repeat_spans, return_segments, lists, confidence is not None)
-    # (addition) pronunciation alternatives: the prep runs on the expanded labels and its matrix is folded in front of the lattice, which
-    # sees the set-equality ids in the labels' place; None / all-empty takes the call as it was
-    rd = _readings_of(alternatives, lists, keep_empty=return_readings)
-    def frame_counts_on_device():
-        return torch.full((B,), T, dtype=torch.int32, device=dev) if n_frames is None else torch.tensor(counts, dtype=torch.int32).to(dev)
-
-    route = None
-    if rd is None:
-        em = ops.emissions_from_logits(pred, lab, n_lab, variant)
-        nf = frame_counts_on_device()
-    else:
-        nf = frame_counts_on_device()
-        route = readings_route(rd, lambda lab_x, n_x: ops.emissions_from_logits(pred, lab_x, n_x, variant), n_lab, nf, dev)
-        em, lab = route.em, route.lattice_ids
-    r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, repeat_from=repeat_from,
-                    repeat_penalty=repeat_penalty)
-    if repeat_scored:
-        seconds, segments, scores = _formatted_repeat(r, lists, counts, hop_size_second, optional_spans, repeat_spans)
-        out = (seconds, segments, scores) if return_segments else (seconds, scores)
-    else:
-        seconds = _formatted(r, lists, hop_size_second, optional_spans)
-        out = (seconds, _segments_from_path(r.path, counts, hop_size_second)) if return_segments else seconds
-    if not return_readings:
-        return out
-    readings = _readings_from_scores(*route.scores(n_lab, r.onset, r.offset), rd)
-    return (*out, readings) if isinstance(out, tuple) else (out, readings)
+    if confidence == "plain" and skip_from is not None:
+        confidence = "span"
+    return align_labels("perform_viterbi", lambda lab_x, n_x, needed=True: (None, ops.emissions_from_logits(pred, lab_x, n_x, variant)), lab,
+                        n_lab, lists, counts, T, nf, hop_size_second, confidence, boundary_window, skip_from, windows, skip_penalty,
+                        optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
@@ -659,7 +730,7 @@ def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_wi
     (perform_viterbi(_ctc)_repeat_scored give the posteriors of that lattice)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    confidence="plain", repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
@@ -667,7 +738,7 @@ def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundar
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    confidence="plain", repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
@@ -682,7 +753,7 @@ def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, bo
     window_log_prob 0.0.  An utterance without a path inside its windows raises as in perform_viterbi."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    anchored=True,
+                    confidence="anchored",
                     repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
@@ -691,7 +762,7 @@ def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02
     """perform_viterbi_ctc plus the confidence given the windows: see perform_viterbi_anchored_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    anchored=True,
+                    confidence="anchored",
                     repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
@@ -704,7 +775,7 @@ def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, bound
     511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    sheet=True,
+                    confidence="sheet",
                     repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
@@ -713,7 +784,7 @@ def perform_viterbi_ctc_sheet_scored(prediction, labels, hop_size_second=0.02, b
     """perform_viterbi_ctc plus the whole-song confidences: see perform_viterbi_sheet_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    sheet=True,
+                    confidence="sheet",
                     repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
 
 
@@ -738,7 +809,7 @@ def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boun
     With no repeat span anywhere the numbers it shares with perform_viterbi_sheet_scored are that function's exactly."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="repeat", alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
@@ -747,7 +818,7 @@ def perform_viterbi_ctc_repeat_scored(prediction, labels, hop_size_second=0.02, 
     """perform_viterbi_ctc plus the confidence of the lattice with repeatable spans: see perform_viterbi_repeat_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, repeat_scored=True, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="repeat", alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
@@ -759,7 +830,7 @@ def perform_viterbi_song_scored(prediction, labels, hop_size_second=0.02, bounda
     utterance beyond 511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings)
 
 
 def perform_viterbi_ctc_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
@@ -768,7 +839,7 @@ def perform_viterbi_ctc_song_scored(prediction, labels, hop_size_second=0.02, bo
     """perform_viterbi_ctc plus the whole-song confidences of the lattice with repeatable spans: see perform_viterbi_song_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, song_scored=True, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):

@@ -186,10 +186,14 @@ def test_python_refusals_that_need_no_device():
         ua.run_lattice(None, wide, None, None, confidence="repeat")
     for name in ("perform_viterbi_repeat_scored", "perform_viterbi_ctc_repeat_scored", "_formatted_repeat"):
         assert callable(getattr(ua, name))
-    r = ua.RepeatLatticeResult(1, 2, 3, 4, 5)                           # the DP alone: eleven fields, seven None, the path behind them
+    r = ua._result((1, 2, 3, 4, 5))                                     # the DP alone: eleven fields, seven None, the path behind them
+    assert isinstance(r, ua.RepeatLatticeResult) and isinstance(r, ua.LatticeResult)
     assert len(r) == 11 and list(r[4:]) == [None] * 7 and r.path == 5 and r.repeat_count is None and r.path_prob is None
-    r = ua.RepeatLatticeResult(1, 2, 3, 4, 5, posteriors=(6, 7, 8, 9, 10, 11, None), repeat_count=12, path_prob=13)
+    r = ua._result((1, 2, 3, 4, 5), (6, 7, 8, 9, "status", 10, 11, 12, 13))      # the repeat sweep's nine outputs behind the DP's five
+    assert isinstance(r, ua.RepeatLatticeResult) and list(r[4:8]) == [6, 7, 8, 9] and r.log_z_free is None
     assert len(r) == 11 and r.present_prob == 10 and r.visits == 10 and r.span_skip_prob == 11 and (r.repeat_count, r.path_prob) == (12, 13)
+    r = ua._result((1, 2, 3, 4))                                        # no path: a LatticeResult, the four attributes readable and None
+    assert type(r) is ua.LatticeResult and (r.path, r.visits, r.repeat_count, r.path_prob) == (None,) * 4
     assert ua._visits_of_row([0, 1, 1, 2, 3, 3, 1, 1, 4, -1]) == [(0, 1, 3), (1, 4, 6), (0, 6, 8)]
     import inspect
     assert "with_visit_confidence" in inspect.signature(align_record_lines).parameters
