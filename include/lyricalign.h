@@ -640,6 +640,52 @@ int la_reading_scores(const float *em_x, int64_t emx_batch_stride, int64_t emx_r
                       double *col_score, int32_t col_stride, int32_t *reading, int32_t reading_stride, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* pronunciation scores: was the sheet's character the one that was sung?     */
+/*   (addition; "goodness of pronunciation" of forced aligners)               */
+/* ------------------------------------------------------------------------- */
+/*
+ * The lattice forces every state onto its sheet class; the confidences above are posteriors GIVEN the sheet.  la_segment_class_scores
+ * looks at the segment the DP gave a position and asks which class was heard there: it sums the emissions of n_cand candidate classes
+ * over the segment, ranks the position's own class among them and names the top_k best.
+ *
+ * em_c[b][t][j] (device, float32) is the emission of candidate class j at frame t; strides in elements and arbitrary -- in practice a
+ * column window of a wider compact emission matrix, so rows need no alignment (rows hold n_cand entries).  onset / offset
+ * [batch][out_stride] are a lattice entry's outputs (frames; -1 = skipped; with repeat spans the reported, first visit); own_col
+ * [batch][own_stride] names the candidate column that holds position n's own class (-1 or outside 0 .. n_cand-1: none).
+ *
+ * Per position n < n_labels[b] with onset >= 0 (all candidates share the segment [t0, t1) = [min(onset, max_frames),
+ * max(t0, min(offset, max_frames)))):
+ *   seg_score[b][n][j]  (optional, null = not wanted) = the float64 sum of em_c[b][t][j] over t ascending in [t0, t1): sequential, so
+ *                       two calls agree bit for bit and a clip's bits are the same alone and in a batch;
+ *   top_col / top_score [b][n][k], k < top_k: the candidates with the largest sums, the largest first, ties to the smaller column;
+ *                       where top_k > n_cand the trailing entries are -1 / -inf;
+ *   own_score[b][n]     = the sum of column own_col (0 without one);
+ *   own_rank[b][n]      = the number of candidates with a larger sum, or an equal sum and a smaller column (0 = the own class is the
+ *                       best; -1 without an own column);
+ *   n_seg_frames[b][n]  = t1 - t0.
+ * A skipped position (onset < 0) gets top_col -1, top_score 0, own_score 0, own_rank -1, n_seg_frames 0 and, where seg_score is given,
+ * a row of zeros.  -inf and clipped (-1000) emissions are ordinary values.  Positions n >= n_labels[b], and every stride's padding,
+ * are left untouched.  n_labels, onset, offset and own_col are device data and are clamped in the kernel (n_labels into 0 ..
+ * max_labels, frames into 0 .. max_frames), so a malformed row reads nothing outside its clip.
+ *
+ * Layout of the outputs: seg_score rows at b * seg_batch_stride + n * seg_row_stride (n_cand doubles each); top_col / top_score rows
+ * at (b * max_labels + n) * top_stride (top_k entries each); own_score / own_rank / n_seg_frames share out_stride with onset / offset.
+ *
+ * batch, max_frames, max_labels, n_cand or top_k <= 0, a null pointer (seg_score excepted) or a stride smaller than its width ->
+ * LA_EINVAL; max_labels or n_cand above 4095, top_k above 16 (or more than 65535 clips) -> LA_EUNSUPPORTED, reported before the
+ * stride checks; answered on the host under the entry's name before anything is enqueued.  The segments of a clip are disjoint, so a
+ * call reads every emission at most once.  The entry does not synchronise, allocate, free or use atomics.
+ */
+int la_segment_class_scores(const float *em_c, int64_t emc_batch_stride, int64_t emc_row_stride,
+                            const int32_t *n_labels, const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                            const int32_t *own_col, int32_t own_stride,
+                            int32_t batch, int32_t max_frames, int32_t max_labels, int32_t n_cand, int32_t top_k,
+                            double *seg_score, int64_t seg_batch_stride, int64_t seg_row_stride,
+                            int32_t *top_col, double *top_score, int32_t top_stride,
+                            double *own_score, int32_t *own_rank, int32_t *n_seg_frames,
+                            void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* log-mel front end  (replaces whisper.audio.log_mel_spectrogram + pad_or_trim, */
 /*                      call sites module/align_model.py:84,89,100,109)           */
 /* ------------------------------------------------------------------------- */

@@ -94,6 +94,9 @@ SYMBOLS = {
     # pronunciation alternatives: fold the expanded emission matrix in front of the lattice, score the readings behind it
     "la_emissions_merge_readings": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P]),
     "la_reading_scores": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P]),
+    # pronunciation scores: every candidate class summed over the segment the DP gave a position, its own class ranked, the top few named
+    "la_segment_class_scores": (c_int32, [_P, _I64, _I64, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P, _P, _I32,
+                                          _P, _P, _P, _P]),
     "la_logmel_workspace_bytes": (c_int32, [_I32, _I32, POINTER(_SZ)]),
     "la_logmel_f32": (c_int32, [_P, _I32, _I32, _P, _P, _P, _I64, _I64, _P, _SZ, _P]),
     "la_logmel_constants_bytes": (c_int32, [POINTER(_SZ)]),

@@ -482,7 +482,8 @@ class FineTuner:
         return out
 
     def micro_step_anchored(self, audios, labels, onset_anchors=None, char_windows=None, optional_spans=None, skip_penalty: float = 0.0,
-                            accum_grad_steps: int = 1, last: bool = False, alternatives=None) -> torch.Tensor:
+                            accum_grad_steps: int = 1, last: bool = False, alternatives=None,
+                            return_pronunciation: bool = False) -> torch.Tensor:
         """One micro-batch trained from what is known about time instead of frame labels (addition): clips of at most 30 s, labels
         [B, Lmax] class ids with -100 padding, onset_anchors / char_windows / optional_spans per clip as AlignModel.align takes them
         (seconds from the clip's start; harness.lrc_training_clips cuts an LRC sheet into such clips).  The loss is
@@ -491,10 +492,13 @@ class FineTuner:
         accum_grad_steps); step() follows as usual.  -> the un-scaled loss, a device scalar.
         ValueError: a model without the silence logit (use_ctc_loss False: the plain variant has no such loss), and -- after the backward,
         where the GRU flags are read anyway; the clip's gradient rows were zero -- a clip without a path inside its windows; alternatives
-        other than None or all-empty (AlignModel.align's pronunciation alternatives: training on merged classes is not part of them)."""
+        other than None or all-empty (AlignModel.align's pronunciation alternatives: training on merged classes is not part of them);
+        return_pronunciation (AlignModel.align's pronunciation scores: a training step has no alignment to report them on)."""
         from .utils.alignment import anchored_loss_inputs, raise_for_loss_status
         if alternatives is not None and any(len(v or ()) for v in alternatives):
             raise ValueError("micro_step_anchored: alternatives are not supported (the loss is not defined on merged classes)")
+        if return_pronunciation:
+            raise ValueError("micro_step_anchored: return_pronunciation is not supported (the pronunciation scores belong to the aligner)")
         m = self.model
         if not self.use_ctc_loss or not m.train_alignment:
             raise ValueError("micro_step_anchored: the anchored alignment loss exists for the CTC variant only (word columns + silence logit, "

@@ -26,6 +26,13 @@ class PinyinClassLUT:
     def __init__(self, token_pinyin: Sequence[str], pinyin_lookup_table: dict):
         self.table = np.asarray([pinyin_lookup_table[p] for p in token_pinyin], dtype=np.int64)
         self.lookup = dict(pinyin_lookup_table)
+        self.syllables = {}                      # class id -> syllable: the first syllable of the lookup table that maps to the class
+        for syllable, c in self.lookup.items():
+            self.syllables.setdefault(int(c), syllable)
+
+    def syllable_of(self, class_id: int) -> str:
+        """The syllable of a class id (the inverse of pinyin_lookup_table; KeyError for an id the table does not hold)."""
+        return self.syllables[int(class_id)]
 
     def __call__(self, tokens) -> torch.Tensor:
         t = torch.as_tensor(tokens).clone().long()
@@ -214,21 +221,70 @@ def _line_anchors(starts: Sequence[float], ids, tolerance_s: float) -> list:
     return anchors
 
 
-def _reading_kw(lut: PinyinClassLUT, ids, heteronyms) -> dict:
+class _SheetKw(dict):
+    """_reading_kw's keywords; _align_sheet leaves the clip's pronunciation scores here (None: not asked for)."""
+    pronunciation = None
+
+
+def _reading_kw(lut: PinyinClassLUT, ids, heteronyms, with_pronunciation: bool = False, top_k: int = 5) -> dict:
     """The keywords the sheet functions add to AlignModel.align for heteronyms (None: none): the alternatives of the one clip and
-    return_readings, so that every character entry can name the class that was sung."""
-    if heteronyms is None:
-        return {}
-    return {"alternatives": lut.readings_of(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long), heteronyms), "return_readings": True}
+    return_readings, so that every character entry can name the class that was sung; with_pronunciation: the three keywords of the
+    pronunciation scores, with every class of the lookup table (ids from 1) as a candidate."""
+    kw = _SheetKw()
+    if heteronyms is not None:
+        kw.update(alternatives=lut.readings_of(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long), heteronyms), return_readings=True)
+    if with_pronunciation:
+        kw.update(return_pronunciation=True, pronunciation_classes=sorted(c for c in lut.syllables if c >= 1), pronunciation_top_k=top_k)
+    return kw
 
 
 def _align_sheet(model, reading_kw: dict, audio, labels, **kw):
-    """model.align on the one clip with _reading_kw's keywords -> (what the call returns without them, the clip's readings or None)."""
+    """model.align on the one clip with _reading_kw's keywords -> (what the call returns without them, the clip's readings or None); the
+    clip's pronunciation scores, where asked for, are left in reading_kw.pronunciation."""
     out = model.align([audio], labels, **kw, **reading_kw)
     if not reading_kw:
         return out, None
-    *rest, readings = out
-    return (rest[0] if len(rest) == 1 else tuple(rest)), readings[0]
+    rest, readings = list(out), None
+    if "return_pronunciation" in reading_kw:
+        reading_kw.pronunciation = rest.pop()[0]
+    if "return_readings" in reading_kw:
+        readings = rest.pop()[0]
+    return (rest[0] if len(rest) == 1 else tuple(rest)), readings
+
+
+def _pronunciation_lines(pronunciation, lines: Sequence[str], lut: PinyinClassLUT) -> List[list]:
+    """One clip's AlignModel.align(return_pronunciation=True) list -> one list per line with, per character, None (left out) or the dict
+    with the character and syllable names added: {"char", "class", "syllable", "frames", "log_prob", "rank", "gop", "top": [(syllable,
+    score per frame), ...]}."""
+    out, pos = [], 0
+    for line in lines:
+        out.append([None if d is None else {"char": line[j], "class": d["class"], "syllable": lut.syllable_of(d["class"]), "frames": d["frames"],
+                                            "log_prob": d["log_prob"], "rank": d["rank"], "gop": d["gop"],
+                                            "top": [(lut.syllable_of(c), v) for c, v in d["top"]]}
+                    for j, d in enumerate(pronunciation[pos: pos + len(line)])])
+        pos += len(line)
+    return out
+
+
+def _done(result, reading_kw, lines: Sequence[str], lut: PinyinClassLUT):
+    """What a sheet function returns: its result, or (result, pronunciation per line) where the pronunciation scores were asked for."""
+    if getattr(reading_kw, "pronunciation", None) is None:
+        return result
+    return result, _pronunciation_lines(reading_kw.pronunciation, lines, lut)
+
+
+def suspect_characters(result, max_rank: int = 0, min_gop: Optional[float] = None) -> List[tuple]:
+    """The characters a proof-reader of the sheet would look at: result = the per-line pronunciation list that align_record_lines /
+    align_record_lrc / align_song return with with_pronunciation=True -> [(line index, character index in the line, the syllable heard
+    best there, gop), ...] for every sung character whose own class ranks behind max_rank candidates (rank > max_rank) or, where min_gop is
+    given, whose gop lies below it.  min_gop is the caller's choice: no threshold has been measured on real singing, so none is built in
+    (None: the rank alone decides)."""
+    out = []
+    for i, line in enumerate(result):
+        for j, d in enumerate(line):
+            if d is not None and (d["rank"] > max_rank or (min_gop is not None and d["gop"] < min_gop)):
+                out.append((i, j, d["top"][0][0], d["gop"]))
+    return out
 
 
 def _align_repeat_sheet(model, reading_kw: dict, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty, repeat_penalty, **kw):
@@ -319,7 +375,8 @@ def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable, r
 
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
-                       repeat_penalty: float = 0.0, with_visit_confidence: bool = False, heteronyms=None):
+                       repeat_penalty: float = 0.0, with_visit_confidence: bool = False, heteronyms=None, with_pronunciation: bool = False,
+                       top_k: int = 5):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
@@ -338,10 +395,15 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     number per listed occurrence, the mean visit_occupancy of its characters}.
     heteronyms (here, in align_record_lrc and in align_song; None: the outputs as above): {token id: [syllable, ...]}, the further syllables
     a character may be sung as (PinyinClassLUT.readings_of; AlignModel.align(alternatives=..., return_readings=True)).  Every character
-    entry is then [onset, offset, char, class_id_sung]."""
+    entry is then [onset, offset, char, class_id_sung].
+    with_pronunciation / top_k (here, in align_record_lrc and in align_song; off: the outputs as above): was the sheet's character the one
+    that was sung?  -> (the result as above, pronunciation): one list per line with, per character, None (left out) or {"char", "class",
+    "syllable", "frames", "log_prob", "rank", "gop", "top": [(syllable, score per frame), ... top_k of them]} -- AlignModel.align(
+    return_pronunciation=True) with every class of the lookup table as a candidate; rank 0 = the sheet's syllable scored best over the
+    character's segment, gop <= 0 its per-frame distance to the best.  suspect_characters picks the entries worth a look."""
     lines = list(lines)
     ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
-    rk = _reading_kw(lut, ids, heteronyms)
+    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k)
     if with_visit_confidence and repeatable is None:
         raise ValueError("align_record_lines: with_visit_confidence goes with repeatable (with_confidence is the keyword without it)")
     if repeatable is not None:
@@ -350,17 +412,17 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
         sheet = (model, rk, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty, repeat_penalty)
         if with_visit_confidence:
             (_, segments, scores), readings = _align_repeat_sheet(*sheet, return_repeat_confidence=True)
-            return _visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings)
+            return _done(_visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings), rk, lines, lut)
         (_, segments), readings = _align_repeat_sheet(*sheet)
-        return _line_occurrences(segments[0], lines, readings)
+        return _done(_line_occurrences(segments[0], lines, readings), rk, lines, lut)
     with torch.no_grad():
         if with_confidence:
             (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
                                                    skip_penalty=skip_penalty, return_span_confidence=True)
             present = scores[0]["sung_prob"]
-            return _sheet_lines_out(res[0], lines, (lambda pos, first: float(present[pos]),), readings)
+            return _done(_sheet_lines_out(res[0], lines, (lambda pos, first: float(present[pos]),), readings), rk, lines, lut)
         res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)
-    return _sheet_lines_out(res[0], lines, (), readings)[0]
+    return _done(_sheet_lines_out(res[0], lines, (), readings)[0], rk, lines, lut)
 
 
 _LRC_TAG = re.compile(r"\[([^\[\]]*)\]")
@@ -390,7 +452,8 @@ def parse_lrc(text: str) -> List[tuple]:
 
 
 def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
-                     use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, heteronyms=None):
+                     use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, heteronyms=None,
+                     with_pronunciation: bool = False, top_k: int = 5):
     """One recording against an LRC sheet (addition): per-character timing from per-line start times.  `lrc` is LRC text (parse_lrc) or a
     list of (start_seconds, line) pairs; the first character of every line gets an onset anchor at the line's start time with tolerance_s
     (AlignModel.align(onset_anchors=...): the line starts within tolerance_s of its tag, and everything before it has ended by then).
@@ -404,26 +467,27 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
             "window_log_prob": float <= 0, the log-probability the unanchored model gives to "the path respects every tag" -- near 0
                                when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}.
     Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song).
-    heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung]."""
+    heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung].
+    with_pronunciation / top_k: as in align_record_lines -- -> (the result as above, pronunciation per line)."""
     pairs = _timed_lines("align_record_lrc", lrc)
     lines = [line for _, line in pairs]
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_record_lrc", lines, optional, lut, tokenize)
     anchors = _line_anchors([start for start, _ in pairs], ids, tolerance_s)
-    rk = _reading_kw(lut, ids, heteronyms)
+    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k)
     with torch.no_grad():
         if with_confidence:
             (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
                                                    skip_penalty=skip_penalty, onset_anchors=[anchors], return_anchored_confidence=True)
-            return _sheet_confidence(res[0], scores[0], lines, readings)
+            return _done(_sheet_confidence(res[0], scores[0], lines, readings), rk, lines, lut)
         res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
                                      onset_anchors=[anchors])
-    return _sheet_lines_out(res[0], lines, (), readings)[0]
+    return _done(_sheet_lines_out(res[0], lines, (), readings)[0], rk, lines, lut)
 
 
 def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
                use_ctc_loss: bool = True, skip_penalty: float = 0.0, repeatable: Optional[Sequence[bool]] = None, repeat_penalty: float = 0.0,
-               heteronyms=None):
+               heteronyms=None, with_pronunciation: bool = False, top_k: int = 5):
     """A whole song against its whole sheet, timing and confidences in one call (addition): up to 4095 characters.  `sheet` is LRC text
     (parse_lrc), a list of (start_seconds, line) pairs -- every line's first character anchored at its start time with tolerance_s, as in
     align_record_lrc -- or a list of plain lines (no times: no anchors, as in align_record_lines).  optional[i] marks lines that may be
@@ -440,7 +504,8 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     first occurrence; None for a line left out) and "window_log_prob", and gains "visits", "repeat_count" and "occurrence_occupancy",
     one value per line as align_record_lines(with_visit_confidence=True) defines them.  ValueError unless one flag per line.
     heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung], and the confidences are
-    posteriors of the merged classes."""
+    posteriors of the merged classes.
+    with_pronunciation / top_k: as in align_record_lines -- -> ((lines_out, conf), pronunciation per line)."""
     if isinstance(sheet, str) or (len(sheet) > 0 and not isinstance(sheet[0], str)):
         pairs = _timed_lines("align_song", sheet)
         lines, starts = [line for _, line in pairs], [start for start, _ in pairs]
@@ -453,20 +518,21 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_song", lines, optional, lut, tokenize)
     kw = {} if starts is None else {"onset_anchors": [_line_anchors(starts, ids, tolerance_s)]}
-    rk = _reading_kw(lut, ids, heteronyms)
+    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k)
     if repeatable is not None:
         (res, segments, scores), readings = _align_repeat_sheet(model, rk, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty,
                                                                 repeat_penalty, return_song_confidence=True, **kw)
         occurrences, per_line = _visit_confidence(segments[0], scores[0], lines, ids, repeatable, readings)
         _, line_onset = _sheet_lines_out(res[0], lines, (lambda pos, first: None if first is None else float(scores[0]["onset_prob"][pos]),))
-        return occurrences, {"sung": [c["visits"] - (c["repeat_count"] or 0.0) for c in per_line], "line_onset_prob": line_onset,
-                             "window_log_prob": float(scores[0].get("window_log_prob", 0.0)),
-                             "visits": [c["visits"] for c in per_line], "repeat_count": [c["repeat_count"] for c in per_line],
-                             "occurrence_occupancy": [c["occurrence_occupancy"] for c in per_line]}
+        conf = {"sung": [c["visits"] - (c["repeat_count"] or 0.0) for c in per_line], "line_onset_prob": line_onset,
+                "window_log_prob": float(scores[0].get("window_log_prob", 0.0)),
+                "visits": [c["visits"] for c in per_line], "repeat_count": [c["repeat_count"] for c in per_line],
+                "occurrence_occupancy": [c["occurrence_occupancy"] for c in per_line]}
+        return _done((occurrences, conf), rk, lines, lut)
     with torch.no_grad():
         (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
                                                skip_penalty=skip_penalty, return_sheet_confidence=True, **kw)
-    return _sheet_confidence(res[0], scores[0], lines, readings)
+    return _done(_sheet_confidence(res[0], scores[0], lines, readings), rk, lines, lut)
 
 
 def lrc_training_clips(audio, lrc, tokenize, max_seconds: float = 30.0, tolerance_s: float = 1.0, sample_rate: int = 16000) -> List[dict]:

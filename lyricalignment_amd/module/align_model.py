@@ -339,7 +339,8 @@ class AlignModel(torch.nn.Module):
               skip_penalty: float = 0.0, return_span_confidence: bool = False, char_windows=None, onset_anchors=None,
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
               repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False,
-              return_song_confidence: bool = False, alternatives=None, return_readings: bool = False):
+              return_song_confidence: bool = False, alternatives=None, return_readings: bool = False,
+              return_pronunciation: bool = False, pronunciation_classes=None, pronunciation_top_k: int = 5):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
         returns in the reference -- but the [B,T,V] logits are never materialised and nothing leaves the GPU
@@ -418,7 +419,20 @@ class AlignModel(torch.nn.Module):
         becomes (seconds, readings)): readings[b][n] = (class id sung, [score per reading, the sheet's own class first]), None for a skipped
         character; a reading's score is the sum of its emissions over the segment the DP chose (the reported, first visit), the class the
         smallest index with the largest score (ops.reading_scores).  With return_frames two more tensors: reading [B, Lmax] int32 (index
-        into the position's readings, -1 = skipped) and col_score [B, columns] float64."""
+        into the position's readings, -1 = skipped) and col_score [B, columns] float64.
+        return_pronunciation / pronunciation_classes / pronunciation_top_k (addition): was the sheet's character the one that was sung?
+        The confidences above are posteriors GIVEN the sheet; this is the "goodness of pronunciation" of forced aligners.
+        pronunciation_classes (required with return_pronunciation: ValueError without) is an int N -- the classes 1 .. N -- or a sequence of
+        class ids; the sheet's own classes (with alternatives every reading's) are unioned in and the list is sorted and unique; label
+        columns plus candidates above 4095 raise NotImplementedError before anything is launched.  The head runs ONCE, on the sheet's rows
+        (or the expanded ones) followed by the candidate classes; the lattice reads the leading columns of that matrix, and
+        ops.segment_class_scores sums every candidate over the segment the DP chose (the reported, first visit), ranks the own class --
+        with alternatives the reading ops.reading_scores picked -- and names the pronunciation_top_k (1 .. 16) best.  The return gains
+        `pronunciation` as its last element, after `readings`: pronunciation[b][n] = None for a skipped character, else {"class": own class
+        id, "frames": n, "log_prob": own_score / n, "rank": candidates that beat the own class (0 = it is the best), "gop": (own_score -
+        best score) / n <= 0 (0.0 at rank 0), "top": [(class id, score / n), ...]}.  With every other keyword, per_clip and the long form.
+        With return_frames five more tensors, last: top_col [B, Lmax, top_k] int32 (columns of the sorted class list), top_score float64,
+        own_score [B, Lmax] float64, own_rank int32, n_seg_frames int32.  Off: the call as it was.  No threshold on gop is calibrated."""
         from ..utils import alignment as ua
         if return_readings and alternatives is None:
             raise ValueError("align: return_readings goes with alternatives (without them every character has the one reading of its label)")
@@ -438,6 +452,8 @@ class AlignModel(torch.nn.Module):
             if widest > ua.POSTERIOR_MAX_LABELS:
                 raise NotImplementedError(f"align: {widest} labels exceed the {ua.POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
         rd = None if alternatives is None else ua._readings_of(alternatives, ua._label_lists(labels, len(labels)), keep_empty=return_readings)
+        pron = ua._pronunciation_of("align", return_pronunciation, pronunciation_classes, pronunciation_top_k,
+                                    ua._label_lists(labels, len(labels)) if return_pronunciation else None, rd)
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -475,10 +491,11 @@ class AlignModel(torch.nn.Module):
 
         out = ua.align_labels("align", head, lab_dev, n_lab, lab_lists, frame_counts, T, kw.get("n_frames"), hop_size_second, confidence,
                               boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
-                              alternatives, return_readings, rd, raw=return_frames)
+                              alternatives, return_readings, rd, raw=return_frames, pron=pron)
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path);
             r, picked = out
-            return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,)) + picked     # reading, col_score last
+            # reading, col_score behind them, the five tensors of the pronunciation scores last
+            return tuple(t for t in r if t is not None) + (() if r.path is None else (r.path,)) + picked
         return out
 
 

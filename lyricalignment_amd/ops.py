@@ -380,6 +380,71 @@ def reading_scores(em_x: torch.Tensor, alt_start: torch.Tensor, n_labels: torch.
     return reading, col_score
 
 
+MAX_PRONUNCIATION_TOP_K = 16
+
+
+def segment_class_scores(em_c: torch.Tensor, n_labels: torch.Tensor, onset: torch.Tensor, offset: torch.Tensor, own_col: torch.Tensor,
+                         top_k: int = 5, want_scores: bool = False, out=None):
+    """la_segment_class_scores: every candidate class summed over the segment the DP gave a position.  em_c [B,T,C] f32 with unit inner
+    stride (any row / batch stride: a column window of a wider matrix is taken as it is), n_labels [B] i32, onset / offset [B,Lmax] i32 (a
+    lattice entry's outputs), own_col [B,Lmax] i32 (the candidate column of the position's own class, -1 = none); all on the device.
+    -> top_col [B,Lmax,top_k] i32, top_score [B,Lmax,top_k] f64 (the largest sequential float64 sums, the largest first, ties to the
+    smaller column; -1 / -inf beyond C entries), own_score [B,Lmax] f64, own_rank [B,Lmax] i32 (candidates before the own class; 0 =
+    it is the best, -1 = no own class), n_seg_frames [B,Lmax] i32 [, seg_score [B,Lmax,C] f64 with want_scores].  A skipped position
+    (onset -1): top_col -1, own_rank -1, zeros elsewhere.  Entries of positions beyond a clip's own labels are not written.
+    out: the caller's tensors in that order (seg_score last where want_scores) -- top_col / top_score with one position pitch and
+    stride(0) = Lmax * stride(1), the three [B,Lmax] ones with one row pitch -- e.g. to keep what they hold beyond a clip's labels."""
+    who = "segment_class_scores"
+    for name, t in (("n_labels", n_labels), ("onset", onset), ("offset", offset), ("own_col", own_col)):
+        _dev(t, name, torch.int32)
+    _dev(em_c, "em_c", torch.float32)
+    if em_c.dim() != 3 or em_c.stride(2) != 1 or onset.dim() != 2:
+        raise ValueError(f"{who}: em_c [B,T,C] with unit inner stride and onset [B,Lmax] expected")
+    B, T, C = em_c.shape
+    Lmax = onset.shape[1]
+    if onset.shape[0] != B or offset.shape != (B, Lmax) or own_col.shape != (B, Lmax) or n_labels.shape != (B,):
+        raise ValueError(f"{who}: inconsistent shapes")
+    top_k = int(top_k)
+    if top_k < 1:
+        raise ValueError(f"{who}: top_k must be >= 1")
+    if top_k > MAX_PRONUNCIATION_TOP_K or C > 4095 or Lmax > 4095:
+        raise NotImplementedError(f"{who}: top_k {top_k} exceeds {MAX_PRONUNCIATION_TOP_K}, or {C} candidates / {Lmax} labels exceed 4095")
+    dev = em_c.device
+    if out is None:
+        top_col = torch.empty((B, Lmax, top_k), dtype=torch.int32, device=dev)
+        top_score = torch.empty((B, Lmax, top_k), dtype=torch.float64, device=dev)
+        own_score = torch.empty((B, Lmax), dtype=torch.float64, device=dev)
+        own_rank, n_seg = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
+        seg = torch.empty((B, Lmax, C), dtype=torch.float64, device=dev) if want_scores else None
+    else:
+        top_col, top_score, own_score, own_rank, n_seg = out[:5]
+        seg = out[5] if want_scores else None
+        for name, t, dt, shape in (("top_col", top_col, torch.int32, (B, Lmax, top_k)), ("top_score", top_score, torch.float64, (B, Lmax, top_k)),
+                                   ("own_score", own_score, torch.float64, (B, Lmax)), ("own_rank", own_rank, torch.int32, (B, Lmax)),
+                                   ("n_seg_frames", n_seg, torch.int32, (B, Lmax))) + ((("seg_score", seg, torch.float64, (B, Lmax, C)),) if want_scores else ()):
+            _dev(t, name, dt)
+            if tuple(t.shape) != shape or t.stride(-1) != 1:
+                raise ValueError(f"{who}: out: {name} {list(shape)} with unit inner stride expected")
+        if (top_col.stride() != top_score.stride() or top_col.stride(0) != Lmax * top_col.stride(1)
+                or not own_score.stride(0) == own_rank.stride(0) == n_seg.stride(0)):
+            raise ValueError(f"{who}: out: top_col / top_score need one position pitch with stride(0) = Lmax * stride(1), own_score / "
+                             "own_rank / n_seg_frames one row pitch")
+    pitch = own_score.stride(0)                        # the C entry's out_stride: onset / offset share it with the three [B,Lmax] outputs
+    if onset.stride() != (pitch, 1) or offset.stride() != (pitch, 1):
+        rows = torch.empty((2, B, pitch), dtype=torch.int32, device=dev)
+        rows[0, :, :Lmax] = onset
+        rows[1, :, :Lmax] = offset
+        onset, offset = rows[0, :, :Lmax], rows[1, :, :Lmax]
+    if own_col.stride(1) != 1:
+        own_col = own_col.contiguous()
+    check(lib().la_segment_class_scores(ptr(em_c), em_c.stride(0), em_c.stride(1), ptr(n_labels.contiguous()), ptr(onset), ptr(offset), pitch,
+                                        ptr(own_col), own_col.stride(0), B, T, Lmax, C, top_k, ptr(seg),
+                                        seg.stride(0) if seg is not None else 0, seg.stride(1) if seg is not None else 0, ptr(top_col),
+                                        ptr(top_score), top_col.stride(1), ptr(own_score), ptr(own_rank), ptr(n_seg), stream_ptr()), who)
+    res = (top_col, top_score, own_score, own_rank, n_seg)
+    return res + (seg,) if want_scores else res
+
+
 # --------------------------------------------------------------------------- #
 # encoder / head building blocks                                                #
 # --------------------------------------------------------------------------- #

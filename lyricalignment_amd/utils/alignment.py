@@ -223,6 +223,100 @@ def readings_route(rd: Readings, emissions_of, n_lab, nf, device) -> ReadingRout
     return ReadingRoute(rd, em_x, alt, ops.merge_readings(em_x, alt, n_lab, nf), rd.lattice_ids.to(device))
 
 
+MAX_PRONUNCIATION_COLUMNS = 4095      # label columns (the sheet's, or the expanded readings') plus candidate classes: what the head / prep take
+
+
+class Pronunciation(NamedTuple):
+    """_pronunciation_of's result (host): what the route with pronunciation scores needs beside the labels."""
+    classes: List[int]              # the candidate class ids, sorted and unique: candidate column j holds classes[j]
+    top_k: int
+    own_col: torch.Tensor           # [B, Lmax] int32: the candidate column of the sheet's class per position, -1 beyond a clip's labels
+    col_of: torch.Tensor            # [largest class id + 1] int32: class id -> candidate column, -1 = not a candidate
+
+
+def _pronunciation_of(who: str, return_pronunciation, pronunciation_classes, pronunciation_top_k, label_lists: List[List[int]],
+                      rd: Optional[Readings] = None) -> Optional[Pronunciation]:
+    """The three keywords of the pronunciation scores -> Pronunciation, or None when return_pronunciation is off (the call as it was).
+    pronunciation_classes: an int N (classes 1 .. N) or a sequence of class ids; the sheet's own classes (with alternatives: every
+    reading's) are unioned in; sorted and unique.  ValueError for a missing class list, an id below 1 or a top_k outside 1 .. 16;
+    NotImplementedError when the label columns (rd: the widest expanded row) plus the candidates exceed MAX_PRONUNCIATION_COLUMNS.
+    Host only."""
+    if not return_pronunciation:
+        return None
+    if pronunciation_classes is None:
+        raise ValueError(f"{who}: return_pronunciation needs pronunciation_classes (an int N for classes 1..N, or a sequence of class ids)")
+    if isinstance(pronunciation_top_k, bool) or int(pronunciation_top_k) != pronunciation_top_k \
+            or not 1 <= int(pronunciation_top_k) <= ops.MAX_PRONUNCIATION_TOP_K:
+        raise ValueError(f"{who}: pronunciation_top_k must be an int in 1..{ops.MAX_PRONUNCIATION_TOP_K}")
+    if isinstance(pronunciation_classes, bool):
+        raise ValueError(f"{who}: pronunciation_classes must be an int N (classes 1..N) or a sequence of class ids")
+    if isinstance(pronunciation_classes, (int, np.integer)):
+        if pronunciation_classes < 1:
+            raise ValueError(f"{who}: pronunciation_classes = {pronunciation_classes}: at least class 1 expected")
+        given = range(1, int(pronunciation_classes) + 1)
+    else:
+        given = [int(c) for c in pronunciation_classes]
+        if any(c < 1 for c in given):
+            raise ValueError(f"{who}: pronunciation_classes: class ids start at 1")
+    sheet = [c for row in rd.sets for r in row for c in r] if rd is not None else [int(c) for row in label_lists for c in row]
+    classes = sorted(set(given) | set(sheet))
+    Lmax = max(1, max((len(l) for l in label_lists), default=1))
+    width = rd.labels_x.shape[1] if rd is not None else Lmax
+    if width + len(classes) > MAX_PRONUNCIATION_COLUMNS:
+        raise NotImplementedError(f"{who}: {width} label columns + {len(classes)} pronunciation classes exceed {MAX_PRONUNCIATION_COLUMNS}")
+    col_of = torch.full((classes[-1] + 1,), -1, dtype=torch.int32)
+    col_of[torch.tensor(classes, dtype=torch.int64)] = torch.arange(len(classes), dtype=torch.int32)
+    own_col = torch.full((len(label_lists), Lmax), -1, dtype=torch.int32)
+    for b, row in enumerate(label_lists):
+        if row:
+            own_col[b, : len(row)] = col_of[torch.tensor(row, dtype=torch.int64)]
+    return Pronunciation(classes, int(pronunciation_top_k), own_col, col_of)
+
+
+def _widened_labels(lab: torch.Tensor, n: torch.Tensor, classes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Label rows lab [B, W] / counts n [B] and the candidate classes [C] (int32, one device) -> the rows the head or the prep is asked
+    for: lab's rows, their padding filled with a valid class (classes[0]; those columns are never read), then the C candidates at the
+    fixed columns W .. W + C - 1, and the count W + C for every clip."""
+    W = lab.shape[1]
+    own = torch.where(torch.arange(W, device=lab.device)[None, :] < n[:, None], lab, classes[0])
+    lab_w = torch.cat([own, classes[None, :].expand(lab.shape[0], -1)], dim=1).contiguous()
+    return lab_w, torch.full_like(n, W + classes.shape[0])
+
+
+def _own_columns(pron: Pronunciation, route, reading, device) -> torch.Tensor:
+    """own_col [B, Lmax] int32 on the device: the sheet's class per position, or with alternatives (route) the reading that
+    ops.reading_scores picked (`reading`), gathered on the device; -1 for a skipped position and beyond a clip's labels."""
+    if route is None:
+        return pron.own_col.to(device)
+    Lmax = reading.shape[1]
+    at = (route.alt_start[:, :Lmax] + reading.clamp(min=0)).clamp(max=route.rd.labels_x.shape[1] - 1).long()
+    picked = torch.gather(route.rd.labels_x.to(device), 1, at).long()
+    valid = (reading >= 0) & (pron.own_col.to(device) >= 0)
+    return torch.where(valid, pron.col_of.to(device)[picked.clamp(max=pron.col_of.shape[0] - 1)], torch.full_like(reading, -1))
+
+
+def _pronunciation_from_scores(scores, own_col, pron: Pronunciation, label_lists):
+    """Device outputs of ops.segment_class_scores -> pronunciation[b][n] = None for a skipped character, else {"class": the own class id,
+    "frames": n, "log_prob": own_score / n, "rank": own_rank, "gop": (own_score - top_score[0]) / n, "top": [(class id, score / n),
+    ...]}.  gop <= 0, and 0.0 where the own class has the best sum (stated without the subtraction: -inf beside -inf)."""
+    top_col, top_score, own_score, own_rank, n_seg = (t.cpu().numpy() for t in scores[:5])
+    own = own_col.cpu().numpy()
+    out = []
+    for b, labs in enumerate(label_lists):
+        row = []
+        for n in range(len(labs)):
+            if top_col[b, n, 0] < 0:
+                row.append(None)
+                continue
+            frames, mine, best = int(n_seg[b, n]), float(own_score[b, n]), float(top_score[b, n, 0])
+            per = max(frames, 1)
+            row.append({"class": pron.classes[own[b, n]] if own[b, n] >= 0 else int(labs[n]), "frames": frames, "log_prob": mine / per,
+                        "rank": int(own_rank[b, n]), "gop": 0.0 if mine == best else (mine - best) / per,
+                        "top": [(pron.classes[j], float(s) / per) for j, s in zip(top_col[b, n], top_score[b, n]) if j >= 0]})
+        out.append(row)
+    return out
+
+
 def _visits_of_row(row):
     """One clip's lattice state per frame -> the time-ordered list of (char_index, first frame, last frame + 1) of every visit: the maximal
     runs of frames in one odd lattice state."""
@@ -591,7 +685,7 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 
 def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, n_frames_max: int, nf, hop_size_second, confidence,
                  boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
-                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False):
+                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False, pron: Optional[Pronunciation] = None):
     """What perform_viterbi* and AlignModel.align (`who`: "perform_viterbi" / "align") do once the labels (lab / n_lab on the device,
     label_lists), the spans and windows (host rows, or None) and the kind of confidence are known: the repeat_from rows
     (_repeat_from_of_spans for "repeat" / "song", whose label limit is refused here; _repeat_rows otherwise), the readings (rd: the
@@ -602,7 +696,13 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     has them anyway (the fused head), else None.  With alternatives it is asked once, for the expanded rows; otherwise once for lab,
     with needed = "another lattice or a sweep reads the emissions" -- a dp without emissions is the result, and nothing else is launched.
     nf: the device frame counts of a ragged batch, or None: every clip has n_frames_max frames (filled here, and only if needed).
-    raw: -> (the LatticeResult, ops.reading_scores' pair or ()) in place of the formatted value."""
+    raw: -> (the LatticeResult, ops.reading_scores' pair or ()) in place of the formatted value.
+    pron (the caller's _pronunciation_of result, or None: the call as it was): the pronunciation scores.  emissions_of is asked ONCE for
+    the widened rows (_widened_labels: the sheet's or the expanded rows, then the candidate classes); whatever DP result it brings is
+    dropped, as the readings route drops it, and the lattice reads the leading columns of the widened matrix through its row stride.
+    ops.segment_class_scores then runs on the trailing column window and the DP's onset / offset, with the sheet's class -- with
+    alternatives the reading ops.reading_scores picked -- as the own class.  The return gains `pronunciation` as its last element
+    (raw: ops.segment_class_scores' five tensors behind the reading pair)."""
     repeat_kind = confidence in ("repeat", "song")
     if repeat_kind:
         repeat_from = _repeat_from_of_spans(repeat_spans, label_lists)
@@ -615,7 +715,15 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     # sees the set-equality ids in the labels' place; None / all-empty takes the call as it was
     if rd is None:
         rd = _readings_of(alternatives, label_lists, keep_empty=return_readings)
-    route, dp, em = None, None, None
+    route, dp, em, em_c = None, None, None, None
+    if pron is not None:
+        classes, plain_emissions_of = torch.tensor(pron.classes, dtype=torch.int32).to(lab.device), emissions_of
+
+        def emissions_of(lab_x, n_x, needed=True):
+            nonlocal em_c
+            em_w = plain_emissions_of(*_widened_labels(lab_x, n_x, classes), True)[1]
+            em_c = em_w[:, :, 1 + lab_x.shape[1]:]
+            return None, em_w[:, :, : 1 + lab_x.shape[1]]
     if rd is None:
         dp, em = emissions_of(lab, n_lab, confidence is not None or skip_from is not None or windows is not None or repeat_from is not None)
     if rd is None and em is None:
@@ -627,27 +735,39 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
             route = readings_route(rd, lambda lab_x, n_x: emissions_of(lab_x, n_x)[1], n_lab, nf, lab.device)
             em, lab = route.em, route.lattice_ids
         r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from, repeat_penalty)
-    picked = route.scores(n_lab, r.onset, r.offset) if return_readings else ()
+    picked = route.scores(n_lab, r.onset, r.offset) if return_readings or (pron is not None and route is not None) else ()
+    if pron is not None:
+        own_col = _own_columns(pron, route, picked[0] if route is not None else None, lab.device)
+        scored = ops.segment_class_scores(em_c, n_lab, r.onset, r.offset, own_col, pron.top_k)
+        picked = picked if return_readings else ()
     if raw:
-        return r, picked
+        return (r, picked) if pron is None else (r, picked + scored)
     if repeat_kind:
         seconds, segments, scores = _formatted_repeat(r, label_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
         out = (seconds, segments, scores) if return_segments else (seconds, scores)
     else:
         seconds = _formatted(r, label_lists, hop_size_second, optional_spans)
         out = (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
-    if not return_readings:
-        return out
-    readings = _readings_from_scores(*picked, rd)
-    return (*out, readings) if isinstance(out, tuple) else (out, readings)
+    if return_readings:
+        readings = _readings_from_scores(*picked, rd)
+        out = (*out, readings) if isinstance(out, tuple) else (out, readings)
+    if pron is not None:
+        pronunciation = _pronunciation_from_scores(scored, own_col, pron, label_lists)
+        out = (*out, pronunciation) if isinstance(out, tuple) else (out, pronunciation)
+    return out
 
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, confidence=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False,
-             alternatives=None, return_readings=False):
+             alternatives=None, return_readings=False, return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """confidence: the kind the public function stands for (run_lattice's); "plain" becomes "span" where a span is given."""
     if return_readings and alternatives is None:
         raise ValueError("return_readings goes with alternatives (without them every character has the one reading of its label)")
+    rd = pron = None
+    if return_pronunciation:                 # the keyword checks, before anything is on a device
+        lists = _label_lists(labels, len(labels))
+        rd = _readings_of(alternatives, lists, keep_empty=return_readings)
+        pron = _pronunciation_of("perform_viterbi", True, pronunciation_classes, pronunciation_top_k, lists, rd)
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -672,11 +792,12 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         confidence = "span"
     return align_labels("perform_viterbi", lambda lab_x, n_x, needed=True: (None, ops.emissions_from_logits(pred, lab_x, n_x, variant)), lab,
                         n_lab, lists, counts, T, nf, hop_size_second, confidence, boundary_window, skip_from, windows, skip_penalty,
-                        optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings)
+                        optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings, rd, pron=pron)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                    char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False):
+                    char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
+                    return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
     aligned over its first n_frames[b] rows, as if it had been handed over alone.
     optional_spans (addition): optional_spans[b] = list of (a, n) pairs, labels a .. n-1 of utterance b may be left out by the path
@@ -704,17 +825,32 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     return_readings (with alternatives; ValueError without): the return gains `readings` as its last element (a bare result becomes
     (result, readings)): readings[b][n] = (class id sung, [score per reading, the sheet's own class first]) -- the score of a reading is
     the sum of its emissions over the segment the DP chose (the reported visit), the class the smallest index with the largest score
-    (la_reading_scores) -- or None for a skipped character."""
+    (la_reading_scores) -- or None for a skipped character.
+    return_pronunciation / pronunciation_classes / pronunciation_top_k (addition; here and in perform_viterbi_ctc): was the sheet's
+    character the one that was sung?  pronunciation_classes (required: ValueError without) is an int N -- classes 1 .. N -- or a sequence of
+    class ids; the sheet's own classes are unioned in, the list sorted and unique; with the label columns at most 4095 columns
+    (NotImplementedError before anything is launched).  The prep runs once on the sheet's rows followed by the candidate classes, the
+    lattice on the leading columns of that matrix, and la_segment_class_scores sums every candidate over the segment the DP chose (the
+    reported, first visit).  The return gains `pronunciation` as its last element, after `readings`: pronunciation[b][n] = None for a
+    skipped character, else {"class": the own class id (with alternatives the reading picked), "frames": n, "log_prob": own_score / n,
+    "rank": the number of candidates that beat the own class (0 = it is the best), "gop": (own_score - best score) / n <= 0, 0.0 at
+    rank 0, "top": [(class id, score / n), ...] the pronunciation_top_k (1 .. 16) best}.  With every other keyword; off: the call as it
+    was.  No threshold on gop is calibrated: none has been measured on real singing."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
-                    repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings)
+                    repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
+                    return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
+                    pronunciation_top_k=pronunciation_top_k)
 
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                        char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False):
+                        char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
+                        return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
-                    repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings)
+                    repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
+                    return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
+                    pronunciation_top_k=pronunciation_top_k)
 
 
 def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0,
@@ -884,7 +1020,8 @@ def anchored_loss_inputs(labels, frame_counts: Sequence[int], onset_anchors=None
 
 
 def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_windows=None, optional_spans=None, skip_penalty=0.0,
-                            hop_size_second=0.02, n_frames=None, on_infeasible="raise", repeat_spans=None, alternatives=None):
+                            hop_size_second=0.02, n_frames=None, on_infeasible="raise", repeat_spans=None, alternatives=None,
+                            return_pronunciation=False):
     """Training from line times (addition; the reference's losses need a label for every frame): -log of the total weight of the alignments
     that char_windows / onset_anchors (per utterance, in windows_from_anchors' form, seconds in the utterance's own frames) and
     optional_spans (as perform_viterbi) allow, per frame and averaged over the batch -- include/lyricalign.h la_anchored_alignment_loss.
@@ -897,11 +1034,14 @@ def anchored_alignment_loss(align_logit, labels, onset_anchors=None, char_window
     without a path inside its windows (or without labels); "skip" does not read it: such a clip adds nothing to the loss (still divided by
     B) and gets a zero gradient.
     repeat_spans: ValueError unless None or all-empty (the loss does not know the lattice with repeatable spans).
-    alternatives: ValueError unless None or all-empty (training on merged classes is not part of the pronunciation alternatives)."""
+    alternatives: ValueError unless None or all-empty (training on merged classes is not part of the pronunciation alternatives).
+    return_pronunciation: ValueError if set (the pronunciation scores are read off an alignment; the loss has none to report)."""
     if repeat_spans is not None and any(len(v or ()) for v in repeat_spans):
         raise ValueError("anchored_alignment_loss: repeat_spans are not supported (no sum-product sweep on the lattice with repeatable spans)")
     if alternatives is not None and any(len(v or ()) for v in alternatives):
         raise ValueError("anchored_alignment_loss: alternatives are not supported (the loss is not defined on merged classes)")
+    if return_pronunciation:
+        raise ValueError("anchored_alignment_loss: return_pronunciation is not supported (the pronunciation scores belong to the aligner)")
     if on_infeasible not in ("raise", "skip"):
         raise ValueError('anchored_alignment_loss: on_infeasible must be "raise" or "skip"')
     if not torch.is_tensor(align_logit) or align_logit.dim() != 3 or not align_logit.is_cuda or align_logit.dtype != torch.float32:
