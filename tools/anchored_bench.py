@@ -1,7 +1,7 @@
 """Cost of the alignment DP with per-state frame windows (la_viterbi_windows_batch) beside la_viterbi_batch and
 la_viterbi_spans_batch; all three are instantiations of one kernel in csrc/la_viterbi.hip.
 
-    python tools/anchored_bench.py [--runs 30] [--parent-lib <liblyricalign_hip.so of the parent commit>] [--out profiles/anchored_alignment.txt]
+    python tools/anchored_bench.py [--runs 30] [--quick] [--parent-lib <liblyricalign_hip.so of the parent commit>] [--out profiles/anchored_alignment.txt]
 
 Two shapes on synthetic emissions -- 32 clips x 1500 frames x 26 labels (four lines of 6 / 7 / 6 / 7 characters; one wave, masks in LDS)
 and one song of 5389 frames x 200 labels (four lines of 50; 8 waves, masks in the workspace); the emissions plant lines 1, 2 and 4.
@@ -18,176 +18,69 @@ bit against la_viterbi_batch's, and every anchored leg's status is LA_OK, before
 """
 from __future__ import annotations
 
-import argparse
-import ctypes
-import os
-import statistics
-import sys
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import benchlib as bl
+
+LEGS = ("la_viterbi_batch", "la_viterbi_spans_batch, no span", "la_viterbi_spans_batch, four optional lines",
+        "la_viterbi_windows_batch, all windows open", "la_viterbi_windows_batch, one onset anchor per line, +-1 s",
+        "la_viterbi_windows_batch, anchors + four optional lines")
 PRESENT = [True, True, False, True]
 SHAPES = [("32 clips x 1500 frames x 26 labels (1 wave, masks in LDS)", 32, 1500, [6, 7, 6, 7]),
           ("1 song x 5389 frames x 200 labels (8 waves, masks in the workspace)", 1, 5389, [50, 50, 50, 50])]
+QUICK = [("2 clips x 160 frames x 8 labels (1 wave)", 2, 160, [2, 2, 2, 2]), ("1 song x 400 frames x 40 labels (2 waves)", 1, 400, [10, 10, 10, 10])]
 TOL_S = 1.0
 
 
-def _time_once(torch, fn):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e)
+def leg_table(quick=False):
+    """Per shape, the names the report gives the legs."""
+    return [list(LEGS) for _ in (QUICK if quick else SHAPES)]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=30)
-    ap.add_argument("--parent-lib", default="")
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    sys.path.insert(0, os.path.join(HERE, ".."))
-    import torch
-    from lyricalignment_amd import _lib
-    from lyricalignment_amd._lib import SYMBOLS, lib, ptr, stream_ptr
-    from lyricalignment_amd.utils.alignment import spans_from_lines, windows_from_anchors
-    _lib.require_gpu()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    parent = None
-    if args.parent_lib:
-        parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
-        for name in ("la_viterbi_workspace_bytes", "la_viterbi_batch", "la_viterbi_spans_workspace_bytes", "la_viterbi_spans_batch"):
-            fn = getattr(parent, name)
-            fn.restype, fn.argtypes = SYMBOLS[name]
+def main(argv=None):
+    args = bl.parse(bl.parser(parent_lib=True, quick=True), argv)
+    report = bl.Report(args.out)
+    say = report.say
+    dev, lib = bl.open_gpu()
+    from lyricalignment_amd.utils.alignment import spans_from_lines
+    parent = bl.load_parent(args.parent_lib, ("viterbi", "viterbi_spans")) if args.parent_lib else None
 
     say(f"# alignment DP with per-state frame windows on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a "
         f"warm-up of 3, legs alternated call by call, device events around one call, ms")
-    for title, B, T, line_lengths in SHAPES:
+    for title, B, T, line_lengths in QUICK if args.quick else SHAPES:
         L = sum(line_lengths)
-        # emissions -rand * 12 - 1 with a 0.8 * 12 bonus on an even segmentation of the SUNG labels (lines 1, 2 and 4)
-        g = torch.Generator().manual_seed(B + T + L)
-        em = -torch.rand((B, T, L + 1), generator=g) * 12 - 1
-        sung, pos = [], 0
-        for n_chars, here in zip(line_lengths, PRESENT):
-            sung += list(range(pos, pos + n_chars)) if here else []
-            pos += n_chars
-        seg = T // (2 * len(sung) + 1)
-        for i, n in enumerate(sung):
-            em[:, (2 * i + 1) * seg:(2 * i + 2) * seg, 1 + n] += 9.6
-        for i in range(len(sung) + 1):
-            em[:, 2 * i * seg:(2 * i + 1) * seg, 0] += 9.6
-        em = em.to(dev)
-        labels = torch.arange(1, L + 1, dtype=torch.int32).repeat(B, 1).to(dev)
-        n_labels = torch.full((B,), L, dtype=torch.int32, device=dev)
-        n_frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+        c = bl.case(bl.planted(B, T, L, bl.sung_lines(line_lengths, PRESENT), B + T + L, dev), *bl.sheet(B, T, L, dev))    # lines 1, 2 and 4
         skip_none = torch.full((B, L + 1), -1, dtype=torch.int32, device=dev)
-        skip_all = torch.tensor(spans_from_lines(line_lengths, [True] * len(line_lengths)), dtype=torch.int32).repeat(B, 1).to(dev)
-        starts = [sum(line_lengths[:i]) for i in range(len(line_lengths))]
+        skip_all = bl.rows(spans_from_lines(line_lengths, [True] * len(line_lengths)), B, dev)
+        starts = bl.starts_of(line_lengths)
 
-        def outputs():
-            return (torch.full((B, L), -7, dtype=torch.int32, device=dev), torch.full((B, L), -7, dtype=torch.int32, device=dev),
-                    torch.full((B,), -7.0, dtype=torch.float64, device=dev), torch.full((B,), -7, dtype=torch.int32, device=dev))
-
-        def workspace(L_, query):
-            need = ctypes.c_size_t(0)
-            assert getattr(L_, query)(B, T, L, ctypes.byref(need)) == 0
-            return torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev), need.value
-
-        def plain_leg(L_):
-            out, (ws, need) = outputs(), workspace(L_, "la_viterbi_workspace_bytes")
-
-            def fn():
-                on, off, score, status = out
-                assert L_.la_viterbi_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), L, ptr(n_labels), ptr(n_frames), B, T, L, ptr(on),
-                                           ptr(off), L, ptr(score), ptr(status), ptr(ws), need, stream_ptr()) == 0
-            return fn, out
-
-        def spans_leg(L_, skip):
-            out, (ws, need) = outputs(), workspace(L_, "la_viterbi_spans_workspace_bytes")
-
-            def fn():
-                on, off, score, status = out
-                assert L_.la_viterbi_spans_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), L, ptr(n_labels), ptr(n_frames), B, T, L, ptr(on),
-                                                 ptr(off), L, ptr(score), ptr(status), ptr(skip), L + 1, 0.0, ptr(ws), need, stream_ptr()) == 0
-            return fn, out
-
-        def windows_leg(skip, lo, hi):
-            out, (ws, need) = outputs(), workspace(lib(), "la_viterbi_windows_workspace_bytes")
-
-            def fn():
-                on, off, score, status = out
-                assert lib().la_viterbi_windows_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), L, ptr(n_labels), ptr(n_frames), B, T, L,
-                                                      ptr(on), ptr(off), L, ptr(score), ptr(status), ptr(skip), L + 1 if skip is not None else 0, 0.0,
-                                                      ptr(lo), ptr(hi), 2 * L + 1, ptr(ws), need, stream_ptr()) == 0, _lib.last_error()
-            return fn, out
-
-        def anchored(onsets):
-            """Windows of every clip from one onset anchor per line, at the frame the given result has for the line's first sung character
-            (a line that was left out: the next line's)."""
-            lo_rows, hi_rows = [], []
-            for b in range(B):
-                anchors, nxt = [], None
-                for a in reversed(starts):
-                    f = int(onsets[b, a])
-                    nxt = f if f >= 0 else nxt
-                    anchors.append((a, (nxt if nxt is not None else T - 1) * 0.02, TOL_S))
-                lo, hi = windows_from_anchors(L, T, onset_anchors=anchors)
-                lo_rows.append(lo); hi_rows.append(hi)
-            return torch.tensor(lo_rows, dtype=torch.int32).to(dev), torch.tensor(hi_rows, dtype=torch.int32).to(dev)
-
-        legs = [("la_viterbi_batch", plain_leg(lib())), ("la_viterbi_spans_batch, no span", spans_leg(lib(), skip_none)),
-                ("la_viterbi_spans_batch, four optional lines", spans_leg(lib(), skip_all))]
-        for _, (fn, _) in legs:
-            fn()
-        torch.cuda.synchronize()
-        open_lo = torch.zeros((B, 2 * L + 1), dtype=torch.int32, device=dev)
-        open_hi = torch.full((B, 2 * L + 1), T, dtype=torch.int32, device=dev)
-        lo_a, hi_a = anchored(legs[0][1][1][0].cpu())
-        lo_s, hi_s = anchored(legs[2][1][1][0].cpu())
-        legs += [("la_viterbi_windows_batch, all windows open", windows_leg(None, open_lo, open_hi)),
-                 ("la_viterbi_windows_batch, one onset anchor per line, +-1 s", windows_leg(None, lo_a, hi_a)),
-                 ("la_viterbi_windows_batch, anchors + four optional lines", windows_leg(skip_all, lo_s, hi_s))]
+        legs = list(zip(LEGS, (bl.dp_leg(lib, "viterbi", c), bl.dp_leg(lib, "viterbi_spans", c, skip_none), bl.dp_leg(lib, "viterbi_spans", c, skip_all))))
+        bl.warm_up(legs, 1)
+        win_a = bl.anchored_windows(legs[0][1][1]["onset"], starts, T, L, TOL_S)
+        win_s = bl.anchored_windows(legs[2][1][1]["onset"], starts, T, L, TOL_S)
+        legs += list(zip(LEGS[3:], (bl.dp_leg(lib, "viterbi_windows", c, None, bl.open_windows(B, T, L, dev)),
+                                    bl.dp_leg(lib, "viterbi_windows", c, None, win_a), bl.dp_leg(lib, "viterbi_windows", c, skip_all, win_s))))
         if parent is not None:
-            legs += [("parent commit: la_viterbi_batch", plain_leg(parent)), ("parent commit: la_viterbi_spans_batch, no span", spans_leg(parent, skip_none))]
-        for _ in range(3):
-            for _, (fn, _) in legs:
-                fn()
-        torch.cuda.synchronize()
-        assert all(torch.equal(a, b) for a, b in zip(legs[0][1][1], legs[3][1][1])), "all-open outputs differ from la_viterbi_batch"
-        assert all(torch.equal(a, b) for a, b in zip(legs[0][1][1], legs[1][1][1])), "span-free outputs differ from la_viterbi_batch"
+            legs += [("parent commit: " + LEGS[0], bl.dp_leg(parent, "viterbi", c)), ("parent commit: " + LEGS[1], bl.dp_leg(parent, "viterbi_spans", c, skip_none))]
+        bl.warm_up(legs)
+        outs = [out for _, (_, out) in legs]
+        assert bl.same_bits(outs[0], outs[3], bl.DP_OUT), "all-open outputs differ from la_viterbi_batch"
+        assert bl.same_bits(outs[0], outs[1], bl.DP_OUT), "span-free outputs differ from la_viterbi_batch"
         for name, (_, out) in legs:
-            assert int(out[3].abs().sum()) == 0, f"{name}: status not LA_OK"
-        same = all(torch.equal(a, b) for a, b in zip(legs[2][1][1], legs[5][1][1]))      # anchors laid around the span DP's own result
-        closed = float(((lo_a > 0) | (hi_a < T)).float().mean())
-        ts = [[] for _ in legs]
-        for _ in range(args.runs):
-            for i, (_, (fn, _)) in enumerate(legs):
-                ts[i].append(_time_once(torch, fn))
+            assert bl.ok(out), f"{name}: status not LA_OK"
+        same = bl.same_bits(outs[2], outs[5], bl.DP_OUT)      # anchors laid around the span DP's own result
+        closed = float(((win_a[0] > 0) | (win_a[1] < T)).float().mean())
+        ts = bl.alternated(legs, args.runs, warmup=0)
         say(f"## {title}")
-        base = statistics.median(ts[0])
-        stats = []
-        for (name, _), t in zip(legs, ts):
-            m, lo_t, hi_t = statistics.median(t), min(t), max(t)
-            stats.append((m, lo_t, hi_t))
-            say(f"{name:62s} {m:8.3f} ({lo_t:.3f} .. {hi_t:.3f})   {m / base:5.2f} x la_viterbi_batch")
+        stats = {name: bl.stat(t) for name, t in ts.items()}
+        for name, st in stats.items():
+            say(bl.timed(name, st, 62) + f"   {st[0] / stats[LEGS[0]][0]:5.2f} x la_viterbi_batch")
         say(f"all-open outputs equal la_viterbi_batch's bit for bit; anchors narrow {100 * closed:.0f} % of the states' windows; every status LA_OK; "
             f"anchored + optional result equals the unanchored one: {same}")
         if parent is not None:
-            m, (pm, plo, phi) = stats[3][0], stats[-1]
-            where = "inside" if plo <= m <= phi else ("BELOW" if m < plo else "ABOVE")
-            say(f"all windows open {m:.3f} against the parent's span-free la_viterbi_spans_batch {pm:.3f} ({plo:.3f} .. {phi:.3f}): {where} its "
-                f"min .. max ({100 * (m / pm - 1):+.1f} % of its median)")
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+            say(bl.against_parent(f"{LEGS[3]} beside the parent's span-free la_viterbi_spans_batch", stats[LEGS[3]], stats["parent commit: " + LEGS[1]]))
+    report.close()
+    return report.lines
 
 
 if __name__ == "__main__":

@@ -14,48 +14,26 @@ resource lines of the new kernels come from the build's record (csrc/_obj/la_anc
 """
 from __future__ import annotations
 
-import argparse
 import ctypes
 import json
 import os
-import statistics
-import sys
+
+import torch
+
+import benchlib as bl
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LINES = [6, 7, 6, 7]
 T, V = 1500, 21128
 
 
-def _time_once(torch, fn):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=30)
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    sys.path.insert(0, os.path.join(HERE, ".."))
-    import torch
-    from lyricalignment_amd import _lib
-    from lyricalignment_amd._lib import check, lib, ptr, stream_ptr
+def main(argv=None):
+    args = bl.parse(bl.parser(), argv)
+    report = bl.Report(args.out)
+    say = report.say
+    dev, Lb = bl.open_gpu()
+    from lyricalignment_amd._lib import check, ptr, stream_ptr
     from lyricalignment_amd.utils.alignment import windows_from_anchors
-    _lib.require_gpu()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    Lb = lib()
     L = sum(LINES)
     say(f"# alignment loss on the windowed lattice on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up "
         f"of 3, legs alternated call by call, device events around one call, ms; {T} frames, {V} classes + silence logit, {L} labels")
@@ -80,38 +58,29 @@ def main():
         nll = torch.empty((B,), dtype=torch.float64, device=dev)
         status = torch.empty((B,), dtype=torch.int32, device=dev)
         losses3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        need_a, need_m = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        check(Lb.la_anchored_alignment_loss_workspace_bytes(B, T, L, ctypes.byref(need_a)), "anchored_alignment_loss_workspace_bytes")
-        check(Lb.la_multitask_loss_workspace_bytes(B, T, L, ctypes.byref(need_m)), "multitask_loss_workspace_bytes")
-        ws_a = torch.empty((need_a.value,), dtype=torch.uint8, device=dev)
-        ws_m = torch.empty((need_m.value,), dtype=torch.uint8, device=dev)
+        ws_a, need_a = bl.workspace(Lb, "la_anchored_alignment_loss_workspace_bytes", (B, T, L), dev)
+        ws_m, need_m = bl.workspace(Lb, "la_multitask_loss_workspace_bytes", (B, T, L), dev)
 
         def anchored(with_grad):
             check(Lb.la_anchored_alignment_loss(ptr(logits), logits.stride(0), logits.stride(1), B, T, V, ptr(labels), L, ptr(n_labels), 0, L, 0, 0,
                                                 0.0, ptr(win_lo), ptr(win_hi), win_lo.stride(0), 1.0, ptr(loss), ptr(nll), ptr(status),
-                                                ptr(dlogits) if with_grad else 0, dlogits.stride(0), dlogits.stride(1), ptr(ws_a), need_a.value,
+                                                ptr(dlogits) if with_grad else 0, dlogits.stride(0), dlogits.stride(1), ptr(ws_a), need_a,
                                                 stream_ptr()), "anchored_alignment_loss")
 
         def multitask():
             check(Lb.la_multitask_loss(ptr(logits), logits.stride(0), logits.stride(1), B, T, V, ptr(frame_labels), ptr(labels), L, ptr(n_labels),
-                                       L, 1, 1, 1.0, ptr(losses3), ptr(dlogits), dlogits.stride(0), dlogits.stride(1), ptr(ws_m), need_m.value,
+                                       L, 1, 1, 1.0, ptr(losses3), ptr(dlogits), dlogits.stride(0), dlogits.stride(1), ptr(ws_m), need_m,
                                        stream_ptr()), "multitask_loss")
 
         legs = [("la_anchored_alignment_loss, loss only", lambda: anchored(False)),
                 ("la_anchored_alignment_loss, loss + gradient", lambda: anchored(True)),
                 ("la_multitask_loss(use_ce = 1, use_ctc = 1), loss + gradient", multitask)]
-        for _ in range(3):
-            for _, fn in legs:
-                fn()
-        torch.cuda.synchronize()
+        bl.warm_up(legs)
         assert status.tolist() == [0] * B, status.tolist()
-        times = [[] for _ in legs]
-        for _ in range(args.runs):
-            for i, (_, fn) in enumerate(legs):
-                times[i].append(_time_once(torch, fn))
-        say(f"\n## B = {B}: loss {float(loss[0]):.4f}, workspace {need_a.value / 2 ** 20:.1f} MiB (la_multitask_loss: {need_m.value / 2 ** 20:.1f} MiB)")
-        for (name, _), t in zip(legs, times):
-            say(f"{name:62s} {statistics.median(t):8.3f} ({min(t):.3f} .. {max(t):.3f})")
+        times = bl.alternated(legs, args.runs, warmup=0)
+        say(f"\n## B = {B}: loss {float(loss[0]):.4f}, workspace {need_a / 2 ** 20:.1f} MiB (la_multitask_loss: {need_m / 2 ** 20:.1f} MiB)")
+        for name, t in times.items():
+            say(bl.timed(name, bl.stat(t), 62))
         # the gradient kernel alone: the library's timer around its launch
         Lb.la_timer_reset(); Lb.la_timer_sample(1); Lb.la_timer_enable(b"anchored_loss_grad")
         for _ in range(args.runs):
@@ -135,9 +104,8 @@ def main():
             usage = json.load(f)["usage"]
         for name, u in usage.items():
             say(f"{name}: " + ", ".join(f"{k} {u.get(k)}" for k in keys if k in u))
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.close()
+    return report.lines
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Cost of the alignment DP with optional lyric lines (la_viterbi_spans_batch) beside la_viterbi_batch; both are
 instantiations of one kernel in csrc/la_viterbi.hip, without and with the span code.
 
-    python tools/optional_spans_bench.py [--runs 30] [--out profiles/optional_spans.txt]
+    python tools/optional_spans_bench.py [--runs 30] [--quick] [--out profiles/optional_spans.txt]
 
 On the same synthetic emissions at 32 clips x 1500 frames x 26 labels (caller-owned buffers, device events around one call, a
 synchronise after each, the three calls alternated call by call):
@@ -14,115 +14,50 @@ bit against la_viterbi_batch's before anything is timed.
 """
 from __future__ import annotations
 
-import argparse
-import ctypes
-import os
-import statistics
-import sys
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-B, T, L = 32, 1500, 26
-LINES = [6, 7, 6, 7]
+import benchlib as bl
+
+LEGS = ("la_viterbi_batch (baseline)", "la_viterbi_spans_batch, no spans", "la_viterbi_spans_batch, lines of {} optional")
+FULL, QUICK = (32, 1500, [6, 7, 6, 7]), (2, 160, [2, 2, 2, 2])
 PRESENT = [True, True, False, True]
 
 
-def _time_once(torch, fn):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e)
+def leg_table(quick=False):
+    """Per shape, the names the report gives the legs."""
+    return [[name.format("/".join(map(str, (QUICK if quick else FULL)[2]))) for name in LEGS]]
 
 
-def _stat(ts):
-    return statistics.median(ts), min(ts), max(ts)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=30)
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    sys.path.insert(0, os.path.join(HERE, ".."))
-    import torch
-    from lyricalignment_amd import _lib
-    from lyricalignment_amd._lib import check, lib, ptr, stream_ptr
+def main(argv=None):
+    args = bl.parse(bl.parser(quick=True), argv)
+    report = bl.Report(args.out)
+    say = report.say
+    dev, lib = bl.open_gpu()
     from lyricalignment_amd.utils.alignment import spans_from_lines
-    _lib.require_gpu()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-
-    # emissions -rand * 12 - 1 with a 0.8 * 12 bonus on an even segmentation of the SUNG labels (lines 1, 2 and 4)
-    g = torch.Generator().manual_seed(B + T + L)
-    em = -torch.rand((B, T, L + 1), generator=g) * 12 - 1
-    sung, pos = [], 0
-    for n_chars, here in zip(LINES, PRESENT):
-        sung += list(range(pos, pos + n_chars)) if here else []
-        pos += n_chars
-    seg = T // (2 * len(sung) + 1)
-    for i, n in enumerate(sung):
-        em[:, (2 * i + 1) * seg:(2 * i + 2) * seg, 1 + n] += 9.6
-    for i in range(len(sung) + 1):
-        em[:, 2 * i * seg:(2 * i + 1) * seg, 0] += 9.6
-    em = em.to(dev)
-    labels = torch.arange(1, L + 1, dtype=torch.int32).repeat(B, 1).to(dev)
-    n_labels = torch.full((B,), L, dtype=torch.int32, device=dev)
-    n_frames = torch.full((B,), T, dtype=torch.int32, device=dev)
+    B, T, LINES = QUICK if args.quick else FULL
+    L = sum(LINES)
+    c = bl.case(bl.planted(B, T, L, bl.sung_lines(LINES, PRESENT), B + T + L, dev), *bl.sheet(B, T, L, dev))     # lines 1, 2 and 4 are sung
     skip_none = torch.full((B, L + 1), -1, dtype=torch.int32, device=dev)
-    skip_all = torch.tensor(spans_from_lines(LINES, [True] * len(LINES)), dtype=torch.int32).repeat(B, 1).to(dev)
-
-    def outputs():
-        return (torch.empty((B, L), dtype=torch.int32, device=dev), torch.empty((B, L), dtype=torch.int32, device=dev),
-                torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev))
-
-    out_v, out_n, out_a = outputs(), outputs(), outputs()
-    need_v, need_s = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    check(lib().la_viterbi_workspace_bytes(B, T, L, ctypes.byref(need_v)))
-    check(lib().la_viterbi_spans_workspace_bytes(B, T, L, ctypes.byref(need_s)))
-    ws_v = torch.empty((max(need_v.value, 16),), dtype=torch.uint8, device=dev)
-    ws_s = torch.empty((max(need_s.value, 16),), dtype=torch.uint8, device=dev)
-
-    def vit():
-        on, off, score, status = out_v
-        check(lib().la_viterbi_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), L, ptr(n_labels), ptr(n_frames), B, T, L, ptr(on),
-                                     ptr(off), L, ptr(score), ptr(status), ptr(ws_v), need_v.value, stream_ptr()), "viterbi_batch")
-
-    def spans(skip, out):
-        on, off, score, status = out
-        check(lib().la_viterbi_spans_batch(ptr(em), em.stride(0), em.stride(1), ptr(labels), L, ptr(n_labels), ptr(n_frames), B, T, L, ptr(on),
-                                           ptr(off), L, ptr(score), ptr(status), ptr(skip), L + 1, 0.0, ptr(ws_s), need_s.value, stream_ptr()),
-              "viterbi_spans_batch")
-
-    for _ in range(3):
-        vit(); spans(skip_none, out_n); spans(skip_all, out_a)
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(out_v, out_n)), "no-span outputs differ from la_viterbi_batch"
-    assert int(out_a[3].abs().sum()) == 0
-    left_out = sorted({int(n) for n in (out_a[0] < 0).nonzero()[:, 1].tolist()})
-    tv, tn, ta = [], [], []
-    for _ in range(args.runs):                           # alternated call by call
-        tv.append(_time_once(torch, vit))
-        tn.append(_time_once(torch, lambda: spans(skip_none, out_n)))
-        ta.append(_time_once(torch, lambda: spans(skip_all, out_a)))
-    (mv, lv, hv), (mn, ln, hn), (ma, la, ha) = _stat(tv), _stat(tn), _stat(ta)
+    skip_all = bl.rows(spans_from_lines(LINES, [True] * len(LINES)), B, dev)
+    names = leg_table(args.quick)[0]
+    legs = list(zip(names, (bl.dp_leg(lib, "viterbi", c), bl.dp_leg(lib, "viterbi_spans", c, skip_none), bl.dp_leg(lib, "viterbi_spans", c, skip_all))))
+    bl.warm_up(legs)
+    out_v, out_n, out_a = (out for _, (_, out) in legs)
+    assert bl.same_bits(out_v, out_n, bl.DP_OUT), "no-span outputs differ from la_viterbi_batch"
+    assert bl.ok(out_a)
+    left_out = sorted({int(n) for n in (out_a["onset"] < 0).nonzero()[:, 1].tolist()})
+    ts = bl.alternated(legs, args.runs, warmup=0)
+    stats = [bl.stat(ts[name]) for name in names]
+    (mv, lv, hv), (mn, _, _), (ma, _, _) = stats
     say(f"# alignment DP with optional lines on {torch.cuda.get_device_name(0)}; {B} clips x {T} frames x {L} labels, median (min .. max) of "
         f"{args.runs} calls after warm-up, device events, ms")
-    say(f"la_viterbi_batch (baseline)                      {mv:8.3f} ({lv:.3f} .. {hv:.3f})")
-    say(f"la_viterbi_spans_batch, no spans                 {mn:8.3f} ({ln:.3f} .. {hn:.3f})   {mn / mv:5.2f} x   {1e3 * (mn - mv) / T:+.3f} us per frame")
-    say(f"la_viterbi_spans_batch, lines of 6/7/6/7 optional {ma:7.3f} ({la:.3f} .. {ha:.3f})   {ma / mv:5.2f} x   {1e3 * (ma - mv) / T:+.3f} us per frame")
+    say(bl.timed(names[0], stats[0], 49, 7))
+    say(bl.timed(names[1], stats[1], 49, 7) + f"   {mn / mv:5.2f} x   {1e3 * (mn - mv) / T:+.3f} us per frame")
+    say(bl.timed(names[2], stats[2], 49, 7) + f"   {ma / mv:5.2f} x   {1e3 * (ma - mv) / T:+.3f} us per frame")
     say(f"baseline's own spread (max - min) {hv - lv:.3f} ms; no-span outputs equal la_viterbi_batch's bit for bit; labels left out with the "
         f"spans: {left_out}")
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.close()
+    return report.lines
 
 
 if __name__ == "__main__":

@@ -21,67 +21,23 @@ against a float64 loop on the host (bit-equal) before anything is timed.  These 
 """
 from __future__ import annotations
 
-import argparse
-import os
-import statistics
-import sys
-import time
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import benchlib as bl
+
 SHAPES = [("32 clips x 1500 frames x 26 labels", 32, 1500, 26), ("1 song x 12000 frames x 800 labels", 1, 12000, 800)]
 N_CAND, TOP_K = 402, 5
 
 
-def _time_once(torch, fn):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e)
-
-
-def _wall_once(torch, fn):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) * 1e3
-
-
-def _alternated(torch, legs, runs, once):
-    for _ in range(3):
-        for _, fn in legs:
-            fn()
-    torch.cuda.synchronize()
-    ts = [[] for _ in legs]
-    for _ in range(runs):
-        for i, (_, fn) in enumerate(legs):
-            ts[i].append(once(torch, fn))
-    return ts
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=30)
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    sys.path.insert(0, os.path.join(HERE, ".."))
-    import numpy as np
-    import torch
+def main(argv=None):
+    args = bl.parse(bl.parser(), argv)
+    report = bl.Report(args.out)
+    say = report.say
+    dev, lib = bl.open_gpu()
     from lyricalignment_amd import _lib, ops, whisper_compat as wc
-    from lyricalignment_amd._lib import lib, ptr, stream_ptr
+    from lyricalignment_amd._lib import ptr, stream_ptr
     from lyricalignment_amd.module.align_model import AlignModel
-    _lib.require_gpu()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
     say(f"# pronunciation scores on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up of 3, legs "
         f"alternated call by call, ms; {N_CAND} candidate classes, top_k {TOP_K}")
     say("# kernel legs: device events around one call")
@@ -121,19 +77,18 @@ def main():
         dst = torch.empty_like(src)
 
         def scores():
-            _lib.check(lib().la_segment_class_scores(ptr(em_c), em_c.stride(0), em_c.stride(1), ptr(n_lab), ptr(onset), ptr(offset), L, ptr(own),
+            _lib.check(lib.la_segment_class_scores(ptr(em_c), em_c.stride(0), em_c.stride(1), ptr(n_lab), ptr(onset), ptr(offset), L, ptr(own),
                                                      L, B, T, L, N_CAND, TOP_K, 0, 0, 0, ptr(top_col), ptr(top_score), TOP_K, ptr(own_score),
                                                      ptr(own_rank), ptr(n_seg), stream_ptr()), "scores")
 
         legs = [("la_segment_class_scores", scores), ("la_viterbi_batch on the leading columns", lambda: ops.viterbi_batch(em, labels, n_lab, nf)),
                 (f"device copy of {n_bytes // 2} bytes (read + write = the entry's largest traffic)", lambda: dst.copy_(src))]
-        ts = _alternated(torch, legs, args.runs, _time_once)
+        stats = bl.stats_of(bl.alternated(legs, args.runs))
         read = int(n_seg.sum()) * N_CAND * 4
         say(f"## {title}: {int(n_seg.sum())} of {B * T} frames lie in a segment, {read / 1e6:.2f} MB read")
-        med = []
-        for (name, _), t in zip(legs, ts):
-            med.append(statistics.median(t))
-            say(f"{name:84s} {med[-1]:8.4f} ({min(t):.4f} .. {max(t):.4f})")
+        for name, st in stats.items():
+            say(bl.timed(name, st, 84, 8, 4))
+        med = [st[0] for st in stats.values()]
         say(f"the entry reads {read / (med[0] * 1e-3) / 1e9:.1f} GB/s (copy: {n_bytes / (med[2] * 1e-3) / 1e9:.1f} GB/s) and costs "
             f"{100 * med[0] / med[1]:.1f} % of the DP; rank > 0 at {int((own_rank[0] > 0).sum())} of {L} positions of clip 0")
 
@@ -152,16 +107,14 @@ def main():
             assert seconds == plain
             legs = [("AlignModel.align", lambda: model.align(audios, labels)),
                     ("AlignModel.align(return_pronunciation=True, pronunciation_classes=402)", lambda: model.align(audios, labels, **kw))]
-            ts = _alternated(torch, legs, args.runs, _wall_once)
+            stats = bl.stats_of(bl.alternated(legs, args.runs, bl.wall_once))
         say(f"## {title}")
-        med = []
-        for (name, _), t in zip(legs, ts):
-            med.append(statistics.median(t))
-            say(f"{name:84s} {med[-1]:8.3f} ({min(t):.3f} .. {max(t):.3f})")
+        for name, st in stats.items():
+            say(bl.timed(name, st, 84))
+        med = [st[0] for st in stats.values()]
         say(f"the keyword adds {med[1] - med[0]:.3f} ms ({100 * (med[1] - med[0]) / med[0]:.1f} %)")
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.close()
+    return report.lines
 
 
 if __name__ == "__main__":

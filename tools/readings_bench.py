@@ -17,55 +17,26 @@ float64 fold on the host (equal or adjacent float32) before anything is timed.
 """
 from __future__ import annotations
 
-import argparse
-import os
-import statistics
-import sys
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import benchlib as bl
+
 SHAPES = [("32 clips x 1500 frames x 26 labels", 32, 1500, 26), ("1 song x 12000 frames x 800 labels", 1, 12000, 800)]
 
 
-def _time_once(torch, fn):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=30)
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    sys.path.insert(0, os.path.join(HERE, ".."))
-    import numpy as np
-    import torch
+def main(argv=None):
+    args = bl.parse(bl.parser(), argv)
+    report = bl.Report(args.out)
+    say = report.say
+    dev, lib = bl.open_gpu()
     from lyricalignment_amd import _lib, ops
-    from lyricalignment_amd._lib import lib, ptr, stream_ptr
+    from lyricalignment_amd._lib import ptr, stream_ptr
     from lyricalignment_amd.utils.alignment import _readings_of
-    _lib.require_gpu()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
     say(f"# pronunciation alternatives on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up of 3, "
         f"legs alternated call by call, device events around one call, ms; every fourth position has two readings")
     for title, B, T, L in SHAPES:
-        g = torch.Generator().manual_seed(B + T + L)
-        em0 = -torch.rand((B, T, L + 1), generator=g) * 12 - 1             # planted as tools/wide_lattice_bench.py plants
-        seg = T // (2 * L + 1)
-        for n in range(L):
-            em0[:, (2 * n + 1) * seg:(2 * n + 2) * seg, 1 + n] += 9.6
-        for i in range(L + 1):
-            em0[:, 2 * i * seg:(2 * i + 1) * seg, 0] += 9.6
+        em0 = bl.planted(B, T, L, list(range(L)), B + T + L, "cpu")
         labels = [list(range(1, L + 1)) for _ in range(B)]
         rd = _readings_of([[(n, [5000 + n]) for n in range(0, L, 4)] for _ in range(B)], labels)
         alt_h = rd.alt_start[0].tolist()
@@ -103,38 +74,29 @@ def main():
         dst = torch.empty_like(src)
 
         def merge():
-            _lib.check(lib().la_emissions_merge_readings(ptr(em_x), em_x.stride(0), em_x.stride(1), ptr(alt), alt.stride(0), ptr(n_lab), ptr(nf),
+            _lib.check(lib.la_emissions_merge_readings(ptr(em_x), em_x.stride(0), em_x.stride(1), ptr(alt), alt.stride(0), ptr(n_lab), ptr(nf),
                                                          B, T, L, X, ptr(em), em.stride(0), em.stride(1), stream_ptr()), "merge")
 
         def scores():
-            _lib.check(lib().la_reading_scores(ptr(em_x), em_x.stride(0), em_x.stride(1), ptr(alt), alt.stride(0), ptr(n_lab), ptr(onset),
+            _lib.check(lib.la_reading_scores(ptr(em_x), em_x.stride(0), em_x.stride(1), ptr(alt), alt.stride(0), ptr(n_lab), ptr(onset),
                                                ptr(offset), L, B, T, L, X, ptr(col), X, ptr(reading), L, stream_ptr()), "scores")
 
         legs = [("la_emissions_merge_readings", merge), ("la_reading_scores", scores),
                 ("la_viterbi_batch on the folded matrix", lambda: ops.viterbi_batch(em, ids, n_lab, nf)),
                 (f"device copy of {n_bytes // 2} bytes (read + write = the fold's traffic)", lambda: dst.copy_(src))]
-        for _ in range(3):
-            for _, fn in legs:
-                fn()
-        torch.cuda.synchronize()
-        ts = [[] for _ in legs]
-        for _ in range(args.runs):
-            for i, (_, fn) in enumerate(legs):
-                ts[i].append(_time_once(torch, fn))
+        stats = bl.stats_of(bl.alternated(legs, args.runs))
         say(f"## {title}: {X} expanded columns, fold traffic {n_bytes / 1e6:.2f} MB")
-        med = []
-        for (name, _), t in zip(legs, ts):
-            med.append(statistics.median(t))
-            say(f"{name:76s} {med[-1]:8.4f} ({min(t):.4f} .. {max(t):.4f})")
+        for name, st in stats.items():
+            say(bl.timed(name, st, 76, 8, 4))
+        med = [st[0] for st in stats.values()]
         rate = n_bytes / (med[3] * 1e-3) / 1e9
         say(f"copy rate {rate:.1f} GB/s; bar for the fold = its traffic at that rate = {med[3]:.4f} ms; achieved fraction {med[3] / med[0]:.2f} "
             f"(fold {n_bytes / (med[0] * 1e-3) / 1e9:.1f} GB/s); fold + scores = {100 * (med[0] + med[1]) / med[2]:.1f} % of the DP")
         picked = reading.cpu()
         say(f"readings picked: {int((picked[0] > 0).sum())} of {L} positions of clip 0 name the other reading"
             + (f", {int((picked[1] > 0).sum())} of clip 1" if B > 1 else ""))
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.close()
+    return report.lines
 
 
 if __name__ == "__main__":
