@@ -686,6 +686,38 @@ int la_segment_class_scores(const float *em_c, int64_t emc_batch_stride, int64_t
                             void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* off-sheet slots: singing that is in the audio but not on the sheet         */
+/*   (addition; the wildcard / "star" label of other forced aligners)         */
+/* ------------------------------------------------------------------------- */
+/*
+ * A slot is an ordinary label position of the lattice whose emission column holds "this frame is voiced, whatever the class", made
+ * skippable by a one-label optional span; the lattice entries run unchanged.  Both emission providers (la_fc_emissions /
+ * la_align_head_forward and la_emissions_from_logits) leave log P(silence), clamped at -1000, in column 0 of the compact matrix in
+ * both variants, and the slot's emission is a function of that column alone:
+ *     v   = log(-expm1((double)em[b][t][0])) - penalty        log P(frame is not silence) - penalty, float64
+ *     out = v > -1000.0 ? (float)v : -1000.0f                 rounded once; v NaN or -inf (em NaN or >= 0): the floor
+ *     em[b][t][1 + x] = out     for every x = slot_cols[b][i], i < n_slots[b], and every t < n_frames[b]
+ * A sheet character's emission is log p_c + log P(voiced) (CTC variant; plain: log p_c), so the slot beats the sheet's character on a
+ * frame exactly when that character holds less than exp(-penalty) of the voiced probability.
+ *
+ * la_emissions_offsheet_columns writes in place.  em may be a column window of a wider matrix: strides are in elements and taken as
+ * given (rows hold max_labels + 1 entries and need no alignment).  slot_cols [batch][slot_stride] (device) holds label positions,
+ * 0-based and ascending; an entry outside 0 .. max_labels-1 is skipped and never used as an index; n_slots / n_frames (device) are
+ * clamped into 0 .. max_slots / 0 .. max_frames.  Rows t >= n_frames[b], every other column and clips with n_slots[b] = 0 are not
+ * touched.  The float64 transcendentals are evaluated once per row; no atomics and nothing shared between clips, so a clip's bits are
+ * the same alone and in a batch and two calls agree bit for bit.  (Subnormal float32 inputs convert by the flush mode: unspecified.)
+ *
+ * A null pointer, batch / max_frames / max_labels / max_slots <= 0, a negative or NaN penalty, em_row_stride < max_labels + 1 or
+ * slot_stride < max_slots -> LA_EINVAL; more than 4095 labels (or more than 65535 clips) -> LA_EUNSUPPORTED, reported before the
+ * stride checks; answered on the host under the entry's name before anything is enqueued.  The entry does not synchronise, allocate
+ * or free.
+ */
+int la_emissions_offsheet_columns(float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                  const int32_t *slot_cols, int32_t slot_stride, const int32_t *n_slots, const int32_t *n_frames,
+                                  int32_t batch, int32_t max_frames, int32_t max_labels, int32_t max_slots, double penalty,
+                                  void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* log-mel front end  (replaces whisper.audio.log_mel_spectrogram + pad_or_trim, */
 /*                      call sites module/align_model.py:84,89,100,109)           */
 /* ------------------------------------------------------------------------- */

@@ -97,6 +97,8 @@ SYMBOLS = {
     # pronunciation scores: every candidate class summed over the segment the DP gave a position, its own class ranked, the top few named
     "la_segment_class_scores": (c_int32, [_P, _I64, _I64, _P, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P, _P, _I32,
                                           _P, _P, _P, _P]),
+    # off-sheet slots: log P(frame is not silence) - penalty into the slots' columns of the compact emission matrix, in place
+    "la_emissions_offsheet_columns": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, c_double, _P]),
     "la_logmel_workspace_bytes": (c_int32, [_I32, _I32, POINTER(_SZ)]),
     "la_logmel_f32": (c_int32, [_P, _I32, _I32, _P, _P, _P, _I64, _I64, _P, _SZ, _P]),
     "la_logmel_constants_bytes": (c_int32, [POINTER(_SZ)]),

@@ -10,6 +10,7 @@ drop-in frame_manual_forward + perform_viterbi(_ctc) pair exactly like the refer
 """
 from __future__ import annotations
 
+import math
 import re
 from typing import Any, Iterable, List, Optional, Sequence
 
@@ -222,15 +223,32 @@ def _line_anchors(starts: Sequence[float], ids, tolerance_s: float) -> list:
 
 
 class _SheetKw(dict):
-    """_reading_kw's keywords; _align_sheet leaves the clip's pronunciation scores here (None: not asked for)."""
+    """_reading_kw's keywords; _align_sheet leaves the clip's pronunciation scores here (None: not asked for), and with off-sheet slots
+    the clip's slot visits and, where the call had a confidence that reports it, its off_sheet_prob dict."""
     pronunciation = None
+    off_sheet = None
+    off_sheet_prob = None
+    line_of_position = None
 
 
-def _reading_kw(lut: PinyinClassLUT, ids, heteronyms, with_pronunciation: bool = False, top_k: int = 5) -> dict:
+def _reading_kw(lut: PinyinClassLUT, ids, heteronyms, with_pronunciation: bool = False, top_k: int = 5, off_sheet=False,
+                off_sheet_penalty: float = math.log(100), who: str = "align") -> dict:
     """The keywords the sheet functions add to AlignModel.align for heteronyms (None: none): the alternatives of the one clip and
     return_readings, so that every character entry can name the class that was sung; with_pronunciation: the three keywords of the
-    pronunciation scores, with every class of the lookup table (ids from 1) as a candidate."""
+    pronunciation scores, with every class of the lookup table (ids from 1) as a candidate; off_sheet (False: none; True: a slot before
+    every line and one after the last; or a list of line indices, len(lines) = after the last line): the three keywords of the off-sheet
+    slots, a slot in front of each such line's first character."""
     kw = _SheetKw()
+    if off_sheet is not False and off_sheet is not None:
+        starts = [0]
+        for tok in ids:
+            starts.append(starts[-1] + len(tok))
+        before = list(range(len(starts))) if off_sheet is True else list(off_sheet)
+        if any(isinstance(i, bool) or int(i) != i or not 0 <= int(i) < len(starts) for i in before) or len(set(before)) != len(before):
+            raise ValueError(f"{who}: off_sheet: True, False or distinct line indices in 0..{len(ids)} ({len(ids)} = after the last line) expected")
+        kw.line_of_position = {starts[int(i)]: int(i) for i in before}
+        if before:
+            kw.update(off_sheet=[sorted(kw.line_of_position)], off_sheet_penalty=off_sheet_penalty, return_off_sheet=True)
     if heteronyms is not None:
         kw.update(alternatives=lut.readings_of(torch.tensor([[v for tok in ids for v in tok]], dtype=torch.long), heteronyms), return_readings=True)
     if with_pronunciation:
@@ -245,10 +263,14 @@ def _align_sheet(model, reading_kw: dict, audio, labels, **kw):
     if not reading_kw:
         return out, None
     rest, readings = list(out), None
+    if "return_off_sheet" in reading_kw:
+        reading_kw.off_sheet = rest.pop()[0]
     if "return_pronunciation" in reading_kw:
         reading_kw.pronunciation = rest.pop()[0]
     if "return_readings" in reading_kw:
         readings = rest.pop()[0]
+    if "return_off_sheet" in reading_kw and len(rest) > 1 and isinstance(rest[-1][0], dict):
+        reading_kw.off_sheet_prob = rest[-1][0].get("off_sheet_prob")          # what is left: seconds [, segments] [, scores]
     return (rest[0] if len(rest) == 1 else tuple(rest)), readings
 
 
@@ -267,10 +289,19 @@ def _pronunciation_lines(pronunciation, lines: Sequence[str], lut: PinyinClassLU
 
 
 def _done(result, reading_kw, lines: Sequence[str], lut: PinyinClassLUT):
-    """What a sheet function returns: its result, or (result, pronunciation per line) where the pronunciation scores were asked for."""
-    if getattr(reading_kw, "pronunciation", None) is None:
-        return result
-    return result, _pronunciation_lines(reading_kw.pronunciation, lines, lut)
+    """What a sheet function returns: its result, or (result, pronunciation per line) where the pronunciation scores were asked for; with
+    off-sheet slots the tuple gains the passages [(before_line, onset_s, offset_s[, [(syllable heard, score per frame), ...]]), ...] in time
+    order and, where the call had a confidence, {before_line: off_sheet_prob} for every slot."""
+    out = (result,)
+    if getattr(reading_kw, "pronunciation", None) is not None:
+        out += (_pronunciation_lines(reading_kw.pronunciation, lines, lut),)
+    if getattr(reading_kw, "off_sheet", None) is not None:
+        line_of = reading_kw.line_of_position
+        out += ([(line_of[v["position"]], v["onset"], v["offset"]) + (([(lut.syllable_of(c), s) for c, s in v["top"]],) if "top" in v else ())
+                 for v in reading_kw.off_sheet],)
+        if reading_kw.off_sheet_prob is not None:
+            out += ({line_of[n]: float(p) for n, p in reading_kw.off_sheet_prob.items()},)
+    return out[0] if len(out) == 1 else out
 
 
 def suspect_characters(result, max_rank: int = 0, min_gop: Optional[float] = None) -> List[tuple]:
@@ -376,7 +407,7 @@ def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable, r
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
                        repeat_penalty: float = 0.0, with_visit_confidence: bool = False, heteronyms=None, with_pronunciation: bool = False,
-                       top_k: int = 5):
+                       top_k: int = 5, off_sheet=False, off_sheet_penalty: float = math.log(100)):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
@@ -400,10 +431,18 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     that was sung?  -> (the result as above, pronunciation): one list per line with, per character, None (left out) or {"char", "class",
     "syllable", "frames", "log_prob", "rank", "gop", "top": [(syllable, score per frame), ... top_k of them]} -- AlignModel.align(
     return_pronunciation=True) with every class of the lookup table as a candidate; rank 0 = the sheet's syllable scored best over the
-    character's segment, gop <= 0 its per-frame distance to the best.  suspect_characters picks the entries worth a look."""
+    character's segment, gop <= 0 its per-frame distance to the best.  suspect_characters picks the entries worth a look.
+    off_sheet / off_sheet_penalty (here, in align_record_lrc and in align_song; False: the outputs as above): singing that is not on the
+    sheet -- ad-libs between lines, backing vocals, an omitted verse.  True puts a slot before every line and one after the last; a list
+    names the lines to put one in front of (len(lines) = after the last line); AlignModel.align(off_sheet=..., return_off_sheet=True).
+    The return gains the passages as its last element: [(before_line, onset_s, offset_s), ...] in time order, one per slot that was used
+    (with with_pronunciation each also holds [(syllable heard, score per frame), ...]); with a confidence option one more element,
+    {before_line: off_sheet_prob}, the probability that the slot was used at all.  off_sheet_penalty (nats per frame, default ln 100: a
+    character must hold less than 1 % of the voiced probability to lose a frame to a slot) has not been tuned on real singing; keep it
+    above skip_penalty."""
     lines = list(lines)
     ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
-    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k)
+    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k, off_sheet, off_sheet_penalty, "align_record_lines")
     if with_visit_confidence and repeatable is None:
         raise ValueError("align_record_lines: with_visit_confidence goes with repeatable (with_confidence is the keyword without it)")
     if repeatable is not None:
@@ -453,7 +492,7 @@ def parse_lrc(text: str) -> List[tuple]:
 
 def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
                      use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, heteronyms=None,
-                     with_pronunciation: bool = False, top_k: int = 5):
+                     with_pronunciation: bool = False, top_k: int = 5, off_sheet=False, off_sheet_penalty: float = math.log(100)):
     """One recording against an LRC sheet (addition): per-character timing from per-line start times.  `lrc` is LRC text (parse_lrc) or a
     list of (start_seconds, line) pairs; the first character of every line gets an onset anchor at the line's start time with tolerance_s
     (AlignModel.align(onset_anchors=...): the line starts within tolerance_s of its tag, and everything before it has ended by then).
@@ -468,13 +507,14 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
                                when the sheet agrees with the audio, strongly negative when a tag is off by more than tolerance_s}.
     Up to 4095 characters in the sheet; with_confidence at most 511 (NotImplementedError; align_song gives the confidences of a whole song).
     heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung].
-    with_pronunciation / top_k: as in align_record_lines -- -> (the result as above, pronunciation per line)."""
+    with_pronunciation / top_k: as in align_record_lines -- -> (the result as above, pronunciation per line).
+    off_sheet / off_sheet_penalty: as in align_record_lines -- the return gains the passages and, with with_confidence, off_sheet_prob."""
     pairs = _timed_lines("align_record_lrc", lrc)
     lines = [line for _, line in pairs]
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_record_lrc", lines, optional, lut, tokenize)
     anchors = _line_anchors([start for start, _ in pairs], ids, tolerance_s)
-    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k)
+    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k, off_sheet, off_sheet_penalty, "align_record_lrc")
     with torch.no_grad():
         if with_confidence:
             (res, scores), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans],
@@ -487,7 +527,7 @@ def align_record_lrc(model, audio, lrc, lut: PinyinClassLUT, tokenize, tolerance
 
 def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: float = 1.0, optional: Optional[Sequence[bool]] = None,
                use_ctc_loss: bool = True, skip_penalty: float = 0.0, repeatable: Optional[Sequence[bool]] = None, repeat_penalty: float = 0.0,
-               heteronyms=None, with_pronunciation: bool = False, top_k: int = 5):
+               heteronyms=None, with_pronunciation: bool = False, top_k: int = 5, off_sheet=False, off_sheet_penalty: float = math.log(100)):
     """A whole song against its whole sheet, timing and confidences in one call (addition): up to 4095 characters.  `sheet` is LRC text
     (parse_lrc), a list of (start_seconds, line) pairs -- every line's first character anchored at its start time with tolerance_s, as in
     align_record_lrc -- or a list of plain lines (no times: no anchors, as in align_record_lines).  optional[i] marks lines that may be
@@ -505,7 +545,9 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     one value per line as align_record_lines(with_visit_confidence=True) defines them.  ValueError unless one flag per line.
     heteronyms: as in align_record_lines -- every character entry becomes [onset, offset, char, class_id_sung], and the confidences are
     posteriors of the merged classes.
-    with_pronunciation / top_k: as in align_record_lines -- -> ((lines_out, conf), pronunciation per line)."""
+    with_pronunciation / top_k: as in align_record_lines -- -> ((lines_out, conf), pronunciation per line).
+    off_sheet / off_sheet_penalty: as in align_record_lines -- the return gains the passages and {before_line: off_sheet_prob}; a partial
+    sheet (only the chorus) against a whole song is off_sheet=True."""
     if isinstance(sheet, str) or (len(sheet) > 0 and not isinstance(sheet[0], str)):
         pairs = _timed_lines("align_song", sheet)
         lines, starts = [line for _, line in pairs], [start for start, _ in pairs]
@@ -518,7 +560,7 @@ def align_song(model, audio, sheet, lut: PinyinClassLUT, tokenize, tolerance_s: 
     optional = [False] * len(lines) if optional is None else list(optional)
     ids, spans, labels = _sheet_inputs("align_song", lines, optional, lut, tokenize)
     kw = {} if starts is None else {"onset_anchors": [_line_anchors(starts, ids, tolerance_s)]}
-    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k)
+    rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k, off_sheet, off_sheet_penalty, "align_song")
     if repeatable is not None:
         (res, segments, scores), readings = _align_repeat_sheet(model, rk, audio, labels, ids, spans, repeatable, use_ctc_loss, skip_penalty,
                                                                 repeat_penalty, return_song_confidence=True, **kw)

@@ -15,6 +15,7 @@ There is no PyTorch / CPU fallback: without the HIP library and a gfx950 device 
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 from typing import List, Optional, Sequence
@@ -340,6 +341,7 @@ class AlignModel(torch.nn.Module):
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
               repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False,
               return_song_confidence: bool = False, alternatives=None, return_readings: bool = False,
+              off_sheet=None, off_sheet_penalty: float = math.log(100), return_off_sheet: bool = False,
               return_pronunciation: bool = False, pronunciation_classes=None, pronunciation_top_k: int = 5):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
@@ -432,7 +434,25 @@ class AlignModel(torch.nn.Module):
         id, "frames": n, "log_prob": own_score / n, "rank": candidates that beat the own class (0 = it is the best), "gop": (own_score -
         best score) / n <= 0 (0.0 at rank 0), "top": [(class id, score / n), ...]}.  With every other keyword, per_clip and the long form.
         With return_frames five more tensors, last: top_col [B, Lmax, top_k] int32 (columns of the sorted class list), top_score float64,
-        own_score [B, Lmax] float64, own_rank int32, n_seg_frames int32.  Off: the call as it was.  No threshold on gop is calibrated."""
+        own_score [B, Lmax] float64, own_rank int32, n_seg_frames int32.  Off: the call as it was.  No threshold on gop is calibrated.
+        off_sheet / off_sheet_penalty / return_off_sheet (addition): singing that is in the audio but not on the sheet -- ad-libs between
+        lines, backing vocals over a break, a spoken intro, an omitted verse, a partial sheet.  off_sheet[b] = [n, ...] puts a SLOT before
+        label n of clip b (0 <= n <= L_b; L_b = after the last label): a label position of its own whose emission is log P(frame is not
+        silence) - off_sheet_penalty (ops.offsheet_columns on column 0 of the head's matrix), made skippable by a one-label optional span;
+        the lattice itself is unchanged.  The slot beats the sheet's character on a frame when that character holds less than
+        exp(-off_sheet_penalty) of the voiced probability; the default ln 100 (a 1 % share, in nats per frame) HAS NOT BEEN TUNED on real
+        singing.  Every other keyword keeps the caller's numbering (a slot strictly inside an optional or repeat span belongs to it; a
+        slot has one reading and no pronunciation entry) and every per-character output keeps its shape; segments name the caller's
+        characters.  With per_clip and the long form.  return_off_sheet: the return gains, as its last element, off_sheet[b] = the
+        time-ordered list of {"position": n, "onset": s, "offset": s, "frames": k}, one per slot visit -- unused slots are absent, a slot
+        under a repeat span may have several; with return_pronunciation each also has "top": [(class id, score per frame), ...]
+        (ops.segment_class_scores over the visit: what was heard there).  The confidence keywords that report sung_prob / visits add
+        "off_sheet_prob": {n: value} for every slot given, used or not.  Two properties of the lattice: with a slot before the first
+        label the first character cannot start at frame 0 (after the last label: the last character cannot end on the last frame); an
+        unused slot is charged skip_penalty like every skipped span, so keep off_sheet_penalty above skip_penalty.  ValueError for a
+        wrong list count, a bad or repeated n, a slot on a clip without labels, a negative / NaN penalty, and together with
+        return_confidence (slots are spans: return_span_confidence is the keyword) or return_frames; NotImplementedError when L_b plus
+        its slots exceed 4095 (511 for the confidence keywords that stop there).  None or all-empty: the call as it was."""
         from ..utils import alignment as ua
         if return_readings and alternatives is None:
             raise ValueError("align: return_readings goes with alternatives (without them every character has the one reading of its label)")
@@ -451,9 +471,23 @@ class AlignModel(torch.nn.Module):
             widest = max((len(l) for l in ua._label_lists(labels, len(labels))), default=0)
             if widest > ua.POSTERIOR_MAX_LABELS:
                 raise NotImplementedError(f"align: {widest} labels exceed the {ua.POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
+        off = None
+        if off_sheet is not None:            # off-sheet slots: from here on the sheet is the expanded one, the keywords are remapped
+            off = ua._off_sheet_of("align", off_sheet, off_sheet_penalty, ua._label_lists(labels, len(labels)), optional_spans, repeat_spans,
+                                   char_windows, onset_anchors, alternatives,
+                                   narrow=return_confidence or return_span_confidence or return_anchored_confidence or return_repeat_confidence)
+        if off is not None:
+            if return_confidence:
+                raise ValueError("align: return_confidence is not defined with off_sheet (a slot is an optional span, and there are no "
+                                 "posteriors over the span lattice by that keyword: return_span_confidence=True gives them)")
+            if return_frames:
+                raise ValueError("align: off_sheet does not go with return_frames (the device tensors are those of the expanded sheet)")
+            labels, optional_spans, repeat_spans = off.label_lists, off.optional_spans, off.repeat_spans
+            char_windows, onset_anchors, alternatives = off.char_windows, off.onset_anchors, off.alternatives
         rd = None if alternatives is None else ua._readings_of(alternatives, ua._label_lists(labels, len(labels)), keep_empty=return_readings)
         pron = ua._pronunciation_of("align", return_pronunciation, pronunciation_classes, pronunciation_top_k,
-                                    ua._label_lists(labels, len(labels)) if return_pronunciation else None, rd)
+                                    ua._label_lists(labels, len(labels)) if return_pronunciation else None, rd,
+                                    None if off is None else off.slot_sets())
         eng = self.engine()
         kw = {}
         if per_clip:
@@ -491,7 +525,7 @@ class AlignModel(torch.nn.Module):
 
         out = ua.align_labels("align", head, lab_dev, n_lab, lab_lists, frame_counts, T, kw.get("n_frames"), hop_size_second, confidence,
                               boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
-                              alternatives, return_readings, rd, raw=return_frames, pron=pron)
+                              alternatives, return_readings, rd, raw=return_frames, pron=pron, off=off, return_off_sheet=return_off_sheet)
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path);
             r, picked = out
             # reading, col_score behind them, the five tensors of the pronunciation scores last

@@ -445,6 +445,33 @@ def segment_class_scores(em_c: torch.Tensor, n_labels: torch.Tensor, onset: torc
     return res + (seg,) if want_scores else res
 
 
+def offsheet_columns(em: torch.Tensor, slot_cols: torch.Tensor, n_slots: torch.Tensor, n_frames: torch.Tensor,
+                     penalty: float) -> torch.Tensor:
+    """la_emissions_offsheet_columns: the emission of the off-sheet slots, in place.  em [B,T,>=1+Lmax] f32 with unit inner stride (any row /
+    batch stride: a column window of a wider matrix is taken as it is) holds log P(silence) in column 0; slot_cols [B,Smax] i32 the
+    slots' label positions (0-based, ascending; an entry outside 0 .. Lmax-1 is skipped), n_slots / n_frames [B] i32; all on the device.
+    Column 1 + x of every slot x of clip b becomes max(log(-expm1(em[b,t,0])) - penalty, -1000) (float64, rounded once) for t <
+    n_frames[b]; nothing else is written.  penalty >= 0 in nats per frame (ValueError otherwise).  -> em."""
+    who = "offsheet_columns"
+    _dev(em, "em", torch.float32)
+    for name, t in (("slot_cols", slot_cols), ("n_slots", n_slots), ("n_frames", n_frames)):
+        _dev(t, name, torch.int32)
+    if em.dim() != 3 or em.stride(2) != 1 or slot_cols.dim() != 2 or slot_cols.stride(1) != 1:
+        raise ValueError(f"{who}: em [B,T,1+Lmax] / slot_cols [B,Smax] with unit inner stride expected")
+    B, T, E = em.shape
+    if slot_cols.shape[0] != B or n_slots.shape != (B,) or n_frames.shape != (B,) or E < 2 or slot_cols.shape[1] < 1:
+        raise ValueError(f"{who}: inconsistent shapes")
+    penalty = float(penalty)
+    if not penalty >= 0.0:
+        raise ValueError(f"{who}: penalty must be >= 0 (nats per frame), not {penalty}")
+    if T == 0:
+        return em
+    check(lib().la_emissions_offsheet_columns(ptr(em), em.stride(0), em.stride(1), ptr(slot_cols), slot_cols.stride(0),
+                                              ptr(n_slots.contiguous()), ptr(n_frames.contiguous()), B, T, E - 1, slot_cols.shape[1],
+                                              penalty, stream_ptr()), who)
+    return em
+
+
 # --------------------------------------------------------------------------- #
 # encoder / head building blocks                                                #
 # --------------------------------------------------------------------------- #

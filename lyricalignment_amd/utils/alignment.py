@@ -223,6 +223,183 @@ def readings_route(rd: Readings, emissions_of, n_lab, nf, device) -> ReadingRout
     return ReadingRoute(rd, em_x, alt, ops.merge_readings(em_x, alt, n_lab, nf), rd.lattice_ids.to(device))
 
 
+OFF_SHEET_ID = 1 << 25          # lattice id of every off-sheet slot: no class id and no READING_SET_ID + k can equal it
+OFF_SHEET_MAX_LABELS = 4095     # expanded labels per clip (sheet + slots): what the lattice takes
+DEFAULT_OFF_SHEET_PENALTY = math.log(100.0)     # nats per frame: a 1 % share (NOT tuned on real singing)
+
+
+class OffSheet(NamedTuple):
+    """_off_sheet_of's result (host): the sheet with its off-sheet slots, in EXPANDED positions (a slot before label n sits in front of it),
+    and the caller's keywords remapped to them.  optional_spans lists the caller's spans first, then one one-label span per slot."""
+    slots: List[List[int]]          # the caller's positions n (0 .. L_b), ascending
+    penalty: float
+    label_lists: List[List[int]]    # expanded label rows: class 0 at a slot (the head and the prep write the floor there)
+    lattice_ids: torch.Tensor       # [B, L'max] int32: the labels, OFF_SHEET_ID at a slot
+    slot_cols: torch.Tensor         # [B, Fmax] int32: the slots' expanded positions, ascending (padding -1)
+    n_slots: torch.Tensor           # [B] int32
+    keep: List[List[int]]           # keep[b][n] = expanded position of the caller's label n
+    optional_spans: list
+    repeat_spans: Optional[list]
+    char_windows: Optional[list]
+    onset_anchors: Optional[list]
+    alternatives: Optional[list]
+    n_caller_spans: List[int]       # how many of optional_spans[b] are the caller's
+
+    def slot_sets(self):
+        return [set(int(q) for q in self.slot_cols[b, : len(s)].tolist()) for b, s in enumerate(self.slots)]
+
+    def ids_with_slots(self, ids: torch.Tensor) -> torch.Tensor:
+        """Host lattice ids [B, L'max] of the expanded rows (_readings_of's) with OFF_SHEET_ID at the slots."""
+        ids = ids.clone()
+        for b, s in enumerate(self.slots):
+            if s:
+                ids[b, self.slot_cols[b, : len(s)].long()] = OFF_SHEET_ID
+        return ids
+
+
+def _off_sheet_of(who: str, off_sheet, penalty, label_lists: List[List[int]], optional_spans=None, repeat_spans=None, char_windows=None,
+                  onset_anchors=None, alternatives=None, narrow: bool = False) -> Optional[OffSheet]:
+    """off_sheet[b] = [n, ...]: a slot BEFORE label n of utterance b, 0 <= n <= L_b (L_b = after the last label) -> OffSheet, or None when
+    off_sheet is None or all-empty (the call as it was).  A slot is a label position of its own: with F slots the lattice has L' = L + F
+    labels, label n at position n + #{slots <= n}.  Each slot gets a one-label optional span.  The caller's keywords move with the labels:
+    an optional or repeat span (a, e) becomes (pos(a), pos(e-1) + 1) -- a slot strictly inside it belongs to it, one at either edge stays
+    outside, so no slot span shares an end (a start) with it --; char_windows / onset_anchors / alternatives get pos(n).  An index the
+    keyword's own check would refuse stays refusable (it is shifted, never clamped).
+    ValueError for a wrong list count, an n that is no integer or outside 0 .. L_b, a duplicate, a slot on an utterance without labels, a
+    negative or NaN penalty; NotImplementedError when L' exceeds OFF_SHEET_MAX_LABELS (narrow: POSTERIOR_MAX_LABELS, the confidences
+    that stop there).  Host only."""
+    if off_sheet is None:
+        return None
+    B = len(label_lists)
+    if len(off_sheet) != B:
+        raise ValueError(f"{who}: off_sheet: {B} lists expected, one per utterance")
+    slots = []
+    for b, given in enumerate(off_sheet):
+        L, row = len(label_lists[b]), []
+        for n in (() if given is None else given):         # a list, an array or a tensor row
+            try:
+                whole = not isinstance(n, bool) and bool(int(n) == n) and 0 <= int(n) <= L
+            except (TypeError, ValueError, OverflowError):  # None, a string, NaN, inf
+                whole = False
+            if not whole:
+                raise ValueError(f"{who}: off_sheet[{b}]: position {n} is not an integer in 0..{L}")
+            row.append(int(n))
+        if len(set(row)) != len(row):
+            raise ValueError(f"{who}: off_sheet[{b}]: a position is named twice")
+        if row and L == 0:
+            raise ValueError(f"{who}: off_sheet[{b}]: a slot on an utterance without labels")
+        slots.append(sorted(row))
+    if not any(slots):
+        return None
+    penalty = float(penalty)
+    if not penalty >= 0.0:
+        raise ValueError(f"{who}: off_sheet_penalty must be >= 0 (nats per frame), not {penalty}")
+    limit = POSTERIOR_MAX_LABELS if narrow else OFF_SHEET_MAX_LABELS
+    for b, s in enumerate(slots):
+        if len(label_lists[b]) + len(s) > limit:
+            raise NotImplementedError(f"{who}: off_sheet[{b}]: {len(label_lists[b])} labels + {len(s)} slots exceed {limit}"
+                                      + (" (the limit of this kind of confidence)" if narrow else ""))
+
+    def pos(b, n):                    # expanded position of label n: every slot before label <= n lies in front of it
+        return n + sum(1 for s in slots[b] if s <= n)
+
+    def per_clip(given, move):
+        if given is None:
+            return None
+        if len(given) != B:           # the keyword's own check refuses it
+            return given
+        return [[move(b, item) for item in (given[b] or ())] for b in range(B)]
+
+    span = lambda b, ae: (pos(b, ae[0]), pos(b, ae[1] - 1) + 1)
+    first = lambda b, item: (pos(b, item[0]), *item[1:])
+    lists, keep, cols = [], [], torch.full((B, max(len(s) for s in slots)), -1, dtype=torch.int32)
+    Lx = max(1, max(len(l) + len(s) for l, s in zip(label_lists, slots)))
+    ids = torch.zeros((B, Lx), dtype=torch.int32)
+    for b, labs in enumerate(label_lists):
+        row = [0] * (len(labs) + len(slots[b]))
+        keep.append([pos(b, n) for n in range(len(labs))])
+        for n, c in enumerate(labs):
+            row[keep[b][n]] = int(c)
+        lists.append(row)
+        if row:
+            ids[b, : len(row)] = torch.tensor(row, dtype=torch.int32)
+        for i, s in enumerate(slots[b]):
+            cols[b, i] = s + i
+            ids[b, s + i] = OFF_SHEET_ID
+    own = per_clip(optional_spans, span)
+    if own is not None and len(own) != B:         # the keyword's own check refuses it
+        spans, n_own = own, [0] * B
+    else:
+        own = own if own is not None else [[] for _ in range(B)]
+        n_own = [len(v) for v in own]
+        spans = [list(own[b]) + [(q, q + 1) for q in cols[b, : len(slots[b])].tolist()] for b in range(B)]
+    return OffSheet(slots, penalty, lists, ids, cols, torch.tensor([len(s) for s in slots], dtype=torch.int32), keep, spans,
+                    per_clip(repeat_spans, span), per_clip(char_windows, first), per_clip(onset_anchors, first),
+                    per_clip(alternatives, first), n_own)
+
+
+def _off_sheet_visits(off: OffSheet, r, frame_counts):
+    """The slot visits of a lattice result -> per clip the time-ordered list of (n, first frame, last frame + 1): from the path where the
+    lattice has one (a slot under a repeat span may be visited several times), else from the slot positions' onset / offset."""
+    out = []
+    rows = None if r.path is None else r.path.cpu().numpy()
+    on, offs = r.onset.cpu().numpy(), r.offset.cpu().numpy()
+    for b, s in enumerate(off.slots):
+        at = {int(q): n for q, n in zip(off.slot_cols[b, : len(s)].tolist(), s)}
+        if rows is not None:
+            out.append([(at[p], t, u) for p, t, u in _visits_of_row(rows[b, : int(frame_counts[b])]) if p in at])
+        else:
+            out.append(sorted(((n, int(on[b, q]), int(offs[b, q])) for q, n in at.items() if on[b, q] >= 0), key=lambda v: v[1]))
+    return out
+
+
+def _off_sheet_top(off: OffSheet, visits, em_c, pron: "Pronunciation", device):
+    """What was heard in every slot visit: ops.segment_class_scores over the visits' frames (no own class) -> per clip, per visit the list
+    [(class id, score per frame), ...]."""
+    V = max(1, max(len(v) for v in visits))
+    on = torch.full((len(visits), V), -1, dtype=torch.int32)
+    offs = torch.full((len(visits), V), -1, dtype=torch.int32)
+    for b, vis in enumerate(visits):
+        for i, (_, t, u) in enumerate(vis):
+            on[b, i], offs[b, i] = t, u
+    n_vis = torch.tensor([len(v) for v in visits], dtype=torch.int32).to(device)
+    top_col, top_score, _, _, n_seg = (t.cpu().numpy() for t in ops.segment_class_scores(
+        em_c, n_vis, on.to(device), offs.to(device), torch.full((len(visits), V), -1, dtype=torch.int32).to(device), pron.top_k))
+    return [[[(pron.classes[j], float(s) / max(int(n_seg[b, i]), 1)) for j, s in zip(top_col[b, i], top_score[b, i]) if j >= 0]
+             for i in range(len(vis))] for b, vis in enumerate(visits)]
+
+
+def _without_slots(off: OffSheet, b: int, row):
+    return [row[p] for p in off.keep[b]]
+
+
+def _scores_without_slots(off: OffSheet, scores, segments_x=None):
+    """The score dicts of the expanded lattice -> the caller's: per-character lists lose the slot entries, span_skip_prob keeps the
+    caller's spans, repeat_count goes back to the caller's (a, e) key by key (a span begins and ends on labels), visit_occupancy loses the slot visits (segments_x: the expanded
+    segments it is parallel to) and "off_sheet_prob" {n: sung_prob / visits of the slot} is added where the dict has that number."""
+    slot_sets = off.slot_sets()
+    for b, d in enumerate(scores):
+        per_char = d.get("sung_prob", d.get("visits"))
+        if per_char is not None:
+            d["off_sheet_prob"] = {n: per_char[int(q)] for n, q in zip(off.slots[b], off.slot_cols[b].tolist())}
+        for key in ("occupancy", "onset_prob", "offset_prob", "sung_prob", "visits"):
+            if key in d:
+                d[key] = _without_slots(off, b, d[key])
+        if "span_skip_prob" in d:
+            d["span_skip_prob"] = d["span_skip_prob"][: off.n_caller_spans[b]]
+        if "repeat_count" in d:
+            back = {p: n for n, p in enumerate(off.keep[b])}          # expanded position -> the caller's label
+            d["repeat_count"] = {(back[a], back[e - 1] + 1): v for (a, e), v in d["repeat_count"].items()}
+        if "visit_occupancy" in d and segments_x is not None:
+            d["visit_occupancy"] = [v for v, seg in zip(d["visit_occupancy"], segments_x[b]) if seg[0] not in slot_sets[b]]
+    return scores
+
+
+def _segments_without_slots(off: OffSheet, segments_x):
+    back = [{p: n for n, p in enumerate(k)} for k in off.keep]
+    return [[(back[b][p], t, u) for p, t, u in segs if p in back[b]] for b, segs in enumerate(segments_x)]
+
+
 MAX_PRONUNCIATION_COLUMNS = 4095      # label columns (the sheet's, or the expanded readings') plus candidate classes: what the head / prep take
 
 
@@ -235,11 +412,12 @@ class Pronunciation(NamedTuple):
 
 
 def _pronunciation_of(who: str, return_pronunciation, pronunciation_classes, pronunciation_top_k, label_lists: List[List[int]],
-                      rd: Optional[Readings] = None) -> Optional[Pronunciation]:
+                      rd: Optional[Readings] = None, slots=None) -> Optional[Pronunciation]:
     """The three keywords of the pronunciation scores -> Pronunciation, or None when return_pronunciation is off (the call as it was).
     pronunciation_classes: an int N (classes 1 .. N) or a sequence of class ids; the sheet's own classes (with alternatives: every
     reading's) are unioned in; sorted and unique.  ValueError for a missing class list, an id below 1 or a top_k outside 1 .. 16;
     NotImplementedError when the label columns (rd: the widest expanded row) plus the candidates exceed MAX_PRONUNCIATION_COLUMNS.
+    slots (OffSheet.slot_sets(), or None): label positions that are off-sheet slots -- the union ignores them and own_col is -1 there.
     Host only."""
     if not return_pronunciation:
         return None
@@ -258,7 +436,8 @@ def _pronunciation_of(who: str, return_pronunciation, pronunciation_classes, pro
         given = [int(c) for c in pronunciation_classes]
         if any(c < 1 for c in given):
             raise ValueError(f"{who}: pronunciation_classes: class ids start at 1")
-    sheet = [c for row in rd.sets for r in row for c in r] if rd is not None else [int(c) for row in label_lists for c in row]
+    rows = rd.sets if rd is not None else [[[int(c)] for c in row] for row in label_lists]
+    sheet = [c for b, row in enumerate(rows) for n, r in enumerate(row) for c in r if slots is None or n not in slots[b]]
     classes = sorted(set(given) | set(sheet))
     Lmax = max(1, max((len(l) for l in label_lists), default=1))
     width = rd.labels_x.shape[1] if rd is not None else Lmax
@@ -270,6 +449,8 @@ def _pronunciation_of(who: str, return_pronunciation, pronunciation_classes, pro
     for b, row in enumerate(label_lists):
         if row:
             own_col[b, : len(row)] = col_of[torch.tensor(row, dtype=torch.int64)]
+        for n in (slots[b] if slots is not None else ()):
+            own_col[b, n] = -1
     return Pronunciation(classes, int(pronunciation_top_k), own_col, col_of)
 
 
@@ -685,7 +866,8 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 
 def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, n_frames_max: int, nf, hop_size_second, confidence,
                  boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
-                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False, pron: Optional[Pronunciation] = None):
+                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False, off: Optional[OffSheet] = None,
+                 return_off_sheet: bool = False, pron: Optional[Pronunciation] = None):
     """What perform_viterbi* and AlignModel.align (`who`: "perform_viterbi" / "align") do once the labels (lab / n_lab on the device,
     label_lists), the spans and windows (host rows, or None) and the kind of confidence are known: the repeat_from rows
     (_repeat_from_of_spans for "repeat" / "song", whose label limit is refused here; _repeat_rows otherwise), the readings (rd: the
@@ -702,7 +884,14 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     dropped, as the readings route drops it, and the lattice reads the leading columns of the widened matrix through its row stride.
     ops.segment_class_scores then runs on the trailing column window and the DP's onset / offset, with the sheet's class -- with
     alternatives the reading ops.reading_scores picked -- as the own class.  The return gains `pronunciation` as its last element
-    (raw: ops.segment_class_scores' five tensors behind the reading pair)."""
+    (raw: ops.segment_class_scores' five tensors behind the reading pair).
+    off (the caller's _off_sheet_of result, or None: the call as it was): off-sheet slots.  Every argument above is then the EXPANDED
+    sheet's (off.label_lists and the remapped keywords).  emissions_of is asked for the expanded rows with needed=True and its DP
+    result is dropped; with alternatives the fold comes first; then ops.offsheet_columns writes the slots' columns of the matrix the
+    lattice reads, and run_lattice and everything behind it run unchanged on L' labels, the slots carrying OFF_SHEET_ID.  On the way out
+    the slot entries leave every per-character output, segments go back to the caller's numbering and the dicts gain "off_sheet_prob"
+    where they hold sung_prob / visits.  return_off_sheet: the return gains, as its last element, per clip the time-ordered list of
+    {"position": n, "onset": s, "offset": s, "frames": k} of every slot visit (with pron also "top"); without slots empty lists."""
     repeat_kind = confidence in ("repeat", "song")
     if repeat_kind:
         repeat_from = _repeat_from_of_spans(repeat_spans, label_lists)
@@ -715,6 +904,8 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     # sees the set-equality ids in the labels' place; None / all-empty takes the call as it was
     if rd is None:
         rd = _readings_of(alternatives, label_lists, keep_empty=return_readings)
+    if off is not None and rd is not None:
+        rd = rd._replace(lattice_ids=off.ids_with_slots(rd.lattice_ids))
     route, dp, em, em_c = None, None, None, None
     if pron is not None:
         classes, plain_emissions_of = torch.tensor(pron.classes, dtype=torch.int32).to(lab.device), emissions_of
@@ -725,7 +916,10 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
             em_c = em_w[:, :, 1 + lab_x.shape[1]:]
             return None, em_w[:, :, : 1 + lab_x.shape[1]]
     if rd is None:
-        dp, em = emissions_of(lab, n_lab, confidence is not None or skip_from is not None or windows is not None or repeat_from is not None)
+        dp, em = emissions_of(lab, n_lab, confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
+                              or off is not None)
+        if off is not None:                  # the provider's own DP ran without the slots' columns
+            dp = None
     if rd is None and em is None:
         r = _result(dp)
     else:
@@ -734,6 +928,10 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
         if rd is not None:
             route = readings_route(rd, lambda lab_x, n_x: emissions_of(lab_x, n_x)[1], n_lab, nf, lab.device)
             em, lab = route.em, route.lattice_ids
+        if off is not None:
+            ops.offsheet_columns(em, off.slot_cols.to(lab.device), off.n_slots.to(lab.device), nf, off.penalty)
+            if route is None:
+                lab = off.lattice_ids.to(lab.device)
         r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from, repeat_penalty)
     picked = route.scores(n_lab, r.onset, r.offset) if return_readings or (pron is not None and route is not None) else ()
     if pron is not None:
@@ -742,32 +940,55 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
         picked = picked if return_readings else ()
     if raw:
         return (r, picked) if pron is None else (r, picked + scored)
+    keep = (lambda rows: rows) if off is None else (lambda rows: [_without_slots(off, b, row) for b, row in enumerate(rows)])
     if repeat_kind:
         seconds, segments, scores = _formatted_repeat(r, label_lists, frame_counts, hop_size_second, optional_spans, repeat_spans)
-        out = (seconds, segments, scores) if return_segments else (seconds, scores)
+        if off is not None:
+            scores, segments = _scores_without_slots(off, scores, segments), _segments_without_slots(off, segments)
+        out = (keep(seconds), segments, scores) if return_segments else (keep(seconds), scores)
     else:
-        seconds = _formatted(r, label_lists, hop_size_second, optional_spans)
-        out = (seconds, _segments_from_path(r.path, frame_counts, hop_size_second)) if return_segments else seconds
+        out = _formatted(r, label_lists, hop_size_second, optional_spans)
+        out = (keep(out[0]), _scores_without_slots(off, out[1]) if off is not None else out[1]) if isinstance(out, tuple) else keep(out)
+        if return_segments:
+            segments = _segments_from_path(r.path, frame_counts, hop_size_second)
+            out = (out, _segments_without_slots(off, segments) if off is not None else segments)
     if return_readings:
-        readings = _readings_from_scores(*picked, rd)
+        readings = keep(_readings_from_scores(*picked, rd))
         out = (*out, readings) if isinstance(out, tuple) else (out, readings)
     if pron is not None:
-        pronunciation = _pronunciation_from_scores(scored, own_col, pron, label_lists)
+        pronunciation = keep(_pronunciation_from_scores(scored, own_col, pron, label_lists))
         out = (*out, pronunciation) if isinstance(out, tuple) else (out, pronunciation)
+    if return_off_sheet:
+        heard = [[] for _ in label_lists]
+        if off is not None:
+            visits = _off_sheet_visits(off, r, frame_counts)
+            top = _off_sheet_top(off, visits, em_c, pron, lab.device) if pron is not None else None
+            heard = [[{"position": n, "onset": float(t) * hop_size_second, "offset": float(u) * hop_size_second, "frames": u - t,
+                       **({"top": top[b][i]} if top is not None else {})} for i, (n, t, u) in enumerate(vis)] for b, vis in enumerate(visits)]
+        out = (*out, heard) if isinstance(out, tuple) else (out, heard)
     return out
 
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, confidence=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False,
-             alternatives=None, return_readings=False, return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
-    """confidence: the kind the public function stands for (run_lattice's); "plain" becomes "span" where a span is given."""
+             alternatives=None, return_readings=False, off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
+             return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
+    """confidence: the kind the public function stands for (run_lattice's); "plain" becomes "span" where a span is given (an off-sheet
+    slot is one)."""
     if return_readings and alternatives is None:
         raise ValueError("return_readings goes with alternatives (without them every character has the one reading of its label)")
-    rd = pron = None
+    rd = pron = off = None
+    if off_sheet is not None:                # off-sheet slots: from here on the sheet is the expanded one, the keywords are remapped
+        off = _off_sheet_of("perform_viterbi", off_sheet, off_sheet_penalty, _label_lists(labels, len(labels)), optional_spans, repeat_spans,
+                            char_windows, onset_anchors, alternatives, narrow=confidence in ("plain", "span", "anchored", "repeat"))
+    if off is not None:
+        labels, optional_spans, repeat_spans = off.label_lists, off.optional_spans, off.repeat_spans
+        char_windows, onset_anchors, alternatives = off.char_windows, off.onset_anchors, off.alternatives
     if return_pronunciation:                 # the keyword checks, before anything is on a device
         lists = _label_lists(labels, len(labels))
         rd = _readings_of(alternatives, lists, keep_empty=return_readings)
-        pron = _pronunciation_of("perform_viterbi", True, pronunciation_classes, pronunciation_top_k, lists, rd)
+        pron = _pronunciation_of("perform_viterbi", True, pronunciation_classes, pronunciation_top_k, lists, rd,
+                                 None if off is None else off.slot_sets())
     dev = _device_of(prediction)
     pred = torch.as_tensor(prediction).to(device=dev, dtype=torch.float32)
     if pred.dim() != 3:
@@ -792,11 +1013,13 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
         confidence = "span"
     return align_labels("perform_viterbi", lambda lab_x, n_x, needed=True: (None, ops.emissions_from_logits(pred, lab_x, n_x, variant)), lab,
                         n_lab, lists, counts, T, nf, hop_size_second, confidence, boundary_window, skip_from, windows, skip_penalty,
-                        optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings, rd, pron=pron)
+                        optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings, rd, pron=pron,
+                        off=off, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
                     char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
+                    off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
                     return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
     aligned over its first n_frames[b] rows, as if it had been handed over alone.
@@ -835,26 +1058,45 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     skipped character, else {"class": the own class id (with alternatives the reading picked), "frames": n, "log_prob": own_score / n,
     "rank": the number of candidates that beat the own class (0 = it is the best), "gop": (own_score - best score) / n <= 0, 0.0 at
     rank 0, "top": [(class id, score / n), ...] the pronunciation_top_k (1 .. 16) best}.  With every other keyword; off: the call as it
-    was.  No threshold on gop is calibrated: none has been measured on real singing."""
+    was.  No threshold on gop is calibrated: none has been measured on real singing.
+    off_sheet / off_sheet_penalty / return_off_sheet (addition; here, in perform_viterbi_ctc and every _scored function): singing that is
+    in the audio but not on the sheet (ad-libs, backing vocals, an omitted verse, a partial sheet).  off_sheet[b] = [n, ...] puts a SLOT
+    before label n of utterance b (0 <= n <= L_b; L_b = after the last label): a label position of its own whose emission is
+    log P(frame is not silence) - off_sheet_penalty (la_emissions_offsheet_columns on column 0 of the prep's matrix), skippable by a
+    one-label optional span.  The slot beats the sheet's character on a frame when that character holds less than exp(-penalty) of the
+    voiced probability; the default ln 100 (a 1 % share, nats per frame) HAS NOT BEEN TUNED on real singing.  The other keywords keep the
+    caller's numbering (a slot strictly inside an optional or repeat span belongs to it) and every per-character output keeps its
+    shape.  return_off_sheet: the return gains, as its last element, off_sheet[b] = the time-ordered list of {"position": n, "onset": s,
+    "offset": s, "frames": k}, one per slot visit (unused slots are absent; with return_pronunciation also "top": [(class id, score per
+    frame), ...], what was heard there).  The _scored functions that report sung_prob / visits add "off_sheet_prob": {n: value} for
+    every slot.  Two properties of the lattice: with a slot before the first label the first character cannot start at frame 0 (after
+    the last: the last character cannot end on the last frame); and an unused slot is charged skip_penalty like every skipped span, so
+    keep off_sheet_penalty above skip_penalty.  ValueError for a wrong list count, a bad or repeated n, a slot on an utterance without
+    labels or a negative / NaN penalty; NotImplementedError when L_b plus its slots exceed 4095 (511 for the confidences that stop
+    there).  None or all-empty: the call as it was."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
                     repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
                     return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
-                    pronunciation_top_k=pronunciation_top_k)
+                    pronunciation_top_k=pronunciation_top_k,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
                         char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
+                        off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
                         return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
                     repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
                     return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
-                    pronunciation_top_k=pronunciation_top_k)
+                    pronunciation_top_k=pronunciation_top_k,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None, skip_penalty=0.0,
-                           char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
+                           char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False,
+                           off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi plus per-character confidence (addition; the reference has none): -> (predicted_onset_offset, scores),
     scores[b] = {"occupancy": [L], "onset_prob": [L], "offset_prob": [L], "path_log_posterior": float} from the forward-backward
     sweep of the same lattice (include/lyricalign.h la_alignment_posteriors).  Same exceptions as perform_viterbi.
@@ -866,19 +1108,23 @@ def perform_viterbi_scored(prediction, labels, hop_size_second=0.02, boundary_wi
     (perform_viterbi(_ctc)_repeat_scored give the posteriors of that lattice)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    confidence="plain", repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    confidence="plain", repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_ctc_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                               skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
+                               skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False,
+                               off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi_ctc plus per-character confidence: see perform_viterbi_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    confidence="plain", repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    confidence="plain", repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                    skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
+                                    skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False,
+                                    off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi with char_windows / onset_anchors plus the confidence GIVEN them (addition): -> (predicted_onset_offset, scores).
     The DP and the forward-backward sweep run on the lattice with per-state frame windows (la_viterbi_windows_batch,
     la_alignment_posteriors_windows), with or without optional_spans.  scores[b] holds perform_viterbi_scored's keys with optional_spans
@@ -890,20 +1136,24 @@ def perform_viterbi_anchored_scored(prediction, labels, hop_size_second=0.02, bo
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     confidence="anchored",
-                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_ctc_anchored_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                        skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
+                                        skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False,
+                                        off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi_ctc plus the confidence given the windows: see perform_viterbi_anchored_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     confidence="anchored",
-                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
+                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False,
+                                 off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """Whole-song timing with its confidences (addition): perform_viterbi_anchored_scored's (predicted_onset_offset, scores) for up to 4095
     labels, with or without optional_spans and char_windows / onset_anchors (la_viterbi_lattice_batch's routing for the DP,
     la_alignment_posteriors_lattice for the posteriors).  window_log_prob is 0.0 without windows.  Up to 511 labels the numbers are
@@ -912,21 +1162,25 @@ def perform_viterbi_sheet_scored(prediction, labels, hop_size_second=0.02, bound
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     confidence="sheet",
-                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_ctc_sheet_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
-                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False):
+                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, alternatives=None, return_readings=False,
+                                     off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi_ctc plus the whole-song confidences: see perform_viterbi_sheet_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     confidence="sheet",
-                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                   skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                  return_segments=False, alternatives=None, return_readings=False):
+                                  return_segments=False, alternatives=None, return_readings=False,
+                                  off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi with repeat_spans plus the confidence of that lattice (addition): -> (predicted_onset_offset, scores), or
     (predicted_onset_offset, segments, scores) with return_segments.  The DP is la_viterbi_repeats_batch, the sweep
     la_alignment_posteriors_repeats, with or without optional_spans, char_windows / onset_anchors and n_frames; up to 511 labels
@@ -945,37 +1199,44 @@ def perform_viterbi_repeat_scored(prediction, labels, hop_size_second=0.02, boun
     With no repeat span anywhere the numbers it shares with perform_viterbi_sheet_scored are that function's exactly."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="repeat", alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="repeat", alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_ctc_repeat_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                       skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                      return_segments=False, alternatives=None, return_readings=False):
+                                      return_segments=False, alternatives=None, return_readings=False,
+                                      off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi_ctc plus the confidence of the lattice with repeatable spans: see perform_viterbi_repeat_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="repeat", alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="repeat", alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                 skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                return_segments=False, alternatives=None, return_readings=False):
+                                return_segments=False, alternatives=None, return_readings=False,
+                                off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """Whole-song timing with repeated lines and its confidences (addition): perform_viterbi_repeat_scored's arguments and return values
     for up to 4095 labels (la_viterbi_repeats_batch for the DP, la_alignment_posteriors_song for the posteriors).  Up to 511 labels
     the numbers are perform_viterbi_repeat_scored's exactly.  The sweep's workspace holds every alpha row: T * 1024 R * 8 bytes per
     utterance beyond 511 labels (R = 2 / 4 / 8 for up to 1023 / 2047 / 4095 labels)."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 def perform_viterbi_ctc_song_scored(prediction, labels, hop_size_second=0.02, boundary_window=2, n_frames=None, optional_spans=None,
                                     skip_penalty=0.0, char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0,
-                                    return_segments=False, alternatives=None, return_readings=False):
+                                    return_segments=False, alternatives=None, return_readings=False,
+                                    off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False):
     """perform_viterbi_ctc plus the whole-song confidences of the lattice with repeatable spans: see perform_viterbi_song_scored."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames,
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
-                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings)
+                    repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings,
+                    off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
