@@ -336,6 +336,43 @@ int la_viterbi_repeats_batch(const float *em, int64_t em_batch_stride, int64_t e
                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Free line order: the DP on the lattice of an UNMARKED lyric sheet -- the caller gives the line breaks and nothing else, and the lines
+ * may be sung in any order, any number of times, or not at all (a sheet prints V1 C V2 B once each; the song sings V1 C V2 C B C).
+ * la_viterbi_batch's arguments through status, then
+ *   line_start [batch][line_stride] (line_stride >= max_labels; entries 0 .. L_b - 1 of row b are read): nonzero = label n begins a
+ *       line.  Entry 0 must be nonzero: a clip where it is zero gets LA_EINVAL, its batch mates are unaffected.  Line m covers the
+ *       labels from its start up to the next start, or up to L_b; the line ENDS e are the starts other than 0, and L_b.
+ *   line_jump_penalty (>= 0, not NaN; +inf allowed): charged per jump, per free start and per free end.
+ *   path [batch][path_stride] (path_stride >= max_frames; may be NULL): as la_viterbi_repeats_batch.
+ * Jump sources: state 0 and, for every line end e, the states 2e-1 (the line's last label) and 2e (the silence after it); a source's
+ * class is labels[s >> 1] for an odd state and "none" for a silence.  Jump targets: the odd state 2a+1 of every line start a, from any
+ * source of the previous frame whose class differs from labels[a] (the equal-neighbour rule; a silence always differs).  Among the
+ * allowed sources the largest dp[t-1][s] wins (the raw value), the smallest state among equals, and the jump is taken only if
+ * dp[t-1][s] - line_jump_penalty is STRICTLY greater than the existing rule's winner; the emission is added last.
+ * Free start: row 0 is la_viterbi_batch's, and every line start a other than 0 gets em[0][1+a] - line_jump_penalty.  Free end: the
+ * choice between S-1 and S-2 first; then the best source other than 0, S-1 and S-2 (largest value, smallest state) replaces it only if
+ * its value minus the penalty is strictly greater.  Float64 adds and subtracts in this order: reproducible to the bit, alone or in a
+ * batch.  The kernel does O(S) work per frame whatever the number of lines (csrc/la_line_order.hip, DESIGN.md "Free line order").
+ * onset / offset are those of a label's FIRST visit in time, -1 / -1 for a label never visited; status is LA_OK even then (lines may
+ * be left out), LA_EEMPTY / LA_EINVAL as in la_viterbi_batch.  With line_jump_penalty = +inf the outputs are la_viterbi_batch's bit for
+ * bit; with a single line they are la_viterbi_repeats_batch's with repeat_from[0] = L_b and the same penalty, up to the order of a tie.
+ * Up to 4095 labels (LA_EUNSUPPORTED above).  The workspace (always needed, 8-byte aligned) holds two 64-bit backpointer masks per
+ * (frame, 64 states) and two int32 per frame.  Argument errors are answered on the host before anything is enqueued; never
+ * synchronises, allocates or frees.  No posteriors and no training loss exist on this lattice.
+ */
+int la_viterbi_lines_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_viterbi_lines_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                           const int32_t *labels, int32_t labels_stride,
+                           const int32_t *n_labels, const int32_t *n_frames,
+                           int32_t batch, int32_t max_frames, int32_t max_labels,
+                           int32_t *onset, int32_t *offset, int32_t out_stride,
+                           double *final_score, int32_t *status,
+                           const int32_t *line_start, int32_t line_stride, double line_jump_penalty,
+                           int32_t *path, int32_t path_stride,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
  * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
  * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable

@@ -70,6 +70,10 @@ SYMBOLS = {
     "la_viterbi_repeats_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_viterbi_repeats_batch": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, c_double,
                                            _P, _P, _I32, _P, _I32, c_double, _P, _I32, _P, _SZ, _P]),
+    # free line order: the plain entry's arguments, then line_start, line_stride, line_jump_penalty, path, path_stride
+    "la_viterbi_lines_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
+    "la_viterbi_lines_batch": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, c_double,
+                                         _P, _I32, _P, _SZ, _P]),
     "la_alignment_posteriors_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_alignment_posteriors": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
                                           _P, _I64, _I64, _P, _SZ, _P]),

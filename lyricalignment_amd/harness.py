@@ -464,6 +464,38 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     return _done(_sheet_lines_out(res[0], lines, (), readings)[0], rk, lines, lut)
 
 
+def align_free_order(model, audio, lines: Sequence[str], lut: PinyinClassLUT, tokenize, use_ctc_loss: bool = True,
+                     line_jump_penalty: float = 0.0, heteronyms=None) -> dict:
+    """One recording against an UNMARKED lyric sheet (addition): the sheet as found prints each verse and the chorus once, in print
+    order; the song sings them in its own order, some of them again, some not at all, and an excerpt starts and ends where it likes.
+    Nothing is marked -- no optional flag, no "x2", no slot: the line breaks are all the lattice is given
+    (AlignModel.align(line_starts=..., return_segments=True); line_jump_penalty >= 0 per change of line that the sheet's own order does
+    not give, per start at another line than the first and per end at another than the last).  The default 0.0 follows skip_penalty /
+    repeat_penalty and HAS NOT BEEN TUNED on real singing.  `tokenize(line)` as in align_records, one class per character; up to 4095
+    characters in the sheet.
+    -> {"occurrences": per line the time-ordered list of its occurrences, each [[onset, offset, char], ...] (empty for a line never
+    sung), "order": the line index of every occurrence in time order, e.g. [1, 0, 1, 2, 1], "unsung": the indices of the lines never
+    sung}.  heteronyms (None: the entries as above): as in align_record_lines; every character entry is then [onset, offset, char,
+    class_id_sung], the class read off the character's first visit."""
+    lines = list(lines)
+    ids, _, labels = _sheet_inputs("align_free_order", lines, [False] * len(lines), lut, tokenize)
+    starts, pos = [], 0
+    for tok in ids:
+        starts.append(pos)
+        pos += len(tok)
+    rk = _reading_kw(lut, ids, heteronyms, who="align_free_order")
+    with torch.no_grad():
+        (_, segments), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, line_starts=[starts],
+                                               line_jump_penalty=line_jump_penalty, return_segments=True)
+    occurrences = _line_occurrences(segments[0], lines, readings)
+    order, last = [], None
+    for i, k, _ in _occurrence_of_visits(segments[0], lines):
+        if (i, k) != last:
+            order.append(i)
+        last = (i, k)
+    return {"occurrences": occurrences, "order": order, "unsung": [i for i, occ in enumerate(occurrences) if not occ]}
+
+
 _LRC_TAG = re.compile(r"\[([^\[\]]*)\]")
 _LRC_TIME = re.compile(r"^(\d+):(\d{1,2})(?:[.:](\d{1,3}))?$")
 

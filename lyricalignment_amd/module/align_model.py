@@ -341,6 +341,7 @@ class AlignModel(torch.nn.Module):
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
               repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False,
               return_song_confidence: bool = False, alternatives=None, return_readings: bool = False,
+              line_starts=None, line_jump_penalty: float = 0.0,
               off_sheet=None, off_sheet_penalty: float = math.log(100), return_off_sheet: bool = False,
               return_pronunciation: bool = False, pronunciation_classes=None, pronunciation_top_k: int = 5):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
@@ -435,6 +436,17 @@ class AlignModel(torch.nn.Module):
         best score) / n <= 0 (0.0 at rank 0), "top": [(class id, score / n), ...]}.  With every other keyword, per_clip and the long form.
         With return_frames five more tensors, last: top_col [B, Lmax, top_k] int32 (columns of the sorted class list), top_score float64,
         own_score [B, Lmax] float64, own_rank int32, n_seg_frames int32.  Off: the call as it was.  No threshold on gop is calibrated.
+        line_starts / line_jump_penalty (addition): an UNMARKED sheet -- the line breaks and nothing else -- whose lines may be sung in any
+        order, any number of times or not at all (a sheet prints V1 C V2 B once each; the song sings V1 C V2 C B C).  line_starts[b] =
+        [0, 7, 15, ...], the label indices at which a line of clip b begins (ops.viterbi_lines_batch): after the last character of any
+        line the path may go on to the first character of any line, it may begin at any line's start and stop at any line's end, each
+        such jump charged line_jump_penalty >= 0 (the default 0.0 follows skip_penalty / repeat_penalty and HAS NOT BEEN TUNED on real
+        singing).  The result keeps its shape: the FIRST visit per character, None for a character never sung; return_segments gives
+        every visit in time order; with return_frames the DP's four tensors and path [B, T].  With per_clip, the long form,
+        alternatives / return_readings and return_pronunciation (both read the first visit), up to 4095 labels (NotImplementedError).
+        ValueError, before a device is asked for, for a row that does not begin with 0, is not strictly ascending or holds an index >=
+        L_b, and together with optional_spans, repeat_spans, onset_anchors, char_windows, off_sheet or any confidence keyword.  None:
+        the call as it was.
         off_sheet / off_sheet_penalty / return_off_sheet (addition): singing that is in the audio but not on the sheet -- ad-libs between
         lines, backing vocals over a break, a spoken intro, an omitted verse, a partial sheet.  off_sheet[b] = [n, ...] puts a SLOT before
         label n of clip b (0 <= n <= L_b; L_b = after the last label): a label position of its own whose emission is log P(frame is not
@@ -471,6 +483,15 @@ class AlignModel(torch.nn.Module):
             widest = max((len(l) for l in ua._label_lists(labels, len(labels))), default=0)
             if widest > ua.POSTERIOR_MAX_LABELS:
                 raise NotImplementedError(f"align: {widest} labels exceed the {ua.POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
+        # free line order: the rows and every refusal, before the engine exists
+        ua._line_starts_alone("align", line_starts, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
+                              char_windows=char_windows, off_sheet=off_sheet, return_confidence=return_confidence,
+                              return_span_confidence=return_span_confidence, return_anchored_confidence=return_anchored_confidence,
+                              return_sheet_confidence=return_sheet_confidence, return_repeat_confidence=return_repeat_confidence,
+                              return_song_confidence=return_song_confidence)
+        line_start = ua._line_start_of("align", line_starts, ua._label_lists(labels, len(labels)))
+        if line_start is not None and not float(line_jump_penalty) >= 0.0:
+            raise ValueError("align: line_jump_penalty must be >= 0")
         off = None
         if off_sheet is not None:            # off-sheet slots: from here on the sheet is the expanded one, the keywords are remapped
             off = ua._off_sheet_of("align", off_sheet, off_sheet_penalty, ua._label_lists(labels, len(labels)), optional_spans, repeat_spans,
@@ -525,7 +546,8 @@ class AlignModel(torch.nn.Module):
 
         out = ua.align_labels("align", head, lab_dev, n_lab, lab_lists, frame_counts, T, kw.get("n_frames"), hop_size_second, confidence,
                               boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
-                              alternatives, return_readings, rd, raw=return_frames, pron=pron, off=off, return_off_sheet=return_off_sheet)
+                              alternatives, return_readings, rd, raw=return_frames, pron=pron, off=off, return_off_sheet=return_off_sheet,
+                              line_start=line_start, line_jump_penalty=float(line_jump_penalty))
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path);
             r, picked = out
             # reading, col_score behind them, the five tensors of the pronunciation scores last

@@ -231,6 +231,39 @@ def viterbi_repeats_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     return _viterbi("viterbi_repeats", em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty)
 
 
+LINES_MAX_LABELS = 4095
+
+
+def viterbi_lines_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor, line_start: torch.Tensor,
+                        line_jump_penalty: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """la_viterbi_lines_batch: viterbi_batch on the lattice of an unmarked sheet, whose lines may be sung in any order, any number of
+    times or not at all, for up to 4095 labels.  line_start [B, >= Lmax] i32 (device): nonzero = the label begins a line; entry 0 of a
+    clip must be nonzero (LA_EINVAL for that clip otherwise).  line_jump_penalty >= 0 (inf allowed) is charged per jump between lines,
+    per start at another line than the first and per end at another line than the last; it has not been tuned on real singing.
+    -> onset, offset (a label's FIRST visit in time; -1 for a label never visited, under status LA_OK), final_score, status, path [B,T]
+    i32 (the lattice state at every frame t < T_b; -1 for t >= T_b and for a clip whose status is LA_EEMPTY or LA_EINVAL)."""
+    who = "viterbi_lines_batch"
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, line_start=line_start)
+    if line_start.dim() != 2 or line_start.shape[0] != B or line_start.shape[1] < Lmax or line_start.stride(1) != 1:
+        raise ValueError(f"{who}: line_start [B, >= Lmax] with unit inner stride expected")
+    line_jump_penalty = float(line_jump_penalty)
+    if not line_jump_penalty >= 0.0:
+        raise ValueError(f"{who}: line_jump_penalty must be >= 0")
+    if Lmax > LINES_MAX_LABELS:
+        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {LINES_MAX_LABELS} ({_LABEL_LIMIT_WHY[4095]})")
+    dev = em.device
+    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
+    score = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    ws, need = _lattice_workspace("viterbi_lines_workspace_bytes", B, T, Lmax, dev)
+    check(lib().la_viterbi_lines_batch(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), ptr(line_start), line_start.stride(0), line_jump_penalty,
+        ptr(path), T, ptr(ws), need, stream_ptr()), who)
+    return onset, offset, score, status, path
+
+
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
                          onset: torch.Tensor, offset: torch.Tensor, boundary_window: int = 2, want_gamma: bool = False):
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,

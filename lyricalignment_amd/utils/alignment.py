@@ -123,6 +123,59 @@ def _repeat_from_of_spans(repeat_spans, label_lists: List[List[int]]):
     return rows if any_span else None
 
 
+LINES_MAX_LABELS = 4095         # what the lattice with free line order takes (ops.viterbi_lines_batch)
+
+
+def lines_from_lengths(line_lengths: Sequence[int]) -> List[int]:
+    """One clip's line_start flag row (include/lyricalign.h la_viterbi_lines_batch) for lyrics given as consecutive lines of
+    line_lengths[i] characters: L entries, 1 at every line's first character, 0 elsewhere."""
+    lengths = [int(v) for v in line_lengths]
+    if not lengths or any(v <= 0 for v in lengths):
+        raise ValueError("lines_from_lengths: at least one line, and every line must hold at least one character")
+    return [flag for n_chars in lengths for flag in [1] + [0] * (n_chars - 1)]
+
+
+def _line_start_of(who: str, line_starts, label_lists: List[List[int]]):
+    """line_starts[b] = the label indices at which a line of utterance b begins, [0, 7, 15, ...] -> host int32 tensor [B, Lmax] of
+    line_start flag rows, or None for line_starts None.  ValueError for a wrong row count or a row that does not begin with 0, is not
+    strictly ascending or holds an index >= L_b (an utterance without labels takes an empty row); NotImplementedError beyond 4095
+    labels.  Nothing here asks for a device."""
+    if line_starts is None:
+        return None
+    if len(line_starts) != len(label_lists):
+        raise ValueError(f"{who}: line_starts: {len(label_lists)} rows expected, one per utterance")
+    widest = max((len(l) for l in label_lists), default=0)
+    if widest > LINES_MAX_LABELS:
+        raise NotImplementedError(f"{who}: line_starts: {widest} labels exceed the {LINES_MAX_LABELS}-label limit of the lattice with free line order")
+    rows = torch.zeros((len(label_lists), max(1, widest)), dtype=torch.int32)
+    for b, row in enumerate(line_starts):
+        L = len(label_lists[b])
+        row = [] if row is None else list(row)
+        if L == 0 and not row:
+            continue
+        if any(isinstance(v, bool) or int(v) != v for v in row):
+            raise ValueError(f"{who}: line_starts[{b}]: label indices expected")
+        row = [int(v) for v in row]
+        if not row or row[0] != 0 or any(x >= y for x, y in zip(row, row[1:])) or row[-1] >= L:
+            raise ValueError(f"{who}: line_starts[{b}] must begin with 0, ascend strictly and stay below the utterance's {L} labels")
+        rows[b, row] = 1
+    return rows
+
+
+def _line_starts_alone(who: str, line_starts, **others) -> None:
+    """The keywords that do not go with line_starts (others: name -> value as the caller got it; None, False and all-empty lists count as
+    not given): ValueError naming both."""
+    if line_starts is None:
+        return
+    for name, value in others.items():
+        given = value is not None and value is not False
+        if given and isinstance(value, (list, tuple)):
+            given = any(bool(row) for row in value)
+        if given:
+            raise ValueError(f"{who}: line_starts does not go with {name} (the lattice with free line order has the line breaks and nothing "
+                             "else: no marked spans, no anchors, no off-sheet slots, no posteriors)")
+
+
 MAX_READINGS = 8                # readings per label position, the sheet's own class included
 MAX_READING_COLUMNS = 4095      # expanded columns per clip: what the head, the prep and the fold take
 READING_SET_ID = 1 << 24        # lattice id of a clip's k-th distinct multi-reading set: READING_SET_ID + k (class ids lie far below)
@@ -721,10 +774,12 @@ ROUTES = {
     ("song", False, True): Route("viterbi_repeats_batch", "alignment_posteriors_song", "alignment_posteriors_song"),
     ("song", True, True): Route("viterbi_repeats_batch", "alignment_posteriors_song", "alignment_posteriors_song"),
 }
-# The two rules that lie across the table.  A given repeat_from sends the DP to the lattice with repeatable spans (the rows of "repeat"
+# The rules that lie across the table.  A given repeat_from sends the DP to the lattice with repeatable spans (the rows of "repeat"
 # and "song" name it themselves); beyond POSTERIOR_MAX_LABELS the DP's span and window entries give way to the general one.
 REPEAT_DP = "viterbi_repeats_batch"
 WIDE_DP = {"viterbi_spans_batch": "viterbi_lattice_batch", "viterbi_windows_batch": "viterbi_lattice_batch"}
+# and a third: a given line_start sends the DP to the lattice with free line order, which knows none of the table's faces
+LINES_DP = "viterbi_lines_batch"
 # the sweeps of one lane per lattice state, and how run_lattice's refusal beyond POSTERIOR_MAX_LABELS ends for each
 NARROW_SWEEPS = {name: "the posterior sweeps (the alignment itself and the sheet confidence take up to 4095)"
                  for name in ("alignment_posteriors", "alignment_posteriors_spans", "alignment_posteriors_windows")}
@@ -757,7 +812,7 @@ def _call(name: str, lattice, groups, boundary_window=None):
 
 
 def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0.0, confidence=None, boundary_window=2, dp=None,
-                repeat_from=None, repeat_penalty=0.0) -> LatticeResult:
+                repeat_from=None, repeat_penalty=0.0, line_start=None, line_jump_penalty=0.0) -> LatticeResult:
     """The one place where the face of an alignment is decided (csrc/la_lattice.h Face, through the ops wrappers): the DP and, if asked
     for, the posteriors on the lattice that skip_from (host rows of _skip_from_of_spans, or None) and windows (host (win_lo, win_hi)
     of _windows_of, or None) describe.  em / lab / n_lab / nf are device tensors.
@@ -779,7 +834,17 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     None otherwise -- and repeat_count / path_prob are attributes of the result.
     "song": "repeat" without the label limit (whole songs, up to 4095 labels): ops.viterbi_repeats_batch, then ONE call of
     ops.alignment_posteriors_song, and a second one without windows for log_z_free where windows were given.  Up to 511 labels its
-    numbers are "repeat"'s exactly."""
+    numbers are "repeat"'s exactly.
+    line_start (host rows of _line_start_of, or None) / line_jump_penalty: the lattice of an unmarked sheet, whose lines may be sung in any
+    order (LINES_DP, ops.viterbi_lines_batch, up to 4095 labels); the result is a RepeatLatticeResult whose `path` holds the state per
+    frame.  That lattice has the line breaks and nothing else: ValueError before anything is launched when line_start comes together
+    with skip_from, windows, repeat_from or any confidence."""
+    if line_start is not None:
+        for name, given in (("skip_from", skip_from), ("windows", windows), ("repeat_from", repeat_from), ("confidence", confidence)):
+            if given is not None:
+                raise ValueError(f"run_lattice: line_start does not go with {name} (the lattice with free line order has neither marked "
+                                 "spans nor windows nor posteriors)")
+        return _result(getattr(ops, LINES_DP)(em, lab, n_lab, nf, line_start.to(em.device), line_jump_penalty))
     key = (confidence, skip_from is not None, windows is not None)
     if key not in ROUTES:
         raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
@@ -866,8 +931,8 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 
 def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, n_frames_max: int, nf, hop_size_second, confidence,
                  boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
-                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False, off: Optional[OffSheet] = None,
-                 return_off_sheet: bool = False, pron: Optional[Pronunciation] = None):
+                 alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False, line_start=None, line_jump_penalty=0.0,
+                 off: Optional[OffSheet] = None, return_off_sheet: bool = False, pron: Optional[Pronunciation] = None):
     """What perform_viterbi* and AlignModel.align (`who`: "perform_viterbi" / "align") do once the labels (lab / n_lab on the device,
     label_lists), the spans and windows (host rows, or None) and the kind of confidence are known: the repeat_from rows
     (_repeat_from_of_spans for "repeat" / "song", whose label limit is refused here; _repeat_rows otherwise), the readings (rd: the
@@ -891,9 +956,14 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     lattice reads, and run_lattice and everything behind it run unchanged on L' labels, the slots carrying OFF_SHEET_ID.  On the way out
     the slot entries leave every per-character output, segments go back to the caller's numbering and the dicts gain "off_sheet_prob"
     where they hold sung_prob / visits.  return_off_sheet: the return gains, as its last element, per clip the time-ordered list of
-    {"position": n, "onset": s, "offset": s, "frames": k} of every slot visit (with pron also "top"); without slots empty lists."""
+    {"position": n, "onset": s, "offset": s, "frames": k} of every slot visit (with pron also "top"); without slots empty lists.
+    line_start (the caller's _line_start_of rows, or None: the call as it was) / line_jump_penalty: the lattice with free line order.  The
+    caller has refused every keyword that does not go with it; the emissions are asked for, run_lattice takes the rows, and the result
+    (a RepeatLatticeResult: first visits, the path for return_segments) goes through everything behind it unchanged."""
     repeat_kind = confidence in ("repeat", "song")
-    if repeat_kind:
+    if line_start is not None:
+        repeat_from = None
+    elif repeat_kind:
         repeat_from = _repeat_from_of_spans(repeat_spans, label_lists)
         if lab.shape[1] > POSTERIOR_MAX_LABELS and confidence == "repeat":
             raise NotImplementedError(f"{who}_repeat_scored: {lab.shape[1]} labels exceed the {POSTERIOR_MAX_LABELS}-label limit of "
@@ -917,7 +987,7 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
             return None, em_w[:, :, : 1 + lab_x.shape[1]]
     if rd is None:
         dp, em = emissions_of(lab, n_lab, confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
-                              or off is not None)
+                              or off is not None or line_start is not None)
         if off is not None:                  # the provider's own DP ran without the slots' columns
             dp = None
     if rd is None and em is None:
@@ -932,7 +1002,8 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
             ops.offsheet_columns(em, off.slot_cols.to(lab.device), off.n_slots.to(lab.device), nf, off.penalty)
             if route is None:
                 lab = off.lattice_ids.to(lab.device)
-        r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from, repeat_penalty)
+        r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from, repeat_penalty,
+                        line_start, line_jump_penalty)
     picked = route.scores(n_lab, r.onset, r.offset) if return_readings or (pron is not None and route is not None) else ()
     if pron is not None:
         own_col = _own_columns(pron, route, picked[0] if route is not None else None, lab.device)
@@ -971,13 +1042,20 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, confidence=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False,
-             alternatives=None, return_readings=False, off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
+             alternatives=None, return_readings=False, line_starts=None, line_jump_penalty=0.0, off_sheet=None,
+             off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
              return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """confidence: the kind the public function stands for (run_lattice's); "plain" becomes "span" where a span is given (an off-sheet
     slot is one)."""
     if return_readings and alternatives is None:
         raise ValueError("return_readings goes with alternatives (without them every character has the one reading of its label)")
     rd = pron = off = None
+    # free line order: the rows and every refusal, before anything is on a device
+    _line_starts_alone("perform_viterbi", line_starts, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
+                       char_windows=char_windows, off_sheet=off_sheet, confidence=confidence)
+    line_start = _line_start_of("perform_viterbi", line_starts, _label_lists(labels, len(labels)))
+    if line_start is not None and not float(line_jump_penalty) >= 0.0:
+        raise ValueError("perform_viterbi: line_jump_penalty must be >= 0")
     if off_sheet is not None:                # off-sheet slots: from here on the sheet is the expanded one, the keywords are remapped
         off = _off_sheet_of("perform_viterbi", off_sheet, off_sheet_penalty, _label_lists(labels, len(labels)), optional_spans, repeat_spans,
                             char_windows, onset_anchors, alternatives, narrow=confidence in ("plain", "span", "anchored", "repeat"))
@@ -1014,11 +1092,12 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     return align_labels("perform_viterbi", lambda lab_x, n_x, needed=True: (None, ops.emissions_from_logits(pred, lab_x, n_x, variant)), lab,
                         n_lab, lists, counts, T, nf, hop_size_second, confidence, boundary_window, skip_from, windows, skip_penalty,
                         optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings, rd, pron=pron,
-                        off=off, return_off_sheet=return_off_sheet)
+                        off=off, return_off_sheet=return_off_sheet, line_start=line_start, line_jump_penalty=float(line_jump_penalty))
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
                     char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
+                    line_starts=None, line_jump_penalty=0.0,
                     off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
                     return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
@@ -1059,6 +1138,16 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     "rank": the number of candidates that beat the own class (0 = it is the best), "gop": (own_score - best score) / n <= 0, 0.0 at
     rank 0, "top": [(class id, score / n), ...] the pronunciation_top_k (1 .. 16) best}.  With every other keyword; off: the call as it
     was.  No threshold on gop is calibrated: none has been measured on real singing.
+    line_starts / line_jump_penalty (addition; here and in perform_viterbi_ctc): an UNMARKED sheet whose lines may be sung in any order, any
+    number of times or not at all.  line_starts[b] = [0, 7, 15, ...], the label indices at which a line of utterance b begins -- the
+    line breaks and nothing else (la_viterbi_lines_batch): after the last character of any line the path may go on to the first
+    character of any line, it may begin at any line's start and stop at any line's end, each such jump charged line_jump_penalty >= 0
+    (the default 0.0 follows skip_penalty / repeat_penalty and HAS NOT BEEN TUNED on real singing).  The result keeps its shape: the
+    FIRST visit per character, None for a character never sung; return_segments gives every visit in time order.  With n_frames,
+    alternatives / return_readings and return_pronunciation (both read the first visit), up to 4095 labels (NotImplementedError).
+    ValueError for a row that does not begin with 0, is not strictly ascending or holds an index >= L_b, and together with
+    optional_spans, repeat_spans, onset_anchors, char_windows or off_sheet; the _scored functions and the training entries do not have
+    the keyword.  None: the call as it was.
     off_sheet / off_sheet_penalty / return_off_sheet (addition; here, in perform_viterbi_ctc and every _scored function): singing that is
     in the audio but not on the sheet (ad-libs, backing vocals, an omitted verse, a partial sheet).  off_sheet[b] = [n, ...] puts a SLOT
     before label n of utterance b (0 <= n <= L_b; L_b = after the last label): a label position of its own whose emission is
@@ -1077,6 +1166,7 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
                     repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
+                    line_starts=line_starts, line_jump_penalty=line_jump_penalty,
                     return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
                     pronunciation_top_k=pronunciation_top_k,
                     off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
@@ -1084,11 +1174,13 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
                         char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
+                    line_starts=None, line_jump_penalty=0.0,
                         off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
                         return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
                     repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
+                    line_starts=line_starts, line_jump_penalty=line_jump_penalty,
                     return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
                     pronunciation_top_k=pronunciation_top_k,
                     off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
