@@ -358,7 +358,8 @@ int la_viterbi_repeats_batch(const float *em, int64_t em_batch_stride, int64_t e
  * bit; with a single line they are la_viterbi_repeats_batch's with repeat_from[0] = L_b and the same penalty, up to the order of a tie.
  * Up to 4095 labels (LA_EUNSUPPORTED above).  The workspace (always needed, 8-byte aligned) holds two 64-bit backpointer masks per
  * (frame, 64 states) and two int32 per frame.  Argument errors are answered on the host before anything is enqueued; never
- * synchronises, allocates or frees.  No posteriors and no training loss exist on this lattice.
+ * synchronises, allocates or frees.  The posteriors of this lattice are la_alignment_posteriors_lines (below); no training loss exists
+ * on it.
  */
 int la_viterbi_lines_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
 
@@ -613,6 +614,59 @@ int la_alignment_posteriors_song(const float *em, int64_t em_batch_stride, int64
                                  double *log_z, int32_t *status,
                                  float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Confidence for FREE LINE ORDER: the sum-product sweep of la_viterbi_lines_batch's lattice (same line_start / line_jump_penalty; no
+ * counterpart in the reference).  States, jump sources, jump targets and the class rule are that entry's.  A path is one state per
+ * frame; it weighs exp(sum_t e_t(path_t)) times one factor per transition, with q = exp(-line_jump_penalty):
+ *   plain transitions weigh 1: k -> k, k -> k+1, and k -> k+2 into an odd state whose neighbour label differs;
+ *   a jump weighs q: a transition source -> target that the class rule allows and that is not a plain transition already (the DP takes
+ *       the free arc where both exist; no pair of states counts twice);
+ *   start: states 0 and 1 weigh 1, every other target 2a+1 weighs q;  end: states S-1 and S-2 weigh 1, every other source but state 0 q.
+ * la_alignment_posteriors' arguments through boundary_window, then line_start, line_stride, line_jump_penalty as la_viterbi_lines_batch,
+ * then path [batch][path_stride] (that entry's output for the same lattice, with onset / offset its first visits; NULL = not given).
+ * A path may visit a label any number of times: a VISIT is a maximal run of frames in one odd state, entry_t(n) / exit_t(n) are the
+ * expected numbers of visits of label n that begin / end at frame t (a jump into 2a+1 is an entry of a and an exit of its source; a
+ * start in an odd state is an entry at frame 0, an end in one an exit at the last frame), and what is summed from them are EXPECTED
+ * COUNTS that can exceed 1; nothing is clamped.  Outputs:
+ *   log_z, gamma_t(k), occupancy, onset_prob, offset_prob, gamma_out, path_prob[b][t] = gamma_t(path[b][t]) ([batch][path_stride], NULL =
+ *       not wanted; LA_EINVAL without a path): as la_alignment_posteriors_repeats, about the reported (first) visit; 0 for a label never
+ *       visited (onset -1);
+ *   visits[b][n] = sum_t entry_t(n): the expected number of times label n is sung.  It is constant along a line: a path enters a line
+ *       only at its start and leaves it only at its end;
+ *   in_order[b][a], for a line start a: the expected number of visits of label a that begin in print order -- by the plain transition
+ *       from 2a or, where the labels differ, from 2a-1, and for a = 0 also a start in state 1.  0 for every other label.
+ *       visits - in_order at a line start is the expected number of arrivals out of print order: jumps plus free starts.
+ *   status[b]: as la_alignment_posteriors; LA_EINVAL also for a clip whose line_start[0] is 0, LA_EINFEASIBLE where no path exists
+ *       (+inf penalty and too few frames).  Rows of failed clips are zero, log_z 0 (-inf when infeasible); batch mates are unaffected.
+ * Identities (tested): the rows of gamma sum to 1; with line_jump_penalty = +inf every shared output is la_alignment_posteriors', visits
+ * 1 and in_order the line starts; with a single line they are la_alignment_posteriors_repeats' with repeat_from[0] = L_b and
+ * repeat_penalty = line_jump_penalty, and visits[0] - in_order[0] its repeat_count[0] -- each within the bound below.
+ * The M^2 jump arcs of M lines cost O(S + M) additions per frame and no subtraction (csrc/la_line_posterior.hip, DESIGN.md "Posteriors
+ * on the line-order lattice"): path scores and the sums over sources are float64, a step's neighbour terms take their correction in
+ * float32 as in la_alignment_posteriors; every probability, count and log_z within 8 T 2^-23 max(1, |value|) of a float64 evaluation.
+ * The sums run in an order fixed by the kernel form: two calls, and a clip alone in the same form, agree bit for bit.
+ * Up to 4095 labels (LA_EUNSUPPORTED above).  `workspace` (8-byte aligned, always needed) holds every alpha row, the jump term of every
+ * label position and three sums per label position: batch * (max_frames * 1.5 S_pad + 1.5 S_pad) * 8 bytes, S_pad = 64 * the
+ * smallest power of two of waves that holds 2 max_labels + 1 states up to 511 labels, 2048 / 4096 / 8192 up to 1023 / 2047 / 4095.
+ * Argument errors (null pointers, strides, a negative or NaN penalty, path_prob without path) are answered on the host under this
+ * entry's name before anything is enqueued; never synchronises, allocates or frees.
+ */
+int la_alignment_posteriors_lines_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes);
+
+int la_alignment_posteriors_lines(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                  const int32_t *labels, int32_t labels_stride,
+                                  const int32_t *n_labels, const int32_t *n_frames,
+                                  int32_t batch, int32_t max_frames, int32_t max_labels,
+                                  const int32_t *onset, const int32_t *offset, int32_t out_stride,
+                                  int32_t boundary_window,
+                                  const int32_t *line_start, int32_t line_stride, double line_jump_penalty,
+                                  const int32_t *path, int32_t path_stride,
+                                  float *occupancy, float *onset_prob, float *offset_prob,
+                                  float *visits, float *in_order, float *path_prob,
+                                  double *log_z, int32_t *status,
+                                  float *gamma_out, int64_t gamma_batch_stride, int64_t gamma_row_stride,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------- */
 /* emission prep from materialised logits                                     */

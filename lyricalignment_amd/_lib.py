@@ -94,6 +94,11 @@ SYMBOLS = {
     "la_alignment_posteriors_song": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, c_double,
                                                _P, _P, _I32, _P, _I32, c_double, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                _I64, _I64, _P, _SZ, _P]),
+    # confidence for free line order: the plain sweep's arguments, then line_start, line_stride, line_jump_penalty, path, path_stride, and
+    # visits, in_order, path_prob among the outputs
+    "la_alignment_posteriors_lines_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
+    "la_alignment_posteriors_lines": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32, c_double,
+                                                _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _SZ, _P]),
     "la_emissions_from_logits": (c_int32, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I64, _I64, _P]),
     # pronunciation alternatives: fold the expanded emission matrix in front of the lattice, score the readings behind it
     "la_emissions_merge_readings": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P]),

@@ -477,23 +477,56 @@ def align_free_order(model, audio, lines: Sequence[str], lut: PinyinClassLUT, to
     sung), "order": the line index of every occurrence in time order, e.g. [1, 0, 1, 2, 1], "unsung": the indices of the lines never
     sung}.  heteronyms (None: the entries as above): as in align_record_lines; every character entry is then [onset, offset, char,
     class_id_sung], the class read off the character's first visit."""
+    return _free_order("align_free_order", model, audio, lines, lut, tokenize, use_ctc_loss, line_jump_penalty, heteronyms)
+
+
+def _free_order(who: str, model, audio, lines, lut, tokenize, use_ctc_loss, line_jump_penalty, heteronyms, boundary_window=None) -> dict:
+    """align_free_order's dict; with a boundary_window the call also asks for the line confidence and the dict gains "confidence"."""
     lines = list(lines)
-    ids, _, labels = _sheet_inputs("align_free_order", lines, [False] * len(lines), lut, tokenize)
+    ids, _, labels = _sheet_inputs(who, lines, [False] * len(lines), lut, tokenize)
     starts, pos = [], 0
     for tok in ids:
         starts.append(pos)
         pos += len(tok)
-    rk = _reading_kw(lut, ids, heteronyms, who="align_free_order")
+    rk = _reading_kw(lut, ids, heteronyms, who=who)
+    kw = {} if boundary_window is None else dict(return_line_confidence=True, boundary_window=int(boundary_window))
     with torch.no_grad():
-        (_, segments), readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, line_starts=[starts],
-                                               line_jump_penalty=line_jump_penalty, return_segments=True)
+        res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, line_starts=[starts],
+                                     line_jump_penalty=line_jump_penalty, return_segments=True, **kw)
+    segments = res[1]
     occurrences = _line_occurrences(segments[0], lines, readings)
+    visits = _occurrence_of_visits(segments[0], lines)
     order, last = [], None
-    for i, k, _ in _occurrence_of_visits(segments[0], lines):
+    for i, k, _ in visits:
         if (i, k) != last:
             order.append(i)
         last = (i, k)
-    return {"occurrences": occurrences, "order": order, "unsung": [i for i, occ in enumerate(occurrences) if not occ]}
+    out = {"occurrences": occurrences, "order": order, "unsung": [i for i, occ in enumerate(occurrences) if not occ]}
+    if boundary_window is not None:
+        d = res[2][0]
+        weight = [[[0.0, 0.0] for _ in occ] for occ in occurrences]          # per occurrence: posterior times seconds, seconds
+        for (n, on, off), (i, k, _), v in zip(segments[0], visits, d["visit_occupancy"]):
+            weight[i][k][0] += v * (off - on)
+            weight[i][k][1] += off - on
+        out["confidence"] = {"expected_occurrences": list(d["line_visits"]), "out_of_order": list(d["line_out_of_order"]),
+                             "occurrence_occupancy": [[a / b for a, b in occ] for occ in weight],
+                             "order_log_posterior": d["path_log_posterior"]}
+    return out
+
+
+def align_free_order_scored(model, audio, lines: Sequence[str], lut: PinyinClassLUT, tokenize, use_ctc_loss: bool = True,
+                            line_jump_penalty: float = 0.0, heteronyms=None, boundary_window: int = 2) -> dict:
+    """align_free_order plus how far to trust it (addition): the same dict and "confidence", from the posteriors of the lattice with free
+    line order (AlignModel.align(line_starts=..., return_line_confidence=True)):
+      "expected_occurrences": per line the expected number of times it is sung under the model -- a COUNT, not a probability: a chorus
+          sung three times is near 3, a line left out near 0, and a line the model cannot place may sit anywhere between;
+      "out_of_order": per line how many of those occurrences are expected to begin out of print order (by a jump or a free start);
+      "occurrence_occupancy": per line one number per reported occurrence, the mean posterior of the reported state over the frames of
+          the occurrence's characters (near 1: the model puts these frames nowhere else);
+      "order_log_posterior": final_score - log_z <= 0, the log-probability of the reported order and timing together.
+    line_jump_penalty (default 0.0) has not been tuned on real singing; these numbers are the means to tune it."""
+    return _free_order("align_free_order_scored", model, audio, lines, lut, tokenize, use_ctc_loss, line_jump_penalty, heteronyms,
+                       boundary_window)
 
 
 _LRC_TAG = re.compile(r"\[([^\[\]]*)\]")

@@ -343,6 +343,7 @@ class AlignModel(torch.nn.Module):
               return_song_confidence: bool = False, alternatives=None, return_readings: bool = False,
               line_starts=None, line_jump_penalty: float = 0.0,
               off_sheet=None, off_sheet_penalty: float = math.log(100), return_off_sheet: bool = False,
+              return_line_confidence: bool = False,
               return_pronunciation: bool = False, pronunciation_classes=None, pronunciation_top_k: int = 5):
         """audios (or a ready mel) + class-id labels ([B,Lmax] with -100 padding, or list of lists) ->
         list[B] of list[L] of [onset_s, offset_s], exactly what perform_viterbi(_ctc)(frame_manual_forward(...))
@@ -445,8 +446,20 @@ class AlignModel(torch.nn.Module):
         every visit in time order; with return_frames the DP's four tensors and path [B, T].  With per_clip, the long form,
         alternatives / return_readings and return_pronunciation (both read the first visit), up to 4095 labels (NotImplementedError).
         ValueError, before a device is asked for, for a row that does not begin with 0, is not strictly ascending or holds an index >=
-        L_b, and together with optional_spans, repeat_spans, onset_anchors, char_windows, off_sheet or any confidence keyword.  None:
-        the call as it was.
+        L_b, and together with optional_spans, repeat_spans, onset_anchors, char_windows, off_sheet or any of the six confidence keywords
+        above (return_line_confidence is this lattice's).  None: the call as it was.
+        return_line_confidence (addition; with line_starts, ValueError without, before a device is asked for): the confidence of the
+        lattice with free line order (ops.alignment_posteriors_lines on the DP's onset / offset / path) -> (seconds, scores), or
+        (seconds, segments, scores) with return_segments.  A path may sing a line any number of times, so some numbers are EXPECTED
+        COUNTS that can exceed 1 (nothing is clamped).  scores[b] holds "occupancy", "onset_prob", "offset_prob" [L] (about the reported,
+        first visit; 0 for a character never sung), "path_log_posterior" (of the reported order and timing together), "visits" [L] (the
+        expected number of times the character is sung; constant along a line), "visit_occupancy" (one number per entry of segments[b]:
+        the mean posterior of the reported state over that visit's frames), "line_visits" [M] (per line the expected number of times it
+        is sung: a count, not a probability) and "line_out_of_order" [M] (how many of those are expected to begin out of print order, by
+        a jump or a free start).  With per_clip, the long form, alternatives / return_readings and return_pronunciation as far as
+        line_starts goes; up to 4095 labels.  With return_frames the DP's four tensors, (occupancy, onset_prob, offset_prob, log_z,
+        visits) and path.  The sweep keeps every alpha row and every line start's jump term: T * 1.5 * (states per workgroup) * 8 bytes
+        per clip.
         off_sheet / off_sheet_penalty / return_off_sheet (addition): singing that is in the audio but not on the sheet -- ad-libs between
         lines, backing vocals over a break, a spoken intro, an omitted verse, a partial sheet.  off_sheet[b] = [n, ...] puts a SLOT before
         label n of clip b (0 <= n <= L_b; L_b = after the last label): a label position of its own whose emission is log P(frame is not
@@ -489,6 +502,8 @@ class AlignModel(torch.nn.Module):
                               return_span_confidence=return_span_confidence, return_anchored_confidence=return_anchored_confidence,
                               return_sheet_confidence=return_sheet_confidence, return_repeat_confidence=return_repeat_confidence,
                               return_song_confidence=return_song_confidence)
+        if return_line_confidence and line_starts is None:
+            raise ValueError("align: return_line_confidence is the confidence of the lattice with free line order: it needs line_starts")
         line_start = ua._line_start_of("align", line_starts, ua._label_lists(labels, len(labels)))
         if line_start is not None and not float(line_jump_penalty) >= 0.0:
             raise ValueError("align: line_jump_penalty must be >= 0")
@@ -530,7 +545,7 @@ class AlignModel(torch.nn.Module):
         if skip_from is not None and return_confidence:
             raise ValueError("align: return_confidence is not defined with optional_spans (no posteriors over the span lattice by that "
                              "keyword: return_span_confidence=True gives them)")
-        confidence = ("song" if return_song_confidence else "repeat" if return_repeat_confidence else "sheet" if return_sheet_confidence
+        confidence = (ua.LINES_CONFIDENCE if return_line_confidence else "song" if return_song_confidence else "repeat" if return_repeat_confidence else "sheet" if return_sheet_confidence
                       else "anchored" if return_anchored_confidence else "span" if return_span_confidence else "plain" if return_confidence
                       else None)
         variant = _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN

@@ -338,6 +338,52 @@ def alignment_posteriors_song(em: torch.Tensor, labels: torch.Tensor, n_labels: 
                        skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty, path)
 
 
+def alignment_posteriors_lines(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
+                               onset: torch.Tensor, offset: torch.Tensor, line_start: torch.Tensor, line_jump_penalty: float = 0.0,
+                               path: Optional[torch.Tensor] = None, boundary_window: int = 2, want_gamma: bool = False):
+    """la_alignment_posteriors_lines: forward-backward on the lattice of viterbi_lines_batch, for up to 4095 labels (NotImplementedError
+    above, before a launch); onset / offset / path = its outputs for the same line_start [B, >= Lmax] i32 and line_jump_penalty.  A path
+    may visit a label any number of times, so visits, in_order, onset_prob and offset_prob are EXPECTED COUNTS that can exceed 1; nothing
+    is clamped (include/lyricalign.h).  in_order[a] counts the visits of a line's first label a that begin in print order (0 for every
+    other label); visits - in_order there is the expected number of arrivals out of print order.  The workspace holds every alpha row
+    and every target's jump term: B * T * 1.5 * (states per workgroup) * 8 bytes.
+    -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, visits [B,Lmax] f32, in_order [B,Lmax] f32,
+    path_prob [B,T] f32 (gamma at the given path; None without a path) [, gamma [B,T,2*Lmax+1] f32]."""
+    who = "alignment_posteriors_lines"
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, onset=onset, offset=offset, line_start=line_start)
+    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
+        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
+    if line_start.dim() != 2 or line_start.shape[0] != B or line_start.shape[1] < Lmax or line_start.stride(1) != 1:
+        raise ValueError(f"{who}: line_start [B, >= Lmax] with unit inner stride expected")
+    if path is not None:
+        _dev(path, "path", torch.int32)
+        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < T or path.stride(1) != 1:
+            raise ValueError(f"{who}: path [B, >= T] with unit inner stride expected")
+    if int(boundary_window) < 0:
+        raise ValueError(f"{who}: boundary_window must be >= 0")
+    line_jump_penalty = float(line_jump_penalty)
+    if not line_jump_penalty >= 0.0:
+        raise ValueError(f"{who}: line_jump_penalty must be >= 0")
+    if Lmax > LINES_MAX_LABELS:
+        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {LINES_MAX_LABELS} ({_LABEL_LIMIT_WHY[4095]})")
+    onset = onset.contiguous(); offset = offset.contiguous()
+    dev = em.device
+    occupancy, onset_prob, offset_prob, visits, in_order = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(5))
+    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
+    path_prob = torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None
+    ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
+    check(lib().la_alignment_posteriors_lines(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, int(boundary_window), ptr(line_start), line_start.stride(0), line_jump_penalty,
+        ptr(path), path.stride(0) if path is not None else 0, ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(visits),
+        ptr(in_order), ptr(path_prob), ptr(log_z), ptr(status), ptr(gamma), gamma.stride(0) if want_gamma else 0,
+        gamma.stride(1) if want_gamma else 0, ptr(ws), need, stream_ptr()), who)
+    res = (occupancy, onset_prob, offset_prob, log_z, status, visits, in_order, path_prob)
+    return res + (gamma,) if want_gamma else res
+
+
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:
     """logits [B,T,V] f32 device -> compact emissions [B,T,Lmax+1] f32."""
     _dev(logits, "logits", torch.float32); _dev(labels, "labels", torch.int32); _dev(n_labels, "n_labels", torch.int32)

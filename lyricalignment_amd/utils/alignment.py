@@ -710,6 +710,7 @@ class LatticeResult(NamedTuple):
     visits = None           # [B, Lmax] (= present_prob, an expected count), repeat_count [B, Lmax], path_prob [B, T]: the repeat sweeps'
     repeat_count = None
     path_prob = None
+    in_order = None         # [B, Lmax]: the line-order sweep's (ops.alignment_posteriors_lines), with `visits` and `path_prob`
 
 
 class RepeatLatticeResult(LatticeResult):
@@ -780,6 +781,7 @@ REPEAT_DP = "viterbi_repeats_batch"
 WIDE_DP = {"viterbi_spans_batch": "viterbi_lattice_batch", "viterbi_windows_batch": "viterbi_lattice_batch"}
 # and a third: a given line_start sends the DP to the lattice with free line order, which knows none of the table's faces
 LINES_DP = "viterbi_lines_batch"
+LINES_SWEEP, LINES_CONFIDENCE = "alignment_posteriors_lines", "lines"       # and, for confidence="lines", its sum-product sweep behind it
 # the sweeps of one lane per lattice state, and how run_lattice's refusal beyond POSTERIOR_MAX_LABELS ends for each
 NARROW_SWEEPS = {name: "the posterior sweeps (the alignment itself and the sheet confidence take up to 4095)"
                  for name in ("alignment_posteriors", "alignment_posteriors_spans", "alignment_posteriors_windows")}
@@ -838,13 +840,27 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     line_start (host rows of _line_start_of, or None) / line_jump_penalty: the lattice of an unmarked sheet, whose lines may be sung in any
     order (LINES_DP, ops.viterbi_lines_batch, up to 4095 labels); the result is a RepeatLatticeResult whose `path` holds the state per
     frame.  That lattice has the line breaks and nothing else: ValueError before anything is launched when line_start comes together
-    with skip_from, windows, repeat_from or any confidence."""
+    with skip_from, windows, repeat_from or any of the six confidences above.
+    "lines" (only with a line_start: ValueError without): the posteriors of that lattice -- LINES_DP, then ONE call of LINES_SWEEP
+    (ops.alignment_posteriors_lines) on the DP's onset / offset / path.  occupancy, onset_prob, offset_prob and log_z are filled,
+    present_prob holds `visits` (an expected count), and visits / in_order / path_prob are attributes of the result."""
+    if confidence == LINES_CONFIDENCE and line_start is None:
+        raise ValueError("run_lattice: confidence=\"lines\" is the posteriors of the lattice with free line order: it needs a line_start")
     if line_start is not None:
-        for name, given in (("skip_from", skip_from), ("windows", windows), ("repeat_from", repeat_from), ("confidence", confidence)):
+        for name, given in (("skip_from", skip_from), ("windows", windows), ("repeat_from", repeat_from),
+                            ("confidence", None if confidence == LINES_CONFIDENCE else confidence)):
             if given is not None:
                 raise ValueError(f"run_lattice: line_start does not go with {name} (the lattice with free line order has neither marked "
-                                 "spans nor windows nor posteriors)")
-        return _result(getattr(ops, LINES_DP)(em, lab, n_lab, nf, line_start.to(em.device), line_jump_penalty))
+                                 "spans nor windows, and its posteriors are confidence=\"lines\")")
+        rows = line_start.to(em.device)
+        dp = getattr(ops, LINES_DP)(em, lab, n_lab, nf, rows, line_jump_penalty)
+        r = _result(dp)
+        if confidence is None:
+            return r
+        post = getattr(ops, LINES_SWEEP)(em, lab, n_lab, nf, dp[0], dp[1], rows, line_jump_penalty, dp[4], boundary_window)
+        r = r._replace(occupancy=post[0], onset_prob=post[1], offset_prob=post[2], log_z=post[3], present_prob=post[5])
+        r.path, r.visits, r.in_order, r.path_prob = dp[4], post[5], post[6], post[7]
+        return r
     key = (confidence, skip_from is not None, windows is not None)
     if key not in ROUTES:
         raise ValueError(f"run_lattice: unknown confidence {confidence!r}")
@@ -910,6 +926,30 @@ def _formatted_repeat(r: RepeatLatticeResult, label_lists, frame_counts, hop_siz
     return seconds, segments, scores
 
 
+def _formatted_lines(r: RepeatLatticeResult, label_lists, frame_counts, hop_size_second, line_start):
+    """What the public functions return for a run_lattice(confidence="lines") result -> seconds, segments, scores.  scores[b] holds
+    "occupancy", "onset_prob", "offset_prob" [L] (about the reported, FIRST visit; 0 for a character never sung), "path_log_posterior",
+    "visits" [L] (the expected number of visits: it can exceed 1, and is constant along a line), "visit_occupancy" (one number per entry
+    of segments[b]: the mean posterior of the reported state over that visit's frames), "line_visits" [M] (visits at each line's first
+    character: the expected number of times the line is sung -- a count, not a probability) and "line_out_of_order" [M] (how many of
+    them are expected to begin out of print order: by a jump or a free start; visits - in_order there, taken in float64)."""
+    seconds = _seconds_from_frames(r.onset, r.offset, r.status, label_lists, hop_size_second, skipped_as_none=True)
+    scores = _scores_from_posteriors(r.occupancy, r.onset_prob, r.offset_prob, r.log_z, r.score, label_lists)
+    rows, pp = r.path.cpu().numpy(), r.path_prob.cpu().numpy()
+    vis, ino, flags = r.visits.cpu().numpy().astype(np.float64), r.in_order.cpu().numpy().astype(np.float64), line_start.cpu().numpy()
+    segments = []
+    for b, T in enumerate(frame_counts):
+        visits = _visits_of_row(rows[b, : int(T)])
+        segments.append([(n, float(t) * hop_size_second, float(u) * hop_size_second) for n, t, u in visits])
+        d, L = scores[b], len(label_lists[b])
+        starts = [n for n in range(L) if flags[b, n] != 0]
+        d["visits"] = [float(v) for v in vis[b, :L]]
+        d["visit_occupancy"] = [float(pp[b, t:u].astype(np.float64).mean()) for _, t, u in visits]
+        d["line_visits"] = [float(vis[b, a]) for a in starts]
+        d["line_out_of_order"] = [float(vis[b, a] - ino[b, a]) for a in starts]
+    return seconds, segments, scores
+
+
 def _device_of(prediction) -> torch.device:
     _lib.require_gpu()
     if torch.is_tensor(prediction) and prediction.is_cuda:
@@ -959,7 +999,11 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     {"position": n, "onset": s, "offset": s, "frames": k} of every slot visit (with pron also "top"); without slots empty lists.
     line_start (the caller's _line_start_of rows, or None: the call as it was) / line_jump_penalty: the lattice with free line order.  The
     caller has refused every keyword that does not go with it; the emissions are asked for, run_lattice takes the rows, and the result
-    (a RepeatLatticeResult: first visits, the path for return_segments) goes through everything behind it unchanged."""
+    (a RepeatLatticeResult: first visits, the path for return_segments) goes through everything behind it unchanged.  confidence="lines"
+    (only with a line_start: ValueError before the emissions are asked for) adds that lattice's sweep: -> (seconds, scores), or (seconds,
+    segments, scores) with return_segments, the dicts _formatted_lines'; readings and pronunciation follow as ever."""
+    if confidence == LINES_CONFIDENCE and line_start is None:
+        raise ValueError(f"{who}: the line confidence is the posteriors of the lattice with free line order: it needs line_starts")
     repeat_kind = confidence in ("repeat", "song")
     if line_start is not None:
         repeat_from = None
@@ -1017,6 +1061,9 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
         if off is not None:
             scores, segments = _scores_without_slots(off, scores, segments), _segments_without_slots(off, segments)
         out = (keep(seconds), segments, scores) if return_segments else (keep(seconds), scores)
+    elif confidence == LINES_CONFIDENCE:
+        seconds, segments, scores = _formatted_lines(r, label_lists, frame_counts, hop_size_second, line_start)
+        out = (seconds, segments, scores) if return_segments else (seconds, scores)
     else:
         out = _formatted(r, label_lists, hop_size_second, optional_spans)
         out = (keep(out[0]), _scores_without_slots(off, out[1]) if off is not None else out[1]) if isinstance(out, tuple) else keep(out)
@@ -1052,7 +1099,9 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     rd = pron = off = None
     # free line order: the rows and every refusal, before anything is on a device
     _line_starts_alone("perform_viterbi", line_starts, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
-                       char_windows=char_windows, off_sheet=off_sheet, confidence=confidence)
+                       char_windows=char_windows, off_sheet=off_sheet, confidence=None if confidence == LINES_CONFIDENCE else confidence)
+    if confidence == LINES_CONFIDENCE and line_starts is None:
+        raise ValueError("perform_viterbi_line_confidence: line_starts is required (the posteriors of the lattice with free line order)")
     line_start = _line_start_of("perform_viterbi", line_starts, _label_lists(labels, len(labels)))
     if line_start is not None and not float(line_jump_penalty) >= 0.0:
         raise ValueError("perform_viterbi: line_jump_penalty must be >= 0")
@@ -1329,6 +1378,38 @@ def perform_viterbi_ctc_song_scored(prediction, labels, hop_size_second=0.02, bo
                     optional_spans=optional_spans, skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors,
                     repeat_spans=repeat_spans, repeat_penalty=repeat_penalty, return_segments=return_segments, confidence="song", alternatives=alternatives, return_readings=return_readings,
                     off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
+
+
+def perform_viterbi_line_confidence(prediction, labels, line_starts, line_jump_penalty=0.0, boundary_window=2, hop_size_second=0.02,
+                                    n_frames=None, return_segments=False, alternatives=None, return_readings=False,
+                                    return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
+    """perform_viterbi with line_starts plus the confidence of that lattice (addition): -> (predicted_onset_offset, scores), or
+    (predicted_onset_offset, segments, scores) with return_segments.  The DP is la_viterbi_lines_batch, the sweep
+    la_alignment_posteriors_lines on the same emissions, up to 4095 labels; line_starts is required (ValueError for None), and
+    line_jump_penalty (default 0.0) has not been tuned on real singing.  A path may sing a line any number of times, so some numbers are
+    EXPECTED COUNTS, can exceed 1 and are not clamped.  scores[b] holds
+      "occupancy", "onset_prob", "offset_prob" [L]: about the reported (first) visit, 0 for a character never sung;
+      "path_log_posterior": final_score - log_z <= 0, the log-probability of the reported order and timing together;
+      "visits" [L]: the expected number of times the character is sung (constant along a line);
+      "visit_occupancy": one number per entry of segments[b], the mean posterior of the reported state over that visit's frames;
+      "line_visits" [M]: per line the expected number of times it is sung -- a count, not a probability;
+      "line_out_of_order" [M]: per line how many of those are expected to begin out of print order (by a jump or a free start).
+    With n_frames, alternatives / return_readings and return_pronunciation as perform_viterbi with line_starts.  The sweep's workspace
+    holds every alpha row and every line start's jump term: T * 1.5 * (states per workgroup) * 8 bytes per utterance."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, int(boundary_window), n_frames=n_frames, confidence=LINES_CONFIDENCE,
+                    return_segments=return_segments, alternatives=alternatives, return_readings=return_readings, line_starts=line_starts,
+                    line_jump_penalty=line_jump_penalty, return_pronunciation=return_pronunciation,
+                    pronunciation_classes=pronunciation_classes, pronunciation_top_k=pronunciation_top_k)
+
+
+def perform_viterbi_ctc_line_confidence(prediction, labels, line_starts, line_jump_penalty=0.0, boundary_window=2, hop_size_second=0.02,
+                                        n_frames=None, return_segments=False, alternatives=None, return_readings=False,
+                                        return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
+    """perform_viterbi_ctc plus the confidence of the lattice with free line order: see perform_viterbi_line_confidence."""
+    return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, int(boundary_window), n_frames=n_frames, confidence=LINES_CONFIDENCE,
+                    return_segments=return_segments, alternatives=alternatives, return_readings=return_readings, line_starts=line_starts,
+                    line_jump_penalty=line_jump_penalty, return_pronunciation=return_pronunciation,
+                    pronunciation_classes=pronunciation_classes, pronunciation_top_k=pronunciation_top_k)
 
 
 class _AnchoredAlignmentLoss(torch.autograd.Function):
