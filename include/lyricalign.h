@@ -374,6 +374,48 @@ int la_viterbi_lines_batch(const float *em, int64_t em_batch_stride, int64_t em_
                            void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Minimum character duration: the DP on the PLAIN lattice with a floor, in frames, under every visit to a label (a sung syllable is never
+ * one 20 ms frame long; la_viterbi_batch lets it be).  la_viterbi_lines_batch's arguments with
+ *   min_frames [batch][min_frames_stride] (min_frames_stride >= max_labels; entries 0 .. L_b - 1 of row b are read): D_n, the least
+ *       number of frames label n lasts, 1 .. max_min_frames.  A clip with an entry outside that range gets LA_EINVAL, its batch mates
+ *       are unaffected.
+ *   max_min_frames (1 .. 8, i.e. up to 160 ms at the model's hop): the bound on the floors of this call; it picks the depth of the
+ *       kernel's chain (2, 4 or 8) and nothing else.
+ * in the place of line_start, line_stride, line_jump_penalty.  Label n carries D_n - 1 "young" values y_1 .. y_{D-1} (in its j-th frame)
+ * and one "mature" value m (has lasted at least D_n frames); only m is visible to the label's successors.
+ *   Row 0: dp[0][0] = em[0][0]; label 0 has m = em[0][1] if D_0 == 1, else y_1 = em[0][1] and m = -1e7; every other value is -1e7.
+ *   Row t reads row t-1 only (out_n = m_n[t-1], sil_i = state 2i, can_skip = n >= 1 && labels[n] != labels[n-1]): state 0 stays; the
+ *   silence 2n+2 stays iff sil_{n+1}[t-1] > out_n (strict), else it comes from out_n; a label with D_n == 1 follows la_viterbi_batch's
+ *   rule on (m_n[t-1], sil_n[t-1], out_{n-1}); a label with D_n >= 2 is ENTERED from out_{n-1} if can_skip and out_{n-1} >= sil_n[t-1],
+ *   else from sil_n[t-1] (no stay candidate): y_1[t] = entry + em, y_j[t] = y_{j-1}[t-1] + em, and m[t] = (m[t-1] > y_{D-1}[t-1] ?
+ *   m[t-1] : y_{D-1}[t-1]) + em.  The emission is added last; everything is float64.
+ *   Termination: the backtrace starts at 2L iff sil_L[T-1] > m_{L-1}[T-1] (strict), else at the last label's mature value -- the last
+ *   visit reaches its floor too; final_score is that value.  A mature cell that graduated at frame t puts its label on frames
+ *   t-D_n+1 .. t and the backtrace goes on from that first frame's entry.
+ * status: LA_OK iff the backtrace arrives at frame 0 in state 0 or in the first frame of label 0; otherwise LA_EINFEASIBLE (the clip is
+ * shorter than its floors ask for), every onset / offset / path entry of the clip is -1 and final_score is still written.  LA_EEMPTY /
+ * LA_EINVAL as in la_viterbi_batch.  With every floor 1 onset, offset, final_score and status are la_viterbi_batch's bit for bit (on an
+ * infeasible clip status and score; the plain entry leaves partial rows there).  onset / offset / path as la_viterbi_lines_batch; every
+ * reported label has offset - onset >= D_n.  Up to 4095 labels (LA_EUNSUPPORTED above).  The workspace (always needed, 8-byte aligned)
+ * holds three 64-bit backpointer masks per (frame, 64 states).  Argument errors -- null pointers, strides below max_labels,
+ * max_min_frames outside 1 .. 8, a workspace too small or misaligned -- are answered on the host before anything is enqueued; batch == 0
+ * is LA_OK; never synchronises, allocates or frees.  Reproducible to the bit, alone or in a batch.  No posteriors and no training loss
+ * exist on this lattice, and the span, window, repeat and line-order lattices have no floor (csrc/la_min_duration.hip, DESIGN.md
+ * "Minimum duration").  No floor has been tuned on real singing.
+ */
+int la_viterbi_min_duration_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, int32_t max_min_frames, size_t *bytes);
+
+int la_viterbi_min_duration_batch(const float *em, int64_t em_batch_stride, int64_t em_row_stride,
+                                  const int32_t *labels, int32_t labels_stride,
+                                  const int32_t *n_labels, const int32_t *n_frames,
+                                  int32_t batch, int32_t max_frames, int32_t max_labels,
+                                  int32_t *onset, int32_t *offset, int32_t out_stride,
+                                  double *final_score, int32_t *status,
+                                  const int32_t *min_frames, int32_t min_frames_stride, int32_t max_min_frames,
+                                  int32_t *path, int32_t path_stride,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-character alignment confidence: forward-backward (sum-product) on the SAME lattice (no counterpart in the
  * reference, whose utils/alignment.py is max-product only).  Start states 0 and 1, end states S-1 and S-2, transitions
  * into k from k, k-1 and (odd k >= 3, differing neighbour labels) k-2; a path weighs exp(sum_t e_t(path_t)); unreachable

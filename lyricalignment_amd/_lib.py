@@ -74,6 +74,10 @@ SYMBOLS = {
     "la_viterbi_lines_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_viterbi_lines_batch": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, c_double,
                                          _P, _I32, _P, _SZ, _P]),
+    # minimum duration: the plain entry's arguments, then min_frames, min_frames_stride, max_min_frames, path, path_stride
+    "la_viterbi_min_duration_workspace_bytes": (c_int32, [_I32, _I32, _I32, _I32, POINTER(_SZ)]),
+    "la_viterbi_min_duration_batch": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32,
+                                                _P, _I32, _P, _SZ, _P]),
     "la_alignment_posteriors_workspace_bytes": (c_int32, [_I32, _I32, _I32, POINTER(_SZ)]),
     "la_alignment_posteriors": (c_int32, [_P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
                                           _P, _I64, _I64, _P, _SZ, _P]),

@@ -148,14 +148,15 @@ def evaluate_batches(model, batches: Sequence[Any], lut: Optional[PinyinClassLUT
     return avg, maes
 
 
-def _align_records_batched(model, records: List[Any], lut, tokenize, use_ctc_loss: bool, with_confidence: bool, batch_size: int) -> List[list]:
+def _align_records_batched(model, records: List[Any], lut, tokenize, use_ctc_loss: bool, with_confidence: bool, batch_size: int,
+                           min_duration=None) -> List[list]:
     """align_records with records of at most 30 s sorted by length and aligned `batch_size` at a time (per_clip=True: each as if alone);
     results in the caller's order.  Longer records go one at a time through the dense long-form call."""
     out: List[Optional[list]] = [None] * len(records)
     short = sorted((i for i, r in enumerate(records) if len(r.audio) <= PER_CLIP_MAX_SAMPLES), key=lambda i: len(records[i].audio))
     for i, rec in enumerate(records):
         if len(rec.audio) > PER_CLIP_MAX_SAMPLES:
-            out[i] = align_records(model, [rec], lut, tokenize, use_ctc_loss, with_confidence)[0]
+            out[i] = align_records(model, [rec], lut, tokenize, use_ctc_loss, with_confidence, min_duration=min_duration)[0]
     for k in range(0, len(short), batch_size):
         idx = short[k: k + batch_size]
         labels = [[int(v) for v in lut(torch.tensor([tokenize(records[i].text)], dtype=torch.long))[0].tolist()] for i in idx]
@@ -163,7 +164,7 @@ def _align_records_batched(model, records: List[Any], lut, tokenize, use_ctc_los
         if with_confidence:
             res, scores = model.align(audios, labels, use_ctc=use_ctc_loss, return_confidence=True, per_clip=True)
         else:
-            res, scores = model.align(audios, labels, use_ctc=use_ctc_loss, per_clip=True), None
+            res, scores = model.align(audios, labels, use_ctc=use_ctc_loss, per_clip=True, **_floor_kw(min_duration)), None
         for j, i in enumerate(idx):
             text = records[i].text
             if with_confidence:
@@ -173,19 +174,29 @@ def _align_records_batched(model, records: List[Any], lut, tokenize, use_ctc_los
     return out
 
 
+def _floor_kw(min_duration) -> dict:
+    """AlignModel.align's min_duration keyword where a floor is given; nothing otherwise (the call as it was)."""
+    return {} if min_duration is None else {"min_duration": min_duration}
+
+
 def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, use_ctc_loss: bool = True,
-                  with_confidence: bool = False, batch_size: int = 1) -> List[list]:
+                  with_confidence: bool = False, batch_size: int = 1, min_duration=None) -> List[list]:
     """inference_alignment_nogt.py:130-178: one record at a time, returns [[onset, offset, char], ...] per record.
     `tokenize(text) -> list[int]` are the BERT ids without [CLS]/[SEP] (the reference slices [1:-1], :158-163).
     with_confidence (addition): each entry is [onset, offset, char, occupancy] (AlignModel.align(return_confidence=True)).
     batch_size (addition; default 1 = one record per device call, as the reference): records of at most 30 s are sorted by length and
     aligned batch_size at a time with AlignModel.align(per_clip=True) -- every record's result is the one it gets alone -- and returned
-    in the caller's order; longer records go one at a time."""
+    in the caller's order; longer records go one at a time.
+    min_duration (addition; None: the call as it was): one number of seconds, the least duration of every character
+    (AlignModel.align(min_duration=...), at most 8 frames; it has not been tuned on real singing).  Not with with_confidence
+    (ValueError: that lattice has no posteriors yet)."""
     if int(batch_size) < 1:
         raise ValueError("align_records: batch_size must be >= 1")
+    if min_duration is not None and with_confidence:
+        raise ValueError("align_records: min_duration does not go with with_confidence (no posteriors on the lattice with a minimum duration)")
     if int(batch_size) > 1:
         with torch.no_grad():
-            return _align_records_batched(model, list(records), lut, tokenize, use_ctc_loss, with_confidence, int(batch_size))
+            return _align_records_batched(model, list(records), lut, tokenize, use_ctc_loss, with_confidence, int(batch_size), min_duration)
     out = []
     with torch.no_grad():
         for rec in records:
@@ -195,7 +206,7 @@ def align_records(model, records: Iterable[Any], lut: PinyinClassLUT, tokenize, 
                 res, occ = res[0], scores[0]["occupancy"]
                 out.append([[res[j][0], res[j][1], rec.text[j], occ[j]] for j in range(len(res))])
                 continue
-            res = model.align([rec.audio], lut(ids), use_ctc=use_ctc_loss)[0]
+            res = model.align([rec.audio], lut(ids), use_ctc=use_ctc_loss, **_floor_kw(min_duration))[0]
             out.append([[res[j][0], res[j][1], rec.text[j]] for j in range(len(res))])
     return out
 
@@ -407,7 +418,7 @@ def _visit_confidence(segments, scores, lines: Sequence[str], ids, repeatable, r
 def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bool], lut: PinyinClassLUT, tokenize,
                        use_ctc_loss: bool = True, skip_penalty: float = 0.0, with_confidence: bool = False, repeatable=None,
                        repeat_penalty: float = 0.0, with_visit_confidence: bool = False, heteronyms=None, with_pronunciation: bool = False,
-                       top_k: int = 5, off_sheet=False, off_sheet_penalty: float = math.log(100)):
+                       top_k: int = 5, off_sheet=False, off_sheet_penalty: float = math.log(100), min_duration=None):
     """One recording against a lyric sheet given line by line (addition; the reference aligns exactly what is sung): lines with
     optional[i] may be absent from the audio (a chorus printed once more than sung, a bracketed ad-lib).  `tokenize(line)` as in
     align_records, one class per character.  -> one entry per line: None if the alignment left the line out, otherwise
@@ -439,8 +450,17 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
     (with with_pronunciation each also holds [(syllable heard, score per frame), ...]); with a confidence option one more element,
     {before_line: off_sheet_prob}, the probability that the slot was used at all.  off_sheet_penalty (nats per frame, default ln 100: a
     character must hold less than 1 % of the voiced probability to lose a frame to a slot) has not been tuned on real singing; keep it
-    above skip_penalty."""
+    above skip_penalty.
+    min_duration (None: the outputs as above): one number of seconds, the least duration of every character
+    (AlignModel.align(min_duration=...), at most 8 frames; not tuned on real singing).  The floor exists on the plain lattice alone:
+    ValueError together with an optional line, with_confidence, repeatable, with_visit_confidence or off_sheet; with heteronyms and
+    with_pronunciation."""
     lines = list(lines)
+    if min_duration is not None:
+        for name, given in (("optional", any(bool(v) for v in optional)), ("with_confidence", with_confidence), ("repeatable", repeatable is not None),
+                            ("with_visit_confidence", with_visit_confidence), ("off_sheet", off_sheet is not False and off_sheet is not None)):
+            if given:
+                raise ValueError(f"align_record_lines: min_duration does not go with {name} (the floor exists on the plain lattice alone)")
     ids, spans, labels = _sheet_inputs("align_record_lines", lines, optional, lut, tokenize)
     rk = _reading_kw(lut, ids, heteronyms, with_pronunciation, top_k, off_sheet, off_sheet_penalty, "align_record_lines")
     if with_visit_confidence and repeatable is None:
@@ -460,7 +480,8 @@ def align_record_lines(model, audio, lines: Sequence[str], optional: Sequence[bo
                                                    skip_penalty=skip_penalty, return_span_confidence=True)
             present = scores[0]["sung_prob"]
             return _done(_sheet_lines_out(res[0], lines, (lambda pos, first: float(present[pos]),), readings), rk, lines, lut)
-        res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty)
+        res, readings = _align_sheet(model, rk, audio, labels, use_ctc=use_ctc_loss, optional_spans=[spans], skip_penalty=skip_penalty,
+                                     **_floor_kw(min_duration))
     return _done(_sheet_lines_out(res[0], lines, (), readings)[0], rk, lines, lut)
 
 

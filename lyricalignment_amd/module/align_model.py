@@ -341,7 +341,7 @@ class AlignModel(torch.nn.Module):
               return_anchored_confidence: bool = False, return_sheet_confidence: bool = False, repeat_spans=None,
               repeat_penalty: float = 0.0, return_segments: bool = False, return_repeat_confidence: bool = False,
               return_song_confidence: bool = False, alternatives=None, return_readings: bool = False,
-              line_starts=None, line_jump_penalty: float = 0.0,
+              min_duration=None, line_starts=None, line_jump_penalty: float = 0.0,
               off_sheet=None, off_sheet_penalty: float = math.log(100), return_off_sheet: bool = False,
               return_line_confidence: bool = False,
               return_pronunciation: bool = False, pronunciation_classes=None, pronunciation_top_k: int = 5):
@@ -477,7 +477,18 @@ class AlignModel(torch.nn.Module):
         unused slot is charged skip_penalty like every skipped span, so keep off_sheet_penalty above skip_penalty.  ValueError for a
         wrong list count, a bad or repeated n, a slot on a clip without labels, a negative / NaN penalty, and together with
         return_confidence (slots are spans: return_span_confidence is the keyword) or return_frames; NotImplementedError when L_b plus
-        its slots exceed 4095 (511 for the confidence keywords that stop there).  None or all-empty: the call as it was."""
+        its slots exceed 4095 (511 for the confidence keywords that stop there).  None or all-empty: the call as it was.
+        min_duration (addition): a floor under every character's duration -- a sung syllable is never one 20 ms frame long, and the plain
+        lattice lets it be: a character that is clear at its onset and whose tail sounds like the vowel before it gets a single frame.
+        One number of seconds for every character, or per clip a row of per-character seconds (a None row: no floor in that clip); a
+        floor is ceil(seconds / hop_size_second - 1e-9) frames, at least 1 and at most 8 (160 ms).  The head's emissions go through the
+        DP on the plain lattice with a minimum duration (ops.viterbi_min_duration_batch): every reported character lasts at least its
+        floor, the last one included, and a clip too short for its floors raises like one too short for its labels.  With per_clip, the
+        long form, alternatives / return_readings (floors belong to positions), return_pronunciation and return_segments, up to 4095
+        labels; with return_frames the DP's four tensors and path [B, T].  ValueError, before a device is asked for, for a negative or
+        non-finite value, a wrong row count or length or a floor above 8 frames, and together with optional_spans, repeat_spans,
+        onset_anchors, char_windows, line_starts, off_sheet or any confidence keyword (this lattice has no posteriors yet).  None, or
+        every floor at most one frame: the call as it was, launch for launch.  No floor HAS BEEN TUNED on real singing: no default."""
         from ..utils import alignment as ua
         if return_readings and alternatives is None:
             raise ValueError("align: return_readings goes with alternatives (without them every character has the one reading of its label)")
@@ -496,6 +507,13 @@ class AlignModel(torch.nn.Module):
             widest = max((len(l) for l in ua._label_lists(labels, len(labels))), default=0)
             if widest > ua.POSTERIOR_MAX_LABELS:
                 raise NotImplementedError(f"align: {widest} labels exceed the {ua.POSTERIOR_MAX_LABELS}-label limit of return_repeat_confidence")
+        # minimum duration: every refusal and the rows, before the engine exists
+        ua._min_duration_alone("align", min_duration, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
+                               char_windows=char_windows, line_starts=line_starts, off_sheet=off_sheet, return_confidence=return_confidence,
+                               return_span_confidence=return_span_confidence, return_anchored_confidence=return_anchored_confidence,
+                               return_sheet_confidence=return_sheet_confidence, return_repeat_confidence=return_repeat_confidence,
+                               return_song_confidence=return_song_confidence, return_line_confidence=return_line_confidence)
+        min_frames = ua._min_frames_of("align", min_duration, ua._label_lists(labels, len(labels)), hop_size_second)
         # free line order: the rows and every refusal, before the engine exists
         ua._line_starts_alone("align", line_starts, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
                               char_windows=char_windows, off_sheet=off_sheet, return_confidence=return_confidence,
@@ -562,7 +580,7 @@ class AlignModel(torch.nn.Module):
         out = ua.align_labels("align", head, lab_dev, n_lab, lab_lists, frame_counts, T, kw.get("n_frames"), hop_size_second, confidence,
                               boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
                               alternatives, return_readings, rd, raw=return_frames, pron=pron, off=off, return_off_sheet=return_off_sheet,
-                              line_start=line_start, line_jump_penalty=float(line_jump_penalty))
+                              line_start=line_start, line_jump_penalty=float(line_jump_penalty), min_frames=min_frames)
         if return_frames:                    # 4, 8 (return_confidence), 10 (return_span_confidence) or 11 tensors; 5 with repeat_spans (path);
             r, picked = out
             # reading, col_score behind them, the five tensors of the pronunciation scores last

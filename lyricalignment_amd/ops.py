@@ -264,6 +264,43 @@ def viterbi_lines_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.
     return onset, offset, score, status, path
 
 
+MIN_DURATION_MAX_FRAMES = 8
+
+
+def viterbi_min_duration_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor, min_frames: torch.Tensor,
+                               max_min_frames: Optional[int] = None, want_path: bool = True):
+    """la_viterbi_min_duration_batch: viterbi_batch on the plain lattice with a floor under every character's duration, for up to 4095
+    labels.  min_frames [B, >= Lmax] i32 (device): label n of clip b lasts at least min_frames[b, n] frames, 1 .. max_min_frames; a clip
+    with an entry outside that range gets LA_EINVAL.  max_min_frames (1 .. 8; None: 8, nothing is read back from the device) is the bound
+    on the floors of this call and picks the kernel's chain depth.  With every floor 1 the first four outputs are viterbi_batch's bit for
+    bit.  No floor has been tuned on real singing.
+    -> onset, offset (offset - onset >= the floor for every reported label), final_score, status, path [B,T] i32 (None without
+    want_path; the lattice state at every frame t < T_b, -1 for t >= T_b and for a clip whose status is not LA_OK).  A clip too short for
+    its floors has status LA_EINFEASIBLE and every onset / offset -1."""
+    who = "viterbi_min_duration_batch"
+    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, min_frames=min_frames)
+    if min_frames.dim() != 2 or min_frames.shape[0] != B or min_frames.shape[1] < Lmax or min_frames.stride(1) != 1:
+        raise ValueError(f"{who}: min_frames [B, >= Lmax] with unit inner stride expected")
+    max_min_frames = MIN_DURATION_MAX_FRAMES if max_min_frames is None else int(max_min_frames)
+    if not 1 <= max_min_frames <= MIN_DURATION_MAX_FRAMES:
+        raise ValueError(f"{who}: max_min_frames must be 1 .. {MIN_DURATION_MAX_FRAMES}")
+    if Lmax > LINES_MAX_LABELS:
+        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {LINES_MAX_LABELS} ({_LABEL_LIMIT_WHY[4095]})")
+    dev = em.device
+    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
+    score = torch.empty((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev) if want_path else None
+    need = ctypes.c_size_t(0)
+    check(lib().la_viterbi_min_duration_workspace_bytes(B, T, Lmax, max_min_frames, ctypes.byref(need)), "viterbi_min_duration_workspace_bytes")
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
+    check(lib().la_viterbi_min_duration_batch(
+        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
+        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), ptr(min_frames), min_frames.stride(0), max_min_frames,
+        ptr(path), T if want_path else 0, ptr(ws), need.value, stream_ptr()), who)
+    return onset, offset, score, status, path
+
+
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
                          onset: torch.Tensor, offset: torch.Tensor, boundary_window: int = 2, want_gamma: bool = False):
     """la_alignment_posteriors: forward-backward on the DP's lattice.  em / labels / n_labels / n_frames as viterbi_batch,

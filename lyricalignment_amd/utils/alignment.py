@@ -176,6 +176,60 @@ def _line_starts_alone(who: str, line_starts, **others) -> None:
                              "else: no marked spans, no anchors, no off-sheet slots, no posteriors)")
 
 
+MIN_DURATION_MAX_FRAMES = ops.MIN_DURATION_MAX_FRAMES     # 8: the deepest floor of the lattice with a minimum duration (ops.viterbi_min_duration_batch): 160 ms
+
+
+def _min_frames_of(who: str, min_duration, label_lists: List[List[int]], hop_size_second: float):
+    """min_duration = one number of seconds for every character, or per utterance a row of per-character seconds (a None row: no floor
+    in that utterance) -> host int32 tensor [B, Lmax] of floors in frames, ceil(seconds / hop - 1e-9) and at least 1 (past L_b: 1), or
+    None for min_duration None and where every floor is at most one frame: the call as it was.  ValueError for a negative or non-finite
+    value, a wrong row count or length, or a floor above MIN_DURATION_MAX_FRAMES frames.  Nothing here asks for a device."""
+    if min_duration is None:
+        return None
+    hop = float(hop_size_second)
+
+    def frames(b, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) or float(v) < 0.0:
+            raise ValueError(f"{who}: min_duration{b}: a finite number of seconds >= 0 expected, not {v!r}")
+        k = max(1, int(math.ceil(float(v) / hop - 1e-9)))
+        if k > MIN_DURATION_MAX_FRAMES:
+            raise ValueError(f"{who}: min_duration{b}: {float(v)} s are {k} frames of {hop} s; the floor is at most {MIN_DURATION_MAX_FRAMES} "
+                             "frames")
+        return k
+
+    rows = torch.ones((len(label_lists), max(1, max((len(l) for l in label_lists), default=1))), dtype=torch.int32)
+    if isinstance(min_duration, (list, tuple)) or (isinstance(min_duration, np.ndarray) and min_duration.ndim > 0) or torch.is_tensor(min_duration):
+        if len(min_duration) != len(label_lists):
+            raise ValueError(f"{who}: min_duration: {len(label_lists)} rows expected, one per utterance (or one number of seconds)")
+        for b, row in enumerate(min_duration):
+            if row is None:
+                continue
+            row = row.tolist() if hasattr(row, "tolist") else row
+            if not isinstance(row, (list, tuple)) or len(row) != len(label_lists[b]):
+                raise ValueError(f"{who}: min_duration[{b}]: {len(label_lists[b])} values expected, one per character")
+            if row:
+                rows[b, : len(row)] = torch.tensor([frames(f"[{b}]", v) for v in row], dtype=torch.int32)
+    else:
+        k = frames("", min_duration.item() if hasattr(min_duration, "item") else min_duration)
+        for b, l in enumerate(label_lists):
+            rows[b, : len(l)] = k
+    return rows if int(rows.max()) > 1 else None
+
+
+def _min_duration_alone(who: str, min_duration, **others) -> None:
+    """The keywords that do not go with min_duration (others: name -> value as the caller got it; None, False and all-empty lists count as
+    not given): ValueError naming both."""
+    if min_duration is None:
+        return
+    for name, value in others.items():
+        given = value is not None and value is not False
+        if given and isinstance(value, (list, tuple)):
+            given = any(bool(row) for row in value)
+        if given:
+            raise ValueError(f"{who}: min_duration does not go with {name} (the floor exists on the plain lattice alone: no spans, no "
+                             "anchors, no line order, no off-sheet slots, no posteriors)")
+
+
 MAX_READINGS = 8                # readings per label position, the sheet's own class included
 MAX_READING_COLUMNS = 4095      # expanded columns per clip: what the head, the prep and the fold take
 READING_SET_ID = 1 << 24        # lattice id of a clip's k-th distinct multi-reading set: READING_SET_ID + k (class ids lie far below)
@@ -892,6 +946,26 @@ def run_lattice(em, lab, n_lab, nf, skip_from=None, windows=None, skip_penalty=0
     return _result(dp, post, None if confidence == "span" else log_z_free)
 
 
+# A fourth rule beside REPEAT_DP, WIDE_DP and LINES_DP: given floors send the DP to the plain lattice with a minimum duration.  It has
+# a function of its own beside run_lattice, whose parameter list is pinned: that lattice knows none of run_lattice's other arguments.
+MIN_DURATION_DP = "viterbi_min_duration_batch"
+
+
+def run_min_duration_lattice(em, lab, n_lab, nf, min_frames, skip_from=None, windows=None, confidence=None, repeat_from=None,
+                             line_start=None) -> RepeatLatticeResult:
+    """run_lattice's counterpart for the plain lattice with a floor under every character's duration: min_frames (host rows of
+    _min_frames_of, never None here) -> MIN_DURATION_DP (ops.viterbi_min_duration_batch, up to 4095 labels) with the smallest chain depth
+    that holds the rows' largest floor; the result is a RepeatLatticeResult whose `path` holds the state per frame.  The floor exists on
+    the plain lattice alone and has no posteriors yet: ValueError before anything is launched when min_frames comes together with
+    skip_from, windows, repeat_from, line_start or any confidence."""
+    for name, given in (("skip_from", skip_from), ("windows", windows), ("repeat_from", repeat_from), ("line_start", line_start),
+                        ("confidence", confidence)):
+        if given is not None:
+            raise ValueError(f"run_min_duration_lattice: min_frames does not go with {name} (the floor exists on the plain lattice alone, "
+                             "and that lattice has no posteriors)")
+    return _result(getattr(ops, MIN_DURATION_DP)(em, lab, n_lab, nf, min_frames.to(em.device), int(min_frames.max())))
+
+
 def _formatted(r: LatticeResult, label_lists, hop_size_second, optional_spans):
     """What the public functions return for r: seconds, or (seconds, scores) when r holds posteriors.  The dicts of the span lattice
     (present_prob computed) name every span of optional_spans, or none where the caller gave no span.  A label with onset -1 under LA_OK
@@ -972,7 +1046,7 @@ def _repeat_rows(who: str, repeat_spans, return_segments: bool, label_lists, sco
 def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, n_frames_max: int, nf, hop_size_second, confidence,
                  boundary_window, skip_from, windows, skip_penalty, optional_spans, repeat_spans, repeat_penalty, return_segments,
                  alternatives, return_readings, rd: Optional[Readings] = None, raw: bool = False, line_start=None, line_jump_penalty=0.0,
-                 off: Optional[OffSheet] = None, return_off_sheet: bool = False, pron: Optional[Pronunciation] = None):
+                 off: Optional[OffSheet] = None, return_off_sheet: bool = False, min_frames=None, pron: Optional[Pronunciation] = None):
     """What perform_viterbi* and AlignModel.align (`who`: "perform_viterbi" / "align") do once the labels (lab / n_lab on the device,
     label_lists), the spans and windows (host rows, or None) and the kind of confidence are known: the repeat_from rows
     (_repeat_from_of_spans for "repeat" / "song", whose label limit is refused here; _repeat_rows otherwise), the readings (rd: the
@@ -1001,11 +1075,20 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
     caller has refused every keyword that does not go with it; the emissions are asked for, run_lattice takes the rows, and the result
     (a RepeatLatticeResult: first visits, the path for return_segments) goes through everything behind it unchanged.  confidence="lines"
     (only with a line_start: ValueError before the emissions are asked for) adds that lattice's sweep: -> (seconds, scores), or (seconds,
-    segments, scores) with return_segments, the dicts _formatted_lines'; readings and pronunciation follow as ever."""
+    segments, scores) with return_segments, the dicts _formatted_lines'; readings and pronunciation follow as ever.
+    min_frames (the caller's _min_frames_of rows, or None: the call as it was): a floor, in frames, under every character's duration.  The
+    caller has refused every keyword that does not go with it (ValueError here too, before the emissions are asked for); the emissions
+    are asked for with needed=True, the provider's own plain DP result is dropped as the off-sheet route drops it, and
+    run_min_duration_lattice takes the rows -- with alternatives the floors belong to the positions and the lattice reads the set ids.
+    Its result (a RepeatLatticeResult: the path for return_segments) goes through everything behind it unchanged."""
+    if min_frames is not None and (confidence is not None or skip_from is not None or windows is not None or line_start is not None
+                                   or off is not None or _repeat_from_of_spans(repeat_spans, label_lists) is not None):
+        raise ValueError(f"{who}: min_duration goes with the plain lattice alone (no spans, anchors, line order, off-sheet slots or "
+                         "confidence)")
     if confidence == LINES_CONFIDENCE and line_start is None:
         raise ValueError(f"{who}: the line confidence is the posteriors of the lattice with free line order: it needs line_starts")
     repeat_kind = confidence in ("repeat", "song")
-    if line_start is not None:
+    if line_start is not None or min_frames is not None:
         repeat_from = None
     elif repeat_kind:
         repeat_from = _repeat_from_of_spans(repeat_spans, label_lists)
@@ -1031,8 +1114,8 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
             return None, em_w[:, :, : 1 + lab_x.shape[1]]
     if rd is None:
         dp, em = emissions_of(lab, n_lab, confidence is not None or skip_from is not None or windows is not None or repeat_from is not None
-                              or off is not None or line_start is not None)
-        if off is not None:                  # the provider's own DP ran without the slots' columns
+                              or off is not None or line_start is not None or min_frames is not None)
+        if off is not None or min_frames is not None:   # the provider's own DP ran without the slots' columns, or without the floors
             dp = None
     if rd is None and em is None:
         r = _result(dp)
@@ -1046,8 +1129,11 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
             ops.offsheet_columns(em, off.slot_cols.to(lab.device), off.n_slots.to(lab.device), nf, off.penalty)
             if route is None:
                 lab = off.lattice_ids.to(lab.device)
-        r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from, repeat_penalty,
-                        line_start, line_jump_penalty)
+        if min_frames is not None:
+            r = run_min_duration_lattice(em, lab, n_lab, nf, min_frames)
+        else:
+            r = run_lattice(em, lab, n_lab, nf, skip_from, windows, skip_penalty, confidence, boundary_window, dp, repeat_from,
+                            repeat_penalty, line_start, line_jump_penalty)
     picked = route.scores(n_lab, r.onset, r.offset) if return_readings or (pron is not None and route is not None) else ()
     if pron is not None:
         own_col = _own_columns(pron, route, picked[0] if route is not None else None, lab.device)
@@ -1089,7 +1175,7 @@ def align_labels(who: str, emissions_of, lab, n_lab, label_lists, frame_counts, 
 
 def _perform(prediction, labels, hop_size_second, variant, boundary_window=None, n_frames=None, optional_spans=None, skip_penalty=0.0,
              char_windows=None, onset_anchors=None, confidence=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False,
-             alternatives=None, return_readings=False, line_starts=None, line_jump_penalty=0.0, off_sheet=None,
+             alternatives=None, return_readings=False, min_duration=None, line_starts=None, line_jump_penalty=0.0, off_sheet=None,
              off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
              return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """confidence: the kind the public function stands for (run_lattice's); "plain" becomes "span" where a span is given (an off-sheet
@@ -1097,6 +1183,10 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     if return_readings and alternatives is None:
         raise ValueError("return_readings goes with alternatives (without them every character has the one reading of its label)")
     rd = pron = off = None
+    # minimum duration: every refusal and the rows, before anything is on a device
+    _min_duration_alone("perform_viterbi", min_duration, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
+                        char_windows=char_windows, line_starts=line_starts, off_sheet=off_sheet, confidence=confidence)
+    min_frames = _min_frames_of("perform_viterbi", min_duration, _label_lists(labels, len(labels)), hop_size_second)
     # free line order: the rows and every refusal, before anything is on a device
     _line_starts_alone("perform_viterbi", line_starts, optional_spans=optional_spans, repeat_spans=repeat_spans, onset_anchors=onset_anchors,
                        char_windows=char_windows, off_sheet=off_sheet, confidence=None if confidence == LINES_CONFIDENCE else confidence)
@@ -1141,12 +1231,13 @@ def _perform(prediction, labels, hop_size_second, variant, boundary_window=None,
     return align_labels("perform_viterbi", lambda lab_x, n_x, needed=True: (None, ops.emissions_from_logits(pred, lab_x, n_x, variant)), lab,
                         n_lab, lists, counts, T, nf, hop_size_second, confidence, boundary_window, skip_from, windows, skip_penalty,
                         optional_spans, repeat_spans, repeat_penalty, return_segments, alternatives, return_readings, rd, pron=pron,
-                        off=off, return_off_sheet=return_off_sheet, line_start=line_start, line_jump_penalty=float(line_jump_penalty))
+                        off=off, return_off_sheet=return_off_sheet, line_start=line_start, line_jump_penalty=float(line_jump_penalty),
+                        min_frames=min_frames)
 
 
 def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
                     char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
-                    line_starts=None, line_jump_penalty=0.0,
+                    min_duration=None, line_starts=None, line_jump_penalty=0.0,
                     off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
                     return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     """n_frames (addition; the reference has none): per-utterance frame counts for a zero-padded [B, Tmax, V] prediction -- utterance b is
@@ -1211,11 +1302,21 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
     the last: the last character cannot end on the last frame); and an unused slot is charged skip_penalty like every skipped span, so
     keep off_sheet_penalty above skip_penalty.  ValueError for a wrong list count, a bad or repeated n, a slot on an utterance without
     labels or a negative / NaN penalty; NotImplementedError when L_b plus its slots exceed 4095 (511 for the confidences that stop
-    there).  None or all-empty: the call as it was."""
+    there).  None or all-empty: the call as it was.
+    min_duration (addition; here and in perform_viterbi_ctc): a floor under every character's duration -- a sung syllable is never one
+    20 ms frame long, and the plain lattice lets it be.  One number of seconds for every character, or per utterance a row of
+    per-character seconds (a None row: no floor there); a floor is ceil(seconds / hop_size_second - 1e-9) frames, at least 1 and at
+    most 8 (160 ms at the model's hop).  The DP is la_viterbi_min_duration_batch on the plain lattice: every reported character lasts
+    at least its floor, the last one included, and an utterance too short for its floors raises like one too short for its labels.
+    With n_frames, alternatives / return_readings (floors belong to positions), return_pronunciation and return_segments, up to 4095
+    labels.  ValueError for a negative or non-finite value, a wrong row count or length or a floor above 8 frames, and together with
+    optional_spans, repeat_spans, onset_anchors, char_windows, line_starts or off_sheet; the _scored functions and the training
+    entries do not have the keyword (no posteriors exist on this lattice yet).  None, or every floor at most one frame: the call as
+    it was, launch for launch.  No floor HAS BEEN TUNED on real singing, so there is no default."""
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_PLAIN, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
                     repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
-                    line_starts=line_starts, line_jump_penalty=line_jump_penalty,
+                    min_duration=min_duration, line_starts=line_starts, line_jump_penalty=line_jump_penalty,
                     return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
                     pronunciation_top_k=pronunciation_top_k,
                     off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)
@@ -1223,13 +1324,13 @@ def perform_viterbi(prediction, labels, hop_size_second=0.02, n_frames=None, opt
 
 def perform_viterbi_ctc(prediction, labels, hop_size_second=0.02, n_frames=None, optional_spans=None, skip_penalty=0.0,
                         char_windows=None, onset_anchors=None, repeat_spans=None, repeat_penalty=0.0, return_segments=False, alternatives=None, return_readings=False,
-                    line_starts=None, line_jump_penalty=0.0,
+                        min_duration=None, line_starts=None, line_jump_penalty=0.0,
                         off_sheet=None, off_sheet_penalty=DEFAULT_OFF_SHEET_PENALTY, return_off_sheet=False,
                         return_pronunciation=False, pronunciation_classes=None, pronunciation_top_k=5):
     return _perform(prediction, labels, hop_size_second, LA_VARIANT_CTC, n_frames=n_frames, optional_spans=optional_spans,
                     skip_penalty=skip_penalty, char_windows=char_windows, onset_anchors=onset_anchors, repeat_spans=repeat_spans,
                     repeat_penalty=repeat_penalty, return_segments=return_segments, alternatives=alternatives, return_readings=return_readings,
-                    line_starts=line_starts, line_jump_penalty=line_jump_penalty,
+                    min_duration=min_duration, line_starts=line_starts, line_jump_penalty=line_jump_penalty,
                     return_pronunciation=return_pronunciation, pronunciation_classes=pronunciation_classes,
                     pronunciation_top_k=pronunciation_top_k,
                     off_sheet=off_sheet, off_sheet_penalty=off_sheet_penalty, return_off_sheet=return_off_sheet)

@@ -1,0 +1,393 @@
+"""The alignment DP with a minimum character duration on the device (la_viterbi_min_duration_batch, ops.viterbi_min_duration_batch and
+the layers over it): onset, offset, path, status and the float64 score bit for bit against the restatement
+tests/min_duration_reference.py (pinned by tests/test_host_min_duration.py) in every kernel form and at every chain depth; every floor 1
+against la_viterbi_batch; the tight path and one frame fewer; L = 1, D_0 = 8, the last label's floor on the last frame; a clip alone
+against the clip in a ragged batch; two calls; a floor out of range; then the Python surface on the tiny random-weight model and the
+bench tool.
+
+Emissions are PLANTED with weak tails (min_duration_reference.weak_tail) plus continuous noise (ties have measure zero), and that a
+shape is not vacuous -- status LA_OK, at least a quarter of the labels bound by their floor on the plain lattice, another path than the
+plain one -- is asserted on the restatements before the device is compared."""
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import line_order_reference as lo
+import min_duration_reference as md
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+HOP = 0.02
+
+# labels x frames per kernel form; the clips of a shape share one launch
+SHAPES = {
+    # five labels cannot hold eight floors: two clips, the second one TIGHT (6 + 7 + 8 + 1 + 2 = 24 frames)
+    "one_wave_5x24": lambda: [md.weak_tail(11, 5, 24, floors=[1, 2, 3, 4, 5]), md.weak_tail(12, 5, 24, floors=[6, 7, 8, 1, 2], equal_pair=False)],
+    # labels 31 and 32 are equal: states 63 (wave 0) and 65 (wave 1)
+    "two_waves_40x200": lambda: [md.weak_tail(13, 40, 200, pair_at=32)],
+    "nw16_300x1400": lambda: [md.weak_tail(14, 300, 1400)],
+    "r2_600x2800": lambda: [md.weak_tail(15, 600, 2800)],
+    "r4_1100x5000": lambda: [md.weak_tail(16, 1100, 5000)],
+    "r8_2100x9500": lambda: [md.weak_tail(17, 2100, 9500)],
+}
+
+
+@functools.lru_cache(maxsize=None)
+def clips_and_references(name):
+    clips = SHAPES[name]()
+    return clips, [md.viterbi(c["em"], c["lab"], c["floors"]) for c in clips], [md.plain(c["em"], c["lab"]) for c in clips]
+
+
+def _launch(clips, Tmax=None, max_min_frames=None, want_path=True):
+    """Clips of different T / L in ONE la_viterbi_min_duration_batch launch -> host arrays (onset, offset, score, status, path)."""
+    from lyricalignment_amd import ops
+    B = len(clips)
+    Lmax = max(max(len(c["lab"]) for c in clips), 1)
+    Tmax = max(c["em"].shape[0] for c in clips) if Tmax is None else Tmax
+    em = torch.zeros((B, Tmax, Lmax + 1), dtype=torch.float32)
+    labels = torch.zeros((B, Lmax), dtype=torch.int32)
+    mf = torch.ones((B, Lmax), dtype=torch.int32)
+    for b, c in enumerate(clips):
+        e, l = c["em"], c["lab"]
+        em[b, : e.shape[0], : e.shape[1]] = torch.from_numpy(e)
+        labels[b, : len(l)] = torch.tensor(list(l), dtype=torch.int32)
+        mf[b, : len(l)] = torch.tensor(c["floors"], dtype=torch.int32)
+    n_labels = torch.tensor([len(c["lab"]) for c in clips], dtype=torch.int32)
+    n_frames = torch.tensor([c["T"] for c in clips], dtype=torch.int32)
+    out = ops.viterbi_min_duration_batch(em.cuda(), labels.cuda(), n_labels.cuda(), n_frames.cuda(), mf.cuda(), max_min_frames, want_path)
+    torch.cuda.synchronize()
+    return tuple(None if t is None else t.cpu().numpy() for t in out)
+
+
+def _assert_equals_reference(got, b, ref, c, what):
+    on, off, score, status, path = got
+    r_on, r_off, r_score, r_status, r_path = ref
+    L, T = len(c["lab"]), c["T"]
+    print(f"{what}: status {status[b]} / {r_status}, score {float(score[b])!r} / {r_score!r}")
+    assert status[b] == r_status, what
+    assert np.float64(score[b]).tobytes() == np.float64(r_score).tobytes(), (what, float(score[b]), r_score)
+    if path is not None:
+        assert path[b, : len(r_path)].tolist() == r_path and (path[b, len(r_path):] == -1).all(), what
+    assert on[b, :L].tolist() == r_on and off[b, :L].tolist() == r_off, what
+    assert (on[b, L:] == -1).all() and (off[b, L:] == -1).all(), what
+    assert len(r_path) in (0, T), what
+    if r_status == md.LA_OK:
+        assert all(int(off[b, n]) - int(on[b, n]) >= c["floors"][n] for n in range(L)), what
+
+
+def _clip(em, lab, floors):
+    em = np.ascontiguousarray(np.asarray(em, dtype=np.float32))
+    return dict(em=em, lab=[int(v) for v in lab], floors=[int(v) for v in floors], T=em.shape[0])
+
+
+def _random_clip(seed, L, T, floors, vocab=40):
+    rs = np.random.RandomState(seed)
+    return _clip(np.log(rs.dirichlet(np.ones(L + 1), size=T)), rs.randint(1, vocab + 1, size=L), floors)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the restatement, every kernel form
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_device_equals_the_restatement(name):
+    clips, refs, plains = clips_and_references(name)
+    seen, short, total = set(), 0, 0
+    for c, r, p in zip(clips, refs, plains):
+        assert r[3] == md.LA_OK and p[3] == md.LA_OK, name
+        assert r[4] != p[4], name                                            # the floor changes the path
+        short += md.short_of_floor(p[0], p[1], c["floors"])
+        total += len(c["lab"])
+        seen |= set(c["floors"])
+        assert md.short_of_floor(r[0], r[1], c["floors"]) == 0
+    print(f"{name}: {short} of {total} labels shorter than their floor on the plain lattice")
+    assert 4 * short >= total, (name, short, total)
+    assert seen == set(range(1, 9)), (name, seen)
+    assert any(c["lab"][n] == c["lab"][n - 1] and min(c["floors"][n - 1: n + 1]) >= 2 for c in clips for n in range(1, len(c["lab"]))), name
+    got = _launch(clips)
+    for b, (c, r) in enumerate(zip(clips, refs)):
+        _assert_equals_reference(got, b, r, c, f"{name} clip {b}")
+
+
+@pytest.mark.parametrize("depth", [2, 4, 8])
+def test_each_chain_depth(depth):
+    """max_min_frames picks the depth: the same clip with floors up to 2, 4 and 8, one wave and sixteen."""
+    for L, T in ((12, 60), (300, 1400)):
+        c = md.weak_tail(20 + depth, L, T, max_floor=depth)
+        assert max(c["floors"]) == depth
+        r, p = md.viterbi(c["em"], c["lab"], c["floors"]), md.plain(c["em"], c["lab"])
+        assert r[3] == md.LA_OK and r[4] != p[4]
+        _assert_equals_reference(_launch([c], max_min_frames=depth), 0, r, c, f"depth {depth}, {L} x {T}")
+        if depth < 8:       # a deeper chain than needed gives the same bits
+            _assert_equals_reference(_launch([c], max_min_frames=8, want_path=False), 0, r, c, f"depth 8 for floors up to {depth}")
+
+
+# ------------------------------------------------------------------------------------------------ 2. every floor 1: the plain lattice
+@pytest.mark.parametrize("L,T", [(26, 300), (600, 1400)])
+def test_every_floor_one_is_the_plain_lattice(L, T):
+    from lyricalignment_amd import ops
+    good = _random_clip(L, L, T, [1] * L)
+    short = _random_clip(L + 1, L, L - 1, [1] * L)                               # fewer frames than labels: infeasible
+    for depth in (1, 8):
+        got = _launch([good, short], max_min_frames=depth)
+        for b, c in enumerate((good, short)):
+            em = torch.from_numpy(c["em"])[None].cuda()
+            want = ops.viterbi_batch(em, torch.tensor([c["lab"]], dtype=torch.int32).cuda(), torch.tensor([L], dtype=torch.int32).cuda(),
+                                     torch.tensor([c["T"]], dtype=torch.int32).cuda())
+            torch.cuda.synchronize()
+            on, off, score, status = (t.cpu().numpy() for t in want)
+            assert got[3][b] == status[0] == (md.LA_OK if b == 0 else md.LA_EINFEASIBLE)
+            assert got[2][b].tobytes() == score[0].tobytes(), (L, T, b)
+            if b == 0:
+                assert got[0][b].tolist() == on[0].tolist() and got[1][b].tolist() == off[0].tolist()
+            else:
+                assert (got[0][b] == -1).all() and (got[1][b] == -1).all() and (got[4][b] == -1).all()
+
+
+# ------------------------------------------------------------------------------------------------ 3. edges
+def test_the_tight_path_is_the_only_one_and_one_frame_fewer_is_infeasible():
+    """T = sum D_n + (number of equal neighbour pairs): every label lasts exactly its floor, a frame of silence between equal neighbours.
+    D_0 = 8 (row 0 is young) and the last label reaches its floor on the last frame."""
+    rs = np.random.RandomState(3)
+    L = 30
+    floors = [8] + [int(v) for v in rs.randint(1, 9, size=L - 2)] + [5]
+    lab = [int(v) for v in rs.randint(1, 4, size=L)]                              # three classes: equal neighbours are common
+    pairs = [n for n in range(1, L) if lab[n] == lab[n - 1]]
+    assert len(pairs) >= 3
+    T = sum(floors) + len(pairs)
+    em = np.log(rs.dirichlet(np.ones(L + 1), size=T))
+    tight, fewer = _clip(em, lab, floors), _clip(em[: T - 1], lab, floors)
+    ref = md.viterbi(tight["em"], lab, floors)
+    on, t = [], 0
+    for n in range(L):
+        t += n in pairs
+        on.append(t)
+        t += floors[n]
+    assert ref[3] == md.LA_OK and ref[0] == on and ref[1] == [a + d for a, d in zip(on, floors)] and ref[1][-1] == T
+    ref_fewer = md.viterbi(fewer["em"], lab, floors)
+    assert ref_fewer[3] == md.LA_EINFEASIBLE and ref_fewer[4] == []
+    got = _launch([tight, fewer, tight])
+    for b, (c, r) in enumerate(((tight, ref), (fewer, ref_fewer), (tight, ref))):
+        _assert_equals_reference(got, b, r, c, f"tight batch clip {b}")
+    assert (got[0][1] == -1).all() and (got[1][1] == -1).all() and (got[4][1] == -1).all()
+
+
+def test_one_label_and_a_deep_first_label():
+    clips = [_random_clip(40, 1, 12, [1]), _random_clip(41, 1, 12, [8]), _random_clip(42, 1, 8, [8]), _random_clip(43, 1, 7, [8]),
+             _random_clip(44, 4, 40, [8, 1, 8, 3]), _random_clip(45, 3, 30, [2, 2, 8], vocab=1)]
+    refs = [md.viterbi(c["em"], c["lab"], c["floors"]) for c in clips]
+    assert [r[3] for r in refs] == [md.LA_OK] * 3 + [md.LA_EINFEASIBLE] + [md.LA_OK] * 2
+    assert refs[2][0] == [0] and refs[2][1] == [8]
+    got = _launch(clips)
+    for b, (c, r) in enumerate(zip(clips, refs)):
+        _assert_equals_reference(got, b, r, c, f"edge clip {b}")
+
+
+def test_a_clip_in_a_ragged_batch_equals_the_clip_alone_and_two_calls_agree():
+    names = ["one_wave_5x24", "nw16_300x1400", "two_waves_40x200"]
+    clips = [clips_and_references(n)[0][0] for n in names]
+    refs = [clips_and_references(n)[1][0] for n in names]
+    batch = _launch(clips)
+    again = _launch(clips)
+    for x, y in zip(batch, again):
+        assert x.tobytes() == y.tobytes()
+    for b, (c, r, n) in enumerate(zip(clips, refs, names)):
+        _assert_equals_reference(batch, b, r, c, f"{n} in the batch")             # (also: every cell beyond L_b / T_b holds -1)
+        alone = _launch([c], Tmax=batch[4].shape[1])
+        L, T = len(c["lab"]), c["T"]
+        assert alone[0][0, :L].tolist() == batch[0][b, :L].tolist() and alone[1][0, :L].tolist() == batch[1][b, :L].tolist()
+        assert alone[2][0].tobytes() == batch[2][b].tobytes() and alone[4][0, :T].tolist() == batch[4][b, :T].tolist()
+
+
+@pytest.mark.parametrize("bad_floor", [0, 9, -3])
+def test_a_floor_out_of_range_is_einval_for_that_clip_only(bad_floor):
+    good = clips_and_references("two_waves_40x200")[0][0]
+    ref = clips_and_references("two_waves_40x200")[1][0]
+    floors = list(good["floors"])
+    floors[17] = bad_floor
+    got = _launch([good, dict(good, floors=floors), good])
+    for b in (0, 2):
+        _assert_equals_reference(got, b, ref, good, f"clip {b} beside the invalid one")
+    assert got[3][1] == md.LA_EINVAL and got[2][1] == 0.0
+    assert (got[0][1] == -1).all() and (got[1][1] == -1).all() and (got[4][1] == -1).all()
+    # a floor above the call's own bound is out of range too
+    low = _launch([good], max_min_frames=4)
+    assert low[3][0] == md.LA_EINVAL
+
+
+# ------------------------------------------------------------------------------------------------ 4. the Python surface
+@pytest.fixture(scope="module")
+def tiny():
+    import test_gpu_ragged as tr
+    from test_gpu_parity_full import _build
+    model, _ = _build("tiny", torch.float32)
+    idx = [0, 1, 3, 5]                                           # clips of tests/test_gpu_ragged.py: 11, 5, 8, 3 labels
+    return dict(model=model, audios=[tr._clip(i) for i in idx], labels=tr._padded_labels(idx), tr=tr, idx=idx)
+
+
+ROWS = [[0.06] * 11, None, [0.16, 0.02, 0.1, 0.0, 0.05, 0.07, 0.12, 0.03], [0.04, 0.08, 0.16]]     # per-character seconds; clip 1 has no floor
+
+
+def _frames_of(min_duration, lists):
+    from lyricalignment_amd.utils import alignment as ua
+    rows = ua._min_frames_of("test", min_duration, lists, HOP)
+    return [rows[b, : len(l)].tolist() for b, l in enumerate(lists)]
+
+
+def _expected(em, lists, counts, floors):
+    """The restatement on a device emission matrix [B, T, >= L+1] (host array) -> (seconds, segments, refs) as the public functions give them."""
+    seconds, segments, refs = [], [], []
+    for b, labs in enumerate(lists):
+        L = len(labs)
+        r = md.viterbi(em[b, : counts[b], : L + 1], labs, floors[b])
+        assert r[3] == md.LA_OK
+        assert all(r[1][n] - r[0][n] >= floors[b][n] for n in range(L))
+        seconds.append([[float(r[0][n]) * HOP, float(r[1][n]) * HOP] for n in range(L)])
+        segments.append([(n, float(t) * HOP, float(u) * HOP) for n, t, u in lo.segments(r[4])])
+        refs.append(r)
+    return seconds, segments, refs
+
+
+@pytest.mark.parametrize("use_ctc", [True, False])
+def test_perform_viterbi_and_align_equal_the_restatement_on_the_devices_emissions(tiny, use_ctc):
+    from lyricalignment_amd import _lib, ops
+    from lyricalignment_amd.utils import alignment as ua
+    model, audios, labels = tiny["model"], tiny["audios"], tiny["labels"]
+    two = ua.perform_viterbi_ctc if use_ctc else ua.perform_viterbi
+    variant = _lib.LA_VARIANT_CTC if use_ctc else _lib.LA_VARIANT_PLAIN
+    changed = 0
+    with torch.no_grad():
+        logits, _ = model.frame_manual_forward(audios)
+        lab, n_lab, lists = ua._labels_to_device(labels, 4, logits.device)
+        T = logits.shape[1]
+        em = ops.emissions_from_logits(logits.float().contiguous(), lab, n_lab, variant).cpu().numpy()
+        eng = model.engine()
+        feats, B, T2, stride = model._features(model._mel_of(audios), True)
+        em_head = eng.emissions(feats, B, T2, stride, lab, n_lab, variant).cpu().numpy()
+        assert T2 == T
+        plain_two, plain_fused = two(logits, labels), model.align(audios, labels, use_ctc=use_ctc)
+        for min_duration in (0.06, ROWS):
+            floors = _frames_of(min_duration, lists)
+            kw = dict(min_duration=min_duration)
+            seconds, segments, refs = _expected(em, lists, [T] * 4, floors)
+            got = two(logits, labels, return_segments=True, **kw)
+            assert got[0] == seconds and got[1] == segments
+            assert two(logits, labels, **kw) == seconds
+            seconds_h, segments_h, refs_h = _expected(em_head, lists, [T] * 4, floors)
+            fused = model.align(audios, labels, use_ctc=use_ctc, return_segments=True, **kw)
+            assert fused[0] == seconds_h and fused[1] == segments_h
+            assert model.align(audios, labels, use_ctc=use_ctc, **kw) == seconds_h
+            frames = model.align(audios, labels, use_ctc=use_ctc, return_frames=True, **kw)
+            assert len(frames) == 5 and frames[3].tolist() == [0] * 4 and frames[4].dtype == torch.int32
+            for b, r in enumerate(refs_h):
+                assert frames[4][b].tolist() == r[4] and np.float64(frames[2][b].item()).tobytes() == np.float64(r[2]).tobytes()
+            changed += seconds != plain_two
+            changed += seconds_h != plain_fused
+        assert changed > 0                                                          # the floor moved a boundary somewhere
+
+
+def test_no_floor_is_the_call_as_it_was_launch_for_launch(tiny):
+    from test_gpu_parity_full import _count_launches
+    from lyricalignment_amd.utils import alignment as ua
+    model, audios, labels = tiny["model"], tiny["audios"], tiny["labels"]
+    with torch.no_grad():
+        logits, _ = model.frame_manual_forward(audios)
+        counts = {}
+        for family in ("viterbi", "viterbi_min_duration"):
+            for key, kw in (("without", {}), ("none", dict(min_duration=None)), ("one frame", dict(min_duration=0.02)),
+                            ("rows", dict(min_duration=[[0.02] * 11, None, [0.0] * 8, [0.01] * 3]))):
+                with _count_launches(family) as n:
+                    fused = model.align(audios, labels, **kw)
+                    two = ua.perform_viterbi_ctc(logits, labels, **kw)
+                counts[family, key] = (n.n, fused, two)
+        for family in ("viterbi", "viterbi_min_duration"):
+            for key in ("none", "one frame", "rows"):
+                assert counts[family, key] == counts[family, "without"], (family, key)
+        assert counts["viterbi_min_duration", "without"][0] == 0 and counts["viterbi", "without"][0] >= 1
+        with _count_launches("viterbi_min_duration") as n:
+            ua.perform_viterbi_ctc(logits, labels, min_duration=0.04)
+        assert n.n == 1
+
+
+def test_per_clip_long_form_readings_pronunciation_and_segments_with_min_duration(tiny):
+    from lyricalignment_amd import _lib, ops
+    from lyricalignment_amd.utils import alignment as ua
+    model, audios, labels, tr = tiny["model"], tiny["audios"], tiny["labels"], tiny["tr"]
+    kw = dict(min_duration=ROWS, return_segments=True)
+    with torch.no_grad():
+        # per_clip: every clip as if it ran alone, and the restatement on its own frames
+        batch = model.align(audios, labels, per_clip=True, **kw)
+        logit_rows = model.frame_logits_per_clip(audios)
+        for r, i in enumerate(tiny["idx"]):
+            alone = model.align([audios[r]], tr._clip_labels(i), per_clip=True, min_duration=[ROWS[r]], return_segments=True)
+            assert batch[0][r] == alone[0][0] and batch[1][r] == alone[1][0], i
+            lg = logit_rows[r][None].float().contiguous()
+            lab, n_lab, lists = ua._labels_to_device(tr._clip_labels(i), 1, lg.device)
+            em = ops.emissions_from_logits(lg, lab, n_lab, _lib.LA_VARIANT_CTC).cpu().numpy()
+            floors = [[1] * len(lists[0])] if ROWS[r] is None else _frames_of([ROWS[r]], lists)
+            seconds, segments, _ = _expected(em, lists, [lg.shape[1]], floors)
+            assert batch[0][r] == seconds[0] and batch[1][r] == segments[0], i
+        # the long form: 33 s, two encoder chunks
+        audio = np.concatenate([tr._clip(4), tr._clip(3)])
+        lab = torch.from_numpy(np.random.RandomState(5).randint(2, 403, size=(1, 14)))
+        long_kw = dict(min_duration=0.1, return_segments=True)
+        logits, _ = model.frame_manual_forward([audio])
+        assert logits.shape[1] > 1500
+        got = model.align([audio], lab, **long_kw)
+        assert got == ua.perform_viterbi_ctc(logits, lab, **long_kw)
+        lab_d, n_lab, lists = ua._labels_to_device(lab, 1, logits.device)
+        em = ops.emissions_from_logits(logits.float().contiguous(), lab_d, n_lab, _lib.LA_VARIANT_CTC).cpu().numpy()
+        seconds, segments, refs = _expected(em, lists, [logits.shape[1]], [[5] * 14])
+        assert got[0] == seconds and got[1] == segments
+        assert refs[0][4] != md.plain(em[0, :, :15], lists[0])[4]                     # not the plain lattice's path
+        # alternatives + return_readings: floors belong to positions, the lattice sees the per-position ids on the folded matrix
+        logits, _ = model.frame_manual_forward(audios)
+        alts = [[(1, [17, 23]), (4, [99])], [], [(0, [5])], [(2, [7, 8, 9])]]
+        lab_d, n_lab, lists = ua._labels_to_device(labels, 4, logits.device)
+        rd = ua._readings_of(alts, lists)
+        nf = torch.full((4,), logits.shape[1], dtype=torch.int32, device=logits.device)
+        pred = logits.float().contiguous()
+        route = ua.readings_route(rd, lambda lab_x, n_x: ops.emissions_from_logits(pred, lab_x, n_x, _lib.LA_VARIANT_CTC), n_lab, nf, logits.device)
+        ids = [route.lattice_ids[b, : len(l)].tolist() for b, l in enumerate(lists)]
+        floors = _frames_of(ROWS, lists)
+        seconds, segments, refs = _expected(route.em.cpu().numpy(), ids, [logits.shape[1]] * 4, floors)
+        got = ua.perform_viterbi_ctc(logits, labels, alternatives=alts, return_readings=True, **kw)
+        assert got[0] == seconds and got[1] == segments and len(got) == 3
+        fused = model.align(audios, labels, alternatives=alts, return_readings=True, **kw)
+        # (the fused head's emissions equal the two-step route's to float32 rounding, not to the bit: the frames agree, the scores nearly)
+        assert fused[0] == got[0] and fused[1] == got[1]
+        assert [[v and v[0] for v in row] for row in fused[2]] == [[v and v[0] for v in row] for row in got[2]]
+        on = torch.tensor([[r[0][n] if n < len(r[0]) else -1 for n in range(labels.shape[1])] for r in refs], dtype=torch.int32).cuda()
+        off = torch.tensor([[r[1][n] if n < len(r[1]) else -1 for n in range(labels.shape[1])] for r in refs], dtype=torch.int32).cuda()
+        assert got[2] == ua._readings_from_scores(*route.scores(n_lab, on, off), rd)
+        # return_pronunciation reads the floored boundaries
+        pkw = dict(return_pronunciation=True, pronunciation_classes=40, pronunciation_top_k=3)
+        out = model.align(audios, labels, **kw, **pkw)
+        two = ua.perform_viterbi_ctc(logits, labels, **kw, **pkw)
+        assert len(out) == 3 and out[0] == two[0] and out[1] == two[1]
+        assert [[d and (d["class"], d["frames"]) for d in row] for row in out[2]] == [[d and (d["class"], d["frames"]) for d in row] for row in two[2]]
+        plain = model.align(audios, labels, **kw)
+        assert out[0] == plain[0] and out[1] == plain[1]
+        for b, row in enumerate(out[2]):
+            for n, d in enumerate(row):
+                assert d["frames"] == round((plain[0][b][n][1] - plain[0][b][n][0]) / HOP) >= floors[b][n]
+
+
+def test_a_clip_too_short_for_its_floors_raises_what_the_plain_call_raises(tiny):
+    from lyricalignment_amd.utils import alignment as ua
+    logits = torch.randn((1, 20, 60), generator=torch.Generator().manual_seed(1)).cuda()
+    with pytest.raises(Exception) as plain:
+        ua.perform_viterbi_ctc(logits[:, :3], [[3, 5, 7, 9, 11]])
+    with pytest.raises(type(plain.value)):
+        ua.perform_viterbi_ctc(logits, [[3, 5, 7, 9, 11]], min_duration=0.1)         # 5 x 5 frames > 20
+    assert len(ua.perform_viterbi_ctc(logits, [[3, 5, 7, 9, 11]], min_duration=0.08)[0]) == 5
+
+
+# ------------------------------------------------------------------------------------------------ 5. the bench tool
+def test_the_bench_tool_runs_quick():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "min_duration_bench.py"), "--quick"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "viterbi_min_duration" in r.stdout and "the bits of la_viterbi_batch" in r.stdout
