@@ -2,6 +2,7 @@
 // common: la_viterbi.hip (max-product), la_posterior.hip and the CTC lattice of la_loss.hip (sum-product).  Device helpers for
 // the neighbour exchange inside one wave64, the span-source rule and the log-sum-exp of a step; on the host the wave count of a label count, the face of
 // an entry point (plain, optional spans, frame windows) with its names, and the description of the lattice with its argument checks.
+// la_lattice_tile.h, on top of this header, is the form of a kernel with R states per thread and the host path of its entry.
 #pragma once
 
 #include "la_common.h"
@@ -103,6 +104,16 @@ __device__ __forceinline__ double wave_gather(double x, int byte_addr) {
     const int lo = __builtin_amdgcn_ds_bpermute(byte_addr, __double2loint(x));
     const int hi = __builtin_amdgcn_ds_bpermute(byte_addr, __double2hiint(x));
     return __hiloint2double(hi, lo);
+}
+// lane i receives x of the lane that the DPP control CTRL names (a permutation inside a row of 16 lanes: every lane has a source)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double x) {
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
+}
+// x of one lane, wave-uniform
+__device__ __forceinline__ double readlane_f64(double x, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), lane), __builtin_amdgcn_readlane(__double2loint(x), lane));
 }
 
 // The span that ends at position n (optional spans, la_viterbi.hip): skip_row[n] = a with 0 <= a < n declares labels a .. n-1 optional.

@@ -17,22 +17,19 @@
 // value, the smallest index among equals, its class -- and (v2, s2), the best source whose class differs from c1.  A target with
 // labels[a] != c1 takes s1, any other target s2.  The work per frame does not depend on the number of lines.
 //
-// Mapping: one workgroup per clip, NW * 64 threads, thread tid owns the R consecutive states tid * R + r (R = 1 up to 511 labels with
-// NW = waves_for_labels(L); 1024 threads with R = 2 / 4 / 8 up to 4095 labels: the mapping of viterbi_kernel / viterbi_strip_kernel).
-// The previous row's k-1 / k-2 neighbours cross threads through a double-buffered f64 row in LDS with one barrier per frame (one wave:
-// DPP shifts, no LDS and no barrier).  The hub: every thread folds its own sources in registers, every wave reduces its lanes by a
-// float64 maximum (four DPP steps inside a row of 16 lanes, the four rows by v_readlane), a ballot and a v_readlane of the winning
-// lane's index, and lane 0 stores the wave's 32-byte partial beside the row BEFORE the frame's one barrier; after it lanes 0 .. NW-1 of
-// every wave load the partials and fold them the same way.  Partials are double-buffered like the row.  Backpointers are four codes
-// {stay, advance, skip, hub jump}: two ballot words per (frame, r, wave) in the workspace, and s1 / s2 of every frame as two int32
-// behind them; the backtrace thread resolves a hub code by the same class compare.  Everything is float64 in this order.
-#include "la_lattice.h"
+// Mapping: the tile form of la_lattice_tile.h.  What is this file's: THE HUB REDUCTION -- every thread folds its own sources in registers,
+// every wave reduces its lanes by a float64 maximum (four DPP steps inside a row of 16 lanes, the four rows by v_readlane), a ballot and a
+// v_readlane of the winning lane's index, and lane 0 stores the wave's 32-byte partial beside the row BEFORE the frame's one barrier;
+// after it lanes 0 .. NW-1 of every wave load the partials and fold them the same way (partials are double-buffered like the row; one
+// wave keeps the hub in registers) -- THE CODE-3 JUMP -- backpointers are four codes {stay, advance, skip, hub jump}: two mask words,
+// and s1 / s2 of every frame as two int32 behind the masks -- and THE BACKTRACE, which resolves a hub code by the same class compare.
+// Everything is float64 in this order.
+#include "la_lattice_tile.h"
 
 namespace {
 
 using namespace la::lattice;
 
-constexpr double kNeg = -10000000.0;      // utils/alignment.py:144
 constexpr int kNone = 0x7fffffff;         // "no source": larger than every state index, so a real source at -inf still wins the tie
 
 struct LinesParams : LatticeIn {          // (penalty: the line jump's)
@@ -57,31 +54,9 @@ struct Hub {
 };
 static_assert(sizeof(Hub) == 32, "one 32-byte partial per wave");
 
-// la_viterbi.hip's choose_neighbour (that file's kernels are not touched): the reference's comparisons in the reference's order
-struct Cell {
-    int code;      // 0 stay, 1 advance, 2 skip, 3 hub jump
-    double best;
-};
-__device__ __forceinline__ Cell choose_neighbour(double p0, double p1, double p2, bool can_skip, bool state0) {
-    const bool stay = p0 > p1;
-    const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);
-    int code = skip ? 2 : (stay ? 0 : 1);
-    double best = skip ? p2 : (stay ? p0 : p1);
-    if (state0) { code = 0; best = p0; }
-    return {code, best};
-}
-
 // Do state s (class c, read only where s is odd) and the hub's first source (s1, c1) have one class?  Two silences do ("none").
 __device__ __forceinline__ bool same_class(int s, int c, int s1, int c1) { return (s & s1 & 1) ? c == c1 : !((s | s1) & 1); }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double x) {
-    const int lo = __double2loint(x), hi = __double2hiint(x);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double readlane_f64(double x, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), lane), __builtin_amdgcn_readlane(__double2loint(x), lane));
-}
 // the maximum over each row of 16 lanes, in every lane of the row: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
 __device__ __forceinline__ double row_max(double x) {
     x = fmax(x, dpp_f64<0xB1>(x));
@@ -313,37 +288,17 @@ __global__ __launch_bounds__(NW * 64) void viterbi_lines_kernel(LinesParams p) {
 }
 
 struct LinesPlan {
-    int nw, r;
+    Tile tile;
     size_t lds_bytes, bt_bytes, ws_bytes;   // bt_bytes: the masks of the whole batch, in front of the hub indices
 };
 
 bool plan_lines(int batch, int max_frames, int max_labels, LinesPlan *pl) {
-    if (max_labels > 4095) return false;
-    int nw = waves_for_labels(max_labels), r = 1;
-    if (nw > 16) {
-        nw = 16;
-        r = 2;
-        while (1024 * r < 2 * max_labels + 1) r *= 2;
-    }
-    pl->nw = nw, pl->r = r;
-    pl->lds_bytes = 2 * (size_t)(nw * 64 * r + 2) * sizeof(double) + 2 * (size_t)nw * sizeof(Hub);   // (one wave: the final row only)
+    if (!plan_tile(max_labels, 4095, &pl->tile)) return false;
+    const int nw = pl->tile.nw, r = pl->tile.r;
+    pl->lds_bytes = 2 * (size_t)(pl->tile.states() + 2) * sizeof(double) + 2 * (size_t)nw * sizeof(Hub);   // (one wave: the final row only)
     pl->bt_bytes = (size_t)batch * max_frames * r * nw * 2 * sizeof(unsigned long long);
     pl->ws_bytes = pl->bt_bytes + (size_t)batch * max_frames * 2 * sizeof(int32_t);
     return true;
-}
-
-template <int NW, int R>
-int launch(const LinesParams &p, const LinesPlan &pl, int batch, hipStream_t stream) {
-    static la::DeviceOnce attr_once;            // once per instantiation, to the lattice kernels' budget (pl.lds_bytes never exceeds it)
-    if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(viterbi_lines_kernel<NW, R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kLdsBudget));
-        attr_once.mark();
-    }
-    la::TimerScope ts("viterbi_lines", stream);
-    hipLaunchKernelGGL((viterbi_lines_kernel<NW, R>), dim3(batch), dim3(NW * 64), pl.lds_bytes, stream, p);
-    LA_LAUNCH_CHECK();
-    return LA_OK;
 }
 
 }  // namespace
@@ -351,10 +306,7 @@ int launch(const LinesParams &p, const LinesPlan &pl, int batch, hipStream_t str
 extern "C" int la_viterbi_lines_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "viterbi_lines_workspace_bytes: bad arguments");
     LinesPlan pl;
-    if (!plan_lines(batch, max_frames, max_labels, &pl)) {
-        la::set_error("viterbi_lines: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
-        return LA_EUNSUPPORTED;
-    }
+    if (!plan_lines(batch, max_frames, max_labels, &pl)) return over_label_limit("viterbi_lines", max_labels);
     *bytes = pl.ws_bytes;
     return LA_OK;
 }
@@ -374,34 +326,16 @@ extern "C" int la_viterbi_lines_batch(const float *em, int64_t em_batch_stride, 
     LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
     LA_CHECK_ARG(p.penalty_ok(Face::Spans), "%s: line_jump_penalty must be >= 0 (and not NaN)", who);
     LinesPlan pl;
-    const bool planned = plan_lines(batch, max_frames, max_labels, &pl);
-    LA_CHECK_ARG(!planned || (p.strides_ok(Face::Plain, out_stride, false) && line_stride >= max_labels), "%s: strides smaller than max_labels", who);
-    if (!planned) {
-        la::set_error("viterbi_lines: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
-        return LA_EUNSUPPORTED;
-    }
-    LA_CHECK_ARG(!path || path_stride >= max_frames, "%s: path_stride smaller than max_frames", who);
-    LA_CHECK_ARG(workspace && workspace_bytes >= pl.ws_bytes, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, pl.ws_bytes);
-    LA_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+    if (!plan_lines(batch, max_frames, max_labels, &pl)) return over_label_limit("viterbi_lines", max_labels);
+    LA_CHECK_ARG(p.strides_ok(Face::Plain, out_stride, false) && line_stride >= max_labels, "%s: strides smaller than max_labels", who);
+    if (const int rc = check_path_and_workspace(who, path != nullptr, path_stride, max_frames, workspace, workspace_bytes, pl.ws_bytes)) return rc;
     p.onset = onset, p.offset = offset, p.out_stride = out_stride, p.final_score = final_score, p.status = status;
     p.line_start = line_start, p.line_stride = line_stride;
     p.path = path, p.path_stride = path_stride;
     p.bt = reinterpret_cast<unsigned long long *>(workspace);
     p.hub = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + pl.bt_bytes);
-    hipStream_t stream = (hipStream_t)stream_;
-    if (pl.r == 1) {
-        switch (pl.nw) {
-            case 1: return launch<1, 1>(p, pl, batch, stream);
-            case 2: return launch<2, 1>(p, pl, batch, stream);
-            case 4: return launch<4, 1>(p, pl, batch, stream);
-            case 8: return launch<8, 1>(p, pl, batch, stream);
-            case 16: return launch<16, 1>(p, pl, batch, stream);
-        }
-    }
-    switch (pl.r) {
-        case 2: return launch<16, 2>(p, pl, batch, stream);
-        case 4: return launch<16, 4>(p, pl, batch, stream);
-        case 8: return launch<16, 8>(p, pl, batch, stream);
-    }
-    return LA_EUNSUPPORTED;
+    return for_tile(pl.tile, [&](auto nw, auto r) {
+        constexpr int NW = decltype(nw)::value, R = decltype(r)::value;
+        return launch<viterbi_lines_kernel<NW, R>>("viterbi_lines", NW * 64, p, pl, batch, (hipStream_t)stream_);
+    });
 }

@@ -23,14 +23,14 @@
 //   fixed shift by the frame's best source would lose every term 708 nats below it).  Additions only, in an order fixed by the thread
 //   layout: no atomics, the same bits from two calls and from a clip alone in the same kernel form.  All float64.
 //
-// Mapping: viterbi_lines_kernel<NW, R>'s -- one workgroup per clip, NW * 64 threads, thread tid owns the R consecutive states tid * R + r
-// (R = 1 with 1 .. 16 waves up to 511 labels; 1024 threads with R = 2 / 4 / 8 up to 1023 / 2047 / 4095 labels).  ONE float64 row in LDS
-// carries alpha_{t-1} (backward: beta_{t+1}) of every state to the neighbours and to the hub; with the slots it is 130 KB at R = 8, so the
-// row is not double-buffered: four barriers per frame.  Forward the alpha rows and every target's jump term go to the workspace; backward
-// beta stays in registers, gamma and the per-label sums are formed by the thread that owns the state: visits and in_order in registers,
-// the sparse ones (occupancy, onset, offset) in a slot of the workspace.  The neighbour terms of a step use la_lattice.h's log_add3 /
-// log_add2 (float64 maximum, float32 correction), the jump terms log_add_jump (float64), as la_posterior.hip does.
-#include "la_lattice.h"
+// Mapping: the tile form of la_lattice_tile.h, with ONE float64 row in LDS that carries alpha_{t-1} (backward: beta_{t+1}) of every
+// state to the neighbours and to the hub; with the slots it is 130 KB at R = 8, so the row is not double-buffered: four barriers per
+// frame.  What is this file's: THE XS SCALED SUMS, THE CLASS SORT and LEAVE_ONE_OUT.  Forward the alpha rows and every target's jump term
+// go to the workspace; backward beta stays in registers, gamma and the per-label sums are formed by the thread that owns the state:
+// visits and in_order in registers, the sparse ones (occupancy, onset, offset) in a slot of the workspace.  The neighbour terms of a step
+// use la_lattice.h's log_add3 / log_add2 (float64 maximum, float32 correction), the jump terms log_add_jump (float64), as
+// la_posterior.hip does.
+#include "la_lattice_tile.h"
 
 namespace {
 
@@ -445,52 +445,26 @@ __global__ __launch_bounds__(NW * 64) void line_posterior_kernel(LinePostParams 
 }
 
 struct LinePostPlan {
-    int nw, r;
+    Tile tile;
     size_t lds_bytes, alpha_bytes, jin_bytes, ws_bytes;
 };
 
 bool plan_line_posterior(int batch, int max_frames, int max_labels, LinePostPlan *pl) {
-    if (max_labels > 4095) return false;
-    int nw = waves_for_labels(max_labels), r = 1;
-    if (nw > 16) {
-        nw = 16;
-        r = 2;
-        while (1024 * r < 2 * max_labels + 1) r *= 2;
-    }
-    pl->nw = nw, pl->r = r;
-    const size_t nt = (size_t)nw * 64, ns = nt * r, ept = (r + 1) / 2;
-    pl->lds_bytes = (ns + 4) * sizeof(double) + nt * ept * sizeof(XS) + 2 * (size_t)nw * sizeof(XS);
+    if (!plan_tile(max_labels, 4095, &pl->tile)) return false;
+    const size_t nw = pl->tile.nw, nt = nw * 64, ns = pl->tile.states(), ept = (pl->tile.r + 1) / 2;
+    pl->lds_bytes = (ns + 4) * sizeof(double) + nt * ept * sizeof(XS) + 2 * nw * sizeof(XS);
     pl->alpha_bytes = (size_t)batch * max_frames * ns * sizeof(double);
     pl->jin_bytes = (size_t)batch * max_frames * (ns / 2) * sizeof(double);
     pl->ws_bytes = pl->alpha_bytes + pl->jin_bytes + (size_t)batch * (ns / 2) * 3 * sizeof(double);
     return true;
 }
 
-template <int NW, int R>
-int launch(const LinePostParams &p, const LinePostPlan &pl, int batch, hipStream_t stream) {
-    static la::DeviceOnce attr_once;            // once per instantiation, to the lattice kernels' budget (pl.lds_bytes never exceeds it)
-    if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(line_posterior_kernel<NW, R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kLdsBudget));
-        attr_once.mark();
-    }
-    la::TimerScope ts("posterior_lines", stream);
-    hipLaunchKernelGGL((line_posterior_kernel<NW, R>), dim3(batch), dim3(NW * 64), pl.lds_bytes, stream, p);
-    LA_LAUNCH_CHECK();
-    return LA_OK;
-}
-
-const char *kOver = "alignment_posteriors_lines: max_labels %d exceeds 4095 (8192 lattice states per workgroup)";
-
 }  // namespace
 
 extern "C" int la_alignment_posteriors_lines_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_labels, size_t *bytes) {
     LA_CHECK_ARG(bytes && batch >= 0 && max_frames > 0 && max_labels > 0, "alignment_posteriors_lines_workspace_bytes: bad arguments");
     LinePostPlan pl;
-    if (!plan_line_posterior(batch, max_frames, max_labels, &pl)) {
-        la::set_error(kOver, max_labels);
-        return LA_EUNSUPPORTED;
-    }
+    if (!plan_line_posterior(batch, max_frames, max_labels, &pl)) return over_label_limit("alignment_posteriors_lines", max_labels);
     *bytes = pl.ws_bytes;
     return LA_OK;
 }
@@ -515,19 +489,12 @@ extern "C" int la_alignment_posteriors_lines(const float *em, int64_t em_batch_s
     LA_CHECK_ARG(p.penalty_ok(Face::Spans), "%s: line_jump_penalty must be >= 0 (and not NaN)", who);
     LA_CHECK_ARG(!path_prob || path, "%s: path_prob needs the path it is asked about", who);
     LinePostPlan pl;
-    const bool planned = plan_line_posterior(batch, max_frames, max_labels, &pl);
-    if (planned) {
-        LA_CHECK_ARG(p.strides_ok(Face::Plain, out_stride, false) && line_stride >= max_labels, "%s: strides smaller than max_labels", who);
-        LA_CHECK_ARG(!gamma_out || (gamma_row_stride >= 2 * (int64_t)max_labels + 1 &&
-                                    (batch == 1 || gamma_batch_stride >= (int64_t)max_frames * gamma_row_stride)),
-                     "%s: gamma strides smaller than [max_frames][2 max_labels + 1]", who);
-        LA_CHECK_ARG(!(path || path_prob) || path_stride >= max_frames, "%s: path_stride smaller than max_frames", who);
-    } else {
-        la::set_error(kOver, max_labels);
-        return LA_EUNSUPPORTED;
-    }
-    LA_CHECK_ARG(workspace && workspace_bytes >= pl.ws_bytes, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, pl.ws_bytes);
-    LA_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+    if (!plan_line_posterior(batch, max_frames, max_labels, &pl)) return over_label_limit(who, max_labels);
+    LA_CHECK_ARG(p.strides_ok(Face::Plain, out_stride, false) && line_stride >= max_labels, "%s: strides smaller than max_labels", who);
+    LA_CHECK_ARG(!gamma_out || (gamma_row_stride >= 2 * (int64_t)max_labels + 1 &&
+                                (batch == 1 || gamma_batch_stride >= (int64_t)max_frames * gamma_row_stride)),
+                 "%s: gamma strides smaller than [max_frames][2 max_labels + 1]", who);
+    if (const int rc = check_path_and_workspace(who, path || path_prob, path_stride, max_frames, workspace, workspace_bytes, pl.ws_bytes)) return rc;
     p.onset = onset, p.offset = offset, p.out_stride = out_stride, p.window = boundary_window;
     p.line_start = line_start, p.line_stride = line_stride;
     p.log_keep = log(-expm1(-line_jump_penalty));
@@ -539,20 +506,8 @@ extern "C" int la_alignment_posteriors_lines(const float *em, int64_t em_batch_s
     p.alpha_ws = reinterpret_cast<double *>(ws);
     p.jin_ws = reinterpret_cast<double *>(ws + pl.alpha_bytes);
     p.acc_ws = reinterpret_cast<double *>(ws + pl.alpha_bytes + pl.jin_bytes);
-    hipStream_t stream = (hipStream_t)stream_;
-    if (pl.r == 1) {
-        switch (pl.nw) {
-            case 1: return launch<1, 1>(p, pl, batch, stream);
-            case 2: return launch<2, 1>(p, pl, batch, stream);
-            case 4: return launch<4, 1>(p, pl, batch, stream);
-            case 8: return launch<8, 1>(p, pl, batch, stream);
-            case 16: return launch<16, 1>(p, pl, batch, stream);
-        }
-    }
-    switch (pl.r) {
-        case 2: return launch<16, 2>(p, pl, batch, stream);
-        case 4: return launch<16, 4>(p, pl, batch, stream);
-        case 8: return launch<16, 8>(p, pl, batch, stream);
-    }
-    return LA_EUNSUPPORTED;
+    return for_tile(pl.tile, [&](auto nw, auto r) {
+        constexpr int NW = decltype(nw)::value, R = decltype(r)::value;
+        return launch<line_posterior_kernel<NW, R>>("posterior_lines", NW * 64, p, pl, batch, (hipStream_t)stream_);
+    });
 }

@@ -17,22 +17,19 @@
 //       LA_EINVAL for that clip.
 // Everything is float64, the emission added last.
 //
-// Mapping (la_line_order.hip's): one workgroup per clip, NW * 64 threads, thread tid owns the R consecutive states tid * R + r (R = 1 up
-// to 511 labels, 1024 threads with R = 2 / 4 / 8 up to 4095).  The previous row's k-1 / k-2 neighbours cross threads through a
-// double-buffered f64 row in LDS with one barrier per frame (one wave: DPP shifts).  The young chain of an odd state lives in DM - 1
-// float64 registers of the thread that owns the state and never crosses a thread; only m goes into the exchanged row.  The chain is
-// kept RIGHT-ALIGNED -- y_j in slot DM - D + j - 1 -- so that y_{D-1}, the one value m reads, is always the last slot and no slot is
-// indexed at run time: per frame every slot takes its left neighbour (slot DM - D the entry instead) plus the emission, off the
-// loop-carried chain of m.  Slots left of DM - D hold values that never reach a slot that is read.  DM (2, 4 or 8) is the smallest
-// depth >= max_min_frames.  Backpointers: three ballot words per (frame, r, wave) in the workspace -- the two-bit code of the entry
-// (D >= 2) or of the cell (D == 1, silences), and the graduate bit.
-#include "la_lattice.h"
+// Mapping: the tile form of la_lattice_tile.h.  What is this file's: THE YOUNG CHAIN of an odd state lives in DM - 1 float64 registers of
+// the thread that owns the state and never crosses a thread; only m goes into the exchanged row.  The chain is kept RIGHT-ALIGNED --
+// y_j in slot DM - D + j - 1 -- so that y_{D-1}, the one value m reads, is always the last slot and no slot is indexed at run time: per
+// frame every slot takes its left neighbour (slot DM - D the entry instead) plus the emission, off the loop-carried chain of m.  Slots
+// left of DM - D hold values that never reach a slot that is read.  DM (2, 4 or 8) is the smallest depth >= max_min_frames.
+// Backpointers: three mask words -- the two-bit code of the entry (D >= 2) or of the cell (D == 1, silences), and THE GRADUATE BIT --
+// and THE BACKTRACE that takes a visit at once.
+#include "la_lattice_tile.h"
 
 namespace {
 
 using namespace la::lattice;
 
-constexpr double kNeg = -10000000.0;      // utils/alignment.py:144
 constexpr int kMaxFloor = 8;              // frames: the deepest chain built
 
 struct FloorParams : LatticeIn {
@@ -47,20 +44,6 @@ struct FloorParams : LatticeIn {
     int32_t path_stride;
     unsigned long long *bt;               // [batch][max_frames][R][NW][3]
 };
-
-// la_viterbi.hip's choose_neighbour (that file's kernels are not touched): the reference's comparisons in the reference's order
-struct Cell {
-    int code;      // 0 stay, 1 advance, 2 skip
-    double best;
-};
-__device__ __forceinline__ Cell choose_neighbour(double p0, double p1, double p2, bool can_skip, bool state0) {
-    const bool stay = p0 > p1;
-    const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);
-    int code = skip ? 2 : (stay ? 0 : 1);
-    double best = skip ? p2 : (stay ? p0 : p1);
-    if (state0) { code = 0; best = p0; }
-    return {code, best};
-}
 
 template <int NW, int R, int DM>
 __global__ __launch_bounds__(NW * 64) void viterbi_min_duration_kernel(FloorParams p) {
@@ -270,56 +253,25 @@ __global__ __launch_bounds__(NW * 64) void viterbi_min_duration_kernel(FloorPara
 }
 
 struct FloorPlan {
-    int nw, r, dm;
+    Tile tile;
+    int dm;
     size_t lds_bytes, ws_bytes;
 };
 
 bool plan_floor(int batch, int max_frames, int max_labels, int max_min_frames, FloorPlan *pl) {
-    if (max_labels > 4095) return false;
-    int nw = waves_for_labels(max_labels), r = 1;
-    if (nw > 16) {
-        nw = 16;
-        r = 2;
-        while (1024 * r < 2 * max_labels + 1) r *= 2;
-    }
-    pl->nw = nw, pl->r = r;
+    if (!plan_tile(max_labels, 4095, &pl->tile)) return false;
     pl->dm = max_min_frames <= 2 ? 2 : max_min_frames <= 4 ? 4 : 8;
-    pl->lds_bytes = 2 * (size_t)(nw * 64 * r + 2) * sizeof(double);   // (one wave: the final row only)
-    pl->ws_bytes = (size_t)batch * max_frames * r * nw * 3 * sizeof(unsigned long long);
+    pl->lds_bytes = 2 * (size_t)(pl->tile.states() + 2) * sizeof(double);   // (one wave: the final row only)
+    pl->ws_bytes = (size_t)batch * max_frames * pl->tile.r * pl->tile.nw * 3 * sizeof(unsigned long long);
     return true;
-}
-
-template <int NW, int R, int DM>
-int launch(const FloorParams &p, const FloorPlan &pl, int batch, hipStream_t stream) {
-    static la::DeviceOnce attr_once;            // once per instantiation, to the lattice kernels' budget (pl.lds_bytes never exceeds it)
-    if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(viterbi_min_duration_kernel<NW, R, DM>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-        attr_once.mark();
-    }
-    la::TimerScope ts("viterbi_min_duration", stream);
-    hipLaunchKernelGGL((viterbi_min_duration_kernel<NW, R, DM>), dim3(batch), dim3(NW * 64), pl.lds_bytes, stream, p);
-    LA_LAUNCH_CHECK();
-    return LA_OK;
 }
 
 template <int DM>
 int launch_depth(const FloorParams &p, const FloorPlan &pl, int batch, hipStream_t stream) {
-    if (pl.r == 1) {
-        switch (pl.nw) {
-            case 1: return launch<1, 1, DM>(p, pl, batch, stream);
-            case 2: return launch<2, 1, DM>(p, pl, batch, stream);
-            case 4: return launch<4, 1, DM>(p, pl, batch, stream);
-            case 8: return launch<8, 1, DM>(p, pl, batch, stream);
-            case 16: return launch<16, 1, DM>(p, pl, batch, stream);
-        }
-    }
-    switch (pl.r) {
-        case 2: return launch<16, 2, DM>(p, pl, batch, stream);
-        case 4: return launch<16, 4, DM>(p, pl, batch, stream);
-        case 8: return launch<16, 8, DM>(p, pl, batch, stream);
-    }
-    return LA_EUNSUPPORTED;
+    return for_tile(pl.tile, [&](auto nw, auto r) {
+        constexpr int NW = decltype(nw)::value, R = decltype(r)::value;
+        return launch<viterbi_min_duration_kernel<NW, R, DM>>("viterbi_min_duration", NW * 64, p, pl, batch, stream);
+    });
 }
 
 }  // namespace
@@ -330,10 +282,7 @@ extern "C" int la_viterbi_min_duration_workspace_bytes(int32_t batch, int32_t ma
     LA_CHECK_ARG(max_min_frames >= 1 && max_min_frames <= kMaxFloor, "viterbi_min_duration_workspace_bytes: max_min_frames must be 1 .. %d",
                  kMaxFloor);
     FloorPlan pl;
-    if (!plan_floor(batch, max_frames, max_labels, max_min_frames, &pl)) {
-        la::set_error("viterbi_min_duration: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
-        return LA_EUNSUPPORTED;
-    }
+    if (!plan_floor(batch, max_frames, max_labels, max_min_frames, &pl)) return over_label_limit("viterbi_min_duration", max_labels);
     *bytes = pl.ws_bytes;
     return LA_OK;
 }
@@ -352,16 +301,9 @@ extern "C" int la_viterbi_min_duration_batch(const float *em, int64_t em_batch_s
     LA_CHECK_ARG(p.sizes_ok(batch), "%s: bad sizes", who);
     LA_CHECK_ARG(max_min_frames >= 1 && max_min_frames <= kMaxFloor, "%s: max_min_frames must be 1 .. %d", who, kMaxFloor);
     FloorPlan pl;
-    const bool planned = plan_floor(batch, max_frames, max_labels, max_min_frames, &pl);
-    LA_CHECK_ARG(!planned || (p.strides_ok(Face::Plain, out_stride, false) && min_frames_stride >= max_labels),
-                 "%s: strides smaller than max_labels", who);
-    if (!planned) {
-        la::set_error("viterbi_min_duration: max_labels %d exceeds 4095 (8192 lattice states per workgroup)", max_labels);
-        return LA_EUNSUPPORTED;
-    }
-    LA_CHECK_ARG(!path || path_stride >= max_frames, "%s: path_stride smaller than max_frames", who);
-    LA_CHECK_ARG(workspace && workspace_bytes >= pl.ws_bytes, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, pl.ws_bytes);
-    LA_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+    if (!plan_floor(batch, max_frames, max_labels, max_min_frames, &pl)) return over_label_limit("viterbi_min_duration", max_labels);
+    LA_CHECK_ARG(p.strides_ok(Face::Plain, out_stride, false) && min_frames_stride >= max_labels, "%s: strides smaller than max_labels", who);
+    if (const int rc = check_path_and_workspace(who, path != nullptr, path_stride, max_frames, workspace, workspace_bytes, pl.ws_bytes)) return rc;
     p.onset = onset, p.offset = offset, p.out_stride = out_stride, p.final_score = final_score, p.status = status;
     p.min_frames = min_frames, p.mf_stride = min_frames_stride, p.max_min_frames = max_min_frames;
     p.path = path, p.path_stride = path_stride;

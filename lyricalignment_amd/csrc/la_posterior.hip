@@ -77,7 +77,7 @@
 //   stored by the thread that owns the state the path names, the path value fetched with the emissions.
 #include <type_traits>
 
-#include "la_lattice.h"
+#include "la_lattice_tile.h"
 
 namespace {
 
@@ -1202,14 +1202,11 @@ struct PostPlan {
 };
 
 bool plan_posterior(int batch, int max_frames, int max_labels, int label_limit, PostPlan *pl, bool rep = false) {
-    if (max_labels > label_limit) return false;
+    Tile tile;
+    if (!plan_tile(max_labels, label_limit, &tile)) return false;
     *pl = PostPlan{};
-    pl->nw = waves_for_labels(max_labels);
-    if (pl->nw > 16) {
-        pl->nw = 16;
-        pl->R = 2;
-        while (1024 * pl->R < 2 * max_labels + 1) pl->R *= 2;
-    }
+    pl->nw = tile.nw;
+    pl->R = tile.r > 1 ? tile.r : 0;   // (0: one lane per state)
     const size_t NS = pl->R ? (size_t)1024 * pl->R : (size_t)pl->nw * 64;
     pl->alpha_bytes = (size_t)batch * (size_t)max_frames * NS * sizeof(double);
     if (pl->R) {
@@ -1218,19 +1215,6 @@ bool plan_posterior(int batch, int max_frames, int max_labels, int label_limit, 
         pl->csr_bytes = (size_t)batch * (rep ? 3 : 2) * NS * sizeof(int32_t);
     }
     return true;
-}
-
-template <auto kern, class Params = PostParams>
-int launch(const char *timer, int threads, const Params &p, const PostPlan &pl, int batch, hipStream_t stream) {
-    static la::DeviceOnce attr_once;  // once per instantiation, to the planner's budget (pl.lds_bytes never exceeds it)
-    if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-        attr_once.mark();
-    }
-    la::TimerScope ts(timer, stream);
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(threads), pl.lds_bytes, stream, p);
-    LA_LAUNCH_CHECK();
-    return LA_OK;
 }
 
 template <bool SPANS, bool WIN>

@@ -51,13 +51,12 @@
 // there is no visit yet, and a visit overwrites it); the backtrace thread recomputes K(kk) from repeat_from.
 #include <type_traits>
 
-#include "la_lattice.h"
+#include "la_lattice_tile.h"
 
 namespace {
 
 using namespace la::lattice;
 
-constexpr double kNeg = -10000000.0;  // utils/alignment.py:144
 constexpr int PF = 8;                 // emission prefetch depth (frames)
 constexpr int kSkipped = -2;          // off_s marker of a label inside a taken jump (written out as -1); the repeat face marks on_s / onset
 
@@ -83,20 +82,8 @@ struct VitParams : LatticeIn {
     }
 };
 
-// The recurrence cell, for both kernels: the winner among a state's predecessors and its backpointer code.
-struct Cell {
-    int code;      // 0 stay, 1 advance, 2 skip: the offset back to the predecessor; 3 jump from J, 4 jump from J-1; 5 repeat from K, 6 from K-1
-    double best;
-};
-// p0, p1, p2: dp[j-1][k], [k-1], [k-2]; the reference's comparisons in the reference's order
-__device__ __forceinline__ Cell choose_neighbour(double p0, double p1, double p2, bool can_skip, bool state0) {
-    const bool stay = p0 > p1;                                   // strict (:85,:94,:110)
-    const bool skip = can_skip && (p2 >= p1) && (p2 >= p0);      // (:104-105)
-    int code = skip ? 2 : (stay ? 0 : 1);
-    double best = skip ? p2 : (stay ? p0 : p1);
-    if (state0) { code = 0; best = p0; }                         // (:78-82)
-    return {code, best};
-}
+// The recurrence cell of both kernels is la_lattice_tile.h's Cell / choose_neighbour; their jumps add the codes 3 jump from J, 4 jump from
+// J-1; 5 repeat from K, 6 from K-1.
 // The two arcs of the span that ends at this state (J >= 0): each is charged pen and must beat the winner so far STRICTLY, J before J-1.
 // dp_jm1 is dereferenced only where that arc exists.  C0 = 5: the same rule for the two arcs of the repeat span that starts at this
 // state (sources K, K-1, codes 5 and 6), applied after the skip span's.
@@ -645,13 +632,12 @@ struct VitPlan {
 // mask_words: 2, or 3 with spans (then the lane-per-state forms also keep J in LDS).  label_limit: 511 = one lane per state only,
 // 4095 = the strip kernel beyond that (R = 8 holds 8192 states).  false: more labels than the limit
 bool plan_viterbi(int batch, int max_frames, int max_labels, int mask_words, int label_limit, VitPlan *pl) {
-    if (max_labels > label_limit) return false;
-    const int nw = waves_for_labels(max_labels);
+    Tile tile;
+    if (!plan_tile(max_labels, label_limit, &tile)) return false;
+    const int nw = tile.nw;
     pl->strip = 0;
-    if (nw > 16) {
-        const int S = 2 * max_labels + 1;
-        int R = 2;
-        while (1024 * R < S) R *= 2;
+    if (tile.r > 1) {
+        const int R = tile.r;
         pl->strip = R;
         pl->nw = 16;
         pl->bt_in_lds = false;
@@ -668,19 +654,6 @@ bool plan_viterbi(int batch, int max_frames, int max_labels, int mask_words, int
     pl->lds_bytes = pl->bt_in_lds ? fixed_al + bt_bytes : fixed_al;
     pl->ws_bytes = pl->bt_in_lds ? 0 : (size_t)batch * bt_bytes;
     return true;
-}
-
-template <void (*Kern)(VitParams)>
-int launch(const char *timer, int threads, const VitParams &p, const VitPlan &pl, int batch, hipStream_t stream) {
-    static la::DeviceOnce attr_once;            // once per instantiation, to the planner's budget (pl.lds_bytes never exceeds it)
-    if (pl.lds_bytes > 48 * 1024 && attr_once.pending()) {
-        LA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-        attr_once.mark();
-    }
-    la::TimerScope ts(timer, stream);
-    hipLaunchKernelGGL(Kern, dim3(batch), dim3(threads), pl.lds_bytes, stream, p);
-    LA_LAUNCH_CHECK();
-    return LA_OK;
 }
 
 // the lane-per-state forms; the single wave takes its neighbours by DPP unless the option is off or dp / bt are dumped

@@ -51,18 +51,24 @@ def _lattice_inputs(who: str, em: torch.Tensor, labels: torch.Tensor, n_labels: 
     return B, T, Lmax, n_labels.contiguous(), n_frames.contiguous()
 
 
-def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device) -> Tuple[torch.Tensor, int]:
-    """lib().la_<query>(B, T, Lmax) -> a device byte buffer of max(need, 16) bytes and `need`."""
+def _lattice_workspace(query: str, B: int, T: int, Lmax: int, device, *more) -> Tuple[torch.Tensor, int]:
+    """lib().la_<query>(B, T, Lmax, *more) -> a device byte buffer of max(need, 16) bytes and `need`."""
     need = ctypes.c_size_t(0)
-    check(getattr(lib(), "la_" + query)(B, T, Lmax, ctypes.byref(need)), query)
+    check(getattr(lib(), "la_" + query)(B, T, Lmax, *more, ctypes.byref(need)), query)
     return torch.empty((max(need.value, 16),), dtype=torch.uint8, device=device), need.value
 
+
+LINES_MAX_LABELS = 4095
+MIN_DURATION_MAX_FRAMES = 8
 
 # One row per C lattice entry (csrc/la_lattice.h Face chooses the kernel; here only what the Python side must know): the stem of its C
 # symbols (la_<stem>_batch for a DP, la_<stem> for a sweep, la_<stem>_workspace_bytes), whether it takes the span arguments (skip_from,
 # skip_stride, skip_penalty), the window arguments (win_lo, win_hi, win_stride; null = no windows where the public function lets them
 # be None) and the repeat / path arguments, whether a sweep writes the span outputs (present_prob, span_skip_prob), and the label limit
-# the Python side refuses beyond (NotImplementedError before a launch; None: the C entry's own).
+# the Python side refuses beyond (NotImplementedError before a launch; None: the C entry's own).  The entries of csrc/la_lattice_tile.h
+# take instead one [B, >= Lmax] int32 tensor `row` with its pitch and one `scalar`: a penalty >= 0, or with scalar_max an integer
+# 1 .. scalar_max (None: scalar_max) that the workspace query is asked with as well; a DP of theirs writes a path unless told not to, a
+# sweep takes a path and writes visits, in_order and path_prob.
 class _Entry(NamedTuple):
     stem: str
     spans: bool = False
@@ -70,6 +76,9 @@ class _Entry(NamedTuple):
     repeats: bool = False
     span_out: bool = False
     max_labels: Optional[int] = None
+    row: Optional[str] = None
+    scalar: Optional[str] = None
+    scalar_max: Optional[int] = None
 
 
 _ENTRIES = {e.stem: e for e in (
@@ -78,13 +87,33 @@ _ENTRIES = {e.stem: e for e in (
     _Entry("alignment_posteriors"), _Entry("alignment_posteriors_spans", True, span_out=True),
     _Entry("alignment_posteriors_windows", True, True, span_out=True), _Entry("alignment_posteriors_lattice", True, True, span_out=True),
     _Entry("alignment_posteriors_repeats", True, True, True, True, 511), _Entry("alignment_posteriors_song", True, True, True, True, 4095))}
+# the entries of csrc/la_lattice_tile.h: the same rows in a table of their own (_ENTRIES stays the eleven faces of la_lattice.h)
+_TILE_ENTRIES = {e.stem: e for e in (
+    _Entry("viterbi_lines", max_labels=LINES_MAX_LABELS, row="line_start", scalar="line_jump_penalty"),
+    _Entry("viterbi_min_duration", max_labels=LINES_MAX_LABELS, row="min_frames", scalar="max_min_frames", scalar_max=MIN_DURATION_MAX_FRAMES),
+    _Entry("alignment_posteriors_lines", max_labels=LINES_MAX_LABELS, row="line_start", scalar="line_jump_penalty"))}
+
+
+def _entry(stem: str) -> _Entry:
+    return _ENTRIES.get(stem) or _TILE_ENTRIES[stem]
+
+
 _LABEL_LIMIT_WHY = {511: "the repeat lattice's posteriors are one lane per state", 4095: "8192 lattice states per workgroup"}
 
 
+def _wide_enough(who: str, name: str, t, B: int, least: str, n: int):
+    """An optional int32 device tensor [B, >= n] with unit inner stride (least: how the message names n)."""
+    if t is not None:
+        _dev(t, name, torch.int32)
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < n or t.stride(1) != 1:
+            raise ValueError(f"{who}: {name} [B, >= {least}] with unit inner stride expected")
+
+
 def _lattice_checked(who: str, e: _Entry, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty,
-                     frames=None, path=None, boundary_window=None):
+                     frames=None, path=None, boundary_window=None, row=None, scalar=None):
     """_lattice_inputs plus the checks of the entry's own arguments (frames = the (onset, offset) the posteriors are asked about)
-    -> B, T, Lmax, the contiguous count tensors, skip_penalty as a float, the windows as a pair or None, repeat_penalty as a float."""
+    -> B, T, Lmax, the contiguous count tensors, skip_penalty as a float, the windows as a pair or None, repeat_penalty as a float, the
+    entry's scalar as the C call takes it."""
     if (win_lo is None) != (win_hi is None):
         raise ValueError(f"{who}: win_lo and win_hi go together")
     windows = None if win_lo is None else (win_lo, win_hi)
@@ -93,6 +122,8 @@ def _lattice_checked(who: str, e: _Entry, em, labels, n_labels, n_frames, skip_f
         more.update(win_lo=win_lo, win_hi=win_hi)
     if skip_from is not None:
         more["skip_from"] = skip_from
+    if e.row:
+        more[e.row] = row
     B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, **more)
     if frames is not None and (frames[0].shape != (B, Lmax) or frames[1].shape != (B, Lmax)):
         raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
@@ -101,62 +132,75 @@ def _lattice_checked(who: str, e: _Entry, em, labels, n_labels, n_frames, skip_f
             raise ValueError(f"{who}: win_lo / win_hi [B, >= 2*Lmax+1] with unit inner stride and one row pitch expected")
     if skip_from is not None and (skip_from.dim() != 2 or skip_from.shape[0] != B or skip_from.shape[1] < Lmax + 1 or skip_from.stride(1) != 1):
         raise ValueError(f"{who}: skip_from [B, >= Lmax+1] with unit inner stride expected")
+    if e.row:                               # (a tile entry answers for its tensors before its numbers, a repeat entry after them)
+        _wide_enough(who, e.row, row, B, "Lmax", Lmax)
+        _wide_enough(who, "path", path, B, "T", T)
     if boundary_window is not None and int(boundary_window) < 0:
         raise ValueError(f"{who}: boundary_window must be >= 0")
     skip_penalty = float(skip_penalty)
     if e.spans and not skip_penalty >= 0.0:
         raise ValueError(f"{who}: skip_penalty must be >= 0")
-    for name, t, least in (("repeat_from", repeat_from, "Lmax"), ("path", path, "T")):
-        if t is not None:
-            _dev(t, name, torch.int32)
-            if t.dim() != 2 or t.shape[0] != B or t.shape[1] < (Lmax if least == "Lmax" else T) or t.stride(1) != 1:
-                raise ValueError(f"{who}: {name} [B, >= {least}] with unit inner stride expected")
+    if not e.row:
+        _wide_enough(who, "repeat_from", repeat_from, B, "Lmax", Lmax)
+        _wide_enough(who, "path", path, B, "T", T)
     repeat_penalty = float(repeat_penalty)
     if e.repeats and not repeat_penalty >= 0.0:
         raise ValueError(f"{who}: repeat_penalty must be >= 0")
+    if e.scalar_max is not None:
+        scalar = e.scalar_max if scalar is None else int(scalar)
+        if not 1 <= scalar <= e.scalar_max:
+            raise ValueError(f"{who}: {e.scalar} must be 1 .. {e.scalar_max}")
+    elif e.scalar:
+        scalar = float(scalar)
+        if not scalar >= 0.0:
+            raise ValueError(f"{who}: {e.scalar} must be >= 0")
     if e.max_labels is not None and Lmax > e.max_labels:
         raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {e.max_labels} ({_LABEL_LIMIT_WHY[e.max_labels]})")
-    return B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty
+    return B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty, scalar
 
 
-def _face_args(e: _Entry, skip_from, skip_stride: int, skip_penalty: float, windows, repeat_from, repeat_penalty: float) -> tuple:
+def _face_args(e: _Entry, skip_from, skip_stride: int, skip_penalty: float, windows, repeat_from, repeat_penalty: float, row=None,
+               scalar=None) -> tuple:
     """The C arguments an entry adds to the plain one's: (skip_from, skip_stride, skip_penalty), (win_lo, win_hi, win_stride) -- null and 0
-    without windows -- and (repeat_from, repeat_stride, repeat_penalty)."""
+    without windows -- and (repeat_from, repeat_stride, repeat_penalty); a tile entry's (row, row_stride, scalar)."""
     lo, hi = windows or (None, None)
     return (((ptr(skip_from), skip_stride, skip_penalty) if e.spans else ())
             + ((ptr(lo), ptr(hi), lo.stride(0) if lo is not None else 0) if e.windows else ())
-            + ((ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty) if e.repeats else ()))
+            + ((ptr(repeat_from), repeat_from.stride(0) if repeat_from is not None else 0, repeat_penalty) if e.repeats else ())
+            + ((ptr(row), row.stride(0), scalar) if e.row else ()))
 
 
 def _viterbi(stem: str, em, labels, n_labels, n_frames, skip_from=None, skip_penalty=0.0, win_lo=None, win_hi=None, repeat_from=None,
-             repeat_penalty=0.0):
+             repeat_penalty=0.0, row=None, scalar=None, want_path=True):
     """The alignment DP through one entry: checks, outputs, workspace and the C call -> onset, offset, final_score, status [, path]."""
-    e, who = _ENTRIES[stem], stem + "_batch"
-    B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty = _lattice_checked(
-        who, e, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty)
+    e, who = _entry(stem), stem + "_batch"
+    B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty, scalar = _lattice_checked(
+        who, e, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty, row=row, scalar=scalar)
     dev = em.device
     onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
     score = torch.empty((B,), dtype=torch.float64, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev) if e.repeats else None
-    ws, need = _lattice_workspace(stem + "_workspace_bytes", B, T, Lmax, dev)
+    has_path = e.repeats or bool(e.row)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev) if has_path and want_path else None
+    ws, need = _lattice_workspace(stem + "_workspace_bytes", B, T, Lmax, dev, *((scalar,) if e.scalar_max is not None else ()))
     skip_stride = skip_from.stride(0) if skip_from is not None else 0
     check(getattr(lib(), "la_" + who)(
         ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
         ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status),
-        *_face_args(e, skip_from, skip_stride, skip_penalty, windows, repeat_from, repeat_penalty), *((ptr(path), T) if e.repeats else ()),
-        ptr(ws), need, stream_ptr()), who)
-    return (onset, offset, score, status, path) if e.repeats else (onset, offset, score, status)
+        *_face_args(e, skip_from, skip_stride, skip_penalty, windows, repeat_from, repeat_penalty, row, scalar),
+        *((ptr(path), T if path is not None else 0) if has_path else ()), ptr(ws), need, stream_ptr()), who)
+    return (onset, offset, score, status, path) if has_path else (onset, offset, score, status)
 
 
 def _posteriors(who: str, em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma, skip_from=None, skip_penalty=0.0,
-                win_lo=None, win_hi=None, repeat_from=None, repeat_penalty=0.0, path=None):
+                win_lo=None, win_hi=None, repeat_from=None, repeat_penalty=0.0, path=None, row=None, scalar=None):
     """The forward-backward sweep through one entry (`who`, the stem of its C symbols): checks, outputs, workspace and the C call ->
-    occupancy, onset_prob, offset_prob, log_z, status [, present_prob, span_skip_prob [, repeat_count, path_prob]] [, gamma]."""
-    e = _ENTRIES[who]
-    B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty = _lattice_checked(
+    occupancy, onset_prob, offset_prob, log_z, status [, present_prob, span_skip_prob [, repeat_count, path_prob]] [, gamma]; a tile
+    entry: ..., status, visits, in_order, path_prob [, gamma]."""
+    e = _entry(who)
+    B, T, Lmax, n_labels, n_frames, skip_penalty, windows, repeat_penalty, scalar = _lattice_checked(
         who, e, em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty, (onset, offset), path,
-        boundary_window)
+        boundary_window, row, scalar)
     onset = onset.contiguous(); offset = offset.contiguous()
     dev = em.device
     occupancy, onset_prob, offset_prob = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(3))
@@ -168,15 +212,17 @@ def _posteriors(who: str, em, labels, n_labels, n_frames, onset, offset, boundar
     if e.span_out:                          # skip_stride is the row pitch the kernel is told for skip_from AND for span_skip_prob
         present_prob = torch.empty((B, Lmax), dtype=torch.float32, device=dev)          # (`visits` on the repeat lattice)
         more = (present_prob, torch.empty((B, max(skip_stride, Lmax + 1)), dtype=torch.float32, device=dev)[:, :Lmax + 1])
-    if e.repeats:                           # path_prob has the row pitch of path
-        more += (torch.empty((B, Lmax), dtype=torch.float32, device=dev),
-                 torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None)
+    path_prob = torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None   # the row pitch of path
+    if e.repeats:
+        more += (torch.empty((B, Lmax), dtype=torch.float32, device=dev), path_prob)
+    if e.row:                               # visits, in_order
+        more += tuple(torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(2)) + (path_prob,)
     ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
     check(getattr(lib(), "la_" + who)(
         ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
         ptr(onset), ptr(offset), Lmax, int(boundary_window),
-        *_face_args(e, skip_from, skip_stride, skip_penalty, windows, repeat_from, repeat_penalty),
-        *((ptr(path), path.stride(0) if path is not None else 0) if e.repeats else ()),
+        *_face_args(e, skip_from, skip_stride, skip_penalty, windows, repeat_from, repeat_penalty, row, scalar),
+        *((ptr(path), path.stride(0) if path is not None else 0) if e.repeats or e.row else ()),
         ptr(occupancy), ptr(onset_prob), ptr(offset_prob), *(ptr(t) for t in more), ptr(log_z), ptr(status), ptr(gamma),
         gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0, ptr(ws), need, stream_ptr()), who)
     res = (occupancy, onset_prob, offset_prob, log_z, status) + more
@@ -231,9 +277,6 @@ def viterbi_repeats_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torc
     return _viterbi("viterbi_repeats", em, labels, n_labels, n_frames, skip_from, skip_penalty, win_lo, win_hi, repeat_from, repeat_penalty)
 
 
-LINES_MAX_LABELS = 4095
-
-
 def viterbi_lines_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor, line_start: torch.Tensor,
                         line_jump_penalty: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """la_viterbi_lines_batch: viterbi_batch on the lattice of an unmarked sheet, whose lines may be sung in any order, any number of
@@ -242,29 +285,7 @@ def viterbi_lines_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.
     per start at another line than the first and per end at another line than the last; it has not been tuned on real singing.
     -> onset, offset (a label's FIRST visit in time; -1 for a label never visited, under status LA_OK), final_score, status, path [B,T]
     i32 (the lattice state at every frame t < T_b; -1 for t >= T_b and for a clip whose status is LA_EEMPTY or LA_EINVAL)."""
-    who = "viterbi_lines_batch"
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, line_start=line_start)
-    if line_start.dim() != 2 or line_start.shape[0] != B or line_start.shape[1] < Lmax or line_start.stride(1) != 1:
-        raise ValueError(f"{who}: line_start [B, >= Lmax] with unit inner stride expected")
-    line_jump_penalty = float(line_jump_penalty)
-    if not line_jump_penalty >= 0.0:
-        raise ValueError(f"{who}: line_jump_penalty must be >= 0")
-    if Lmax > LINES_MAX_LABELS:
-        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {LINES_MAX_LABELS} ({_LABEL_LIMIT_WHY[4095]})")
-    dev = em.device
-    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
-    score = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev)
-    ws, need = _lattice_workspace("viterbi_lines_workspace_bytes", B, T, Lmax, dev)
-    check(lib().la_viterbi_lines_batch(
-        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), ptr(line_start), line_start.stride(0), line_jump_penalty,
-        ptr(path), T, ptr(ws), need, stream_ptr()), who)
-    return onset, offset, score, status, path
-
-
-MIN_DURATION_MAX_FRAMES = 8
+    return _viterbi("viterbi_lines", em, labels, n_labels, n_frames, row=line_start, scalar=line_jump_penalty)
 
 
 def viterbi_min_duration_batch(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor, min_frames: torch.Tensor,
@@ -277,28 +298,7 @@ def viterbi_min_duration_batch(em: torch.Tensor, labels: torch.Tensor, n_labels:
     -> onset, offset (offset - onset >= the floor for every reported label), final_score, status, path [B,T] i32 (None without
     want_path; the lattice state at every frame t < T_b, -1 for t >= T_b and for a clip whose status is not LA_OK).  A clip too short for
     its floors has status LA_EINFEASIBLE and every onset / offset -1."""
-    who = "viterbi_min_duration_batch"
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, min_frames=min_frames)
-    if min_frames.dim() != 2 or min_frames.shape[0] != B or min_frames.shape[1] < Lmax or min_frames.stride(1) != 1:
-        raise ValueError(f"{who}: min_frames [B, >= Lmax] with unit inner stride expected")
-    max_min_frames = MIN_DURATION_MAX_FRAMES if max_min_frames is None else int(max_min_frames)
-    if not 1 <= max_min_frames <= MIN_DURATION_MAX_FRAMES:
-        raise ValueError(f"{who}: max_min_frames must be 1 .. {MIN_DURATION_MAX_FRAMES}")
-    if Lmax > LINES_MAX_LABELS:
-        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {LINES_MAX_LABELS} ({_LABEL_LIMIT_WHY[4095]})")
-    dev = em.device
-    onset, offset = (torch.empty((B, Lmax), dtype=torch.int32, device=dev) for _ in range(2))
-    score = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev) if want_path else None
-    need = ctypes.c_size_t(0)
-    check(lib().la_viterbi_min_duration_workspace_bytes(B, T, Lmax, max_min_frames, ctypes.byref(need)), "viterbi_min_duration_workspace_bytes")
-    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
-    check(lib().la_viterbi_min_duration_batch(
-        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, ptr(score), ptr(status), ptr(min_frames), min_frames.stride(0), max_min_frames,
-        ptr(path), T if want_path else 0, ptr(ws), need.value, stream_ptr()), who)
-    return onset, offset, score, status, path
+    return _viterbi("viterbi_min_duration", em, labels, n_labels, n_frames, row=min_frames, scalar=max_min_frames, want_path=want_path)
 
 
 def alignment_posteriors(em: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, n_frames: torch.Tensor,
@@ -386,39 +386,8 @@ def alignment_posteriors_lines(em: torch.Tensor, labels: torch.Tensor, n_labels:
     and every target's jump term: B * T * 1.5 * (states per workgroup) * 8 bytes.
     -> occupancy, onset_prob, offset_prob [B,Lmax] f32, log_z [B] f64, status [B] i32, visits [B,Lmax] f32, in_order [B,Lmax] f32,
     path_prob [B,T] f32 (gamma at the given path; None without a path) [, gamma [B,T,2*Lmax+1] f32]."""
-    who = "alignment_posteriors_lines"
-    B, T, Lmax, n_labels, n_frames = _lattice_inputs(who, em, labels, n_labels, n_frames, onset=onset, offset=offset, line_start=line_start)
-    if onset.shape != (B, Lmax) or offset.shape != (B, Lmax):
-        raise ValueError(f"{who}: onset / offset must be [B,Lmax]")
-    if line_start.dim() != 2 or line_start.shape[0] != B or line_start.shape[1] < Lmax or line_start.stride(1) != 1:
-        raise ValueError(f"{who}: line_start [B, >= Lmax] with unit inner stride expected")
-    if path is not None:
-        _dev(path, "path", torch.int32)
-        if path.dim() != 2 or path.shape[0] != B or path.shape[1] < T or path.stride(1) != 1:
-            raise ValueError(f"{who}: path [B, >= T] with unit inner stride expected")
-    if int(boundary_window) < 0:
-        raise ValueError(f"{who}: boundary_window must be >= 0")
-    line_jump_penalty = float(line_jump_penalty)
-    if not line_jump_penalty >= 0.0:
-        raise ValueError(f"{who}: line_jump_penalty must be >= 0")
-    if Lmax > LINES_MAX_LABELS:
-        raise NotImplementedError(f"{who}: max_labels {Lmax} exceeds {LINES_MAX_LABELS} ({_LABEL_LIMIT_WHY[4095]})")
-    onset = onset.contiguous(); offset = offset.contiguous()
-    dev = em.device
-    occupancy, onset_prob, offset_prob, visits, in_order = (torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(5))
-    log_z = torch.empty((B,), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    gamma = torch.empty((B, T, 2 * Lmax + 1), dtype=torch.float32, device=dev) if want_gamma else None
-    path_prob = torch.empty((B, path.stride(0)), dtype=torch.float32, device=dev)[:, :T] if path is not None else None
-    ws, need = _lattice_workspace(who + "_workspace_bytes", B, T, Lmax, dev)
-    check(lib().la_alignment_posteriors_lines(
-        ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, Lmax,
-        ptr(onset), ptr(offset), Lmax, int(boundary_window), ptr(line_start), line_start.stride(0), line_jump_penalty,
-        ptr(path), path.stride(0) if path is not None else 0, ptr(occupancy), ptr(onset_prob), ptr(offset_prob), ptr(visits),
-        ptr(in_order), ptr(path_prob), ptr(log_z), ptr(status), ptr(gamma), gamma.stride(0) if want_gamma else 0,
-        gamma.stride(1) if want_gamma else 0, ptr(ws), need, stream_ptr()), who)
-    res = (occupancy, onset_prob, offset_prob, log_z, status, visits, in_order, path_prob)
-    return res + (gamma,) if want_gamma else res
+    return _posteriors("alignment_posteriors_lines", em, labels, n_labels, n_frames, onset, offset, boundary_window, want_gamma, path=path,
+                       row=line_start, scalar=line_jump_penalty)
 
 
 def emissions_from_logits(logits: torch.Tensor, labels: torch.Tensor, n_labels: torch.Tensor, variant: int) -> torch.Tensor:

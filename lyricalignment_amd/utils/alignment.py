@@ -123,7 +123,7 @@ def _repeat_from_of_spans(repeat_spans, label_lists: List[List[int]]):
     return rows if any_span else None
 
 
-LINES_MAX_LABELS = 4095         # what the lattice with free line order takes (ops.viterbi_lines_batch)
+LINES_MAX_LABELS = ops.LINES_MAX_LABELS     # 4095: what the lattice with free line order takes (ops.viterbi_lines_batch)
 
 
 def lines_from_lengths(line_lengths: Sequence[int]) -> List[int]:

@@ -437,6 +437,10 @@ def test_align_free_order_scored_on_the_tiny_model(tiny):
 
 # ------------------------------------------------------------------------------------------------ 7. the bench tool
 def test_the_bench_tool_runs_quick():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "line_confidence_bench.py"), "--quick"], capture_output=True, text=True, timeout=120)
+    # --parent-lib: the tree's own library loaded a second time, the control of two loads of one build
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "line_confidence_bench.py"), "--quick", "--parent-lib",
+                        os.path.join(ROOT, "lyricalignment_amd", "liblyricalign_hip.so")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
+    same = [line for line in r.stdout.splitlines() if "same bits as the parent commit's" in line]
+    assert same and all(line.endswith(": yes") for line in same), r.stdout
     assert "alignment_posteriors_lines" in r.stdout

@@ -388,6 +388,10 @@ def test_a_clip_too_short_for_its_floors_raises_what_the_plain_call_raises(tiny)
 
 # ------------------------------------------------------------------------------------------------ 5. the bench tool
 def test_the_bench_tool_runs_quick():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "min_duration_bench.py"), "--quick"], capture_output=True, text=True, timeout=120)
+    # --parent-lib: the tree's own library loaded a second time, the control of two loads of one build
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "min_duration_bench.py"), "--quick", "--parent-lib",
+                        os.path.join(ROOT, "lyricalignment_amd", "liblyricalign_hip.so")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
+    same = [line for line in r.stdout.splitlines() if "same bits as the parent commit's" in line]
+    assert same and all(line.endswith(": yes") for line in same), r.stdout
     assert "viterbi_min_duration" in r.stdout and "the bits of la_viterbi_batch" in r.stdout

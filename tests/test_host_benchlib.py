@@ -19,15 +19,18 @@ if TOOLS not in sys.path:
 import benchlib as bl  # noqa: E402
 
 B, T, L = 2, 6, 2
-DP = ("viterbi", "viterbi_spans", "viterbi_windows", "viterbi_lattice", "viterbi_repeats")
+DP = ("viterbi", "viterbi_spans", "viterbi_windows", "viterbi_lattice", "viterbi_repeats", "viterbi_lines", "viterbi_min_duration")
 POST = ("alignment_posteriors", "alignment_posteriors_spans", "alignment_posteriors_windows", "alignment_posteriors_lattice",
-        "alignment_posteriors_repeats", "alignment_posteriors_song")
+        "alignment_posteriors_repeats", "alignment_posteriors_song", "alignment_posteriors_lines")
+# what a tile entry takes: the keyword of its row tensor and of its scalar in ops' public function, the scalar the legs are given
+TILE = {"viterbi_lines": ("line_start", "line_jump_penalty", 1.5), "viterbi_min_duration": ("min_frames", "max_min_frames", 3),
+        "alignment_posteriors_lines": ("line_start", "line_jump_penalty", 1.5)}
 KERNEL_TOOLS = ("optional_spans_bench", "anchored_bench", "wide_lattice_bench", "repeat_lattice_bench", "dp_ab_bench", "span_confidence_bench",
                 "anchored_confidence_bench", "wide_confidence_bench", "repeat_confidence_bench", "song_confidence_bench")
 MODEL_TOOLS = ("confidence_bench", "readings_bench", "pronunciation_bench", "anchored_loss_bench")
 # the C parameters a leg fills with addresses of its own (include/lyricalign.h's names): a sweep's onset / offset are inputs
-OWN = {"final_score", "status", "occupancy", "onset_prob", "offset_prob", "present_prob", "visits", "span_skip_prob", "repeat_count", "path_prob",
-       "log_z", "workspace"}
+OWN = {"final_score", "status", "occupancy", "onset_prob", "offset_prob", "present_prob", "visits", "in_order", "span_skip_prob", "repeat_count",
+       "path_prob", "log_z", "workspace"}
 
 
 @pytest.mark.parametrize("B_, T_, L_, sung", [(2, 40, 3, [0, 1, 2]), (1, 90, 5, [0, 1, 2, 1, 2, 3, 4])])
@@ -103,24 +106,26 @@ def _inputs():
              onset=torch.zeros((B, L), **i32), offset=torch.ones((B, L), **i32),
              skip=torch.full((B, L + 6), -1, **i32)[:, : L + 1], win_lo=torch.zeros((B, 2 * L + 8), **i32)[:, : 2 * L + 1],
              win_hi=torch.full((B, 2 * L + 8), T, **i32)[:, : 2 * L + 1], repeat=torch.full((B, L + 3), -1, **i32)[:, :L],
-             path=torch.zeros((B, T + 5), **i32)[:, :T])
-    assert len({d[k].stride(0) for k in ("em", "labels", "skip", "win_lo", "repeat", "path")}) == 6
+             path=torch.zeros((B, T + 5), **i32)[:, :T], row=torch.ones((B, L + 7), **i32)[:, :L])
+    assert len({d[k].stride(0) for k in ("em", "labels", "skip", "win_lo", "repeat", "path", "row")}) == 7
     return d
 
 
 def _admitted(stem):
     """(skip, windows, repeat, path given or not) in every combination the entry admits: an entry named for its argument always gets it."""
     from lyricalignment_amd import ops
-    e = ops._ENTRIES[stem]
+    e = ops._entry(stem)
     skip = (True,) if stem.endswith("_spans") else (False, True) if e.spans else (False,)
     windows = (True,) if stem.endswith("_windows") else (False, True) if e.windows else (False,)
     repeat = (False, True) if e.repeats else (False,)
-    path = (False, True) if e.repeats and stem in POST else (False,)
+    path = (False, True) if (e.repeats or e.row) and stem in POST else (False,)
     return list(itertools.product(skip, windows, repeat, path))
 
 
 def test_every_combination_is_covered():
-    assert sum(len(_admitted(s)) for s in DP) == 1 + 1 + 2 + 4 + 8 and sum(len(_admitted(s)) for s in POST) == 1 + 1 + 2 + 4 + 16 + 16
+    assert sum(len(_admitted(s)) for s in DP) == 1 + 1 + 2 + 4 + 8 + 1 + 1 and sum(len(_admitted(s)) for s in POST) == 1 + 1 + 2 + 4 + 16 + 16 + 2
+    from lyricalignment_amd import ops
+    assert set(DP + POST) == set(ops._ENTRIES) | set(ops._TILE_ENTRIES) and len(DP + POST) == 14 and set(TILE) == set(ops._TILE_ENTRIES)
 
 
 @pytest.fixture
@@ -144,17 +149,21 @@ def test_the_c_call_of_every_leg(stand_ins, stem):
     symbol = "la_" + stem + ("_batch" if stem in DP else "")
     names, _ = _parameters(symbol)
     argtypes = _lib.SYMBOLS[symbol][1]
+    row_kw, scalar_kw, scalar = TILE.get(stem, (None, None, None))
+    tile = dict(row=d["row"], scalar=scalar) if stem in TILE else {}
+    dims = (B, T, L) + ((scalar,) if stem == "viterbi_min_duration" else ())
+    assert len(_lib.SYMBOLS[f"la_{stem}_workspace_bytes"][1]) == len(dims) + 1                        # the query's own dimensions, then &need
     for skip_given, win_given, repeat_given, path_given in _admitted(stem):
         skip = d["skip"] if skip_given else None
         windows = (d["win_lo"], d["win_hi"]) if win_given else None
         repeat = d["repeat"] if repeat_given else None
         path = d["path"] if path_given else None
-        del ours.calls[:], ours.queries[:], theirs.calls[:]
+        del ours.calls[:], ours.queries[:], theirs.calls[:], theirs.queries[:]
         if stem in DP:
-            fn, out = bl.dp_leg(ours, stem, c, skip, windows, repeat)
+            fn, out = bl.dp_leg(ours, stem, c, skip, windows, repeat, **tile)
         else:
-            fn, out = bl.posterior_leg(ours, stem, c, (d["onset"], d["offset"]), skip, windows, repeat, path, boundary_window=2)
-        assert ours.calls == [] and ours.queries == [(f"la_{stem}_workspace_bytes", (B, T, L))]       # the leg's own query, nothing launched yet
+            fn, out = bl.posterior_leg(ours, stem, c, (d["onset"], d["offset"]), skip, windows, repeat, path, boundary_window=2, **tile)
+        assert ours.calls == [] and ours.queries == [(f"la_{stem}_workspace_bytes", dims)]            # the leg's own query, nothing launched yet
         assert all(float(t.double().min()) == float(t.double().max()) == -7 for t in out.values())
         fn()
         fn()
@@ -163,8 +172,8 @@ def test_the_c_call_of_every_leg(stand_ins, stem):
         assert len(got) == len(argtypes) == len(names)
         for a, argtype in zip(got, argtypes):
             argtype.from_param(a)                                                                      # raises on an argument ctypes would refuse
-        takes = ops._ENTRIES[stem]
-        kw = {}
+        takes = ops._entry(stem)
+        kw = {row_kw: d["row"], scalar_kw: scalar} if stem in TILE else {}
         if takes.spans:
             kw.update(skip_from=skip, skip_penalty=0.0)
         if windows is not None:
@@ -172,15 +181,16 @@ def test_the_c_call_of_every_leg(stand_ins, stem):
         if takes.repeats:
             kw.update(repeat_from=repeat, repeat_penalty=0.0)
         if stem in POST:
-            kw.update(boundary_window=2, want_gamma=False, **(dict(path=path) if takes.repeats else {}))
+            kw.update(boundary_window=2, want_gamma=False, **(dict(path=path) if takes.repeats or takes.row else {}))
         frames = (d["onset"], d["offset"]) if stem in POST else ()
         getattr(ops, stem + "_batch" if stem in DP else stem)(d["em"], d["labels"], d["n_labels"], d["n_frames"], *frames, **kw)
-        assert [name for name, _ in theirs.calls] == [symbol]
+        assert [name for name, _ in theirs.calls] == [symbol] and theirs.queries == [(f"la_{stem}_workspace_bytes", dims)]
         want = theirs.calls[0][1]
         own = OWN | ({"onset", "offset", "path"} if stem in DP else set())
         mine = dict(onset=out.get("onset"), offset=out.get("offset"), final_score=out.get("score"), status=out["status"], path=out.get("path"),
                     occupancy=out.get("occupancy"), onset_prob=out.get("onset_prob"), offset_prob=out.get("offset_prob"),
-                    present_prob=out.get("present"), visits=out.get("present"), span_skip_prob=out.get("span_skip"),
+                    present_prob=out.get("present"), visits=out.get("visits", out.get("present")), in_order=out.get("in_order"),
+                    span_skip_prob=out.get("span_skip"),
                     repeat_count=out.get("repeat_count"), path_prob=out.get("path_prob"), log_z=out.get("log_z"))
         for name, a, w in zip(names, got, want):
             where = (stem, skip_given, win_given, repeat_given, path_given, name)
@@ -194,7 +204,7 @@ def test_the_c_call_of_every_leg(stand_ins, stem):
             assert out["span_skip"].stride(0) == got[names.index("skip_stride")] and out["span_skip"].shape == (B, L + 1)
         if "path_prob" in out:
             assert out["path_prob"].stride(0) == got[names.index("path_stride")] and out["path_prob"].shape == (B, T)
-        assert ("path_prob" in out) == (path is not None and takes.repeats)
+        assert ("path_prob" in out) == (path is not None and bool(takes.repeats or takes.row))
 
 
 def test_same_bits_and_a_failing_call():

@@ -33,8 +33,9 @@ class _StandIn:
         self.calls, self.queries = [], []
 
     def __getattr__(self, name):
-        def query(b, t, l, need):
-            self.queries.append((name, (b, t, l)))
+        def query(*dims_and_need):
+            *dims, need = dims_and_need
+            self.queries.append((name, tuple(dims)))
             ctypes.cast(need, ctypes.POINTER(ctypes.c_size_t))[0] = NEED
             return 0
 

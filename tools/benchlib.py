@@ -1,8 +1,8 @@
-"""What the lattice bench tools share: timing, the report, synthetic inputs, a second library, and the C calls of the eleven lattice entries.
+"""What the lattice bench tools share: timing, the report, synthetic inputs, a second library, and the C calls of the fourteen lattice entries.
 
 Importing this module opens nothing: no GPU, no library, no argument list.  Every function is handed the device and the library it works on
 (open_gpu() supplies both to a tool's main()).  The positional argument list of a la_viterbi*_batch / la_alignment_posteriors* call is built
-in one place, lattice_args(), from ops._ENTRIES and ops._face_args in the order ops._viterbi / ops._posteriors use;
+in one place, lattice_args(), from ops' entry tables and ops._face_args in the order ops._viterbi / ops._posteriors use;
 tests/test_host_benchlib.py holds it to _lib.SYMBOLS and to the call ops makes, so an entry that gains an argument fails there and not on
 the GPU.
 """
@@ -273,30 +273,32 @@ def workspace(lib, query, dims, device):
     return torch.empty((max(need.value, 16),), dtype=torch.uint8, device=device), need.value
 
 
-def lattice_args(stem, c, out, frames=None, skip=None, windows=None, repeat=None, path=None, boundary_window=2):
+def lattice_args(stem, c, out, frames=None, skip=None, windows=None, repeat=None, path=None, boundary_window=2, row=None, scalar=None):
     """The positional C arguments of la_<stem>_batch (frames None: a DP, which writes out's onset / offset) or la_<stem> (a sweep, asked about
-    frames = the DP's (onset, offset)) up to the workspace: include/lyricalign.h's order, both penalties 0, no gamma output."""
+    frames = the DP's (onset, offset)) up to the workspace: include/lyricalign.h's order, both penalties 0, no gamma output.  row, scalar:
+    what a tile entry takes (line_start and its penalty, min_frames and max_min_frames)."""
     _lib, ops = _package()
-    ptr, e, dp = _lib.ptr, ops._ENTRIES[stem], frames is None
+    ptr, e, dp = _lib.ptr, ops._entry(stem), frames is None
     onset, offset = (out["onset"], out["offset"]) if dp else frames
     B, T, L, em, labels, n_labels, n_frames = c
     skip_stride = skip.stride(0) if skip is not None else (0 if dp else L + 1)             # a sweep: also span_skip_prob's pitch
-    face = ops._face_args(e, skip, skip_stride, 0.0, windows, repeat, 0.0)
+    face = ops._face_args(e, skip, skip_stride, 0.0, windows, repeat, 0.0, row, scalar)
     head = (ptr(em), em.stride(0), em.stride(1), ptr(labels), labels.stride(0), ptr(n_labels), ptr(n_frames), B, T, L, ptr(onset), ptr(offset), L)
     if dp:
-        return head + (ptr(out["score"]), ptr(out["status"])) + face + ((ptr(out["path"]), out["path"].stride(0)) if e.repeats else ())
+        return head + (ptr(out["score"]), ptr(out["status"])) + face + ((ptr(out["path"]), out["path"].stride(0)) if "path" in out else ())
     written = ("occupancy", "onset_prob", "offset_prob") + (("present", "span_skip") if e.span_out else ()) + (
-        ("repeat_count", "path_prob") if e.repeats else ()) + ("log_z", "status")
-    return (head + (int(boundary_window),) + face + ((ptr(path), path.stride(0) if path is not None else 0) if e.repeats else ())
+        ("repeat_count", "path_prob") if e.repeats else ()) + (("visits", "in_order", "path_prob") if e.row else ()) + ("log_z", "status")
+    return (head + (int(boundary_window),) + face + ((ptr(path), path.stride(0) if path is not None else 0) if e.repeats or e.row else ())
             + tuple(ptr(out.get(k)) for k in written) + (0, 0, 0))
 
 
 def _leg(lib, stem, c, out, **lattice):
     """-> (fn, out): fn makes one call of the entry into `out` with a workspace of the leg's own.  The argument list is built here, once: its
     addresses stay good because fn holds every tensor behind them; only the stream is looked up per call."""
-    _lib = _package()[0]
+    _lib, ops = _package()
     entry = getattr(lib, f"la_{stem}_batch" if lattice.get("frames") is None else f"la_{stem}")
-    ws, need = workspace(lib, f"la_{stem}_workspace_bytes", (c.B, c.T, c.L), c.em.device)
+    dims = (c.B, c.T, c.L) + ((lattice["scalar"],) if ops._entry(stem).scalar_max is not None else ())
+    ws, need = workspace(lib, f"la_{stem}_workspace_bytes", dims, c.em.device)
     args = lattice_args(stem, c, out, **lattice) + (ws.data_ptr(), need)
 
     def fn(_held=(c, out, lattice, ws)):
@@ -306,34 +308,39 @@ def _leg(lib, stem, c, out, **lattice):
     return fn, out
 
 
-def dp_leg(lib, stem, case, skip=None, windows=None, repeat=None):
-    """One DP entry (stem viterbi, viterbi_spans, ...) of `lib` on `case` -> (fn, outputs): onset, offset, score, status (and path where the
-    entry writes one), caller-owned and pre-filled with -7."""
+def dp_leg(lib, stem, case, skip=None, windows=None, repeat=None, row=None, scalar=None):
+    """One DP entry (stem viterbi, viterbi_spans, ..., viterbi_lines, viterbi_min_duration) of `lib` on `case` -> (fn, outputs): onset, offset,
+    score, status (and path where the entry writes one), caller-owned and pre-filled with -7."""
     B, T, L, dev = case.B, case.T, case.L, case.em.device
+    e = _package()[1]._entry(stem)
     full = lambda shape, dtype: torch.full(shape, -7, dtype=dtype, device=dev)
     out = dict(onset=full((B, L), torch.int32), offset=full((B, L), torch.int32), score=full((B,), torch.float64), status=full((B,), torch.int32))
-    if _package()[1]._ENTRIES[stem].repeats:
+    if e.repeats or e.row:
         out["path"] = full((B, T), torch.int32)
-    return _leg(lib, stem, case, out, skip=skip, windows=windows, repeat=repeat)
+    return _leg(lib, stem, case, out, skip=skip, windows=windows, repeat=repeat, row=row, scalar=scalar)
 
 
-def posterior_leg(lib, stem, case, frames, skip=None, windows=None, repeat=None, path=None, boundary_window=2):
-    """One sweep entry (stem alignment_posteriors, alignment_posteriors_spans, ...) of `lib` on `case`, asked about frames = the DP's contiguous
-    (onset, offset) (and its path) -> (fn, outputs): occupancy, onset_prob, offset_prob, log_z, status and, where the entry writes them, present
-    (`visits` on the repeat lattice), span_skip, repeat_count and (with a path) path_prob; caller-owned and pre-filled with -7."""
+def posterior_leg(lib, stem, case, frames, skip=None, windows=None, repeat=None, path=None, boundary_window=2, row=None, scalar=None):
+    """One sweep entry (stem alignment_posteriors, alignment_posteriors_spans, ..., alignment_posteriors_lines) of `lib` on `case`, asked about
+    frames = the DP's contiguous (onset, offset) (and its path) -> (fn, outputs): occupancy, onset_prob, offset_prob, log_z, status and, where
+    the entry writes them, present (`visits` on the repeat lattice), span_skip, repeat_count, visits, in_order and (with a path) path_prob;
+    caller-owned and pre-filled with -7."""
     B, T, L, dev = case.B, case.T, case.L, case.em.device
-    e = _package()[1]._ENTRIES[stem]
+    e = _package()[1]._entry(stem)
     assert all(t.stride() == (L, 1) for t in frames), "onset / offset [B,L] contiguous expected"
     f32 = lambda rows_, pitch: torch.full((B, pitch), -7.0, dtype=torch.float32, device=dev)[:, :rows_]
     out = dict(occupancy=f32(L, L), onset_prob=f32(L, L), offset_prob=f32(L, L), log_z=torch.full((B,), -7.0, dtype=torch.float64, device=dev),
                status=torch.full((B,), -7, dtype=torch.int32, device=dev))
     if e.span_out:                              # span_skip_prob has the row pitch the kernel is told for skip_from
         out.update(present=f32(L, L), span_skip=f32(L + 1, max(skip.stride(0) if skip is not None else 0, L + 1)))
-    if e.repeats:                               # path_prob has the row pitch of path
+    if e.repeats:
         out["repeat_count"] = f32(L, L)
-        if path is not None:
-            out["path_prob"] = f32(T, path.stride(0))
-    return _leg(lib, stem, case, out, frames=tuple(frames), skip=skip, windows=windows, repeat=repeat, path=path, boundary_window=boundary_window)
+    if e.row:
+        out.update(visits=f32(L, L), in_order=f32(L, L))
+    if (e.repeats or e.row) and path is not None:   # path_prob has the row pitch of path
+        out["path_prob"] = f32(T, path.stride(0))
+    return _leg(lib, stem, case, out, frames=tuple(frames), skip=skip, windows=windows, repeat=repeat, path=path, boundary_window=boundary_window,
+                row=row, scalar=scalar)
 
 
 def same_bits(a, b, keys):
@@ -344,6 +351,26 @@ def same_bits(a, b, keys):
 DP_OUT = ("onset", "offset", "score", "status")
 POSTERIOR_OUT = ("occupancy", "onset_prob", "offset_prob", "log_z", "status")
 SPAN_OUT = POSTERIOR_OUT + ("present", "span_skip")
+PATH_OUT = DP_OUT + ("path",)
+LINES_OUT = POSTERIOR_OUT + ("visits", "in_order", "path_prob")
+
+
+PARENT = "parent commit: "
+
+
+def with_parent(build, lib, parent):
+    """build(lib) -> [(name, leg)]; with a parent library the same legs of it behind them, named PARENT + name."""
+    return build(lib) + ([(PARENT + name, leg) for name, leg in build(parent)] if parent is not None else [])
+
+
+def say_against_parent(say, legs, stats):
+    """For every leg that has a PARENT twin: whether every output is the twin's byte for byte, and the verdict line of its times."""
+    twins = dict(legs)
+    for name, (_, out) in legs:
+        if PARENT + name in twins:
+            same = same_bits(out, twins[PARENT + name][1], tuple(out))
+            say(f"{name}: same bits as the parent commit's: {'yes' if same else 'NO'}")
+            say(against_parent(name, stats[name], stats[PARENT + name]))
 
 
 def ok(out):

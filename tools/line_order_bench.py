@@ -1,6 +1,6 @@
 """Cost of the alignment DP with free line order (la_viterbi_lines_batch; csrc/la_line_order.hip) beside the entries it stands next to.
 
-    python tools/line_order_bench.py [--runs 30] [--quick] [--out profiles/line_order.txt]
+    python tools/line_order_bench.py [--runs 30] [--quick] [--parent-lib <liblyricalign_hip.so of the parent commit>] [--out profiles/line_order.txt]
 
 Four shapes on synthetic emissions -- 32 clips x 1500 frames x 26 labels in 4 lines (one wave), one song of 5389 frames x 200 labels (8
 waves), one of 12000 x 800 in 60 lines (2 states per thread) and one of 12000 x 2500 (8 states per thread); the emissions plant the sheet
@@ -12,7 +12,8 @@ synchronise after each):
     compared with those of la_viterbi_repeats_batch with the chorus repeatable, and the report says whether they are the same;
   * at 12000 x 800 also la_viterbi_lines_batch with 10 lines and with 100 lines: the hub's work per frame does not depend on the number
     of lines, so the two should be equal; what is measured is reported.
-Every number is the median of `runs` calls after a warm-up; min .. max is printed next to it.
+Every number is the median of `runs` calls after a warm-up; min .. max is printed next to it.  With --parent-lib the parent commit's legs run
+in the same alternation: every output is compared byte for byte and every leg's median is reported against the parent's min .. max.
 """
 from __future__ import annotations
 
@@ -44,22 +45,8 @@ def flags(L, n_lines, B, dev):
 
 
 def lines_leg(lib, c, line_start, penalty=1.0):
-    """la_viterbi_lines_batch of `lib` on `c` -> (fn, outputs), as bl.dp_leg gives them for the other entries."""
-    _lib = bl._package()[0]
-    ptr, dev = _lib.ptr, c.em.device
-    full = lambda shape, dtype: torch.full(shape, -7, dtype=dtype, device=dev)
-    out = dict(onset=full((c.B, c.L), torch.int32), offset=full((c.B, c.L), torch.int32), score=full((c.B,), torch.float64),
-               status=full((c.B,), torch.int32), path=full((c.B, c.T), torch.int32))
-    ws, need = bl.workspace(lib, "la_viterbi_lines_workspace_bytes", (c.B, c.T, c.L), dev)
-    args = (ptr(c.em), c.em.stride(0), c.em.stride(1), ptr(c.labels), c.labels.stride(0), ptr(c.n_labels), ptr(c.n_frames), c.B, c.T, c.L,
-            ptr(out["onset"]), ptr(out["offset"]), c.L, ptr(out["score"]), ptr(out["status"]), ptr(line_start), line_start.stride(0),
-            float(penalty), ptr(out["path"]), out["path"].stride(0), ws.data_ptr(), need)
-
-    def fn(_held=(c, out, line_start, ws)):
-        rc = lib.la_viterbi_lines_batch(*args, _lib.stream_ptr())
-        assert rc == 0, ("viterbi_lines", rc, lib.la_last_error())
-    fn.workspace_bytes = need
-    return fn, out
+    """la_viterbi_lines_batch of `lib` on `c` -> (fn, outputs)."""
+    return bl.dp_leg(lib, "viterbi_lines", c, row=line_start, scalar=float(penalty))
 
 
 def visits_of(out):
@@ -72,10 +59,11 @@ def visits_of(out):
 
 
 def main(argv=None):
-    args = bl.parse(bl.parser(quick=True), argv)
+    args = bl.parse(bl.parser(parent_lib=True, quick=True), argv)
     report = bl.Report(args.out)
     say = report.say
     dev, lib = bl.open_gpu()
+    parent = bl.load_parent(args.parent_lib, ("viterbi", "viterbi_repeats", "viterbi_lines")) if args.parent_lib else None
     from lyricalignment_amd.utils.alignment import repeats_from_lines
 
     say(f"# alignment DP with free line order on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after a warm-up "
@@ -85,9 +73,10 @@ def main(argv=None):
         c = bl.case(bl.planted(B, T, L, bl.sung_lines(lengths, [2 if i == 1 else 1 for i in range(len(lengths))]), B + T + L, dev),
                     *bl.sheet(B, T, L, dev))
         chorus = bl.rows(repeats_from_lines(lengths, [i == 1 for i in range(len(lengths))]), B, dev)
-        legs = list(zip(LEGS, [bl.dp_leg(lib, "viterbi", c), bl.dp_leg(lib, "viterbi_repeats", c),
-                               bl.dp_leg(lib, "viterbi_repeats", c, None, None, chorus), lines_leg(lib, c, flags(L, n_lines, B, dev))]))
-        legs += [(f"la_viterbi_lines_batch, {n} lines", lines_leg(lib, c, flags(L, n, B, dev))) for n in more]
+        legs = bl.with_parent(lambda lib_: list(zip(LEGS, [
+            bl.dp_leg(lib_, "viterbi", c), bl.dp_leg(lib_, "viterbi_repeats", c), bl.dp_leg(lib_, "viterbi_repeats", c, None, None, chorus),
+            lines_leg(lib_, c, flags(L, n_lines, B, dev))])) + [(f"la_viterbi_lines_batch, {n} lines", lines_leg(lib_, c, flags(L, n, B, dev)))
+                                                               for n in more], lib, parent)
         bl.warm_up(legs)
         for name, (_, out) in legs:
             assert bl.ok(out), f"{name}: status not LA_OK"
@@ -106,6 +95,7 @@ def main(argv=None):
             a, b = (stats[f"la_viterbi_lines_batch, {n} lines"] for n in more)
             say(f"{more[0]} lines {a[0]:.3f} ({a[1]:.3f} .. {a[2]:.3f}) against {more[1]} lines {b[0]:.3f} ({b[1]:.3f} .. {b[2]:.3f}): "
                 f"{100 * (b[0] / a[0] - 1):+.1f} %")
+        bl.say_against_parent(say, legs, stats)
         say()
         del legs, c
         torch.cuda.empty_cache()

@@ -1,7 +1,7 @@
 """Cost of the alignment DP with a minimum character duration (la_viterbi_min_duration_batch; csrc/la_min_duration.hip) beside
 la_viterbi_batch on the same build.
 
-    python tools/min_duration_bench.py [--runs 30] [--quick] [--out profiles/min_duration.txt]
+    python tools/min_duration_bench.py [--runs 30] [--quick] [--parent-lib <liblyricalign_hip.so of the parent commit>] [--out profiles/min_duration.txt]
 
 Four shapes on synthetic emissions -- 32 clips x 1500 frames x 26 labels (one wave), one song of 5389 frames x 200 labels (8 waves), one
 of 12000 x 800 (2 states per thread) and one of 12000 x 2500 (8 states per thread); the emissions plant the sheet sung straight through.
@@ -12,7 +12,8 @@ Legs, alternated call by call (caller-owned buffers, device events around one ca
     into nine tenths of the frames (8 x 2500 > 12000) only the first K labels get the floor and the rest 1; K is reported.
 The floor-1 outputs are compared with la_viterbi_batch's and the report says whether they are the same bits; under a floor the report
 gives the shortest character of clip 0.  Every number is the median of `runs` calls after a warm-up; min .. max is printed next to it.
-The times are recorded, not gated.
+The times are recorded, not gated.  With --parent-lib the parent commit's legs run in the same alternation: every output is compared byte for
+byte and every leg's median is reported against the parent's min .. max.
 """
 from __future__ import annotations
 
@@ -33,25 +34,9 @@ FLOORS = [(1, 1), (3, 3), (8, 8), (1, 8)]
 
 
 def floor_leg(lib, c, floor, max_min_frames):
-    """la_viterbi_min_duration_batch of `lib` on `c` with one floor for every label that fits (floored_labels) -> (fn, outputs), as
-    bl.dp_leg gives them."""
-    _lib = bl._package()[0]
-    ptr, dev = _lib.ptr, c.em.device
-    full = lambda shape, dtype: torch.full(shape, -7, dtype=dtype, device=dev)
-    out = dict(onset=full((c.B, c.L), torch.int32), offset=full((c.B, c.L), torch.int32), score=full((c.B,), torch.float64),
-               status=full((c.B,), torch.int32), path=full((c.B, c.T), torch.int32))
+    """la_viterbi_min_duration_batch of `lib` on `c` with one floor for every label that fits (floored_labels) -> (fn, outputs)."""
     K = floored_labels(c.T, c.L, floor)
-    min_frames = bl.rows([floor] * K + [1] * (c.L - K), c.B, dev)
-    ws, need = bl.workspace(lib, "la_viterbi_min_duration_workspace_bytes", (c.B, c.T, c.L, max_min_frames), dev)
-    args = (ptr(c.em), c.em.stride(0), c.em.stride(1), ptr(c.labels), c.labels.stride(0), ptr(c.n_labels), ptr(c.n_frames), c.B, c.T, c.L,
-            ptr(out["onset"]), ptr(out["offset"]), c.L, ptr(out["score"]), ptr(out["status"]), ptr(min_frames), min_frames.stride(0),
-            int(max_min_frames), ptr(out["path"]), out["path"].stride(0), ws.data_ptr(), need)
-
-    def fn(_held=(c, out, min_frames, ws)):
-        rc = lib.la_viterbi_min_duration_batch(*args, _lib.stream_ptr())
-        assert rc == 0, ("viterbi_min_duration", rc, lib.la_last_error())
-    fn.workspace_bytes = need
-    return fn, out
+    return bl.dp_leg(lib, "viterbi_min_duration", c, row=bl.rows([floor] * K + [1] * (c.L - K), c.B, c.em.device), scalar=int(max_min_frames))
 
 
 def floored_labels(T, L, floor):
@@ -64,16 +49,18 @@ def name_of(floor, max_min_frames):
 
 
 def main(argv=None):
-    args = bl.parse(bl.parser(quick=True), argv)
+    args = bl.parse(bl.parser(parent_lib=True, quick=True), argv)
     report = bl.Report(args.out)
     say = report.say
     dev, lib = bl.open_gpu()
+    parent = bl.load_parent(args.parent_lib, ("viterbi", "viterbi_min_duration")) if args.parent_lib else None
 
     say(f"# alignment DP with a minimum character duration on {torch.cuda.get_device_name(0)}: median (min .. max) of {args.runs} calls after "
         f"a warm-up of 3, legs alternated call by call, device events around one call, ms")
     for title, B, T, L in QUICK if args.quick else SHAPES:
         c = bl.case(bl.planted(B, T, L, list(range(L)), B + T + L, dev), *bl.sheet(B, T, L, dev))
-        legs = [("la_viterbi_batch", bl.dp_leg(lib, "viterbi", c))] + [(name_of(*f), floor_leg(lib, c, *f)) for f in FLOORS]
+        legs = bl.with_parent(lambda lib_: [("la_viterbi_batch", bl.dp_leg(lib_, "viterbi", c))] + [(name_of(*f), floor_leg(lib_, c, *f)) for f in FLOORS],
+                              lib, parent)
         bl.warm_up(legs)
         for name, (_, out) in legs:
             assert bl.ok(out), f"{name}: status not LA_OK"
@@ -97,6 +84,7 @@ def main(argv=None):
         a, b = stats[name_of(1, 1)], stats[name_of(1, 8)]
         say(f"chain depth 2 {a[0]:.3f} ({a[1]:.3f} .. {a[2]:.3f}) against depth 8 {b[0]:.3f} ({b[1]:.3f} .. {b[2]:.3f}) at floor 1: "
             f"{100 * (b[0] / a[0] - 1):+.1f} %")
+        bl.say_against_parent(say, legs, stats)
         say()
         del legs, c
         torch.cuda.empty_cache()
